@@ -14,9 +14,17 @@ Workload (default): the grid of BASELINE.md's headline cfg 3 at every N -- unit 
           9 938 375 dofs, 147 968 803 nonzeros -- split into 1x1x1, 1x1x2, 1x2x2, 2x2x2 blocks
           (strong scaling; N = 8 is the reference's N = 2, M = 107 decomposition, the 2- and 4-block
           splits of the same grid are BASELINE.md section 2's stated extension: the reference
-          generator needs N^3 ranks, laplace/main.cpp:132).  At N = 1 the line also carries
+          generator needs N^3 ranks, laplace/main.cpp:132).  At N = 1 the --full line also carries
           `cfg2_one_gpu`: the same path on BASELINE.json configs[1] (100^3 cells, 1 030 301 dofs).
           --cells M switches to M^3 cells per GPU (weak scaling; development and rehearsals).
+
+A plain run sets up, warms up, times the K steps, checks the true residual of the last one and prints the result line
+(with the per-class device times and roofline of those same steps).  Everything measured beyond that -- the two-level
+variant, the back-to-back SpMV and read-bandwidth figures, the extra configurations, the CPU baseline, the N > 1
+communication self-check and A/B of the multi-GPU switches -- runs only with --full (the --no-* switches then leave parts
+out).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64, 48 MB at most): the
+solution (a fixed, seeded sample of it beyond 3 M entries, with the global ids of the sample), the iteration count and
+the relative residual.
 """
 from __future__ import annotations
 
@@ -35,6 +43,8 @@ sys.path.insert(0, ROOT)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 DECOMP = {1: (1, 1, 1), 2: (1, 1, 2), 4: (1, 2, 2), 8: (2, 2, 2)}
+DUMP_MAX_ENTRIES = 3_000_000   # --dump-outputs: values + their global ids as float64, 48 MB
+DUMP_SEED = 0
 MFMA_F64_PEAK_TFLOPS = 78.6    # dense f64 matrix rate: 256 CUs x 4 SIMDs x 32 flop/clk x 2.4 GHz (v_mfma_f64_16x16x4_f64)
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 
@@ -66,8 +76,19 @@ def parse():
     ap.add_argument("--no-multi-ab", action="store_true",
                     help="N > 1: skip the A/B of the multi-GPU switches that follows the result line (stderr only)")
     ap.add_argument("--cpu-full", action="store_true",
-                    help="time the CPU restatement on the full grid of the GPU run instead of the bounded sample (minutes)")
-    return ap.parse_args()
+                    help="with --full: time the CPU restatement on the full grid of the GPU run instead of the bounded "
+                         "sample (minutes)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline (see the module docstring); "
+                         "the --no-* switches then leave parts out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.cpu_full and not a.full:
+        ap.error("--cpu-full needs --full")
+    return a
 
 
 def one_step(c, capi, a, two_level=False):
@@ -92,7 +113,7 @@ def _cycle_cols(its, restart):
 
 
 def _recorded_full_cpu_run(full_cells, target):
-    """the full-grid CPU run of this round (bench.py --cpu-full on a GPU box, committed as profiles/cpu_full.json): the
+    """the full-grid CPU run of this round (bench.py --full --cpu-full on a GPU box, committed as profiles/cpu_full.json): the
     measured partner of the extrapolated figure, quoted when it is of the same grid"""
     try:
         pj = json.load(open(os.path.join(ROOT, "profiles", "cpu_full.json")))
@@ -148,7 +169,7 @@ def cpu_baseline(a, full_cells, gpu_its, full=False, nthr=0):
     (BASELINE.md 4.3-4.4): assembly, Dirichlet and Schwarz setup scale with the dofs; the solve is
     iterations x (operator time per iteration and dof + Gram-Schmidt time per basis column and dof), with the
     iteration count of the full grid taken from the GPU run (same algorithm; the tests hold the two counts within
-    +-2).  --cpu-full runs the full grid instead (recorded once per round under profiles/)."""
+    +-2).  --full --cpu-full runs the full grid instead (recorded once per round under profiles/)."""
     nthr = nthr or int(os.environ.get("FEDD_CPU_THREADS", "0")) or host_cores()
     n_full = (full_cells + 1) ** 3
     M = full_cells if full else min(a.cpu_cells, full_cells)
@@ -174,7 +195,7 @@ def cpu_baseline(a, full_cells, gpu_its, full=False, nthr=0):
                       "time x dofs ratio x iterations %d/%d (count of the GPU run on the full grid), Gram-Schmidt time x "
                       "dofs ratio x basis columns %d/%d (GMRES(%d) cycles) = %.1f s; oracle/oracle.c (C/OpenMP "
                       "restatement, not Trilinos), one-level RAS with %d-node subdomains; a full-grid CPU run is "
-                      "recorded under profiles/ (bench.py --cpu-full)"
+                      "recorded under profiles/ (bench.py --full --cpu-full)"
                       % (M, r["dofs"], desc, r["seconds"], r["dofs"] / r["seconds"], full_cells, scale, gpu_its, r["its"],
                          cols_f, cols_s, a.restart, t_full, a.target),
             "seconds": t_full, "extrapolated": True, "full_grid_measured": _recorded_full_cpu_run(full_cells, a.target),
@@ -222,6 +243,22 @@ def timed_passes(c, step, steps, warmup, stride=1, wall_without_timers=False):
 
 def phases(tm, steps):
     return {k: round(v[0] / steps, 4) for k, v in tm.items() if not k.startswith("_")}
+
+
+def dump_index(n):
+    """the global ids --dump-outputs writes of a vector of n entries: all of them, or beyond DUMP_MAX_ENTRIES a sorted sample
+    drawn with a fixed seed (the same ids in every run of the same grid)"""
+    if n <= DUMP_MAX_ENTRIES:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_ENTRIES, replace=False))
+
+
+def sample_of(idx, gid, x):
+    """(positions into idx, values) of this rank's entries x[i] with global id gid[i] among the sorted ids idx"""
+    pos = np.searchsorted(idx, gid)
+    mine = pos < idx.size
+    mine[mine] = idx[pos[mine]] == gid[mine]
+    return pos[mine], x[mine]
 
 
 def spmv_bytes_model(si, nr):
@@ -668,10 +705,28 @@ def main():
     nr, ncol, nnz = c.csr_sizes()
     info = c.schwarz_info()
     info["spmv"] = c.spmv_info()
+    if a.dump_outputs:
+        # what a caller of the timed path receives from its last step: the solution (gathered on rank 0 by global id), the
+        # iteration count and the relative residual the solver reports
+        idx = dump_index(n_global)
+        pos, val = sample_of(idx, m["gid_uni"], c.solution_get())
+        parts = [(pos, val)]
+        if N > 1:
+            parts = [None] * N if rank == 0 else None
+            dist.gather_object((pos, val), parts, dst=0)
+        if rank == 0:
+            x_s, seen = np.zeros(idx.size), np.zeros(idx.size, dtype=bool)
+            for p_, v_ in parts:
+                x_s[p_], seen[p_] = v_, True
+            if not seen.all():
+                raise SystemExit("bench.py: --dump-outputs: %d ids of the solution sample have no owner" % (~seen).sum())
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            for name, v in (("solution", x_s), ("solution_global_ids", idx), ("gmres_iterations", [its]), ("relres", [rel])):
+                np.save(os.path.join(a.dump_outputs, name + ".npy"), np.asarray(v, dtype=np.float64))
 
     # ---- extra, outside the headline number: the same step with the coarse level switched on ----
     two = None
-    if not a.no_two_level:
+    if a.full and not a.no_two_level:
         dt2, its2, rel2, tm2 = measure(c, n_global, True)
         true_rel2 = checked(c, "two-level variant")
         g2, n02 = c.schwarz_coarse_sizes()
@@ -684,7 +739,7 @@ def main():
     # ---- extra: SpMV launched back to back on resident vectors (single GPU; no halo in the loop) ----
     spmv_b2b = None
     read_ceiling = None
-    if N == 1:
+    if a.full and N == 1:
         c.timing_enable(1)
         c.spmv_device(5)
         c.timing_reset()
@@ -701,7 +756,7 @@ def main():
 
     # ---- N > 1, outside every timed region: the communication checked against communication-free references ----
     self_check = None
-    if N > 1:
+    if a.full and N > 1:
         import scipy.sparse as sp
 
         def sum_over_ranks(v):
@@ -732,7 +787,7 @@ def main():
 
     # ---- extra (N = 1, fixed-grid mode): the same path on BASELINE.json configs[1], 100^3 cells ----
     cfg2 = None
-    if N == 1 and not weak and not a.no_cfg2:
+    if a.full and N == 1 and not weak and not a.no_cfg2:
         m2 = capi.structured_mesh(3, dec, [100] * 3, 0)
         c2 = capi.Context(device=dev, rank=0, nranks=1, nccl_id=None)
         for kv in filter(None, os.environ.get("FEDD_OPTIONS", "").split(",")):
@@ -767,7 +822,7 @@ def main():
             cfg2["gpu_over_cpu"] = cfg2["value"] / cfg2["cpu_baseline"]["value"]
 
     extras = {}
-    if N == 1 and not weak and not a.no_extras:
+    if a.full and N == 1 and not weak and not a.no_extras:
         extras["per_gpu_share_n8"] = extra_per_gpu_share(capi, dev, a, its)
         extras["cfg5_share_one_gpu"] = extra_cfg5_share(capi, dev, a)
         e4 = extra_cfg4(capi, dev)
@@ -881,7 +936,8 @@ def main():
         }
         if N > 1:
             out["rccl_preflight"] = preflight
-            out["self_check"] = self_check
+            if self_check is not None:
+                out["self_check"] = self_check
             out["communication_note"] = ("phases 'halo' (pack kernel, grouped RCCL send/receive, unpack kernel; one before every SpMV "
                                          "and every Schwarz apply) and 'allreduce' are HIP-event times on the library's stream, rank 0, "
                                          "sampled every 8th call; 'allreduce' is also contained in 'ortho' and 'coarse_*'")
@@ -892,7 +948,7 @@ def main():
         if cfg2 is not None:
             out["cfg2_one_gpu"] = cfg2
         out.update(extras)
-        if N == 1 and not a.no_cpu_baseline:
+        if a.full and N == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a, cells[0], its, full=a.cpu_full)
             out["cpu_baseline"]["host"] = {"cpu_model": host_cpu_model(), "os_cpu_count": os.cpu_count(),
                                            "cores_available_to_this_process": host_cores()}
@@ -901,7 +957,7 @@ def main():
                 out["cpu_baseline"]["with_16_threads"] = {"value": c16["value"], "seconds": c16["seconds"], "cores": c16["cores"]}
             out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
         print(json.dumps(out), flush=True)
-    if N > 1 and not rehearse and not a.no_multi_ab:
+    if a.full and N > 1 and not rehearse and not a.no_multi_ab:
         # ---- after the one JSON line, to STDERR, under a watchdog: A/B of the multi-GPU switches that cannot be measured on the
         # one-GPU development boxes (ghost import of r behind the interior subdomains, operator applications issued ahead of a
         # block's host round trip, the one-vector solver).  Whatever happens here, the result above has been printed.

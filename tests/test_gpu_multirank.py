@@ -203,13 +203,13 @@ def test_multirank_elasticity_two_level(fedd_lib):
 
 def test_bench_contract_n2_rehearsal(fedd_lib):
     """bench.py's N > 1 code path (decomposition, ghost meshes, halo plan, barriers, max over ranks, one
-    JSON line from rank 0) with two ranks on one GPU over gloo (`--rehearse-one-gpu`)."""
+    JSON line from rank 0) with two ranks on one GPU over gloo (`--rehearse-one-gpu`), with the --full extras."""
     import json
     import subprocess
     import sys
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1",
-           "--warmup", "0", "--cells", "12", "--rehearse-one-gpu"]
+           "--warmup", "0", "--cells", "12", "--rehearse-one-gpu", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -231,7 +231,7 @@ def test_bench_contract_n2_fixed_grid_rehearsal(fedd_lib):
     import sys
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1",
-           "--warmup", "0", "--global-cells", "24", "--rehearse-one-gpu"]
+           "--warmup", "0", "--global-cells", "24", "--rehearse-one-gpu", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -242,12 +242,13 @@ def test_bench_contract_n2_fixed_grid_rehearsal(fedd_lib):
 
 
 def test_bench_contract_one_gpu(fedd_lib):
-    """`python bench.py` end to end at a reduced grid: one JSON line with every contract key, the roofline and
+    """`python bench.py --full` end to end at a reduced grid: one JSON line with every contract key, the roofline and
     cpu_baseline objects, and the configs[1] extra."""
     import json
     import subprocess
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--global-cells", "20"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--global-cells", "20",
+                        "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -480,7 +481,7 @@ def test_bench_contract_n4_fixed_grid_rehearsal(fedd_lib):
     import sys
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1",
-           "--warmup", "0", "--global-cells", "32", "--rehearse-one-gpu", "--no-two-level"]
+           "--warmup", "0", "--global-cells", "32", "--rehearse-one-gpu", "--full", "--no-two-level"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -1,5 +1,5 @@
 # Round profile: kernel statistics of the bench command, PMC traffic passes (FETCH_SIZE / WRITE_SIZE in their own runs),
-# then the plain bench line.  usage (on the GPU box): bash tools/profile_round.sh <tag> <git sha of the tree>   e.g. r03_a 4c2c77d
+# then the bench line with --full.  usage (on the GPU box): bash tools/profile_round.sh <tag> <git sha of the tree>   e.g. r03_a 4c2c77d
 set -e
 TAG=${1:-r03_a}
 SHA=${2:-unknown}
@@ -12,7 +12,7 @@ mkdir -p $P $R/gpurun_out/pmc_${TAG}_FETCH_SIZE $R/gpurun_out/pmc_${TAG}_WRITE_S
 rocprofv3 --kernel-trace --stats --output-format csv -d $P -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-cfg2 --no-two-level --no-extras > $P/bench.json 2> $P/err.log
 echo stats done
 mkdir -p ${P}_two
-rocprofv3 --kernel-trace --stats --output-format csv -d ${P}_two -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-cfg2 --no-extras > ${P}_two/bench.json 2> ${P}_two/err.log
+rocprofv3 --kernel-trace --stats --output-format csv -d ${P}_two -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-cfg2 --no-extras > ${P}_two/bench.json 2> ${P}_two/err.log
 find ${P}_two -name "*kernel_trace.csv" -size +20M -delete
 echo stats with the two-level steps done
 for C in FETCH_SIZE WRITE_SIZE; do
@@ -23,5 +23,5 @@ cd $R
 python3 tools/pmc_summary.py gpurun_out/pmc_${TAG}_FETCH_SIZE gpurun_out/pmc_${TAG}_WRITE_SIZE gpurun_out/pmc_traffic_$TAG.json 214,214,214 $TAG $SHA
 find gpurun_out/pmc_${TAG}_FETCH_SIZE gpurun_out/pmc_${TAG}_WRITE_SIZE -name "*counter_collection.csv" -size +20M -delete
 find $P -name "*kernel_trace.csv" -size +20M -delete
-python3 bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err
+python3 bench.py --full > $(dirname $P)/bench_$TAG.json 2> $(dirname $P)/bench_$TAG.err
 echo bench done
