@@ -21,6 +21,8 @@ TIMER_NAMES = ["symbolic", "assemble", "rhs", "dirichlet", "spmv", "schwarz_setu
 COARSE_Q1 = 1
 COARSE_GDSW = 2
 COARSE_RGDSW = 3
+LEVELS_ADDITIVE = 0         # FROSch "Level Combination" (fedd_schwarz_set_level_combination)
+LEVELS_MULTIPLICATIVE = 1
 
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
@@ -77,6 +79,8 @@ SIGNATURES = {
     "fedd_schwarz_setup": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int],
     "fedd_schwarz_set_target": [C.c_void_p, C.c_int, C.c_double],
     "fedd_schwarz_set_coarse": [C.c_void_p, C.c_double],
+    "fedd_schwarz_set_level_combination": [C.c_void_p, C.c_int],
+    "fedd_schwarz_get_level_combination": [C.c_void_p, _ip],
     "fedd_schwarz_coarse_sizes": [C.c_void_p, _i32p, _i64p],
     "fedd_schwarz_coarse_get": [C.c_void_p, _f64p],
     "fedd_schwarz_apply": [C.c_void_p, _f64p, _f64p],
@@ -496,6 +500,15 @@ class Context:
 
     def schwarz_set_coarse(self, cells_target):
         _chk(self._L.fedd_schwarz_set_coarse(self._h, float(cells_target)))
+
+    def schwarz_set_level_combination(self, combination):
+        """LEVELS_ADDITIVE (default) or LEVELS_MULTIPLICATIVE: z = (I - Pc A) M1^-1 r, read at apply time"""
+        _chk(self._L.fedd_schwarz_set_level_combination(self._h, int(combination)))
+
+    def schwarz_get_level_combination(self):
+        k = C.c_int()
+        _chk(self._L.fedd_schwarz_get_level_combination(self._h, C.byref(k)))
+        return k.value
 
     def schwarz_coarse_sizes(self):
         g = np.zeros(3, dtype=np.int32)

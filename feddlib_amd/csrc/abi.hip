@@ -664,6 +664,32 @@ extern "C" int fedd_schwarz_set_coarse(fedd_ctx* c, double cells_target) {
     return 0;
 }
 
+// FROSch "Level Combination" (parametersPrec.xml:19; the pre-apply of LinearSolver_def.hpp:98-104 is fedd_schwarz_coarse_apply,
+// the combination inside every apply of the solve is this setting)
+extern "C" int fedd_schwarz_set_level_combination(fedd_ctx* c, int combination) {
+    FEDD_CHECK(c, "null context");
+    FEDD_CHECK(combination == FEDD_LEVELS_ADDITIVE || combination == FEDD_LEVELS_MULTIPLICATIVE,
+               "fedd_schwarz_set_level_combination: %d (FEDD_LEVELS_ADDITIVE = %d, FEDD_LEVELS_MULTIPLICATIVE = %d)", combination,
+               FEDD_LEVELS_ADDITIVE, FEDD_LEVELS_MULTIPLICATIVE);
+    c->sw_levels = combination;
+    return 0;
+}
+
+extern "C" int fedd_schwarz_get_level_combination(fedd_ctx* c, int* combination) {
+    FEDD_CHECK(c && combination, "fedd_schwarz_get_level_combination: null context / pointer");
+    *combination = c->sw_levels;
+    return 0;
+}
+
+// the multiplicative combination is refused where it is not built, rather than run as the additive one
+static int levels_check(const fedd_ctx* c, const char* who) {
+    if (c->sw_levels != FEDD_LEVELS_MULTIPLICATIVE) return 0;
+    FEDD_CHECK(!c->merged, "%s: the multiplicative level combination is not built for merged block systems", who);
+    FEDD_CHECK(!c->sw_big_active, "%s: the multiplicative level combination is not built on the large-subdomain path (schwarz_big)", who);
+    FEDD_CHECK(c->have_coarse, "%s: the multiplicative level combination needs a coarse level (fedd_schwarz_setup with two_level = 1)", who);
+    return 0;
+}
+
 extern "C" int fedd_schwarz_coarse_sizes(fedd_ctx* c, int32_t cells[3], int64_t* n0) {
     FEDD_CHECK(c && c->have_coarse, "fedd_schwarz_coarse_sizes: no coarse level");
     if (cells)
@@ -693,6 +719,7 @@ extern "C" int fedd_schwarz_info(fedd_ctx* c, int64_t* n_sub, int64_t* max_size,
 extern "C" int fedd_schwarz_apply(fedd_ctx* c, const double* r_owned, double* z_owned) {
     NEED_DEVICE(c);
     FEDD_CHECK(c->have_schwarz && r_owned && z_owned, "fedd_schwarz_apply: no preconditioner / null pointer");
+    FEDD_TRY(levels_check(c, "fedd_schwarz_apply"));
     FEDD_HIP(hipSetDevice(c->device));
     FEDD_TRY(c->d_dtmp0.ensure((size_t)c->n_rows * 2));
     double* dr = c->d_dtmp0.p;
@@ -707,6 +734,7 @@ extern "C" int fedd_schwarz_apply(fedd_ctx* c, const double* r_owned, double* z_
 extern "C" int fedd_schwarz_apply_device(fedd_ctx* c, int reps) {
     NEED_DEVICE(c);
     FEDD_CHECK(c->have_schwarz, "fedd_schwarz_apply_device: no preconditioner");
+    FEDD_TRY(levels_check(c, "fedd_schwarz_apply_device"));
     FEDD_HIP(hipSetDevice(c->device));
     FEDD_TRY(c->d_dtmp0.ensure((size_t)c->n_rows * 2));
     double* dr = c->d_dtmp0.p;
@@ -722,6 +750,7 @@ extern "C" int fedd_gmres(fedd_ctx* c, const double* b_owned, double* x_owned, d
     FEDD_CHECK(c->have_pattern, "fedd_gmres: no matrix");
     FEDD_CHECK(!use_prec || c->have_schwarz, "fedd_gmres: preconditioner requested but fedd_schwarz_setup was not called");
     FEDD_CHECK(rtol > 0 && max_it >= 1 && restart >= 1 && restart <= 1000, "fedd_gmres: bad rtol/max_it/restart");
+    if (use_prec) FEDD_TRY(levels_check(c, "fedd_gmres"));
     FEDD_HIP(hipSetDevice(c->device));
     if (b_owned) FEDD_HIP(hipMemcpyAsync(c->d_rhs.p, b_owned, (size_t)c->n_rows * sizeof(double), hipMemcpyHostToDevice, c->stream));
     FEDD_TRY(gmres_solve(c, c->d_rhs.p, c->d_x.p, rtol, max_it, restart, use_prec, its_out, relres_out));
@@ -740,6 +769,7 @@ extern "C" int fedd_gmres_x0(fedd_ctx* c, const double* b_owned, double* x_owned
     FEDD_CHECK(c->have_pattern, "fedd_gmres_x0: no matrix");
     FEDD_CHECK(!use_prec || c->have_schwarz, "fedd_gmres_x0: preconditioner requested but fedd_schwarz_setup was not called");
     FEDD_CHECK(rtol > 0 && max_it >= 1 && restart >= 1 && restart <= 1000, "fedd_gmres_x0: bad rtol/max_it/restart");
+    if (use_prec) FEDD_TRY(levels_check(c, "fedd_gmres_x0"));
     FEDD_HIP(hipSetDevice(c->device));
     if (b_owned) FEDD_HIP(hipMemcpyAsync(c->d_rhs.p, b_owned, (size_t)c->n_rows * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (x_owned) FEDD_HIP(hipMemcpyAsync(c->d_x.p, x_owned, (size_t)c->n_rows * sizeof(double), hipMemcpyHostToDevice, c->stream));

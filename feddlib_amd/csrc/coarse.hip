@@ -1155,9 +1155,9 @@ __global__ void k_restrict_nodes(CoarseGeom cg, int dofs, int64_t n_lat, const d
     r0[t] = sum;
 }
 
-// y = K x for the dense n0 x n0 matrix, one wave per row
+// y = alpha K x for the dense n0 x n0 matrix, one wave per row (alpha = -1: the prolongation that adds subtracts; +-1 is exact)
 __global__ __launch_bounds__(256) void k_dense_mv(const double* __restrict__ K, int64_t ld, int64_t n0,
-                                                  const double* __restrict__ x, double* __restrict__ y) {
+                                                  const double* __restrict__ x, double* __restrict__ y, double alpha) {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= n0) return;
@@ -1174,7 +1174,7 @@ __global__ __launch_bounds__(256) void k_dense_mv(const double* __restrict__ K, 
     double v = (s0 + s1) + (s2 + s3);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0) y[row] = v;
+    if (lane == 0) y[row] = alpha * v;
 }
 
 template <int DIM>
@@ -1561,7 +1561,8 @@ static int gdsw_setup(fedd_ctx* c) {
     return 0;
 }
 
-static int gdsw_apply_add(fedd_ctx* c, const double* d_r_owned, double* d_z_owned) {
+// z += alpha Phi K0^-1 Phi^T r (alpha = +-1)
+static int gdsw_apply_add(fedd_ctx* c, const double* d_r_owned, double* d_z_owned, double alpha) {
     ScopedTimer timer(c, FEDD_T_COARSE_APPLY);
     const int64_t n0 = c->co_n0, ld = c->co_ld;
     FEDD_TRY(gdsw_restrict(c, d_r_owned, c->d_co_r0.p));
@@ -1571,7 +1572,7 @@ static int gdsw_apply_add(fedd_ctx* c, const double* d_r_owned, double* d_z_owne
         timer.resume();
     }
     hipLaunchKernelGGL(k_dense_mv, dim3((unsigned)((n0 + 3) / 4)), dim3(256), 0, c->stream, (const double*)c->d_co_K.p, ld, n0,
-                       (const double*)c->d_co_r0.p, c->d_co_z0.p);
+                       (const double*)c->d_co_r0.p, c->d_co_z0.p, alpha);
     FEDD_TRY(gdsw_prolong<true>(c, c->d_co_z0.p, d_z_owned));
     FEDD_HIP(hipGetLastError());
     return 0;
@@ -1708,8 +1709,9 @@ int coarse_setup(fedd_ctx* c) {
     return 0;
 }
 
-int coarse_apply_add(fedd_ctx* c, const double* d_r_owned, double* d_z_owned) {
-    if (c->co_kind == FEDD_COARSE_GDSW || c->co_kind == FEDD_COARSE_RGDSW) return gdsw_apply_add(c, d_r_owned, d_z_owned);
+// z += alpha Phi K0^-1 Phi^T r (alpha = +-1: the sign rides in the dense product, not in a pass over z)
+static int coarse_apply_alpha(fedd_ctx* c, const double* d_r_owned, double* d_z_owned, double alpha) {
+    if (c->co_kind == FEDD_COARSE_GDSW || c->co_kind == FEDD_COARSE_RGDSW) return gdsw_apply_add(c, d_r_owned, d_z_owned, alpha);
     ScopedTimer timer(c, FEDD_T_COARSE_APPLY);
     const int dim = c->dim, dofs = c->dofs;
     const CoarseGeom cg = c->co_geom;
@@ -1739,13 +1741,25 @@ int coarse_apply_add(fedd_ctx* c, const double* d_r_owned, double* d_z_owned) {
         timer.resume();   // dense_mv and prolongation belong to the same apply (one sampling decision)
     }
     hipLaunchKernelGGL(k_dense_mv, dim3((unsigned)((n0 + 3) / 4)), blk, 0, c->stream, (const double*)c->d_co_K.p, ld, n0,
-                       (const double*)c->d_co_r0.p, c->d_co_z0.p);
+                       (const double*)c->d_co_r0.p, c->d_co_z0.p, alpha);
 #define K_PROLONG(D, ...) hipLaunchKernelGGL(k_prolong_add<D>, dim3((unsigned)((c->n_rows + 255) / 256)), blk, 0, c->stream, __VA_ARGS__)
     COARSE_DIM(K_PROLONG, cg, dofs, c->n_rows, (const double*)c->d_xyz.p, (const double*)c->d_co_mask.p,
                (const double*)c->d_co_z0.p, d_z_owned);
 #undef K_PROLONG
     FEDD_HIP(hipGetLastError());
     return 0;
+}
+
+int coarse_apply_add(fedd_ctx* c, const double* d_r_owned, double* d_z_owned) { return coarse_apply_alpha(c, d_r_owned, d_z_owned, 1.0); }
+
+// The coarse half of the multiplicative combination (fedd_schwarz_set_level_combination): z = y1 - Pc (A y1) for the one-level
+// apply y1 in z.  w = A z with the halo import of z's ghost entries (into a copy: the caller's z need not have a tail), then the
+// restriction of w, K0^-1 with the sign, and the prolongation adds -Pc w into z.  The traffic of the additive apply's coarse
+// part plus one SpMV and, on several ranks, one copy of z.
+int coarse_apply_mult(fedd_ctx* c, double* d_z_owned) {
+    FEDD_TRY(c->d_co_w.ensure((size_t)std::max<int64_t>(c->n_rows, 1)));
+    FEDD_TRY(spmv_owned(c, d_z_owned, c->d_co_w.p));
+    return coarse_apply_alpha(c, c->d_co_w.p, d_z_owned, -1.0);
 }
 
 }  // namespace fedd

@@ -305,6 +305,7 @@ struct fedd_ctx {
 
     // ---- coarse level (two-level Schwarz) ----
     int sw_two_level = 0;
+    int sw_levels = FEDD_LEVELS_ADDITIVE;       // fedd_schwarz_set_level_combination, read at apply time
     double co_cells_target = 0.0;               // 0 = default
     fedd::CoarseGeom co_geom;
     int64_t co_ncell = 0, co_nlat = 0, co_n0 = 0, co_ld = 0;
@@ -316,6 +317,7 @@ struct fedd_ctx {
     fedd::DevBuf<double> d_co_K;                // [ld*ld] K0, then K0^-1
     fedd::DevBuf<double> d_dense_ws;            // dense_invert_batched: per matrix Dinv [64*64] | R [64*ld] | C [ld*64]
     fedd::DevBuf<double> d_co_part, d_co_r0, d_co_z0;
+    fedd::DevBuf<double> d_co_w;                // [n_rows] A z of the multiplicative combination
     bool have_coarse = false;
     int co_kind = FEDD_COARSE_Q1;               // FEDD_COARSE_Q1 (lattice hat functions) / FEDD_COARSE_GDSW
     double gdsw_tol = 0.0;                      // option "gdsw_tol": relative residual of the interior extension solves; 0 = GDSW 1e-4, RGDSW 1e-3
@@ -485,6 +487,10 @@ int dense_invert_batched(fedd_ctx* c, double* K, int64_t ld, int batch, int64_t 
 // coarse.hip
 int coarse_setup(fedd_ctx* c);
 int coarse_apply_add(fedd_ctx* c, const double* d_r_owned, double* d_z_owned);   // z += Phi K0^-1 Phi^T r
+// the multiplicative level combination is in force: asked for (sw_levels) and a coarse level built.  The GDSW extension solves
+// run before have_coarse is set, and so stay one-level
+inline bool levels_mult(const fedd_ctx* c) { return c->sw_levels == FEDD_LEVELS_MULTIPLICATIVE && c->have_coarse; }
+int coarse_apply_mult(fedd_ctx* c, double* d_z_owned);   // z -= Phi K0^-1 Phi^T (A z)
 
 // multi.hip: operator and one-level Schwarz preconditioner on sixteen stacked right-hand sides, X[row * MULTI_NR + j]
 constexpr int MULTI_NR = 16;

@@ -572,6 +572,27 @@ int allreduce_sum(fedd_ctx* c, double* d_buf, int n) {
     return 0;
 }
 
+// Multiplicative level combination (fedd_schwarz_set_level_combination): Phi^T A (I - Pc A) M1^-1 = (I - K0 K0^-1) Phi^T A M1^-1
+// vanishes up to the regularisation of K0^-1, so the Krylov space cannot reduce the part of the residual that Phi^T sees.  Every
+// cycle therefore starts from a coarse-orthogonal residual: x += Pc r, r = b - A x (in exact arithmetic r -= A Pc r), one coarse
+// apply and one SpMV.  K0^-1 inverts K0 + 1e-12 diag(K0), so one such step leaves 1e-12 of Phi^T r behind.  At a restart that is
+// far below the target; at the start, where r = b and ||b - A Pc b|| can be orders of magnitude below ||b||, it is not (3D
+// Laplace, 27-node boxes, Q1: 29 iterations to 1e-12 after one step, 14 after two), so the start takes two steps:
+// x_0 + Pc (b - A x_0), the reference's pre-apply for x_0 = 0, refined once.  At a restart the step removes what the shift let
+// grow during the cycle.
+static bool cycle_projection(const fedd_ctx* c, int use_prec) {
+    return use_prec && levels_mult(c) && !c->gm_mask && c->gm_nr <= 1;
+}
+static int coarse_project(fedd_ctx* c, const double* d_b, double* d_x, double* d_r, int use_compact, int steps) {
+    const int64_t n = c->n_rows;
+    for (int k = 0; k < steps; ++k) {
+        FEDD_TRY(coarse_apply_add(c, d_r, d_x));
+        FEDD_TRY(spmv_owned(c, d_x, d_r, false, nullptr, 0.0, use_compact));
+        hipLaunchKernelGGL(k_axpby, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, 1.0, d_b, -1.0, (const double*)d_r, d_r, n);
+    }
+    return 0;
+}
+
 // GMRES with the delayed second Gram-Schmidt pass (kernels and formulas above).  Same iterates as
 // the two-pass variant below in exact arithmetic; one operator application more per restart cycle
 // (the lag), half the passes over the basis and one all-reduce per iteration.
@@ -647,6 +668,8 @@ static int gmres_solve_dcgs2(fedd_ctx* c, const double* d_b, double* d_x, double
         FEDD_HIP(hipMemsetAsync(d_x, 0, (size_t)n * sizeof(double), st));  // "Zero Initial Guess" (LinearSolver_def.hpp:76-78)
         FEDD_HIP(hipMemcpyAsync(r, d_b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
+    const bool project = cycle_projection(c, use_prec);
+    if (project) FEDD_TRY(coarse_project(c, d_b, d_x, r, -1, 2));
     FEDD_TRY(norm2_into(r, S + o.nrm + 3));
     FEDD_HIP(hipMemcpyAsync(c->h_pinned, S + o.nrm + 3, sizeof(double), hipMemcpyDeviceToHost, st));
     FEDD_HIP(hipStreamSynchronize(st));
@@ -774,6 +797,7 @@ static int gmres_solve_dcgs2(fedd_ctx* c, const double* d_b, double* d_x, double
             FEDD_TRY(spmv_owned(c, d_x, r));
             if (mk) hipLaunchKernelGGL(k_mask_mix, gn, blk, 0, st, mk, (const double*)r, (const double*)d_x, r, n);
             hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, d_b, -1.0, (const double*)r, r, n);
+            if (project) FEDD_TRY(coarse_project(c, d_b, d_x, r, -1, 1));
             FEDD_TRY(norm2_into(r, S + o.nrm + 3));
             if (broke) {   // rare path: the host reads the true residual (every rank takes the same decision)
                 FEDD_HIP(hipMemcpyAsync(c->h_pinned, S + o.nrm + 3, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1652,6 +1676,8 @@ static int gmres_solve_sstep(fedd_ctx* c, const double* d_b, double* d_x, double
         FEDD_HIP(hipMemsetAsync(d_x, 0, (size_t)n * sizeof(double), st));  // "Zero Initial Guess" (LinearSolver_def.hpp:76-78)
         FEDD_HIP(hipMemcpyAsync(r, d_b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
+    const bool project = cycle_projection(c, use_prec);
+    if (project) FEDD_TRY(coarse_project(c, d_b, d_x, r, 0, 2));
     FEDD_TRY(norm2_into(r, Sx + o.nrm + 3));
     FEDD_HIP(hipMemcpyAsync(c->h_pinned, Sx + o.nrm + 3, sizeof(double), hipMemcpyDeviceToHost, st));
     FEDD_HIP(hipStreamSynchronize(st));
@@ -1748,7 +1774,16 @@ static int gmres_solve_sstep(fedd_ctx* c, const double* d_b, double* d_x, double
     c->gmres_blocks = 0;
     c->gmres_cut_blocks = 0;
     c->gmres_fused_blocks = 0;
+    bool first_cycle = true;
     while (!done && its < max_it) {
+        if (project && !first_cycle) {   // r = b - A x is the true residual here (trial): project it, x += Pc r, r = b - A x
+            double ta = 0.0;
+            FEDD_TRY(coarse_apply_add(c, r, d_x));
+            FEDD_TRY(trial(0, &ta));
+            last_true = ta;
+            relres = ta / beta0;
+        }
+        first_cycle = false;
         hipLaunchKernelGGL(k_ss_cycle_init, dim3(1), dim3(256), 0, st, Sx, o, o3, m, S, (const double*)(Sx + o.nrm + 3));
         hipLaunchKernelGGL(k_scale_to, gn, blk, 0, st, (const double*)r, (const double*)(Sx + o.misc + 1), V, n);
         int k = 1;                 // final basis vectors; k - 1 Hessenberg columns are final
@@ -2095,6 +2130,8 @@ int gmres_solve(fedd_ctx* c, const double* d_b, double* d_x, double rtol, int ma
         FEDD_HIP(hipMemsetAsync(d_x, 0, (size_t)n * sizeof(double), st));  // "Zero Initial Guess" (LinearSolver_def.hpp:76-78)
         FEDD_HIP(hipMemcpyAsync(r, d_b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
+    const bool project = cycle_projection(c, use_prec);
+    if (project) FEDD_TRY(coarse_project(c, d_b, d_x, r, -1, 2));
     FEDD_TRY(norm2_into(r, S + o.nrm + 3));
     FEDD_HIP(hipMemcpyAsync(c->h_pinned, S + o.nrm + 3, sizeof(double), hipMemcpyDeviceToHost, st));
     FEDD_HIP(hipStreamSynchronize(st));
@@ -2200,6 +2237,7 @@ int gmres_solve(fedd_ctx* c, const double* d_b, double* d_x, double rtol, int ma
         }
         if (!converged && its < max_it) {
             FEDD_TRY(residual());
+            if (project) FEDD_TRY(coarse_project(c, d_b, d_x, r, -1, 1));
             FEDD_TRY(norm2_into(r, S + o.nrm + 3));
         }
     }

@@ -2275,7 +2275,8 @@ int schwarz_apply(fedd_ctx* c, const double* d_r_owned, double* d_z_owned, bool 
                                (const double*)c->d_mult.p, c->n_rows);
         FEDD_HIP(hipMemcpyAsync(d_z_owned, z, (size_t)c->n_rows * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     }
-    if (c->have_coarse) FEDD_TRY(coarse_apply_add(c, d_r_owned, d_z_owned));
+    if (levels_mult(c)) FEDD_TRY(coarse_apply_mult(c, d_z_owned));    // z = (I - Pc A) M1^-1 r
+    else if (c->have_coarse) FEDD_TRY(coarse_apply_add(c, d_r_owned, d_z_owned));
     FEDD_HIP(hipGetLastError());
     return 0;
 }

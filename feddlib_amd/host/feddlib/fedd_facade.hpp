@@ -1150,6 +1150,11 @@ int LinearSolver<SC, LO, GO, NO>::solve(Problem_Type* problem, BlockMultiVectorP
             feddCheck(fedd_set_option(ctx, "gdsw_rotations", nodeLists && rotations ? 1.0 : 0.0), "fedd_set_option(gdsw_rotations)");
         }
         feddCheck(fedd_schwarz_setup(ctx, overlap, cmb, two ? 1 : 0, two ? coarseKind : 0), "fedd_schwarz_setup");
+        // "Level Combination" = "Multiplicative" (parametersPrec.xml:19): FROSch's TwoLevelPreconditioner combines the levels
+        // in every apply of the solve, z = (I - Pc A) M1^-1 r; the coarse pre-apply below supplies the Pc b term
+        const bool mult = two && std::string(frosch.get("Level Combination", "Additive")) == "Multiplicative";
+        feddCheck(fedd_schwarz_set_level_combination(ctx, mult ? FEDD_LEVELS_MULTIPLICATIVE : FEDD_LEVELS_ADDITIVE),
+                  "fedd_schwarz_set_level_combination");
     }
     auto b = rhs.is_null() ? problem->getRhs() : rhs;
     auto x = problem->getSolution();
@@ -1157,7 +1162,8 @@ int LinearSolver<SC, LO, GO, NO>::solve(Problem_Type* problem, BlockMultiVectorP
     double rel = 0.;
     // "Zero Initial Guess" (LinearSolver_def.hpp:76-78): true clears the solution vector, false keeps it as x_0.
     // "Level Combination" = "Multiplicative" (:98-104): one coarse-only application of the preconditioner to the right-hand
-    // side goes into the solution vector before the solve, which then starts from it
+    // side goes into the solution vector before the solve, which then starts from it (and runs the multiplicative
+    // preconditioner set up above)
     const bool zeroGuess = pl->get("Zero Initial Guess", true);
     if (zeroGuess) x->putScalar(0.);
     const bool multiplicative = usePrec && std::string(frosch.get("Level Combination", "Additive")) == "Multiplicative";

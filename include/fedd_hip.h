@@ -298,6 +298,20 @@ int fedd_schwarz_set_target(fedd_ctx* ctx, int target_nodes, double scale);
 /* number of lattice cells the coarse level aims at (0 = default: global nodes / 1000, clamped to
  * [1, 1728]); call before fedd_schwarz_setup */
 int fedd_schwarz_set_coarse(fedd_ctx* ctx, double cells_target);
+/* How the two levels combine (FROSch "Level Combination", parametersPrec.xml:19 of laplace, stokes, steadyLinElas, ...; the
+ * reference pre-applies the coarse level for "Multiplicative", LinearSolver_def.hpp:98-104, and FROSch's TwoLevelPreconditioner
+ * then combines the levels in every apply).  FEDD_LEVELS_ADDITIVE (the default): z = M1^-1 r + Pc r.  FEDD_LEVELS_MULTIPLICATIVE:
+ * y1 = M1^-1 r, z = y1 - Pc (A y1), i.e. z = (I - Pc A) M1^-1 r (the overlapping level first, then the coarse one; no + Pc r
+ * term), with Pc = Phi K0^-1 Phi^T.  This operator cannot reduce the part of a residual that Phi^T sees, so under it
+ * fedd_gmres and fedd_gmres_x0 start from x_0 + Pc (b - A x_0) (for x_0 = 0: the reference's pre-apply; the step is taken twice,
+ * as K0^-1 carries a 1e-12 diagonal shift) and project the true residual the same way at every restart.  A property of the
+ * context, read at apply time (no new fedd_schwarz_setup needed; it may be set before the setup, whose coarse-space solves stay
+ * one-level).  fedd_schwarz_apply and fedd_gmres* report an error
+ * when the multiplicative combination meets a setup without a coarse level, the large-subdomain path or a merged block system. */
+#define FEDD_LEVELS_ADDITIVE 0
+#define FEDD_LEVELS_MULTIPLICATIVE 1
+int fedd_schwarz_set_level_combination(fedd_ctx* ctx, int combination);
+int fedd_schwarz_get_level_combination(fedd_ctx* ctx, int* combination);
 /* coarse level read-back (parity): lattice cells per direction, coarse dofs n0, K0^-1 row-major */
 int fedd_schwarz_coarse_sizes(fedd_ctx* ctx, int32_t cells[3], int64_t* n0);
 int fedd_schwarz_coarse_get(fedd_ctx* ctx, double* k0_inverse);
@@ -325,7 +339,9 @@ int fedd_gmres(fedd_ctx* ctx, const double* b_owned, double* x_owned, double rto
 /* The same solve from a given initial guess: the reference's "Zero Initial Guess" = false (LinearSolver_def.hpp:76-78, where
  * the solution vector is only cleared when the key is true).  x_owned in: x_0, out: the solution; NULL: x_0 is the vector the
  * device holds (the last solution, or what fedd_schwarz_coarse_apply(ctx, NULL, NULL) left there) and the solution stays on
- * the device.  The relative residual refers to ||r_0|| = ||b - A x_0||, as Belos' default scaling does. */
+ * the device.  The relative residual refers to ||r_0|| = ||b - A x_0||, as Belos' default scaling does.  Under
+ * FEDD_LEVELS_MULTIPLICATIVE x_0 is first projected, x_0 + Pc (b - A x_0) twice, and r_0 is the residual of the projected guess
+ * (for a guess that fedd_schwarz_coarse_apply made, the projection changes nothing in exact arithmetic). */
 int fedd_gmres_x0(fedd_ctx* ctx, const double* b_owned, double* x_owned, double rtol, int max_it,
                   int restart, int use_prec, int* its_out, double* relres_out);
 /* The structures that depend on the mesh alone are built once per mesh, at the first call that needs them, and reused by every
@@ -342,8 +358,10 @@ int fedd_mesh_setup_info(fedd_ctx* ctx, double* adjacency_ms, double* tiles_ms, 
 int fedd_gmres_status(fedd_ctx* ctx, int* floor_reached, double* recurrence_relres);
 /* The second level alone, z = Phi K0^-1 Phi^T r: FROSch's "Only apply coarse", which the reference uses for
  * "Level Combination" = "Multiplicative" (LinearSolver_def.hpp:98-104: one coarse pre-apply of the right-hand side into the
- * solution vector, then the solve).  r_owned / z_owned both NULL: r = the assembled right-hand side, z -> the device's solution
- * vector (then fedd_gmres_x0(ctx, NULL, NULL, ...) continues from it).  Needs fedd_schwarz_setup(two_level = 1). */
+ * solution vector, then the solve).  That pre-apply is half of "Multiplicative": the other half is the preconditioner of the
+ * solve itself, fedd_schwarz_set_level_combination(FEDD_LEVELS_MULTIPLICATIVE).  r_owned / z_owned both NULL: r = the assembled
+ * right-hand side, z -> the device's solution vector (then fedd_gmres_x0(ctx, NULL, NULL, ...) continues from it).  Needs
+ * fedd_schwarz_setup(two_level = 1). */
 int fedd_schwarz_coarse_apply(fedd_ctx* ctx, const double* r_owned, double* z_owned);
 /* the orthogonalisation in use ("gmres_kind") and, for the s-step form, its block length and the blocks of the last solve
  * (all, and those that were cut short because the block basis became numerically dependent); outputs may be NULL */
