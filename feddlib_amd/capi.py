@@ -23,6 +23,7 @@ COARSE_GDSW = 2
 COARSE_RGDSW = 3
 LEVELS_ADDITIVE = 0         # FROSch "Level Combination" (fedd_schwarz_set_level_combination)
 LEVELS_MULTIPLICATIVE = 1
+ADV_N, ADV_W, ADV_NEWTON = range(3)     # fedd_assemble_advection
 
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
@@ -68,6 +69,8 @@ SIGNATURES = {
     "fedd_block_merge": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int],
     "fedd_matrix_sizes": [C.c_void_p, C.c_int, _i64p, _i64p, _i64p],
     "fedd_matrix_get": [C.c_void_p, C.c_int, _i64p, _i32p, _f64p],
+    "fedd_velocity_set": [C.c_void_p, _f64p],
+    "fedd_assemble_advection": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int],
     "fedd_csr_sizes": [C.c_void_p, _i64p, _i64p, _i64p],
     "fedd_csr_get": [C.c_void_p, _i64p, _i32p, _f64p, _i64p],
     "fedd_rhs_get": [C.c_void_p, _f64p],
@@ -439,6 +442,15 @@ class Context:
         _chk(self._L.fedd_matrix_get(self._h, slot, _p(rowptr, _i64p), _p(col, _i32p), _p(val, _f64p)))
         import scipy.sparse as sp
         return sp.csr_matrix((val, col, rowptr), shape=(a.value, b.value))
+
+    def velocity_set(self, u_rep):
+        """u_rep: [n_rep, dim] or flat dim * node + d, on the repeated map of mesh_set"""
+        u = np.ascontiguousarray(u_rep, dtype=np.float64).ravel()
+        _chk(self._L.fedd_velocity_set(self._h, _p(u, _f64p)))
+
+    def assemble_advection(self, kind, scale=1.0, slot_add=-1, slot_out=4):
+        """slot_out <- scale * (N | W | N + W)(u) + M[slot_add], FULL velocity pattern (fedd_assemble_advection)"""
+        _chk(self._L.fedd_assemble_advection(self._h, kind, float(scale), slot_add, slot_out))
 
     def csr_sizes(self):
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()

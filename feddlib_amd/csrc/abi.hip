@@ -158,6 +158,13 @@ extern "C" void fedd_ctx_destroy(fedd_ctx* c) {
         fedd::DevBuf<double>* cdb[] = {&c->d_co_mask, &c->d_co_cellK, &c->d_co_K, &c->d_dense_ws,
                                        &c->d_co_part, &c->d_co_r0, &c->d_co_z0};
         for (auto* b : cdb) b->release();
+        c->d_vel.release();
+        c->d_adv_nptr.release();
+        c->d_adv_ncol.release();
+        c->d_adv_soff.release();
+        c->d_adv_src.release();
+        c->d_adv_tab.release();
+        c->d_adv_ke.release();
         for (auto& m : c->aux) {
             m.rowptr.release();
             m.colind.release();
@@ -199,6 +206,11 @@ static int mesh_set_impl(fedd_ctx* c, int dim, int nen, int64_t n_elem, const in
     c->have_adj = c->have_pattern = c->have_schwarz = c->have_coarse = false;
     c->tl_state = 0;     // the assembly's tile structures belong to the old mesh
     c->p2_state = 0;     // ... and so do the gather lists of the P2 row sums
+    c->adv_state = 0;    // ... and the pattern and lists of the advection matrices; the velocity belonged to the old nodes
+    c->have_vel = false;
+    for (auto& id : c->adv_pattern_id) id = 0;
+    c->d_adv_ke.release();   // the element-block scratch is sized by the mesh (the largest buffer of the advection path)
+    ++c->mesh_id;
     c->halo.reset();
 
     // column-local numbering: owned nodes in unique-map order, then ghosts sorted by global id
@@ -253,6 +265,7 @@ static int mesh_set_impl(fedd_ctx* c, int dim, int nen, int64_t n_elem, const in
                (long long)(n_rg - ng_rows), (long long)n_rg);
     c->n_rowg = ng_rows;
     c->n_node = n_uni + ng;
+    c->h_col_of_rep = col_of_rep;
     c->h_node_gid.assign(gid_uni, gid_uni + n_uni);
     c->h_node_gid.insert(c->h_node_gid.end(), ghost_gid.begin(), ghost_gid.end());
 
@@ -412,6 +425,25 @@ extern "C" int fedd_block_merge(fedd_ctx* c, int slot_a, int slot_bt, int slot_b
     FEDD_TRY(block_merge(c, slot_a, slot_bt, slot_b, slot_c));
     c->have_pattern = true;
     return 0;
+}
+
+extern "C" int fedd_velocity_set(fedd_ctx* c, const double* u_rep) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(c->n_node > 0, "fedd_velocity_set: call fedd_mesh_set first");
+    FEDD_CHECK(u_rep, "fedd_velocity_set: null array");
+    FEDD_HIP(hipSetDevice(c->device));
+    return velocity_set(c, u_rep);
+}
+
+extern "C" int fedd_assemble_advection(fedd_ctx* c, int kind, double scale, int slot_add, int slot_out) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(kind == FEDD_ADV_N || kind == FEDD_ADV_W || kind == FEDD_ADV_NEWTON, "fedd_assemble_advection: unknown kind %d", kind);
+    CHECK_SLOT(slot_out);
+    FEDD_CHECK(slot_add < fedd::MAX_AUX, "matrix slot %d out of range", slot_add);
+    FEDD_CHECK(slot_add != slot_out, "fedd_assemble_advection: slot_add and slot_out must differ");
+    FEDD_CHECK(c->n_node > 0, "fedd_assemble_advection: call fedd_mesh_set first");
+    FEDD_HIP(hipSetDevice(c->device));
+    return assemble_advection(c, kind, scale, slot_add, slot_out);
 }
 
 extern "C" int fedd_matrix_sizes(fedd_ctx* c, int slot, int64_t* n_rows, int64_t* n_cols, int64_t* nnz) {

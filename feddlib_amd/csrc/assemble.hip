@@ -2374,12 +2374,350 @@ int assemble_div(fedd_ctx* c, int64_t n_p, int slot_b, int slot_bt) {
     else DIV_LAUNCH(3, 10);
 #undef DIV_LAUNCH
     B.valid = BT.valid = true;
+    B.pattern_id = ++c->pattern_counter;
+    BT.pattern_id = ++c->pattern_counter;
+    B.block_mode = BT.block_mode = -1;
     c->have_pattern = false;  // the system slot only holds the scratch node pattern now
     c->have_schwarz = false;
     return 0;
 }
 
 namespace {
+
+// ---------------------------------------------------------------------------------------------
+// Advection matrices of Navier-Stokes for a velocity u given at the nodes (d_vel, dim * node + d):
+//   N(u)  FE::assemblyAdvectionVecField     FE_def.hpp:1759-1832   n_ij = |det B| sum_q w_q (u_h . grad phi_j) phi_i, on the dim
+//                                                                   diagonal component pairs (dim * i + d, dim * j + d)
+//   W(u)  FE::assemblyAdvectionInUVecField  FE_def.hpp:1839-1925   (dim * i + d1, dim * j + d2) = |det B| sum_q w_q (d u_d1 / d x_d2) phi_i phi_j
+// Element-major like the P2 scalar forms, ONE ELEMENT PER WAVEFRONT: the reference tables of both rules are staged in LDS once per
+// workgroup; a wave loads its element's vertices and its NEN x dim velocity values once, its lanes evaluate u_h (as the weighted
+// reference-space vector w_q B^-1 u_h) and w_q grad u_h at the quadrature points into LDS, and then take the NEN^2 node pairs:
+// n_ij and the dim x dim block of W are summed in registers and leave as one contiguous stream, [i][j][dim x dim] (N alone:
+// [i][j]).  ADV_NEWTON adds n_ij to the diagonal of the block, so N + W costs one pass over the geometry and u.
+// The rows are then summed by gather lists (k_p2_lists on the node-level pattern, built once per mesh): a wave per node, a lane
+// per node-level nonzero, the element blocks added in adjacency order -- no atomics, bitwise reproducible -- and written as
+// scale * block + M[slot_add] into the FULL pattern, whose positions follow from the node-level pattern in closed form.
+// ---------------------------------------------------------------------------------------------
+struct AdvArgs {
+    const int32_t* conn;
+    const double* xyz;
+    const double* u;
+    const double* tab;      // w | phi | dphi of the rule of N; the same of the rule of W at off_w (0: one rule for both)
+    int nq_n, nq_w, off_w;
+    double zero_eps;        // setZeros_ / myeps_ (FE_def.hpp:1816, 1908): element values of N and of W below it are set to zero
+};
+
+template <int DIM, int NEN, int KIND>
+__global__ __launch_bounds__(256) void k_adv_elem(AdvArgs a, int64_t n_elem, double* __restrict__ ke) {
+    constexpr int BLK = KIND == FEDD_ADV_N ? 1 : DIM * DIM;
+    extern __shared__ double sm[];
+    const int nqn = a.nq_n, nqw = a.nq_w;
+    const int ntab = a.off_w + nqw * (1 + NEN + NEN * DIM);
+    const double* wn = sm;
+    const double* phin = wn + nqn;
+    const double* dphin = phin + nqn * NEN;
+    const double* ww = sm + a.off_w;
+    const double* phiw = ww + nqw;
+    const double* dphiw = phiw + nqw * NEN;
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int per_wave = NEN * DIM + nqn * DIM + nqw * DIM * DIM;
+    double* Us = sm + ntab + (size_t)w * per_wave;      // this wave's velocity values [i][d]
+    double* beta = Us + NEN * DIM;                      // w_q B^-1 u_h(x_q) [q][r]
+    double* wG = beta + nqn * DIM;                      // w_q (d u_d1 / d x_d2)(x_q) [q][d1][d2]
+    for (int i = tid; i < ntab; i += 256) sm[i] = a.tab[i];
+    const int64_t nwave = (int64_t)gridDim.x * 4;
+    const int64_t trips = (n_elem + nwave - 1) / nwave;
+    for (int64_t k = 0; k < trips; ++k) {
+        const int64_t e = k * nwave + (int64_t)blockIdx.x * 4 + w;
+        const bool on = e < n_elem;
+        double xv = 0.0;
+        if (on && lane < (DIM + 1) * DIM) xv = a.xyz[(int64_t)a.conn[e * NEN + lane / DIM] * DIM + (lane % DIM)];
+        if (on && lane < NEN * DIM) Us[lane] = a.u[(int64_t)a.conn[e * NEN + lane / DIM] * DIM + (lane % DIM)];
+        double X[DIM + 1][DIM];
+#pragma unroll
+        for (int v = 0; v <= DIM; ++v)
+#pragma unroll
+            for (int d = 0; d < DIM; ++d) X[v][d] = __shfl(xv, v * DIM + d, 64);
+        double Binv[DIM][DIM];
+        const double absdet = on ? fabs(affine<DIM>(X, Binv)) : 0.0;
+        __syncthreads();        // tables (first trip) and Us
+        if (on) {
+            if constexpr (KIND != FEDD_ADV_W) {
+                for (int q = lane; q < nqn; q += 64) {
+                    double uq[DIM];
+#pragma unroll
+                    for (int d = 0; d < DIM; ++d) uq[d] = 0.0;
+                    for (int i = 0; i < NEN; ++i)
+#pragma unroll
+                        for (int d = 0; d < DIM; ++d) uq[d] += Us[i * DIM + d] * phin[q * NEN + i];
+#pragma unroll
+                    for (int r = 0; r < DIM; ++r) {
+                        double s = 0.0;
+#pragma unroll
+                        for (int d = 0; d < DIM; ++d) s += Binv[r][d] * uq[d];
+                        beta[q * DIM + r] = wn[q] * s;
+                    }
+                }
+            }
+            if constexpr (KIND != FEDD_ADV_N) {
+                for (int t = lane; t < nqw * DIM; t += 64) {
+                    const int q = t / DIM, d1 = t - q * DIM;
+                    double gr[DIM];
+#pragma unroll
+                    for (int r = 0; r < DIM; ++r) gr[r] = 0.0;
+                    for (int i = 0; i < NEN; ++i)
+#pragma unroll
+                        for (int r = 0; r < DIM; ++r) gr[r] += Us[i * DIM + d1] * dphiw[(q * NEN + i) * DIM + r];
+#pragma unroll
+                    for (int d2 = 0; d2 < DIM; ++d2) {
+                        double s = 0.0;
+#pragma unroll
+                        for (int r = 0; r < DIM; ++r) s += gr[r] * Binv[r][d2];
+                        wG[t * DIM + d2] = ww[q] * s;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        if (on) {
+            double* __restrict__ out = ke + e * (NEN * NEN * BLK);
+            for (int t = lane; t < NEN * NEN; t += 64) {
+                const int i = t / NEN, j = t - i * NEN;
+                double n = 0.0;
+                if constexpr (KIND != FEDD_ADV_W) {
+                    for (int q = 0; q < nqn; ++q) {
+                        const double* dp = dphin + (q * NEN + j) * DIM;
+                        double cq = 0.0;
+#pragma unroll
+                        for (int r = 0; r < DIM; ++r) cq += dp[r] * beta[q * DIM + r];
+                        n += cq * phin[q * NEN + i];
+                    }
+                    n *= absdet;
+                    n = (a.zero_eps > 0.0 && fabs(n) < a.zero_eps) ? 0.0 : n;
+                }
+                if constexpr (KIND == FEDD_ADV_N) {
+                    out[t] = n;
+                } else {
+                    double blk[BLK];
+#pragma unroll
+                    for (int m = 0; m < BLK; ++m) blk[m] = 0.0;
+                    for (int q = 0; q < nqw; ++q) {
+                        const double pp = phiw[q * NEN + i] * phiw[q * NEN + j];
+#pragma unroll
+                        for (int m = 0; m < BLK; ++m) blk[m] += pp * wG[q * BLK + m];
+                    }
+#pragma unroll
+                    for (int m = 0; m < BLK; ++m) {
+                        double v = blk[m] * absdet;
+                        v = (a.zero_eps > 0.0 && fabs(v) < a.zero_eps) ? 0.0 : v;
+                        if (KIND == FEDD_ADV_NEWTON && m / DIM == m % DIM) v += n;
+                        out[t * BLK + m] = v;
+                    }
+                }
+            }
+        }
+        __syncthreads();        // Us, beta, wG are rewritten by the next trip
+    }
+}
+
+// rows of the FULL pattern from the element blocks: val = scale * sum + M[slot_add] (add_full: M has the FULL pattern, else DIAG)
+template <int DIM, int NEN, int BLK>
+__global__ __launch_bounds__(256) void k_adv_gather(const int32_t* __restrict__ n2e_ptr, const int32_t* __restrict__ n2e,
+                                                    const int32_t* __restrict__ nptr, int32_t nn, const uint16_t* __restrict__ soff,
+                                                    const uint16_t* __restrict__ src, const double* __restrict__ ke, double scale,
+                                                    const double* __restrict__ addval, int add_full, double* __restrict__ val) {
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int64_t p = (int64_t)blockIdx.x * 4 + w; p < nn; p += (int64_t)gridDim.x * 4) {
+        const int32_t ab = n2e_ptr[p], deg = n2e_ptr[p + 1] - ab;
+        const int32_t nb = nptr[p], nslot = nptr[p + 1] - nb;
+        const uint16_t* __restrict__ sp = src + (int64_t)ab * NEN;
+        const int total = deg * NEN;
+        for (int sl = lane; sl < nslot; sl += 64) {
+            const int b = soff[nb + sl], e2 = sl + 1 < nslot ? (int)soff[nb + sl + 1] : total;
+            double acc[BLK];
+#pragma unroll
+            for (int m = 0; m < BLK; ++m) acc[m] = 0.0;
+            for (int k = b; k < e2; ++k) {
+                const uint32_t sr = sp[k];
+                const double* __restrict__ kb = ke + ((int64_t)n2e[ab + (sr >> 4)] * NEN + (sr & 15u)) * BLK;
+#pragma unroll
+                for (int m = 0; m < BLK; ++m) acc[m] += kb[m];
+            }
+#pragma unroll
+            for (int r = 0; r < DIM; ++r) {
+                const int64_t rs = (int64_t)nb * DIM * DIM + (int64_t)r * nslot * DIM + (int64_t)sl * DIM;
+#pragma unroll
+                for (int cc = 0; cc < DIM; ++cc) {
+                    double v = scale * (BLK == 1 ? (r == cc ? acc[0] : 0.0) : acc[(r * DIM + cc) % BLK]);
+                    if (addval) {
+                        if (add_full) v += addval[rs + cc];
+                        else if (r == cc) v += addval[(int64_t)nb * DIM + (int64_t)r * nslot + sl];
+                    }
+                    val[rs + cc] = v;
+                }
+            }
+        }
+    }
+}
+
+// the per-mesh structures: node-level pattern, gather lists, quadrature tables (determineDegree, FE_def.hpp:1770-1772, 1859-1861:
+// P2 5 / 5; P1 2 / 3, remapped by fe_quadrature)
+template <int NEN>
+int adv_setup(fedd_ctx* c) {
+    const int dim = c->dim, nen = c->nen;
+    const int64_t nn = c->n_own;
+    {
+        ScopedTimer t(c, FEDD_T_SYMBOLIC);
+        int32_t mx = 0;
+        FEDD_TRY(build_node_pattern(c, c->d_adv_nptr, c->d_adv_ncol, &mx, &c->adv_node_nnz));
+        c->adv_max_nn = mx;
+        FEDD_CHECK(c->adv_node_nnz * dim * dim < ((int64_t)1 << 31), "advection: %lld nonzeros exceed 32-bit local offsets",
+                   (long long)(c->adv_node_nnz * dim * dim));
+        int32_t n2e_total = 0;
+        FEDD_HIP(hipMemcpyAsync(&n2e_total, c->d_n2e_ptr.p + nn, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        FEDD_HIP(hipStreamSynchronize(c->stream));
+        FEDD_TRY(c->d_adv_soff.ensure((size_t)c->adv_node_nnz + 2));
+        FEDD_TRY(c->d_adv_src.ensure((size_t)n2e_total * NEN + 2));
+        FEDD_TRY(c->d_flags.ensure(16));
+        int32_t* bad = c->d_flags.p + 6;
+        FEDD_HIP(hipMemsetAsync(bad, 0, sizeof(int32_t), c->stream));
+        const int nwg = (int)std::min<int64_t>((nn + 3) / 4, 256 * 32);
+        hipLaunchKernelGGL(k_p2_lists<NEN>, dim3((unsigned)nwg), dim3(256), 0, c->stream, (const int32_t*)c->d_conn.p,
+                           (const int32_t*)c->d_n2e_ptr.p, (const int32_t*)c->d_n2e.p, (const int32_t*)c->d_adv_nptr.p,
+                           (const int32_t*)c->d_adv_ncol.p, 1, 0, (int32_t)nn, c->d_adv_soff.p, c->d_adv_src.p, bad);
+        int32_t h_bad = 0;
+        FEDD_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        FEDD_HIP(hipStreamSynchronize(c->stream));
+        FEDD_HIP(hipGetLastError());
+        FEDD_CHECK(!h_bad, "advection: a node with more than 4095 incident elements does not fit the gather lists");
+    }
+    const bool p2 = nen > dim + 1;
+    const int deg_n = p2 ? 5 : 2, deg_w = p2 ? 5 : 3;
+    FeTables tn, tw;
+    FEDD_TRY(fe_tables(dim, nen, deg_n, tn));
+    FEDD_TRY(fe_tables(dim, nen, deg_w, tw));
+    const bool same = tn.nq == tw.nq && tn.w == tw.w && tn.phi == tw.phi;
+    std::vector<double> host;
+    auto put = [&](const FeTables& t) {
+        host.insert(host.end(), t.w.begin(), t.w.end());
+        host.insert(host.end(), t.phi.begin(), t.phi.end());
+        host.insert(host.end(), t.dphi.begin(), t.dphi.end());
+    };
+    put(tn);
+    c->adv_tab_off_w = same ? 0 : (int)host.size();
+    if (!same) put(tw);
+    c->adv_nq[0] = tn.nq;
+    c->adv_nq[1] = tw.nq;
+    FEDD_TRY(c->d_adv_tab.ensure(host.size()));
+    FEDD_HIP(hipMemcpyAsync(c->d_adv_tab.p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    FEDD_HIP(hipStreamSynchronize(c->stream));  // `host` is a local
+    c->adv_state = 1;
+    return 0;
+}
+
+template <int DIM, int NEN, int KIND>
+int launch_advection(fedd_ctx* c, double scale, const DevCsr* add, DevCsr& out) {
+    constexpr int BLK = KIND == FEDD_ADV_N ? 1 : DIM * DIM;
+    FEDD_TRY(c->d_adv_ke.ensure((size_t)c->n_elem * NEN * NEN * BLK));
+    AdvArgs a;
+    a.conn = c->d_conn.p; a.xyz = c->d_xyz.p; a.u = c->d_vel.p; a.tab = c->d_adv_tab.p;
+    a.nq_n = c->adv_nq[0]; a.nq_w = c->adv_nq[1]; a.off_w = c->adv_tab_off_w;
+    a.zero_eps = c->asm_zero_eps;
+    const int ntab = a.off_w + a.nq_w * (1 + NEN + NEN * DIM);
+    const int per_wave = NEN * DIM + a.nq_n * DIM + a.nq_w * DIM * DIM;
+    const size_t lds = ((size_t)ntab + 4 * (size_t)per_wave) * sizeof(double);
+    FEDD_CHECK(lds <= 64 * 1024, "advection: the quadrature tables do not fit the LDS");
+    const int64_t nn = c->n_own;
+    ScopedTimer t(c, FEDD_T_ASSEMBLE);
+    if (c->n_elem > 0) {
+        const int64_t nwg = std::min<int64_t>((c->n_elem + 3) / 4, 256 * 8);
+        hipLaunchKernelGGL((k_adv_elem<DIM, NEN, KIND>), dim3((unsigned)nwg), dim3(256), lds, c->stream, a, c->n_elem, c->d_adv_ke.p);
+    }
+    const int nwg2 = (int)std::min<int64_t>((nn + 3) / 4, 256 * 32);
+    const int add_full = add && add->block_mode == FEDD_BLOCK_FULL ? 1 : 0;
+    hipLaunchKernelGGL((k_adv_gather<DIM, NEN, BLK>), dim3((unsigned)nwg2), dim3(256), 0, c->stream, (const int32_t*)c->d_n2e_ptr.p,
+                       (const int32_t*)c->d_n2e.p, (const int32_t*)c->d_adv_nptr.p, (int32_t)nn, (const uint16_t*)c->d_adv_soff.p,
+                       (const uint16_t*)c->d_adv_src.p, (const double*)c->d_adv_ke.p, scale, add ? (const double*)add->val.p : nullptr,
+                       add_full, out.val.p);
+    // byte model: geometry, u and connectivity once per element, the element blocks written and read once, the FULL values written
+    t.bytes(((double)c->n_elem * (NEN * 4.0 + 2.0 * NEN * NEN * BLK * 8.0) + (double)c->n_node * DIM * 16.0 +
+             (double)c->adv_node_nnz * (DIM * DIM * 8.0 + (add ? (add_full ? DIM * DIM : DIM) * 8.0 : 0.0))));
+    t.stop();
+    FEDD_HIP(hipGetLastError());
+    return 0;
+}
+
+template <int DIM, int NEN>
+int advection_kind(fedd_ctx* c, int kind, double scale, const DevCsr* add, DevCsr& out) {
+    if (kind == FEDD_ADV_N) return launch_advection<DIM, NEN, FEDD_ADV_N>(c, scale, add, out);
+    if (kind == FEDD_ADV_W) return launch_advection<DIM, NEN, FEDD_ADV_W>(c, scale, add, out);
+    return launch_advection<DIM, NEN, FEDD_ADV_NEWTON>(c, scale, add, out);
+}
+
+}  // namespace
+
+// what NavierStokes::u_rep_ holds (NavierStokes_def.hpp:282-321), brought to the column-local numbering of the mesh
+int velocity_set(fedd_ctx* c, const double* u_rep) {
+    FEDD_CHECK(c->nranks == 1, "fedd_velocity_set: one rank only for now");
+    const int dim = c->dim;
+    const size_t n_rep = c->h_col_of_rep.size();
+    std::vector<double> u((size_t)c->n_node * dim, 0.0);
+    for (size_t i = 0; i < n_rep; ++i)
+        for (int d = 0; d < dim; ++d) u[(size_t)c->h_col_of_rep[i] * dim + d] = u_rep[i * dim + d];
+    FEDD_TRY(c->d_vel.ensure(u.size()));
+    FEDD_HIP(hipMemcpyAsync(c->d_vel.p, u.data(), u.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    FEDD_HIP(hipStreamSynchronize(c->stream));  // `u` is a local
+    c->have_vel = true;
+    return 0;
+}
+
+// aux[slot_out] <- scale * (N | W | N + W)(u) + aux[slot_add]: NavierStokes::reAssemble (NavierStokes_def.hpp:282-321) in one pass
+int assemble_advection(fedd_ctx* c, int kind, double scale, int slot_add, int slot_out) {
+    FEDD_CHECK(c->nranks == 1, "fedd_assemble_advection: one rank only for now");
+    FEDD_CHECK(c->have_vel, "fedd_assemble_advection: call fedd_velocity_set first");
+    const int dim = c->dim, nen = c->nen;
+    if (!c->have_adj) {
+        ScopedTimer t(c, FEDD_T_SYMBOLIC);
+        FEDD_TRY(build_adjacency(c));
+    }
+    if (c->adv_state == 0) {
+        if (nen == 3) FEDD_TRY(adv_setup<3>(c));
+        else if (nen == 4) FEDD_TRY(adv_setup<4>(c));
+        else if (nen == 6) FEDD_TRY(adv_setup<6>(c));
+        else FEDD_TRY(adv_setup<10>(c));
+    }
+    const int64_t n_rows = c->n_own * dim, nnz = c->adv_node_nnz * dim * dim;
+    const DevCsr* add = slot_add >= 0 ? &c->aux[slot_add] : nullptr;
+    if (add) {
+        FEDD_CHECK(add->valid, "fedd_assemble_advection: slot %d is empty", slot_add);
+        // stored from a fedd_pattern_build pattern of THIS mesh (or written here): its entries then sit where the closed form says
+        const bool tagged = add->mesh_id == c->mesh_id && add->dofs == dim &&
+                            (add->block_mode == FEDD_BLOCK_DIAG || add->block_mode == FEDD_BLOCK_FULL);
+        const int64_t want = add->block_mode == FEDD_BLOCK_FULL ? nnz : c->adv_node_nnz * dim;
+        FEDD_CHECK(tagged && add->n_rows == n_rows && add->n_cols == c->n_node * dim && add->nnz == want,
+                   "fedd_assemble_advection: slot %d does not hold a DIAG or FULL velocity matrix of this mesh", slot_add);
+    }
+    DevCsr& out = c->aux[slot_out];
+    if (!(out.valid && out.pattern_id != 0 && out.pattern_id == c->adv_pattern_id[slot_out])) {
+        FEDD_TRY(out.rowptr.ensure((size_t)n_rows + 1));
+        FEDD_TRY(out.colind.ensure((size_t)nnz));
+        FEDD_TRY(out.val.ensure((size_t)nnz));
+        FEDD_TRY(expand_node_pattern(c, c->d_adv_nptr.p, c->d_adv_ncol.p, dim, 1, out.rowptr.p, out.colind.p));
+        out.n_rows = n_rows;
+        out.n_cols = c->n_node * dim;
+        out.nnz = nnz;
+        out.max_row_nnz = c->adv_max_nn * dim;
+        out.pattern_id = c->adv_pattern_id[slot_out] = ++c->pattern_counter;
+    }
+    out.dofs = dim;
+    out.block_mode = FEDD_BLOCK_FULL;
+    out.mesh_id = c->mesh_id;
+    if (dim == 2 && nen == 3) FEDD_TRY((advection_kind<2, 3>(c, kind, scale, add, out)));
+    else if (dim == 2 && nen == 6) FEDD_TRY((advection_kind<2, 6>(c, kind, scale, add, out)));
+    else if (dim == 3 && nen == 4) FEDD_TRY((advection_kind<3, 4>(c, kind, scale, add, out)));
+    else FEDD_TRY((advection_kind<3, 10>(c, kind, scale, add, out)));
+    out.valid = true;
+    return 0;
 }
 
 int assemble_matrix(fedd_ctx* c, int form, const double* params) {

@@ -61,6 +61,21 @@ __global__ void k_merge_fill(CsrView A, CsrView BT, CsrView B, CsrView C, int32_
         }
 }
 
+// the same rows with the pattern already in place: values only
+__global__ void k_merge_values(CsrView A, CsrView BT, CsrView B, CsrView C, int32_t nA, int32_t nB,
+                               const int32_t* __restrict__ rowptr, double* __restrict__ val) {
+    const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nA + nB) return;
+    int32_t p = rowptr[r];
+    const CsrView& L = r < nA ? A : B;
+    const CsrView& R = r < nA ? BT : C;
+    const int32_t i = r < nA ? r : r - nA;
+    if (L.rowptr)
+        for (int32_t q = L.rowptr[i]; q < L.rowptr[i + 1]; ++q, ++p) val[p] = L.val[q];
+    if (R.rowptr)
+        for (int32_t q = R.rowptr[i]; q < R.rowptr[i + 1]; ++q, ++p) val[p] = R.val[q];
+}
+
 __global__ void k_dof_node(int32_t nA, int32_t nB, int dofsA, int32_t* __restrict__ dof_node) {
     const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= nA + nB) return;
@@ -92,6 +107,10 @@ int matrix_store(fedd_ctx* c, int slot) {
     m.nnz = c->nnz;
     m.max_row_nnz = c->max_row_nnz;
     m.valid = true;
+    m.pattern_id = ++c->pattern_counter;
+    m.dofs = c->dofs;
+    m.block_mode = c->merged ? -1 : c->block_mode;
+    m.mesh_id = c->mesh_id;
     return 0;
 }
 
@@ -122,9 +141,29 @@ int block_merge(fedd_ctx* c, int slot_a, int slot_bt, int slot_b, int slot_c) {
     const int64_t n = nA + nB;
     FEDD_CHECK(n < ((int64_t)1 << 31), "block merge: too many rows");
     const int dofsA = (int)(nA / std::max<int64_t>(1, c->n_own));
-    FEDD_TRY(c->d_rowptr.ensure((size_t)n + 1));
     const CsrView vA = view(A), vBT = view(BT), vB = view(B), vC = view(C);
     const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
+    // The blocks of a nonlinear iteration change their values, not their patterns: when the system matrix still is the merge of
+    // these slots and none of their patterns has been rewritten since, the merged pattern stands and only values move.
+    const int slots[4] = {slot_a, slot_bt, slot_b, slot_c};
+    const DevCsr* blocks[4] = {A, BT, B, C};
+    bool same = c->merged && c->n_rows == n;
+    for (int k = 0; k < 4; ++k) {
+        const uint64_t id = blocks[k] && blocks[k]->valid ? blocks[k]->pattern_id : 0;
+        same = same && c->merge_slots[k] == slots[k] && c->merge_ids[k] == id && (id != 0 || !(blocks[k] && blocks[k]->valid));
+    }
+    if (same) {
+        hipLaunchKernelGGL(k_merge_values, grid, blk, 0, c->stream, vA, vBT, vB, vC, (int32_t)nA, (int32_t)nB,
+                           (const int32_t*)c->d_rowptr.p, c->d_val.p);
+        FEDD_HIP(hipMemsetAsync(c->d_rhs.p, 0, (size_t)n * sizeof(double), c->stream));
+        FEDD_HIP(hipMemsetAsync(c->d_x.p, 0, (size_t)n * sizeof(double), c->stream));
+        FEDD_HIP(hipMemsetAsync(c->d_isdir.p, 0, (size_t)n * sizeof(int32_t), c->stream));
+        FEDD_HIP(hipGetLastError());
+        c->have_schwarz = false;
+        return 0;
+    }
+    c->merged = false;      // until this merge has completed, the system matrix is not the merge of anything
+    FEDD_TRY(c->d_rowptr.ensure((size_t)n + 1));
     hipLaunchKernelGGL(k_merge_count, grid, blk, 0, c->stream, vA, vBT, vB, vC, (int32_t)nA, (int32_t)nB, c->d_rowptr.p);
     int32_t mx = 0;
     FEDD_TRY(reduce_max_i32(c, c->d_rowptr.p, n, &mx));
@@ -142,7 +181,6 @@ int block_merge(fedd_ctx* c, int slot_a, int slot_bt, int slot_b, int slot_c) {
     c->nnz = nnz;
     c->nnz_ext = nnz;
     c->max_row_nnz = mx;
-    c->merged = true;
     c->merged_nA = nA;
     c->merged_dofsA = dofsA;
     c->dofs = 1;
@@ -157,6 +195,12 @@ int block_merge(fedd_ctx* c, int slot_a, int slot_bt, int slot_b, int slot_c) {
     FEDD_HIP(hipGetLastError());
     c->have_schwarz = false;
     c->spmv_rows_ready = false;
+    // recorded last: a merge that failed on the way leaves merged = false, and the next one builds the pattern again
+    c->merged = true;
+    for (int k = 0; k < 4; ++k) {
+        c->merge_slots[k] = slots[k];
+        c->merge_ids[k] = blocks[k] && blocks[k]->valid ? blocks[k]->pattern_id : 0;
+    }
     return 0;
 }
 

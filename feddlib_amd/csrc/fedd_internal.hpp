@@ -103,8 +103,11 @@ struct DevCsr {
     int64_t n_rows = 0, n_cols = 0, nnz = 0;
     int max_row_nnz = 0;
     bool valid = false;
+    int dofs = 0, block_mode = -1;  // velocity-space matrices (fedd_matrix_store of a fedd_pattern_build pattern, fedd_assemble_advection): dofs per node and
+    uint64_t mesh_id = 0;           // FEDD_BLOCK_* of the pattern, and the fedd_ctx::mesh_id it was built on; block_mode -1 = another origin
+    uint64_t pattern_id = 0;    // drawn from fedd_ctx::pattern_counter whenever rowptr / colind are rewritten: equal ids = same pattern
 };
-constexpr int MAX_AUX = 4;
+constexpr int MAX_AUX = 5;      // A, B, B^T, C and the linearised velocity block F = A + rho (N | N + W) of Navier-Stokes
 
 // regular lattice of the coarse level: g cells and np = g + 1 points per direction (1 point in
 // directions beyond dim), over the global bounding box [lo, lo + L]
@@ -238,7 +241,25 @@ struct fedd_ctx {
     fedd::DevBuf<double> d_cs_clsval;           // [classes][8] values of a class
     fedd::DevBuf<int32_t> d_cs_clsi;            // slot of row [n] | table min row | class of slot | counters
     fedd::DevBuf<uint64_t> d_cs_clskey;         // table keys
-    fedd::DevCsr aux[fedd::MAX_AUX];            // stored blocks (A, B, B^T, C) of a mixed problem
+    fedd::DevCsr aux[fedd::MAX_AUX];            // stored blocks (A, B, B^T, C, F) of a mixed problem
+    uint64_t pattern_counter = 0;               // source of DevCsr::pattern_id
+    uint64_t mesh_id = 0;                       // counts the fedd_mesh_set calls: which mesh a stored pattern belongs to
+    int merge_slots[4] = {-2, -2, -2, -2};      // the slots and pattern ids the merged system matrix was built from: a merge of the
+    uint64_t merge_ids[4] = {0, 0, 0, 0};       // same patterns moves values only (blocks.hip)
+
+    // ---- advection matrices N(u), W(u) of Navier-Stokes (assemble.hip assemble_advection; one rank) ----
+    std::vector<int32_t> h_col_of_rep;          // [n_rep] column-local node id of every repeated node (fedd_mesh_set)
+    fedd::DevBuf<double> d_vel;                 // [n_node * dim] velocity at the nodes, column-local numbering (fedd_velocity_set)
+    bool have_vel = false;
+    int adv_state = 0;                          // per-mesh structures below: 0 = not built, 1 = ready
+    int64_t adv_node_nnz = 0;                   // nonzeros of the node-level pattern
+    int adv_max_nn = 0;                         // its longest row
+    fedd::DevBuf<int32_t> d_adv_nptr, d_adv_ncol;   // node-level pattern [n_own + 1], [adv_node_nnz]: the FULL dof pattern follows in closed form
+    fedd::DevBuf<uint16_t> d_adv_soff, d_adv_src;   // gather lists of the node-level nonzeros (k_p2_lists)
+    fedd::DevBuf<double> d_adv_tab;             // quadrature tables of N, then of W where its rule differs (w | phi | dphi each)
+    int adv_nq[2] = {0, 0}, adv_tab_off_w = 0;
+    fedd::DevBuf<double> d_adv_ke;              // [n_elem][nen][nen][1 | dim * dim] element blocks of the assembly in progress
+    uint64_t adv_pattern_id[fedd::MAX_AUX] = {0, 0, 0, 0, 0};   // pattern id of the slots that hold the FULL pattern written here
     bool merged = false;                        // system matrix = merged blocks (dof -> node map below)
     int64_t merged_nA = 0;                      // rows of block row 0
     int merged_dofsA = 1;                       // dofs per node of block row 0
@@ -435,6 +456,9 @@ int radix_sort_pairs_i32(fedd_ctx* c, int32_t* keys[2], int32_t* vals[2], int32_
 // symbolic.hip
 int build_adjacency(fedd_ctx* c);
 int build_pattern(fedd_ctx* c, int dofs, int block_mode);
+// the node-level pattern alone into buffers of the caller's (the system slot is not touched), and its closed-form expansion to dofs
+int build_node_pattern(fedd_ctx* c, DevBuf<int32_t>& nptr, DevBuf<int32_t>& ncol, int32_t* max_nn, int64_t* node_nnz);
+int expand_node_pattern(fedd_ctx* c, const int32_t* nptr, const int32_t* ncol, int dofs, int full, int32_t* rowptr, int32_t* colind);
 
 // assemble.hip
 int assemble_matrix(fedd_ctx* c, int form, const double* params);
@@ -445,6 +469,8 @@ int apply_dirichlet_nodes(fedd_ctx* c, int64_t n, const int32_t* nodes, const in
                           const double* values);
 int apply_dirichlet_rows(fedd_ctx* c, int64_t n, const int32_t* rows, const double* values);
 int assemble_div(fedd_ctx* c, int64_t n_pressure_nodes, int slot_b, int slot_bt);
+int velocity_set(fedd_ctx* c, const double* u_rep);
+int assemble_advection(fedd_ctx* c, int kind, double scale, int slot_add, int slot_out);
 
 // blocks.hip
 int matrix_store(fedd_ctx* c, int slot);

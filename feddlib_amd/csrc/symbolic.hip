@@ -8,6 +8,7 @@
 // No dynamic insert here: counting sort by node, per-row sorted-unique merge in LDS, closed-form
 // expansion to dofs.
 #include "fedd_internal.hpp"
+#include <algorithm>
 #include <chrono>
 
 namespace fedd {
@@ -290,6 +291,41 @@ static int build_adjacency_impl(fedd_ctx* c) {
     }
     FEDD_HIP(hipGetLastError());
     c->have_adj = true;
+    return 0;
+}
+
+// The node-level pattern of the current mesh into nptr / ncol: the same sorted-unique merge as build_pattern (ordered
+// insertion, count pass then fill pass), leaving the system matrix and its scratch alone.  For callers that keep a pattern of
+// their own beside the system matrix (the FULL velocity pattern of the advection matrices).
+int build_node_pattern(fedd_ctx* c, DevBuf<int32_t>& nptr, DevBuf<int32_t>& ncol, int32_t* max_nn, int64_t* node_nnz) {
+    const int32_t n_own = (int32_t)(c->n_own + c->n_rowg);
+    const int nen = c->nen;
+    const int cap = std::max(1, c->max_deg * (nen - 1) + 1);
+    const size_t lds = (size_t)cap * 64 * sizeof(int32_t);
+    FEDD_CHECK(lds <= 160 * 1024, "pattern build: a node with %d incident elements exceeds the LDS list (cap %d)", c->max_deg, cap);
+    const dim3 grid((n_own + 63) / 64), block(64);
+    FEDD_TRY(nptr.ensure((size_t)n_own + 1));
+    if (lds > 64 * 1024) {
+        FEDD_HIP(hipFuncSetAttribute((const void*)k_node_pattern<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        FEDD_HIP(hipFuncSetAttribute((const void*)k_node_pattern<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    hipLaunchKernelGGL(k_node_pattern<false>, grid, block, lds, c->stream, c->d_conn.p, nen, c->d_n2e_ptr.p, c->d_n2e.p, n_own, cap,
+                       nptr.p, (const int32_t*)nullptr, (int32_t*)nullptr);
+    FEDD_TRY(reduce_max_i32(c, nptr.p, n_own, max_nn));
+    FEDD_TRY(exclusive_scan_i32(c, nptr.p, nptr.p, n_own, node_nnz));
+    FEDD_TRY(ncol.ensure((size_t)*node_nnz));
+    hipLaunchKernelGGL(k_node_pattern<true>, grid, block, lds, c->stream, c->d_conn.p, nen, c->d_n2e_ptr.p, c->d_n2e.p, n_own, cap,
+                       (int32_t*)nullptr, (const int32_t*)nptr.p, ncol.p);
+    FEDD_HIP(hipGetLastError());
+    return 0;
+}
+
+int expand_node_pattern(fedd_ctx* c, const int32_t* nptr, const int32_t* ncol, int dofs, int full, int32_t* rowptr, int32_t* colind) {
+    const int32_t n_own = (int32_t)(c->n_own + c->n_rowg);
+    const int64_t nthreads = (int64_t)n_own * dofs + 1;
+    hipLaunchKernelGGL(k_expand_pattern, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, c->stream, nptr, ncol, n_own, dofs,
+                       full, rowptr, colind);
+    FEDD_HIP(hipGetLastError());
     return 0;
 }
 

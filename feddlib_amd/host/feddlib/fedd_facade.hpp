@@ -778,14 +778,11 @@ public:
             A->invalidateHost();
         }
     }
-private:
-    void setMerged(const BlockMatrixPtr_Type& blockMatrix, const BlockMultiVectorPtr_Type& blockMV, int block, double t) const {
-        auto dev = blockMatrix->mergedDevice();
-        TEUCHOS_TEST_FOR_EXCEPTION(dev.is_null(), std::runtime_error, "BCBuilder: the block system has not been merged on the device");
+    // the Dirichlet rows of `block` in the numbering of the merged system (the blocks one after the other) and their values
+    void mergedDirichletRows(const BlockMultiVectorPtr_Type& blockMV, int block, double t, std::vector<int32_t>& rows,
+                             std::vector<double>& values) const {
         int64_t rowOffset = 0;
         for (int b = 0; b < block; ++b) rowOffset += (int64_t)blockMV->getBlock(b)->getLocalLength();
-        std::vector<int32_t> rows;
-        std::vector<double> values;
         for (size_t k = 0; k < vecFlag_.size(); ++k) {
             if (vecBlockID_[k] != block || vecBCType_[k].compare(0, 9, "Dirichlet") != 0) continue;
             auto dom = vecDomain_[k];
@@ -809,6 +806,44 @@ private:
                 }
             }
         }
+    }
+    // BCBuilder::setSystem alone on a merged block system (BCBuilder_def.hpp:589-707): unit rows, no right-hand side
+    void setSystem(const BlockMatrixPtr_Type& blockMatrix, const BlockMultiVectorPtr_Type& layout) const {
+        auto dev = blockMatrix->mergedDevice();
+        TEUCHOS_TEST_FOR_EXCEPTION(dev.is_null(), std::runtime_error, "BCBuilder: the block system has not been merged on the device");
+        std::vector<int32_t> rows;
+        std::vector<double> values;
+        for (UN b = 0; b < blockMatrix->size(); ++b) mergedDirichletRows(layout, (int)b, 0., rows, values);
+        std::fill(values.begin(), values.end(), 0.);
+        feddCheck(fedd_dirichlet_rows(dev->ctx, (int64_t)rows.size(), rows.data(), values.data()), "fedd_dirichlet_rows");
+    }
+    // BCBuilder::setRHS (:93-170), setVectorMinusBC and setBCMinusVector (the boundary rows of a nonlinear residual):
+    // which = 0: v <- g, 1: v <- x - g, 2: v <- g - x on the Dirichlet rows
+    void setRows(const BlockMultiVectorPtr_Type& v, const BlockMultiVectorPtr_Type& x, double t, int which) const {
+        std::vector<int32_t> rows;
+        std::vector<double> values;
+        for (UN b = 0; b < v->size(); ++b) mergedDirichletRows(v, (int)b, t, rows, values);
+        std::vector<int64_t> start(v->size() + 1, 0);
+        for (UN b = 0; b < v->size(); ++b) start[b + 1] = start[b] + (int64_t)v->getBlock(b)->getLocalLength();
+        for (size_t k = 0; k < rows.size(); ++k) {
+            UN b = 0;
+            while (rows[k] >= start[b + 1]) ++b;
+            const size_t i = (size_t)(rows[k] - start[b]);
+            double& dst = v->getBlockNonConst(b)->raw()[i];
+            const double xi = which == 0 ? 0. : x->getBlock(b)->raw()[i];
+            dst = which == 0 ? values[k] : (which == 1 ? xi - values[k] : values[k] - xi);
+        }
+    }
+    void setRHS(const BlockMultiVectorPtr_Type& rhs, double t = 0.) const { setRows(rhs, rhs, t, 0); }
+    void setVectorMinusBC(const BlockMultiVectorPtr_Type& v, const BlockMultiVectorPtr_Type& x, double t = 0.) const { setRows(v, x, t, 1); }
+    void setBCMinusVector(const BlockMultiVectorPtr_Type& v, const BlockMultiVectorPtr_Type& x, double t = 0.) const { setRows(v, x, t, 2); }
+private:
+    void setMerged(const BlockMatrixPtr_Type& blockMatrix, const BlockMultiVectorPtr_Type& blockMV, int block, double t) const {
+        auto dev = blockMatrix->mergedDevice();
+        TEUCHOS_TEST_FOR_EXCEPTION(dev.is_null(), std::runtime_error, "BCBuilder: the block system has not been merged on the device");
+        std::vector<int32_t> rows;
+        std::vector<double> values;
+        mergedDirichletRows(blockMV, block, t, rows, values);
         // the merged rhs = the blocks' right-hand sides one after the other
         std::vector<double> rhs;
         for (UN b = 0; b < blockMV->size(); ++b) rhs.insert(rhs.end(), blockMV->getBlock(b)->raw().begin(), blockMV->getBlock(b)->raw().end());
@@ -1344,6 +1379,271 @@ public:
         this->system_->setMerged(dev);
         if (this->verbose_) std::cout << "done -- " << std::endl;
     }
+};
+
+// NonLinearProblem (feddlib/problems/abstract/NonLinearProblem_def.hpp:97-160): residual vector, its norm, and the update solve
+// system * dx = residual, solution <- dx + previous solution.
+template <class SC = default_sc, class LO = default_lo, class GO = default_go, class NO = default_no>
+class NonLinearProblem : public Problem<SC, LO, GO, NO> {
+public:
+    typedef Problem<SC, LO, GO, NO> Problem_Type;
+    typedef typename Problem_Type::BlockMultiVector_Type BlockMultiVector_Type;
+    typedef typename Problem_Type::BlockMultiVectorPtr_Type BlockMultiVectorPtr_Type;
+    typedef typename Problem_Type::MultiVector_Type MultiVector_Type;
+    typedef typename Problem_Type::CommConstPtr_Type CommConstPtr_Type;
+    NonLinearProblem(ParameterListPtr_Type parameterList, CommConstPtr_Type comm) : Problem_Type(parameterList, comm) {}
+    virtual void reAssemble(std::string type) const = 0;
+    virtual void calculateNonLinResidualVec(std::string type = "standard", double time = 0.) const = 0;
+    void infoNonlinProblem() {
+        if (this->verbose_)
+            std::cout << "\t ### Nonlinear problem: Linearization " << this->parameterList_->sublist("General").get("Linearization", "FixedPoint")
+                      << ", relNonLinTol " << this->parameterList_->sublist("Parameter").get("relNonLinTol", 1.0e-6) << std::endl;
+    }
+    void initializeProblem(int nmbVectors = 1) {                      // NonLinearProblem_def.hpp:60-76
+        Problem_Type::initializeProblem(nmbVectors);
+        residualVec_ = likeSolution(nmbVectors);
+        previousSolution_ = likeSolution(nmbVectors);
+    }
+    double calculateResidualNorm() const {                            // :121-127
+        double s = 0.;
+        for (UN b = 0; b < residualVec_->size(); ++b)
+            for (double v : residualVec_->getBlock(b)->raw()) s += v * v;
+        return std::sqrt(s);
+    }
+    int solveUpdate() {                                               // :130-138
+        previousSolution_->update(1., *this->solution_, 0.);
+        return this->solve(residualVec_);
+    }
+    int solveAndUpdate(const std::string& criterion, double& criterionValue) {   // :141-154
+        int its = solveUpdate();
+        if (criterion == "Update") {
+            double s = 0.;
+            for (UN b = 0; b < this->solution_->size(); ++b)
+                for (double v : this->solution_->getBlock(b)->raw()) s += v * v;
+            criterionValue = std::sqrt(s);
+        }
+        this->solution_->update(1., *previousSolution_, 1.);
+        return its;
+    }
+    BlockMultiVectorPtr_Type getResidualVector() const { return residualVec_; }
+    void setBoundariesSystem() const {                                // Problem_def.hpp: BCBuilder::setSystem on the system alone
+        TEUCHOS_TEST_FOR_EXCEPTION(this->bcFactory_.is_null(), std::runtime_error, "No boundary conditions added.");
+        this->bcFactory_->setSystem(this->system_, this->rhs_);
+    }
+    void setBoundariesRHS(double time = .0) const {
+        TEUCHOS_TEST_FOR_EXCEPTION(this->bcFactory_.is_null(), std::runtime_error, "No boundary conditions added.");
+        this->bcFactory_->setRHS(this->rhs_, time);
+    }
+protected:
+    BlockMultiVectorPtr_Type likeSolution(int nmbVectors) const {
+        BlockMultiVectorPtr_Type v(new BlockMultiVector_Type(this->solution_->size()));
+        for (UN i = 0; i < this->solution_->size(); ++i)
+            v->addBlock(Teuchos::rcp(new MultiVector_Type(this->solution_->getBlock(i)->getMap(), nmbVectors)), i);
+        return v;
+    }
+    mutable BlockMultiVectorPtr_Type residualVec_, previousSolution_;
+};
+
+// NavierStokes (feddlib/problems/specific/NavierStokes_def.hpp): A = density * viscosity * vector Laplacian, B and B^T = -div
+// blocks, C = -1 / (viscosity density) BD for P1 / P1 (assembleConstantMatrices); per nonlinear iteration block (0,0) =
+// A + density N(u) ("FixedPoint") or A + density (N(u) + W(u)) ("Newton"), reAssemble :282-321, from one device pass
+// (fedd_assemble_advection) into slot 4, merged again with the constant blocks (values only after the first time).
+template <class SC = default_sc, class LO = default_lo, class GO = default_go, class NO = default_no>
+class NavierStokes : public NonLinearProblem<SC, LO, GO, NO> {
+public:
+    typedef NonLinearProblem<SC, LO, GO, NO> NonLinearProblem_Type;
+    typedef Problem<SC, LO, GO, NO> Problem_Type;
+    typedef typename Problem_Type::DomainConstPtr_Type DomainConstPtr_Type;
+    typedef typename Problem_Type::Matrix_Type Matrix_Type;
+    typedef typename Problem_Type::MatrixPtr_Type MatrixPtr_Type;
+    typedef typename Problem_Type::BlockMatrix_Type BlockMatrix_Type;
+    NavierStokes(const DomainConstPtr_Type& domainVelocity, std::string FETypeVelocity, const DomainConstPtr_Type& domainPressure,
+                 std::string FETypePressure, ParameterListPtr_Type parameterList)
+        : NonLinearProblem_Type(parameterList, domainVelocity->getComm()) {
+        this->addVariable(domainVelocity, FETypeVelocity, "u", (int)domainVelocity->getDimension());
+        this->addVariable(domainPressure, FETypePressure, "p", 1);
+        this->dim_ = (int)this->getDomain(0)->getDimension();
+    }
+    void info() override { this->infoProblem(); this->infoNonlinProblem(); }
+    void assemble(std::string type = "") const override {
+        if (type == "") {
+            if (this->verbose_) std::cout << "-- Assembly Navier-Stokes ... " << std::endl;
+            assembleConstantMatrices();
+            if (this->verbose_) std::cout << "done -- " << std::endl;
+        } else {
+            reAssemble(type);
+        }
+    }
+    void assembleConstantMatrices() const {
+        if (this->verbose_) std::cout << "-- Assembly constant matrices Navier-Stokes ... " << std::flush;
+        auto& par = this->parameterList_->sublist("Parameter");
+        const double viscosity = par.get("Viscosity", 1.), density = par.get("Density", 1.);
+        TEUCHOS_TEST_FOR_EXCEPTION(par.get("Symmetric gradient", false), std::logic_error,
+                                   "\"Symmetric gradient\" = true: assemblyStress is not built");
+        TEUCHOS_TEST_FOR_EXCEPTION(this->getFEType(1) != "P1", std::logic_error, "NavierStokes: P1 pressure in this build");
+        TEUCHOS_TEST_FOR_EXCEPTION(this->comm_->getSize() > 1, std::logic_error, "NavierStokes: one rank in this build");
+        auto domV = this->getDomain(0);
+        auto dev = domV->device();
+        if (par.get("Set Zeros", false)) this->feFactory_->doSetZeros(par.get("Myeps", 1.0e-14));
+        MatrixPtr_Type A(new Matrix_Type(domV->getMapVecFieldUnique(), domV->getApproxEntriesPerRow()));
+        MatrixPtr_Type BT(new Matrix_Type(domV->getMapVecFieldUnique(), this->getDomain(1)->getDimension() * this->getDomain(1)->getApproxEntriesPerRow()));
+        auto pressureMap = this->getDomain(1)->getMapUnique();
+        MatrixPtr_Type B(new Matrix_Type(pressureMap, domV->getDimension() * domV->getApproxEntriesPerRow()));
+        this->feFactory_->assemblyLaplaceVecField(this->dim_, this->domain_FEType_vec_.at(0), 2, A, true);
+        A->resumeFill();
+        feddCheck(fedd_matrix_scale(dev->ctx, -1, viscosity * density), "fedd_matrix_scale");   // A_->scale(viscosity); A_->scale(density)
+        feddCheck(fedd_matrix_store(dev->ctx, 0), "fedd_matrix_store");
+        A->bindSlot(dev, 0);
+        this->feFactory_->assemblyDivAndDivT(this->dim_, this->getFEType(0), this->getFEType(1), 2, B, BT, domV->getMapVecFieldUnique(), pressureMap, true);
+        B->resumeFill();
+        BT->resumeFill();
+        B->scale(-1.);
+        BT->scale(-1.);
+        A->fillComplete(domV->getMapVecFieldUnique(), domV->getMapVecFieldUnique());
+        B->fillComplete(domV->getMapVecFieldUnique(), pressureMap);
+        BT->fillComplete(pressureMap, domV->getMapVecFieldUnique());
+        A_ = A;
+        this->system_.reset(new BlockMatrix_Type(2));
+        this->system_->addBlock(BT, 0, 1);
+        this->system_->addBlock(B, 1, 0);
+        slotC_ = -1;
+        if (this->getFEType(0) == "P1") {
+            MatrixPtr_Type C(new Matrix_Type(pressureMap, this->getDomain(1)->getApproxEntriesPerRow()));
+            this->feFactory_->assemblyBDStabilization(this->dim_, "P1", C, true);
+            C->resumeFill();
+            feddCheck(fedd_matrix_scale(dev->ctx, -1, -1. / (viscosity * density)), "fedd_matrix_scale");
+            feddCheck(fedd_matrix_store(dev->ctx, 3), "fedd_matrix_store");
+            C->bindSlot(dev, 3);
+            C->fillComplete(pressureMap, pressureMap);
+            this->system_->addBlock(C, 1, 1);
+            slotC_ = 3;
+        }
+        if (this->verbose_) std::cout << "done -- " << std::endl;
+        reAssemble("FixedPoint");      // block (0,0) = A + density N(u) for the initial (zero) velocity, and the merged system
+    }
+    void reAssemble(std::string type) const override {
+        if (this->verbose_) std::cout << "-- Reassembly Navier-Stokes (" << type << ") ... " << std::flush;
+        TEUCHOS_TEST_FOR_EXCEPTION(type != "FixedPoint" && type != "Newton", std::logic_error, "reAssemble: unknown type " + type);
+        const double density = this->parameterList_->sublist("Parameter").get("Density", 1.);
+        auto domV = this->getDomain(0);
+        auto dev = domV->device();
+        if (type == "FixedPoint") {     // u_rep_->importFromVector(u): the "Newton" call that follows keeps this velocity
+            auto mapRep = domV->getMapRepeated();
+            auto mapUni = domV->getMapUnique();
+            const auto& u = this->solution_->getBlock(0)->raw();
+            const int dim = this->dim_;
+            u_rep_.assign((size_t)mapRep->getNodeNumElements() * dim, 0.);
+            for (LO i = 0; i < mapRep->getNodeNumElements(); ++i) {
+                const LO k = mapUni->getLocalElement(mapRep->getGlobalElement(i));
+                for (int d = 0; d < dim; ++d) u_rep_[(size_t)i * dim + d] = u[(size_t)k * dim + d];
+            }
+            feddCheck(fedd_velocity_set(dev->ctx, u_rep_.data()), "fedd_velocity_set");
+        }
+        feddCheck(fedd_assemble_advection(dev->ctx, type == "Newton" ? FEDD_ADV_NEWTON : FEDD_ADV_N, density, 0, 4), "fedd_assemble_advection");
+        MatrixPtr_Type ANW(new Matrix_Type(domV->getMapVecFieldUnique(), domV->getDimension() * domV->getApproxEntriesPerRow()));
+        ANW->bindSlot(dev, 4);
+        ANW->fillComplete(domV->getMapVecFieldUnique(), domV->getMapVecFieldUnique());
+        this->system_->addBlock(ANW, 0, 0);
+        feddCheck(fedd_block_merge(dev->ctx, 4, 2, 1, slotC_), "fedd_block_merge");
+        dev->generation++;
+        this->system_->setMerged(dev);
+        if (this->verbose_) std::cout << "done -- " << std::endl;
+    }
+    // NavierStokes_def.hpp:723-751: residual = system(u) x - rhs ("standard") or rhs - system(u) x ("reverse"), the Dirichlet
+    // rows x - g / g - x
+    void calculateNonLinResidualVec(std::string type = "standard", double time = 0.) const override {
+        reAssemble("FixedPoint");
+        auto dev = this->getDomain(0)->device();
+        std::vector<double> x, y;
+        for (UN b = 0; b < this->solution_->size(); ++b)
+            x.insert(x.end(), this->solution_->getBlock(b)->raw().begin(), this->solution_->getBlock(b)->raw().end());
+        y.assign(x.size(), 0.);
+        feddCheck(fedd_spmv(dev->ctx, x.data(), y.data()), "fedd_spmv");
+        size_t off = 0;
+        const bool standard = type == "standard";
+        TEUCHOS_TEST_FOR_EXCEPTION(!standard && type != "reverse", std::logic_error, "calculateNonLinResidualVec: unknown type " + type);
+        for (UN b = 0; b < this->residualVec_->size(); ++b) {
+            auto& r = this->residualVec_->getBlockNonConst(b)->raw();
+            const auto& f = this->rhs_->getBlock(b)->raw();
+            for (size_t i = 0; i < r.size(); ++i) r[i] = standard ? y[off + i] - f[i] : f[i] - y[off + i];
+            off += r.size();
+        }
+        if (standard) this->bcFactory_->setVectorMinusBC(this->residualVec_, this->solution_, time);
+        else this->bcFactory_->setBCMinusVector(this->residualVec_, this->solution_, time);
+    }
+private:
+    mutable MatrixPtr_Type A_;
+    mutable std::vector<double> u_rep_;
+    mutable int slotC_ = -1;
+};
+
+// NonLinearSolver (feddlib/problems/Solver/NonLinearSolver_def.hpp:274-391): solveFixedPoint and solveNewton, line by line --
+// residual first ("reverse"), "Criterion" = Residual | Update, relNonLinTol, MaxNonLinIts, "Cancel MaxNonLinIts".  What the
+// reference's parameter files can ask for beyond that is refused with the key named.
+template <class SC = default_sc, class LO = default_lo, class GO = default_go, class NO = default_no>
+class NonLinearSolver {
+public:
+    typedef NonLinearProblem<SC, LO, GO, NO> NonLinearProblem_Type;
+    NonLinearSolver() : type_("") {}
+    NonLinearSolver(std::string type) : type_(type) {}
+    void solve(NonLinearProblem_Type& problem) {
+        auto pl = problem.getParameterList();
+        TEUCHOS_TEST_FOR_EXCEPTION(type_ == "NOX", std::logic_error, "\"Linearization\" = \"NOX\" is not built (FixedPoint and Newton are)");
+        TEUCHOS_TEST_FOR_EXCEPTION(type_ != "FixedPoint" && type_ != "Newton", std::logic_error,
+                                   "\"Linearization\" = \"" + type_ + "\" is not built (FixedPoint and Newton are)");
+        const std::string prec = pl->sublist("General").get("Preconditioner Method", "Monolithic");
+        TEUCHOS_TEST_FOR_EXCEPTION(prec != "Monolithic", std::logic_error,
+                                   "\"Preconditioner Method\" = \"" + prec + "\" is not built (Monolithic is; Teko is out of scope)");
+        TEUCHOS_TEST_FOR_EXCEPTION(pl->sublist("Parameter").get("Symmetric gradient", false), std::logic_error,
+                                   "\"Symmetric gradient\" = true: assemblyStress is not built");
+        const std::string levels = pl->sublist("ThyraPreconditioner").sublist("Preconditioner Types").sublist("FROSch").get("Level Combination", "Additive");
+        TEUCHOS_TEST_FOR_EXCEPTION(levels == "Multiplicative", std::logic_error,
+                                   "\"Level Combination\" = \"Multiplicative\" is not supported for nonlinear problems (NonLinearProblem_def.hpp:578)");
+        iterate(problem, type_ == "Newton");
+    }
+private:
+    void iterate(NonLinearProblem_Type& problem, bool newton) {
+        const bool verbose = problem.getVerbose();
+        TEUCHOS_TEST_FOR_EXCEPTION(problem.getRhs()->getNumVectors() != 1, std::logic_error, "We need to change the code for numVectors>1.");
+        const char* name = newton ? "Newton" : "Fixed Point";
+        double gmresIts = 0., residual0 = 1., residual = 1.;
+        auto& par = problem.getParameterList()->sublist("Parameter");
+        const double tol = par.get("relNonLinTol", 1.0e-6);
+        const int maxNonLinIts = par.get("MaxNonLinIts", 10);
+        int nlIts = 0;
+        double criterionValue = 1.;
+        const std::string criterion = par.get("Criterion", "Residual");
+        while (nlIts < maxNonLinIts) {
+            problem.calculateNonLinResidualVec("reverse");
+            if (newton) {
+                if (criterion == "Residual") residual = problem.calculateResidualNorm();
+                problem.assemble("Newton");
+                problem.setBoundariesSystem();
+            } else {
+                problem.setBoundariesSystem();
+                if (criterion == "Residual") residual = problem.calculateResidualNorm();
+            }
+            if (nlIts == 0) residual0 = residual;
+            if (criterion == "Residual") {
+                criterionValue = residual / residual0;
+                if (verbose) std::cout << "### " << name << " iteration : " << nlIts << "  relative nonlinear residual : " << criterionValue << std::endl;
+                if (criterionValue < tol) break;
+            }
+            gmresIts += problem.solveAndUpdate(criterion, criterionValue);
+            nlIts++;
+            if (criterion == "Update") {
+                if (verbose) std::cout << "### " << name << " iteration : " << nlIts << "  residual of update : " << criterionValue << std::endl;
+                if (criterionValue < tol) break;
+            }
+        }
+        gmresIts /= std::max(nlIts, 1);
+        if (verbose)
+            std::cout << "### Total " << (newton ? "Newton iterations" : "FPI") << " : " << nlIts << "  with average gmres its : " << gmresIts << std::endl;
+        if (par.get("Cancel MaxNonLinIts", false))
+            TEUCHOS_TEST_FOR_EXCEPTION(nlIts == maxNonLinIts, std::runtime_error,
+                                       "Maximum nonlinear Iterations reached. Problem might have converged in the last step. Still we cancel here.");
+    }
+    std::string type_;
 };
 
 // MeshPartitioner (feddlib/core/Mesh/MeshPartitioner_decl.hpp): reads the mesh named by "Mesh 1 Name" into the domain;

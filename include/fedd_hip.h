@@ -11,6 +11,8 @@
  *     (feddlib/core/General/DefaultTypeDefs.hpp:6-15).
  *   - vector fields are node-wise interleaved: dof = dofs_per_node*node + d
  *     (feddlib/core/LinearAlgebra/Map_def.hpp:101-104).
+ * Problem classes covered: Laplace, LinElas, Stokes (fedd_assemble, fedd_assemble_div, fedd_block_merge) and the matrices of
+ * steady Navier-Stokes that change with the velocity (fedd_velocity_set, fedd_assemble_advection).
  */
 #ifndef FEDD_HIP_H
 #define FEDD_HIP_H
@@ -34,6 +36,15 @@ enum fedd_form {
     FEDD_FORM_BDSTAB      = 5  /* FE::assemblyBDStabilization  FE_def.hpp:2151-2220 (dofs 1, P1 only): the Bochev-Dohrmann
                                   pressure block of P1/P1 Stokes, C_ij = |det B| (sum_q w_q phi_i phi_j - |ref| scale),
                                   scaled by -1/viscosity by the caller (Stokes_def.hpp:98-105)        */
+};
+
+/* ---- what fedd_assemble_advection builds from the velocity of fedd_velocity_set ---- */
+enum fedd_advection {
+    FEDD_ADV_N      = 0,       /* FE::assemblyAdvectionVecField     FE_def.hpp:1759-1832: n_ij = |det B| sum_q w_q (u_h . grad phi_j) phi_i
+                                  on the dim pairs (dim*i+d, dim*j+d) -- the fixed-point linearisation                       */
+    FEDD_ADV_W      = 1,       /* FE::assemblyAdvectionInUVecField  FE_def.hpp:1839-1925: (dim*i+d1, dim*j+d2) =
+                                  |det B| sum_q w_q (d u_d1 / d x_d2) phi_i phi_j                                            */
+    FEDD_ADV_NEWTON = 2        /* N + W, both from one pass over the elements -- the Newton linearisation                   */
 };
 
 /* ---- how the dofs of a node couple in the CSR pattern ---- */
@@ -223,14 +234,18 @@ int fedd_dirichlet_rows(fedd_ctx* ctx, int64_t n, const int32_t* rows, const dou
 
 /* ------------------------------------------------------------------------------------------------
  * mixed / block problems (one rank for now).  Blocks live in numbered slots beside the system matrix.
- *   fedd_matrix_store     copy the system matrix into `slot` (0..3)
+ *   fedd_matrix_store     copy the system matrix into `slot` (0..4; Stokes uses 0..3 = A, B, B^T, C, Navier-Stokes adds 4 = the
+ *                         linearised velocity block of fedd_assemble_advection)
  *   fedd_matrix_scale     Matrix::scale (Stokes_def.hpp:83-85,102); slot < 0 = system matrix
  *   fedd_assemble_div     FE::assemblyDivAndDivT (FE_def.hpp:1932-2057): velocity = the mesh's element,
  *                         pressure = P1 on the vertices = the first n_pressure_nodes node ids; B -> slot_b
  *                         (n_p x dim*n_v), B^T -> slot_bt.  Overwrites the system slot (scratch).
  *   fedd_block_merge      BlockMatrix::merge + BlockMap::merge (BlockMatrix_def.hpp:119-148,212-287;
  *                         BlockMap_def.hpp:55-80): system <- [A B^T; B C] (slot < 0 = empty block); merged
- *                         global ids = block-local gid + cumulated (maxAllGlobalIndex + 1).
+ *                         global ids = block-local gid + cumulated (maxAllGlobalIndex + 1).  A merge of the same slots
+ *                         whose patterns have not been rewritten since the last merge (values may have: the blocks of a
+ *                         nonlinear iteration) keeps the merged pattern and moves values only; right-hand side, solution
+ *                         and Dirichlet marks are reset as by every merge.
  *   fedd_matrix_sizes/get read a stored block back (local column ids).
  * ---------------------------------------------------------------------------------------------- */
 int fedd_matrix_store(fedd_ctx* ctx, int slot);
@@ -239,6 +254,32 @@ int fedd_assemble_div(fedd_ctx* ctx, int64_t n_pressure_nodes, int slot_b, int s
 int fedd_block_merge(fedd_ctx* ctx, int slot_a, int slot_bt, int slot_b, int slot_c);
 int fedd_matrix_sizes(fedd_ctx* ctx, int slot, int64_t* n_rows, int64_t* n_cols, int64_t* nnz);
 int fedd_matrix_get(fedd_ctx* ctx, int slot, int64_t* rowptr, int32_t* colind, double* val);
+
+/* ------------------------------------------------------------------------------------------------
+ * steady Navier-Stokes (one rank, like the block system it feeds): the matrices NavierStokes::reAssemble builds in every
+ * nonlinear iteration (feddlib/problems/specific/NavierStokes_def.hpp:282-321) from the current velocity.
+ *   fedd_velocity_set        u_rep[n_rep * dim], node-wise interleaved on the repeated map of fedd_mesh_set: what
+ *                            NavierStokes::u_rep_ holds (NavierStokes_def.hpp:290-291, 305-306).
+ *   fedd_assemble_advection  slot_out <- scale * (N(u) | W(u) | N(u) + W(u)) + M[slot_add]   (slot_add < 0: nothing added):
+ *                            FE::assemblyAdvectionVecField / assemblyAdvectionInUVecField (FE_def.hpp:1759-1832, 1839-1925)
+ *                            with scale = density (N->scale(density), :295, 313), then A_->addMatrix(1., ANW, 0.) and
+ *                            N->addMatrix(1., ANW, 1.) (:297-298, 316-319) in one device pass.  slot_out has the FULL
+ *                            dim x dim node-block pattern of the velocity space whatever the kind (N leaves structural zeros
+ *                            off the diagonal pairs); M[slot_add] is a velocity matrix of the same mesh with the DIAG pattern
+ *                            (the stored FEDD_FORM_LAPLACE_VEC block) or the FULL one, in a slot other than slot_out.
+ *                            Quadrature: determineDegree (FE_def.hpp:1770-1772, 1859-1861) -- P2 degree 5 for both, P1 2 for N
+ *                            and 3 for W.  Option "asm_zero_eps" thresholds the element values of N and of W as the reference
+ *                            does under setZeros_ (:1816, 1908).  The node-level pattern, the gather lists of the row sums and
+ *                            the adjacency are built at the first call after fedd_mesh_set (timer FEDD_T_SYMBOLIC) and kept;
+ *                            later calls move values only (timer FEDD_T_ASSEMBLE), also after fedd_block_merge has replaced
+ *                            the system matrix, which this call never touches.  No atomics: two calls on the same input
+ *                            agree bit for bit.  fedd_matrix_get reads the result.
+ *                            Memory: the element blocks pass through a device scratch of 8 * n_elem * nen^2 * dim^2 bytes
+ *                            (N alone: 8 * n_elem * nen^2) -- 7.2 KB per P2 tetrahedron, 11.3 GB on the P2 mesh of a 64^3-cell
+ *                            cube -- held between calls and released by the next fedd_mesh_set.
+ * ---------------------------------------------------------------------------------------------- */
+int fedd_velocity_set(fedd_ctx* ctx, const double* u_rep);
+int fedd_assemble_advection(fedd_ctx* ctx, int kind, double scale, int slot_add, int slot_out);
 
 /* read-back for Tpetra::CrsMatrix fill / parity (Matrix::getLocalRowView analog). col_gid maps
  * a local column index to its global dof id. */
