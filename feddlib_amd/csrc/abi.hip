@@ -776,44 +776,37 @@ extern "C" int fedd_schwarz_apply_device(fedd_ctx* c, int reps) {
     return 0;
 }
 
-extern "C" int fedd_gmres(fedd_ctx* c, const double* b_owned, double* x_owned, double rtol, int max_it,
-                          int restart, int use_prec, int* its_out, double* relres_out) {
+// x0: "Zero Initial Guess" = false (LinearSolver_def.hpp:76-78): the solve starts from x_owned (NULL: from the vector the
+// device holds -- the last solution, or what fedd_schwarz_coarse_apply(ctx, NULL, NULL) left there)
+static int gmres_entry(fedd_ctx* c, const char* who, bool x0, const double* b_owned, double* x_owned, double rtol, int max_it,
+                       int restart, int use_prec, int* its_out, double* relres_out) {
     NEED_DEVICE(c);
-    FEDD_CHECK(c->have_pattern, "fedd_gmres: no matrix");
-    FEDD_CHECK(!use_prec || c->have_schwarz, "fedd_gmres: preconditioner requested but fedd_schwarz_setup was not called");
-    FEDD_CHECK(rtol > 0 && max_it >= 1 && restart >= 1 && restart <= 1000, "fedd_gmres: bad rtol/max_it/restart");
-    if (use_prec) FEDD_TRY(levels_check(c, "fedd_gmres"));
+    FEDD_CHECK(c->have_pattern, "%s: no matrix", who);
+    FEDD_CHECK(!use_prec || c->have_schwarz, "%s: preconditioner requested but fedd_schwarz_setup was not called", who);
+    FEDD_CHECK(rtol > 0 && max_it >= 1 && restart >= 1 && restart <= 1000, "%s: bad rtol/max_it/restart", who);
+    if (use_prec) FEDD_TRY(levels_check(c, who));
     FEDD_HIP(hipSetDevice(c->device));
-    if (b_owned) FEDD_HIP(hipMemcpyAsync(c->d_rhs.p, b_owned, (size_t)c->n_rows * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    FEDD_TRY(gmres_solve(c, c->d_rhs.p, c->d_x.p, rtol, max_it, restart, use_prec, its_out, relres_out));
+    const size_t bytes = (size_t)c->n_rows * sizeof(double);
+    if (b_owned) FEDD_HIP(hipMemcpyAsync(c->d_rhs.p, b_owned, bytes, hipMemcpyHostToDevice, c->stream));
+    if (x0 && x_owned) FEDD_HIP(hipMemcpyAsync(c->d_x.p, x_owned, bytes, hipMemcpyHostToDevice, c->stream));
+    GmresCall call{c->d_rhs.p, c->d_x.p, rtol, max_it, restart, use_prec};
+    call.x0 = x0;
+    FEDD_TRY(gmres_solve(c, call, its_out, relres_out));
     if (x_owned) {
-        FEDD_HIP(hipMemcpyAsync(x_owned, c->d_x.p, (size_t)c->n_rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        FEDD_HIP(hipMemcpyAsync(x_owned, c->d_x.p, bytes, hipMemcpyDeviceToHost, c->stream));
         FEDD_HIP(hipStreamSynchronize(c->stream));
     }
     return 0;
 }
 
-// "Zero Initial Guess" = false (LinearSolver_def.hpp:76-78): the solve starts from x_owned (NULL: from the vector the
-// device holds -- the last solution, or what fedd_schwarz_coarse_apply(ctx, NULL, NULL) left there)
+extern "C" int fedd_gmres(fedd_ctx* c, const double* b_owned, double* x_owned, double rtol, int max_it,
+                          int restart, int use_prec, int* its_out, double* relres_out) {
+    return gmres_entry(c, "fedd_gmres", false, b_owned, x_owned, rtol, max_it, restart, use_prec, its_out, relres_out);
+}
+
 extern "C" int fedd_gmres_x0(fedd_ctx* c, const double* b_owned, double* x_owned, double rtol, int max_it,
                              int restart, int use_prec, int* its_out, double* relres_out) {
-    NEED_DEVICE(c);
-    FEDD_CHECK(c->have_pattern, "fedd_gmres_x0: no matrix");
-    FEDD_CHECK(!use_prec || c->have_schwarz, "fedd_gmres_x0: preconditioner requested but fedd_schwarz_setup was not called");
-    FEDD_CHECK(rtol > 0 && max_it >= 1 && restart >= 1 && restart <= 1000, "fedd_gmres_x0: bad rtol/max_it/restart");
-    if (use_prec) FEDD_TRY(levels_check(c, "fedd_gmres_x0"));
-    FEDD_HIP(hipSetDevice(c->device));
-    if (b_owned) FEDD_HIP(hipMemcpyAsync(c->d_rhs.p, b_owned, (size_t)c->n_rows * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (x_owned) FEDD_HIP(hipMemcpyAsync(c->d_x.p, x_owned, (size_t)c->n_rows * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    c->gm_x0 = 1;
-    const int rc = gmres_solve(c, c->d_rhs.p, c->d_x.p, rtol, max_it, restart, use_prec, its_out, relres_out);
-    c->gm_x0 = 0;
-    if (rc) return rc;
-    if (x_owned) {
-        FEDD_HIP(hipMemcpyAsync(x_owned, c->d_x.p, (size_t)c->n_rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        FEDD_HIP(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    return gmres_entry(c, "fedd_gmres_x0", true, b_owned, x_owned, rtol, max_it, restart, use_prec, its_out, relres_out);
 }
 
 extern "C" int fedd_mesh_setup_info(fedd_ctx* c, double* adjacency_ms, double* tiles_ms, int* tiles_state, int64_t* n_tiles) {
@@ -914,7 +907,6 @@ extern "C" int fedd_set_option(fedd_ctx* c, const char* key, double value) {
     else if (k == "spmv_pattern") { c->spmv_pattern = (int)value; c->cs_valid = false; }
     else if (k == "spmv_pat_nu") { c->spmv_pat_nu = (int)value; c->cs_valid = false; }
     else if (k == "spmv_win_nu") { c->spmv_win_nu = (int)value; c->cs_valid = false; }
-    else if (k == "md2_nch") c->md2_nch = (int)value;
     else if (k == "halo_overlap") { c->halo_overlap = (int)value; c->have_schwarz = false; }
     else if (k == "schwarz_big") c->sw_big = (int)value;
     else if (k == "schwarz_big_target") c->sw_big_target = (int)value;
@@ -938,8 +930,6 @@ extern "C" int fedd_set_option(fedd_ctx* c, const char* key, double value) {
     } else if (k == "gmres_dot_gy") {
         FEDD_CHECK(value >= 0 && value <= 8, "fedd_set_option: gmres_dot_gy %g", value);
         c->gmres_dot_gy = (int)value;
-    } else if (k == "gmres_dotv") {
-        c->gmres_dotv = (int)value;
     } else if (k == "gmres_newton") {
         c->gmres_newton = (int)value;
     } else if (k == "gmres_chol_tol") {

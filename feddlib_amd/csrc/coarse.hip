@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256) void k_fix_diag(double* __restrict__ K, int64_
 //     interiors: the interiors of different cells are not coupled, and a cell sees exactly one entity of each of the
 //     3^dim - 1 CLASSES (per direction: e_d even / e_d = 1 mod 4 / e_d = 3 mod 4), so one constrained solve per
 //     (class, component) extends all entities of the class at once.  The solves run on the device with the
-//     library's own GMRES + one-level Schwarz on the constrained operator (gmres.hip, gm_mask) to `gdsw_tol`
+//     library's own GMRES + one-level Schwarz on the constrained operator (gmres.hip, GmresCall::mask) to `gdsw_tol`
 //     (default 1e-4): an iterative interior solver in place of FROSch's direct ExtensionSolver;
 //   * K0 = Phi^T K Phi, column by colour: entities whose coordinates agree modulo 5 (RGDSW: coarse nodes, modulo 6) in every
 //     direction have supports that no row couples, so one prolongation - SpMV - restriction gives one column of K0 for all of them;
@@ -1437,14 +1437,13 @@ static int gdsw_setup(fedd_ctx* c) {
             hipLaunchKernelGGL(k_cols_scale, gs, blk, 0, c->stream, Bs, ns, (const double*)csf);
             int its = 0;
             double rel = 0.0;
-            c->gm_mask = c->d_gd_imask.p;
-            c->gm_nr = MULTI_NR;
+            GmresCall call{Bs, Xs, ext_tol, 1000, restart_s, 1};
+            call.mask = c->d_gd_imask.p;
+            call.nr = MULTI_NR;
             const bool timing = c->timing;
             c->timing = false;
-            const int rc = gmres_solve(c, Bs, Xs, ext_tol, 1000, restart_s, 1, &its, &rel);
+            const int rc = gmres_solve(c, call, &its, &rel);
             c->timing = timing;
-            c->gm_mask = nullptr;
-            c->gm_nr = 0;
             if (rc) return rc;
             hipLaunchKernelGGL(k_cols_scale, gs, blk, 0, c->stream, Xs, ns, (const double*)(csf + MULTI_NR));
             its_max = std::max(its_max, its);
@@ -1461,14 +1460,14 @@ static int gdsw_setup(fedd_ctx* c) {
         hipLaunchKernelGGL(k_gd_rhs, gr, blk, 0, c->stream, (const double*)c->d_gd_imask.p, (const double*)w, n_rows, b);
         int its = 0;
         double rel = 0.0;
-        c->gm_mask = c->d_gd_imask.p;
+        GmresCall call{b, x, ext_tol, 1000, 100, 1};
+        call.mask = c->d_gd_imask.p;
         // the launches of these inner solves belong to the coarse setup (whose timer is open), not to the per-iteration
         // classes of the outer solve: their timers are suspended (the tables double-counted them)
         const bool timing = c->timing;
         c->timing = false;
-        const int rc = gmres_solve(c, b, x, ext_tol, 1000, 100, 1, &its, &rel);
+        const int rc = gmres_solve(c, call, &its, &rel);
         c->timing = timing;
-        c->gm_mask = nullptr;
         if (rc) return rc;
         its_max = std::max(its_max, its);
         rel_max = std::max(rel_max, rel);

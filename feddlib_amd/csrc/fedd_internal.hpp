@@ -277,7 +277,6 @@ struct fedd_ctx {
     int gmres_s = 0;                            // s-step GMRES: Krylov vectors per block (1 ... 16; 0 = 16 from 1.2 M rows per rank, else 8)
     int gmres_tol_blocks = 1;                   // ... tolerances below 1e-9 / 1e-11 take blocks of at most 5 / 3 vectors (0: no cap)
     int gmres_dot_gy = 0;                       // ... column groups in flight per row block of the block dot kernel (0 = by vector length) (A/B)
-    int gmres_dotv = 0;                         // ... launch shape of the block dot kernel (A/B)
     int gmres_s_used = 0;                       // ... the block length of the last solve
     int gmres_spec = 0;                         // ... operator applications of the next block issued before the host reads a block's outcome (A/B switch for multi-GPU runs)
     int gmres_newton = 1;                       // ... Newton block basis (Leja-ordered Ritz shifts) once the first s Arnoldi steps exist; 0 = monomial, blocks <= 8
@@ -285,7 +284,6 @@ struct fedd_ctx {
     int gmres_blocks = 0, gmres_cut_blocks = 0; // ... blocks / blocks that were cut in the last solve
     int gmres_floor = 0;                        // ... the last solve stopped at the rounding floor of b - A x (relres returned = true residual, may exceed rtol)
     double gmres_rec_relres = -1.0;             // ... and the recurrence residual it had reached then (-1: not that case)
-    int gm_x0 = 0;                              // the next solve starts from the vector in d_x ("Zero Initial Guess" = false), set per call by fedd_gmres_x0
     fedd::DevBuf<int32_t> d_node_bin;           // [n_own] compact bin id of each owned node
     fedd::DevBuf<int32_t> d_bin_ptr, d_bin_nodes;   // [nsub+1], [n_own]
     fedd::DevBuf<int32_t> d_sub_n, d_sub_nown;  // [nsub] total / owned dofs of each subdomain
@@ -294,7 +292,6 @@ struct fedd_ctx {
     fedd::DevBuf<double> d_inv;                 // per subdomain [n_i][rp_i] column-major slab
     fedd::DevBuf<double> d_mult;                // [n_cols] multiplicity (averaging)
     bool have_schwarz = false;
-    int md2_nch = 4;                            // k_multidot2: 512-row chunks per workgroup (2 or 4)
     int md2_gy = 0;                             // k_multidot2: column groups in flight per row block (0 = by vector length)
     int halo_overlap = 0;                       // several ranks: interior subdomains first, ghost import of r on a second stream meanwhile
     hipStream_t stream2 = nullptr;              // (created on first use)
@@ -360,7 +357,6 @@ struct fedd_ctx {
     double* h_pinned = nullptr;                 // small pinned host mirror
     int gm_restart_alloc = 0;
     int64_t gm_V_ldv = -1;                      // leading dimension the zeroed padding rows of d_V belong to (s-step solver)
-    int gm_nr = 0;                              // > 1: GMRES runs on stacked vectors X[row * gm_nr + j] (multi.hip; the GDSW extension solves)
     int multi_ch = 4;                           // option "multi_ch": matrix-core steps per flight of gathers in k_apply_multi (4, 8, 16)
     int pat_hash = 1;                           // option "pat_hash": 1 = hashed node-pattern merge for vertex-only elements (symbolic.hip)
     int gmres_fused_blocks = 0;                 // blocks of the last s-step solve whose first update and second dot ran as one sweep
@@ -370,7 +366,6 @@ struct fedd_ctx {
     fedd::DevBuf<double> d_gd_gram;             // [entities * 21] Gram matrices of the entities' functions (selection of the independent ones)
     fedd::DevBuf<int32_t> d_gd_keep;            // [entities] bit masks of the functions kept
     int gdsw_block = 1;                         // option "gdsw_block": 1 = extension solves sixteen columns at a time, 0 = one by one
-    const double* gm_mask = nullptr;            // != nullptr: GMRES solves the constrained system (dofs with mask 0 held), see gmres.hip
 
     // ---- generic scratch ----
     fedd::DevBuf<int32_t> d_itmp0, d_itmp1, d_itmp2;
@@ -525,8 +520,16 @@ int spmm_owned(fedd_ctx* c, double* d_X, double* d_Y, const double* mk, const do
 int schwarz_apply_multi(fedd_ctx* c, double* d_R, double* d_Z, const double* mk);
 
 // gmres.hip
-int gmres_solve(fedd_ctx* c, const double* d_b, double* d_x, double rtol, int max_it, int restart,
-                int use_prec, int* its_out, double* relres_out);
+struct GmresCall {
+    const double* b;                // right-hand side (device, owned rows)
+    double* x;                      // solution; the initial guess if x0
+    double rtol;
+    int max_it, restart, use_prec;
+    bool x0 = false;                // start from the vector in x ("Zero Initial Guess" = false) instead of zero
+    const double* mask = nullptr;   // != nullptr: the constrained system (dofs with mask 0 held), see Frame in gmres.hip
+    int nr = 1;                     // > 1: stacked vectors X[row * nr + j] (multi.hip; the GDSW extension solves)
+};
+int gmres_solve(fedd_ctx* c, const GmresCall& call, int* its_out, double* relres_out);
 int allreduce_sum(fedd_ctx* c, double* d_buf, int n);
 
 // FE tables (fe_tables.cpp): reference-simplex quadrature and basis values

@@ -538,7 +538,7 @@ __global__ __launch_bounds__(256) void k_axpy2(double* __restrict__ V, int64_t l
     }
 }
 
-// out = m o a + (1 - m) o b  (m = 0 / 1 mask): the constrained operator of the interior solves, see gmres_solve
+// out = m o a + (1 - m) o b  (m = 0 / 1 mask): the constrained operator of the interior solves, see Frame::mk
 __global__ void k_mask_mix(const double* __restrict__ m, const double* __restrict__ a, const double* __restrict__ b,
                            double* __restrict__ out, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -580,9 +580,6 @@ int allreduce_sum(fedd_ctx* c, double* d_buf, int n) {
 // Laplace, 27-node boxes, Q1: 29 iterations to 1e-12 after one step, 14 after two), so the start takes two steps:
 // x_0 + Pc (b - A x_0), the reference's pre-apply for x_0 = 0, refined once.  At a restart the step removes what the shift let
 // grow during the cycle.
-static bool cycle_projection(const fedd_ctx* c, int use_prec) {
-    return use_prec && levels_mult(c) && !c->gm_mask && c->gm_nr <= 1;
-}
 static int coarse_project(fedd_ctx* c, const double* d_b, double* d_x, double* d_r, int use_compact, int steps) {
     const int64_t n = c->n_rows;
     for (int k = 0; k < steps; ++k) {
@@ -593,119 +590,302 @@ static int coarse_project(fedd_ctx* c, const double* d_b, double* d_x, double* d
     return 0;
 }
 
-// GMRES with the delayed second Gram-Schmidt pass (kernels and formulas above).  Same iterates as
-// the two-pass variant below in exact arithmetic; one operator application more per restart cycle
-// (the lag), half the passes over the basis and one all-reduce per iteration.
-static int gmres_solve_dcgs2(fedd_ctx* c, const double* d_b, double* d_x, double rtol, int max_it, int restart,
-                             int use_prec, int* its_out, double* relres_out) {
-    const int64_t n = c->n_rows;
-    const int m = std::min(restart, max_it);
-    const int64_t ldv = (n + 15) & ~(int64_t)15;
-    FEDD_CHECK(m + 2 <= 1024, "gmres: restart length above 1022 is not supported");
-    const int nblk = (int)((n + MD_ROWS - 1) / MD_ROWS), nblk2 = (int)((n + AX_ROWS - 1) / AX_ROWS);
-    FEDD_TRY(c->d_V.ensure((size_t)(m + 1) * ldv));
-    if (c->gm_V_ldv != ldv) c->gm_V_ldv = -1;   // another column layout: the s-step solver clears the basis before its next use
-    // work vectors carry room for the ghost entries behind the owned ones (several ranks): the halo import of an
-    // operator input then goes straight into the vector, without a copy into a column-length buffer first
-    const int64_t nc = (std::max<int64_t>(n, c->n_cols) + 15) & ~(int64_t)15;
-    FEDD_TRY(c->d_w.ensure(std::max<size_t>((size_t)2 * nc, c->d_w.cap)));   // u | w~
-    FEDD_TRY(c->d_Z.ensure((size_t)nc * 2));
-    FEDD_TRY(c->d_part.ensure(std::max((size_t)(2 * m + 4) * nblk * 2, (size_t)nblk2)));
-    Off o;
-    Off2 o2;
-    int p = 0;
-    o.H = p; p += (m + 1) * m;
-    o.cs = p; p += m;
-    o.sn = p; p += m;
-    o.g = p; p += m + 1;
-    o.h1 = p; p += m + 2;
-    o.h2 = p; p += m + 2;
-    o.nrm = p; p += 4;
-    o.y = p; p += m;
-    o.misc = p; p += 8;
-    o2.Hraw = p; p += (m + 1) * m;
-    o2.hp = p; p += m + 2;
-    o2.st = p; p += 2 * m + 4;
-    o2.cf = p; p += 2 * m + 4;
-    FEDD_TRY(c->d_small.ensure((size_t)p + 8));
-    double* S = c->d_small.p;
-    double* V = c->d_V.p;
-    double* u = c->d_w.p;        // first-pass result / next basis vector before its second pass
-    double* wt = c->d_w.p + nc;  // B u
-    double* z = c->d_Z.p;        // M^-1 v
-    double* r = c->d_Z.p + nc;   // residual / V y
-    const dim3 gn((unsigned)((n + 255) / 256)), blk(256);
-    hipStream_t st = c->stream;
+namespace {
 
-    auto norm2_into = [&](const double* v, double* out) -> int {
+// What the three solvers share, built once per solve: sizes, the layout of the scalars, the work vectors, the operator, the
+// start, the solution update, the true residual and the tail.  A solver appends its own scalars behind `p` before alloc().
+struct Frame {
+    fedd_ctx* c;
+    const GmresCall* a;
+    // a->nr > 1: stacked vectors X[row * nr + j] (nr right-hand sides with one matrix: the GDSW extension solves); the
+    // operator and the preconditioner are the stacked ones of multi.hip, everything else sees vectors nr times as long
+    int nr;
+    // tail: the work vectors carry room for the ghost entries behind the owned ones (several ranks): the halo import of an
+    // operator input then goes straight into the vector, without a copy into a column-length buffer first
+    bool tail, ghosts;
+    int64_t n, ldv, nc;    // vector length, leading dimension of the basis (128-byte aligned columns), stride of the work vectors
+    int m, nblk, nblk2;
+    Off o;
+    int p;                 // doubles of d_small taken so far
+    double *S, *V, *w0, *w1, *z, *r;   // scalars, basis, two work vectors (w1 only with tail), M^-1 v, residual / V y
+    dim3 gn, blk;
+    hipStream_t st;
+    // mk != nullptr: the constrained system  A^ = D A D + (I - D),  M^^-1 = D M^-1 D + (I - D)  with D = diag(mask): dofs
+    // with mask 0 are held at the value the right-hand side gives them and decouple (the discrete harmonic extensions of
+    // the GDSW coarse space: interface dofs held, interiors solved).  The inputs already carry D x = x wherever it
+    // matters: in = D in + (I - D) in.
+    const double* mk;
+    bool project;          // every cycle starts from a coarse-orthogonal residual (comment above)
+    double beta0 = 0.0, relres = 0.0;
+    int its = 0;
+
+    int setup(fedd_ctx* ctx, const GmresCall& call, bool with_tail) {
+        c = ctx;
+        a = &call;
+        nr = std::max(call.nr, 1);
+        tail = with_tail;
+        ghosts = c->n_cols != c->n_rows || !c->halo.peers.empty();
+        n = c->n_rows * nr;
+        m = std::min(call.restart, call.max_it);
+        ldv = (n + 15) & ~(int64_t)15;
+        FEDD_CHECK(m + 2 <= 1024, "gmres: restart length above 1022 is not supported");
+        nblk = (int)((n + MD_ROWS - 1) / MD_ROWS);
+        nblk2 = (int)((n + AX_ROWS - 1) / AX_ROWS);
+        nc = tail ? (std::max<int64_t>(c->n_rows, c->n_cols) * nr + 15) & ~(int64_t)15 : n;
+        p = 0;
+        o.H = p; p += (m + 1) * m;
+        o.cs = p; p += m;
+        o.sn = p; p += m;
+        o.g = p; p += m + 1;
+        o.h1 = p; p += m + 2;
+        o.h2 = p; p += m + 2;
+        o.nrm = p; p += 4;
+        o.y = p; p += m;
+        o.misc = p; p += 8;
+        gn = dim3((unsigned)((n + 255) / 256));
+        blk = dim3(256);
+        st = c->stream;
+        mk = call.mask;
+        project = call.use_prec && levels_mult(c) && !mk && nr <= 1;
+        return 0;
+    }
+
+    // block_kernels (s-step solver): they read whole 16-byte row pairs and rely on the padding rows [n, ldv) of every basis
+    // column being zero (and on finite data everywhere): a freshly (re)allocated basis, or one last used with another
+    // vector length, is cleared
+    int alloc(size_t part, bool block_kernels) {
+        const double* before = c->d_V.p;
+        FEDD_TRY(c->d_V.ensure((size_t)(m + 1) * ldv));
+        if (!block_kernels) {
+            if (c->gm_V_ldv != ldv) c->gm_V_ldv = -1;   // another column layout: the s-step solver clears the basis before its next use
+        } else {
+            // (a buffer that another vector length used holds finite values everywhere: only its padding rows need the clearing)
+            if (c->d_V.p != before) FEDD_HIP(hipMemsetAsync(c->d_V.p, 0, c->d_V.cap * sizeof(double), st));
+            else if (c->gm_V_ldv != ldv && ldv != n) FEDD_HIP(hipMemsetAsync(c->d_V.p, 0, (size_t)(m + 1) * ldv * sizeof(double), st));
+            c->gm_V_ldv = ldv;
+        }
+        FEDD_TRY(c->d_w.ensure(std::max<size_t>((size_t)(tail ? 2 : 1) * nc, c->d_w.cap)));
+        FEDD_TRY(c->d_Z.ensure((size_t)nc * (nr > 1 && ghosts ? 3 : 2)));   // (stacked, several ranks: + a copy with a ghost tail)
+        FEDD_TRY(c->d_part.ensure(part));
+        FEDD_TRY(c->d_small.ensure((size_t)p + 8));
+        S = c->d_small.p;
+        V = c->d_V.p;
+        w0 = c->d_w.p;
+        w1 = c->d_w.p + nc;
+        z = c->d_Z.p;
+        r = c->d_Z.p + nc;
+        return 0;
+    }
+
+    int norm2(const double* v, double* out) {   // out[0] = v.v (global)
         hipLaunchKernelGGL(k_multidot, dim3(nblk, 1), blk, 0, st, v, ldv, n, 0, v, c->d_part.p, nblk, (const int32_t*)nullptr);
         hipLaunchKernelGGL(k_reduce_cols, dim3(1), blk, 0, st, (const double*)c->d_part.p, out, nblk, (const int32_t*)nullptr);
         return allreduce_sum(c, out, 1);
-    };
-    // c->gm_mask != nullptr: the constrained system  A^ = D A D + (I - D),  M^^-1 = D M^-1 D + (I - D)  with
-    // D = diag(mask): dofs with mask 0 are held at the value the right-hand side gives them and decouple (the
-    // discrete harmonic extensions of the GDSW coarse space: interface dofs held, interiors solved).  The inputs
-    // already carry D x = x wherever it matters: in = D in + (I - D) in.
-    const double* mk = c->gm_mask;
-    auto apply_B = [&](const double* in, double* out) -> int {  // out = A M^-1 in
-        const bool tail = in == u;     // u, z and r have a ghost tail, a basis column does not
-        if (use_prec) FEDD_TRY(schwarz_apply(c, in, z, tail));
+    }
+    // the host reads sqrt(S[nrm + 3]) (every rank takes the same decision)
+    int read_norm(double* out) {
+        FEDD_HIP(hipMemcpyAsync(c->h_pinned, S + o.nrm + 3, sizeof(double), hipMemcpyDeviceToHost, st));
+        FEDD_HIP(hipStreamSynchronize(st));
+        *out = std::sqrt(std::max(c->h_pinned[0], 0.0));
+        return 0;
+    }
+
+    // out = A M^-1 in - theta in  (in_tail: `in` is a work vector with a ghost tail, a basis column has none; the shift rides
+    // in the SpMV kernel's store)
+    int apply(const double* in, double* out, bool in_tail = false, double theta = 0.0) {
+        const int use_prec = a->use_prec;
+        if (nr > 1) {       // masks ride in the kernels' stores
+            double* src = const_cast<double*>(in);
+            if (ghosts) {
+                src = c->d_Z.p + 2 * nc;
+                FEDD_HIP(hipMemcpyAsync(src, in, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+            }
+            FEDD_TRY(schwarz_apply_multi(c, src, z, mk));
+            return spmm_owned(c, z, out, mk, z);
+        }
+        if (use_prec) FEDD_TRY(schwarz_apply(c, in, z, in_tail));
         if (mk) {
             // z <- D M^-1 D in + (I - D) in   (M^-1 D in: the masked entries of `in` are excluded by a copy)
             if (use_prec) hipLaunchKernelGGL(k_mask_mix, gn, blk, 0, st, mk, (const double*)z, in, z, n);
             else FEDD_HIP(hipMemcpyAsync(z, in, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-            FEDD_TRY(spmv_owned(c, z, out, true));
+            FEDD_TRY(spmv_owned(c, z, out, tail));
             hipLaunchKernelGGL(k_mask_mix, gn, blk, 0, st, mk, (const double*)out, (const double*)z, out, n);
             return 0;
         }
-        return spmv_owned(c, use_prec ? z : in, out, use_prec ? true : tail);
-    };
-
-    if (c->gm_x0 && !mk) {   // "Zero Initial Guess" = false (LinearSolver_def.hpp:76-78): d_x holds x_0, r_0 = b - A x_0
-        FEDD_TRY(spmv_owned(c, d_x, wt));
-        hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, d_b, -1.0, (const double*)wt, r, n);
-    } else {
-        FEDD_HIP(hipMemsetAsync(d_x, 0, (size_t)n * sizeof(double), st));  // "Zero Initial Guess" (LinearSolver_def.hpp:76-78)
-        FEDD_HIP(hipMemcpyAsync(r, d_b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+        return spmv_owned(c, use_prec ? z : in, out, use_prec ? tail : in_tail, theta != 0.0 ? in : nullptr, theta);
     }
-    const bool project = cycle_projection(c, use_prec);
-    if (project) FEDD_TRY(coarse_project(c, d_b, d_x, r, -1, 2));
-    FEDD_TRY(norm2_into(r, S + o.nrm + 3));
-    FEDD_HIP(hipMemcpyAsync(c->h_pinned, S + o.nrm + 3, sizeof(double), hipMemcpyDeviceToHost, st));
-    FEDD_HIP(hipStreamSynchronize(st));
-    const double beta0 = std::sqrt(c->h_pinned[0]);
-    int its = 0;
-    double relres = beta0 > 0 ? 1.0 : 0.0;
-    if (!(beta0 > 0)) {
-        if (its_out) *its_out = 0;
-        if (relres_out) *relres_out = 0.0;
+
+    // r = b - A x, the product landing in ax (which may be r)
+    int residual(double* x, double* ax, bool x_tail, int use_compact) {
+        if (nr > 1) {
+            FEDD_TRY(spmm_owned(c, x, ax, mk, x));
+        } else {
+            FEDD_TRY(spmv_owned(c, x, ax, x_tail, nullptr, 0.0, use_compact));
+            if (mk) hipLaunchKernelGGL(k_mask_mix, gn, blk, 0, st, mk, (const double*)ax, (const double*)x, ax, n);
+        }
+        hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, a->b, -1.0, (const double*)ax, r, n);
         return 0;
     }
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    for (int q = 0; q < 2; ++q) FEDD_HIP(hipEventCreateWithFlags(&ev[q], hipEventDisableTiming));
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard() {
-            for (int q = 0; q < 2; ++q)
-                if (e[q]) (void)hipEventDestroy(e[q]);
+
+    // initial guess, two projection steps, beta0 = ||r_0|| on the host (0: nothing to solve, report() and return)
+    int start(double* ax, int use_compact) {
+        if (a->x0 && !mk && nr == 1) {   // "Zero Initial Guess" = false (LinearSolver_def.hpp:76-78): x holds x_0, r_0 = b - A x_0
+            FEDD_TRY(residual(a->x, ax, false, -1));
+        } else {
+            FEDD_HIP(hipMemsetAsync(a->x, 0, (size_t)n * sizeof(double), st));  // "Zero Initial Guess" (LinearSolver_def.hpp:76-78)
+            FEDD_HIP(hipMemcpyAsync(r, a->b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
         }
-    } ev_guard{ev};
+        if (project) FEDD_TRY(coarse_project(c, a->b, a->x, r, use_compact, 2));
+        FEDD_TRY(norm2(r, S + o.nrm + 3));
+        FEDD_TRY(read_norm(&beta0));
+        its = 0;
+        relres = beta0 > 0 ? 1.0 : 0.0;
+        return 0;
+    }
+
+    // dst = x + M^-1 (V y) with `cols` columns of this cycle (combined: sum_c y_c V_c is already in r)
+    int add_correction(int cols, double* dst, bool combined = false) {
+        const double* x = a->x;
+        if (!combined) {
+            hipLaunchKernelGGL(k_backsolve, dim3(1), dim3(256), (size_t)(cols + 1) * sizeof(double), st, S, o, cols, m);
+            hipLaunchKernelGGL(k_combine, dim3((unsigned)((n + AX_ROWS - 1) / AX_ROWS)), blk, 0, st, (const double*)V, ldv, n, cols, (const double*)(S + o.y), r);
+        }
+        if (nr > 1) {
+            FEDD_TRY(schwarz_apply_multi(c, r, z, mk));
+            hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, x, 1.0, (const double*)z, dst, n);
+        } else if (a->use_prec) {
+            FEDD_TRY(schwarz_apply(c, r, z, tail));
+            if (mk) hipLaunchKernelGGL(k_mask_mix, gn, blk, 0, st, mk, (const double*)z, (const double*)r, z, n);
+            hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, x, 1.0, (const double*)z, dst, n);
+        } else {
+            hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, x, 1.0, (const double*)r, dst, n);
+        }
+        return 0;
+    }
+
+    // r = b - A x [one projection step], ||r||^2 -> S[nrm + 3].  use_compact: -1 = the stream the Krylov process runs on;
+    // 0 = the parity CSR (every stored entry), like fedd_spmv (the compacted stream leaves out sub-ulp cancellation noise)
+    int true_residual(double* x, double* ax, bool x_tail, int use_compact, bool proj) {
+        FEDD_TRY(residual(x, ax, x_tail, use_compact));
+        if (proj) FEDD_TRY(coarse_project(c, a->b, a->x, r, use_compact, 1));
+        return norm2(r, S + o.nrm + 3);
+    }
+
+    void report(int* its_out, double* relres_out) const {
+        if (its_out) *its_out = its;
+        if (relres_out) *relres_out = relres;
+    }
+    int finish(int* its_out, double* relres_out) {
+        FEDD_HIP(hipGetLastError());
+        FEDD_HIP(hipStreamSynchronize(st));
+        report(its_out, relres_out);
+        return 0;
+    }
+};
+
+// The convergence test of the one-vector solvers: iteration j is read on the host while iteration j + 1 is already queued
+// (two pinned slots of three doubles -- residual, 1 / norm, norm -- one event each): the device never waits for the host
+// round trip.  An iteration queued past convergence only writes basis column j + 2, Hessenberg column j + 1 and
+// g[j+1..j+2], none of which the update of x with cols = j + 1 columns reads.
+struct LaggedCheck {
+    Frame& f;
+    // what a breakdown (norm <= 0) that has not converged yields: 2 = the cycle ends and the true residual decides (DCGS2:
+    // beta^2 = u.u - s.s <= 0 is a lucky breakdown, or cancellation after the first pass lost orthogonality); 1 = stop
+    // (CGS2: ||w|| after both passes, behind the DGKS gate, is a true breakdown)
+    const int on_breakdown;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int cols = 0, issued = 0, checked = 0, queued = 0;   // of this cycle: columns read, iterations issued / read / queued
+
+    LaggedCheck(Frame& frame, int breakdown) : f(frame), on_breakdown(breakdown) {}
+    ~LaggedCheck() {
+        for (int q = 0; q < 2; ++q)
+            if (ev[q]) (void)hipEventDestroy(ev[q]);
+    }
+    int create() {
+        for (int q = 0; q < 2; ++q) FEDD_HIP(hipEventCreateWithFlags(&ev[q], hipEventDisableTiming));
+        return 0;
+    }
+    void begin_cycle() {
+        cols = checked = queued = 0;
+        issued = f.its;
+    }
+    int check(int jj) {   // 0 = go on, 1 = converged, on_breakdown, < 0 = error
+        if (hipEventSynchronize(ev[jj & 1]) != hipSuccess) return -1;
+        const double* hp = f.c->h_pinned + 4 * (jj & 1);
+        ++f.its;
+        ++checked;
+        cols = jj + 1;
+        f.relres = hp[0] / f.beta0;
+        const bool breakdown = !(hp[2] > 0.0);
+        return f.relres <= f.a->rtol ? 1 : (breakdown ? on_breakdown : 0);
+    }
+    // iteration j is in the stream (copy: its three numbers still have to be copied to the host): read iteration j - 1
+    int record(int j, bool copy, int* stop) {
+        if (copy) FEDD_HIP(hipMemcpyAsync(f.c->h_pinned + 4 * (j & 1), f.S + f.o.misc, 3 * sizeof(double), hipMemcpyDeviceToHost, f.st));
+        FEDD_HIP(hipEventRecord(ev[j & 1], f.st));
+        ++issued;
+        ++queued;
+        if (j > 0) {
+            *stop = check(j - 1);
+            FEDD_CHECK(*stop >= 0, "gmres: waiting for iteration %d failed", j - 1);
+        }
+        return 0;
+    }
+    int drain(int* stop) {   // end of the cycle: the iteration still in flight
+        if (!*stop && checked < queued) {
+            *stop = check(queued - 1);
+            FEDD_CHECK(*stop >= 0, "gmres: waiting for iteration %d failed", queued - 1);
+        }
+        return 0;
+    }
+};
+
+}  // namespace
+
+// GMRES with the delayed second Gram-Schmidt pass (kernels and formulas above).  Same iterates as
+// the two-pass variant below in exact arithmetic; one operator application more per restart cycle
+// (the lag), half the passes over the basis and one all-reduce per iteration.
+static int gmres_solve_dcgs2(fedd_ctx* c, const GmresCall& call, int* its_out, double* relres_out) {
+    Frame f;
+    FEDD_TRY(f.setup(c, call, true));
+    const int64_t n = f.n, ldv = f.ldv;
+    const int m = f.m, nblk = f.nblk, nblk2 = f.nblk2, max_it = call.max_it;
+    const Off o = f.o;
+    Off2 o2;
+    o2.Hraw = f.p; f.p += (m + 1) * m;
+    o2.hp = f.p; f.p += m + 2;
+    o2.st = f.p; f.p += 2 * m + 4;
+    o2.cf = f.p; f.p += 2 * m + 4;
+    FEDD_TRY(f.alloc(std::max((size_t)(2 * m + 4) * nblk * 2, (size_t)nblk2), false));
+    double* S = f.S;
+    double* V = f.V;
+    double* u = f.w0;    // first-pass result / next basis vector before its second pass
+    double* wt = f.w1;   // B u
+    double* r = f.r;
+    const dim3 gn = f.gn, blk = f.blk;
+    hipStream_t st = f.st;
+
+    FEDD_TRY(f.start(wt, -1));
+    if (!(f.beta0 > 0)) {
+        f.report(its_out, relres_out);
+        return 0;
+    }
+    LaggedCheck lag(f, 2);
+    FEDD_TRY(lag.create());
     // launch shape of k_multidot2: 2048 rows per workgroup, one grid row per group of 8 columns.
     // Measured alternatives on cfg 2 (ms per step): 1024 rows 43.9, column groups looped inside one
     // grid row 46.4 (2048 rows) / 44.5 (1024 rows), 2 or 4 grid rows 42.7-44.6; this one 43.1.
     // grid rows of k_multidot2 = column groups in flight per row block: every workgroup reads its rows of u and B u once
     // and keeps them across its column groups, so fewer grid rows = fewer re-reads of those two vectors (PMC: 1.24x the
     // algorithmic bytes with one group per workgroup at 214^3); enough of them to fill the GPU when the vectors are short
-    const int md2_nch = c->md2_nch == 2 ? 2 : 4;
-    const int64_t nblkd_ = (n + 512 * md2_nch - 1) / (512 * md2_nch);
-    const int md2_gy = c->md2_gy > 0 ? c->md2_gy : (int)std::max<int64_t>(1, (2048 + nblkd_ - 1) / nblkd_);
-    const int nblkd = (int)((n + 512 * md2_nch - 1) / (512 * md2_nch));
+    const int nblkd = (int)((n + 2047) / 2048);
+    const int md2_gy = c->md2_gy > 0 ? c->md2_gy : (int)std::max<int64_t>(1, (2048 + nblkd - 1) / nblkd);
     bool converged = false;
-    while (!converged && its < max_it) {
+    while (!converged && f.its < max_it) {
         // v_1 = r / ||r||, then the (not delayed) first pass of B v_1: hp = v_1 . w, u = w - v_1 hp
         hipLaunchKernelGGL(k_cycle_init, dim3(1), dim3(1), 0, st, S, o, m, (const double*)(S + o.nrm + 3));
         hipLaunchKernelGGL(k_scale_to, gn, blk, 0, st, (const double*)r, (const double*)(S + o.misc + 1), V, n);
-        FEDD_TRY(apply_B(V, u));
+        FEDD_TRY(f.apply(V, u));
         {
             ScopedTimer t(c, FEDD_T_ORTHO);
             hipLaunchKernelGGL(k_multidot, dim3(nblk, 1), blk, 0, st, (const double*)V, ldv, n, 1, (const double*)u,
@@ -717,36 +897,18 @@ static int gmres_solve_dcgs2(fedd_ctx* c, const double* d_b, double* d_x, double
                                u, c->d_part.p, (const int32_t*)nullptr);
             t.stop();
         }
-        int kfin = 0;  // finalised columns of this cycle
-        int issued = its, checked = 0, queued = 0;
-        auto check = [&](int jj) -> int {
-            if (hipEventSynchronize(ev[jj & 1]) != hipSuccess) return -1;
-            const double* hp = c->h_pinned + 4 * (jj & 1);
-            ++its;
-            ++checked;
-            kfin = jj + 1;
-            relres = hp[0] / beta0;
-            // beta^2 = u.u - s.s <= 0: a lucky breakdown, or cancellation after the first pass lost
-            // orthogonality.  Only the implicit residual says "converged"; otherwise the cycle ends here and
-            // the true residual decides (below).
-            const bool breakdown = !(hp[2] > 0.0);
-            return relres <= rtol ? 1 : (breakdown ? 2 : 0);
-        };
-        bool broke = false;
-        for (int j = 0; j < m && issued < max_it; ++j) {
+        lag.begin_cycle();
+        int stop = 0;   // 1: converged, 2: breakdown
+        for (int j = 0; j < m && lag.issued < max_it && !stop; ++j) {
             const int k = j + 1;  // basis vectors final before this step; the step finalises column j of H
-            FEDD_TRY(apply_B(u, wt));
+            FEDD_TRY(f.apply(u, wt, true));
             {
                 ScopedTimer t(c, FEDD_T_ORTHO);
                 const int ncg = (k + 1 + MD2_CG - 1) / MD2_CG;
                 ScopedTimer td(c, FEDD_T_GS_DOT);
                 td.bytes(8.0 * (double)n * (k + 2));   // k basis columns, u, B u
-                if (md2_nch == 2)
-                    hipLaunchKernelGGL(k_multidot2<2>, dim3(nblkd, std::min(md2_gy, ncg)), blk, 0, st, (const double*)V, ldv, n,
-                                       k, (const double*)u, (const double*)wt, c->d_part.p, nblkd);
-                else
-                    hipLaunchKernelGGL(k_multidot2<4>, dim3(nblkd, std::min(md2_gy, ncg)), blk, 0, st, (const double*)V, ldv, n,
-                                       k, (const double*)u, (const double*)wt, c->d_part.p, nblkd);
+                hipLaunchKernelGGL(k_multidot2<4>, dim3(nblkd, std::min(md2_gy, ncg)), blk, 0, st, (const double*)V, ldv, n,
+                                   k, (const double*)u, (const double*)wt, c->d_part.p, nblkd);
                 td.stop();
                 hipLaunchKernelGGL(k_reduce_cols, dim3(2 * k + 2), blk, 0, st, (const double*)c->d_part.p, S + o2.st, nblkd,
                                    (const int32_t*)nullptr);
@@ -762,56 +924,23 @@ static int gmres_solve_dcgs2(fedd_ctx* c, const double* d_b, double* d_x, double
                 }
                 t.stop();
             }
-            if (!c->h_pinned_dev)
-                FEDD_HIP(hipMemcpyAsync(c->h_pinned + 4 * (j & 1), S + o.misc, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-            FEDD_HIP(hipEventRecord(ev[j & 1], st));
-            ++issued;
-            ++queued;
-            if (j > 0) {
-                const int rc = check(j - 1);
-                FEDD_CHECK(rc >= 0, "gmres: waiting for iteration %d failed", j - 1);
-                if (rc) {
-                    converged = rc == 1;
-                    broke = rc == 2;
-                    break;
-                }
-            }
+            FEDD_TRY(lag.record(j, !c->h_pinned_dev, &stop));
         }
-        if (!converged && !broke && checked < queued) {
-            const int rc = check(queued - 1);
-            FEDD_CHECK(rc >= 0, "gmres: waiting for iteration %d failed", queued - 1);
-            converged = rc == 1;
-            broke = rc == 2;
-        }
-        // x += M^-1 (V y) with the kfin finalised columns
-        hipLaunchKernelGGL(k_backsolve, dim3(1), dim3(256), (size_t)(kfin + 1) * sizeof(double), st, S, o, kfin, m);
-        hipLaunchKernelGGL(k_combine, dim3((unsigned)((n + AX_ROWS - 1) / AX_ROWS)), blk, 0, st, (const double*)V, ldv, n, kfin, (const double*)(S + o.y), r);
-        if (use_prec) {
-            FEDD_TRY(schwarz_apply(c, r, z, true));
-            if (mk) hipLaunchKernelGGL(k_mask_mix, gn, blk, 0, st, mk, (const double*)z, (const double*)r, z, n);
-            hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, (const double*)d_x, 1.0, (const double*)z, d_x, n);
-        } else {
-            hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, (const double*)d_x, 1.0, (const double*)r, d_x, n);
-        }
-        if (!converged && (its < max_it || broke)) {
-            FEDD_TRY(spmv_owned(c, d_x, r));
-            if (mk) hipLaunchKernelGGL(k_mask_mix, gn, blk, 0, st, mk, (const double*)r, (const double*)d_x, r, n);
-            hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, d_b, -1.0, (const double*)r, r, n);
-            if (project) FEDD_TRY(coarse_project(c, d_b, d_x, r, -1, 1));
-            FEDD_TRY(norm2_into(r, S + o.nrm + 3));
-            if (broke) {   // rare path: the host reads the true residual (every rank takes the same decision)
-                FEDD_HIP(hipMemcpyAsync(c->h_pinned, S + o.nrm + 3, sizeof(double), hipMemcpyDeviceToHost, st));
-                FEDD_HIP(hipStreamSynchronize(st));
-                relres = std::sqrt(std::max(c->h_pinned[0], 0.0)) / beta0;
-                if (relres <= rtol) converged = true;
+        FEDD_TRY(lag.drain(&stop));
+        converged = stop == 1;
+        const bool broke = stop == 2;   // only the implicit residual says "converged"; here the true residual decides
+        FEDD_TRY(f.add_correction(lag.cols, call.x));   // the columns whose results the host has read
+        if (!converged && (f.its < max_it || broke)) {
+            FEDD_TRY(f.true_residual(call.x, r, false, -1, f.project));
+            if (broke) {   // rare path: the host reads the true residual
+                double ta = 0.0;
+                FEDD_TRY(f.read_norm(&ta));
+                f.relres = ta / f.beta0;
+                if (f.relres <= call.rtol) converged = true;
             }
         }
     }
-    FEDD_HIP(hipGetLastError());
-    FEDD_HIP(hipStreamSynchronize(st));
-    if (its_out) *its_out = its;
-    if (relres_out) *relres_out = relres;
-    return 0;
+    return f.finish(its_out, relres_out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -914,33 +1043,29 @@ constexpr int SS_LDS_GROUPS = 32;   // column groups whose wave totals are parke
 // (W_j = V_{k+j}); the W tile stays in registers across the column groups, every basis column is read once.
 // The wave totals of a column group are parked in LDS and added (fixed order) once per SS_LDS_GROUPS groups:
 // no barrier between the loads of consecutive groups.
-// HV = 2 ("split"): the two halves of the workgroup take the SAME rows and one half of the block's columns each (S / 2 per
-// lane): a basis value is then loaded by two lanes of the workgroup (the second finds it in the L1), but a lane's register
-// tile and reduction are those of the 8-column kernel, which runs at 0.69 of peak where the 16-column tile (232 VGPRs, two
-// FMAs and two exchanges per byte) reaches 0.59.
-template <int S, int NCH, int SS_CG, int HV = 1>
+template <int S, int NCH, int SS_CG>
 __global__ __launch_bounds__(256) void k_blockdot(const double* __restrict__ V, int64_t ldv, int64_t n, int k, int sa_req,
                                                   const int32_t* __restrict__ d_sa, double* __restrict__ partial, int nblk) {
-    constexpr int SW = S / HV;              // block columns per lane
-    constexpr int NV = SS_CG * SW;
-    constexpr int LH = 256 / HV;            // lanes of a half
-    constexpr int WPH = 4 / HV;             // waves of a half
+    constexpr int NV = SS_CG * S;
     static_assert(NV == 16 || NV == 32 || NV == 64, "block size");
     __shared__ double sh[SS_LDS_GROUPS][4][NV];
     const int sa = d_sa ? min(*d_sa, sa_req) : sa_req;
     if (sa <= 0) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = tid / LH, th = tid % LH;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // (th == tid and half == 0 under the launch bounds.  They stay spelled this way: the compiler folds them late, and with
+    // plain tid / 0 it schedules the loads of the three instantiations differently from the code that was measured)
+    const int half = tid / 256, th = tid % 256;
     RowPair rp[NCH];
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch)
-        rp[ch] = row_pair((int64_t)blockIdx.x * (2 * LH * NCH) + 2 * LH * ch + 2 * th, n);
-    double2 w[SW][NCH];
+        rp[ch] = row_pair((int64_t)blockIdx.x * (512 * NCH) + 512 * ch + 2 * th, n);
+    double2 w[S][NCH];
 #pragma unroll
-    for (int j = 0; j < SW; ++j)
+    for (int j = 0; j < S; ++j)
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) {
             // (columns past sa: any readable column, zeroed by the select)
-            const int jj = half * SW + j;
+            const int jj = half * S + j;
             const double2 t = ldp<false>(V + (int64_t)(k + (jj < sa ? jj : 0)) * ldv, rp[ch]);
             w[j][ch].x = jj < sa ? t.x : 0.0;
             w[j][ch].y = jj < sa ? t.y : 0.0;
@@ -951,15 +1076,10 @@ __global__ __launch_bounds__(256) void k_blockdot(const double* __restrict__ V, 
     constexpr int GRP = 64 / NV;
     auto flush = [&](int count) {
         __syncthreads();
-        for (int e = tid; e < count * NV * HV; e += 256) {
-            const int g = e / (NV * HV), rem = e % (NV * HV), hv = rem / NV, idx = rem % NV;
-            const int col = (first_cg + g * (int)gridDim.y) * SS_CG + idx / SW;
-            if (col < ncol) {
-                double tsum = sh[g][hv * WPH][idx];
-#pragma unroll
-                for (int q = 1; q < WPH; ++q) tsum += sh[g][hv * WPH + q][idx];
-                partial[((int64_t)col * S + hv * SW + (idx % SW)) * nblk + blockIdx.x] = tsum;
-            }
+        for (int e = tid; e < count * NV; e += 256) {
+            const int g = e / NV, idx = e % NV;
+            const int col = (first_cg + g * (int)gridDim.y) * SS_CG + idx / S;
+            if (col < ncol) partial[((int64_t)col * S + (idx % S)) * nblk + blockIdx.x] = ((sh[g][0][idx] + sh[g][1][idx]) + sh[g][2][idx]) + sh[g][3][idx];
         }
         __syncthreads();
     };
@@ -985,11 +1105,11 @@ __global__ __launch_bounds__(256) void k_blockdot(const double* __restrict__ V, 
 #pragma unroll
         for (int cc = 0; cc < SS_CG; ++cc)
 #pragma unroll
-            for (int j = 0; j < SW; ++j) {
+            for (int j = 0; j < S; ++j) {
                 double s = 0.0;
 #pragma unroll
                 for (int ch = 0; ch < NCH; ++ch) s += v[cc][ch].x * w[j][ch].x + v[cc][ch].y * w[j][ch].y;
-                acc[cc * SW + j] = s;
+                acc[cc * S + j] = s;
             }
         // the next group's loads are in flight while this one is reduced
         if (cg + (int)gridDim.y < ncg) load_group(cg + gridDim.y);
@@ -1560,76 +1680,44 @@ static void leja_order(double* v, int n) {
     std::copy(out.begin(), out.end(), v);
 }
 
+// s: the block length asked for (S: the kernels' block size, >= the blocks actually run)
 template <int S>
-static int gmres_solve_sstep(fedd_ctx* c, const double* d_b, double* d_x, double rtol, int max_it, int restart,
-                             int use_prec, int* its_out, double* relres_out) {
-    // c->gm_nr > 1: stacked vectors X[row * nr + j] (nr right-hand sides with one matrix: the GDSW extension solves); the
-    // operator and the preconditioner are the stacked ones of multi.hip, everything else sees vectors nr times as long
-    const int nr = c->gm_nr > 1 ? c->gm_nr : 1;
-    FEDD_CHECK(nr == 1 || (nr == MULTI_NR && use_prec && multi_rhs_ok(c)), "gmres: stacked solve with %d right-hand sides", nr);
-    const int64_t n = c->n_rows * nr;
-    const int m = std::min(restart, max_it);
-    const int64_t ldv = (n + 15) & ~(int64_t)15;
-    FEDD_CHECK(m + 2 <= 1024, "gmres: restart length above 1022 is not supported");
-    const int nblk = (int)((n + MD_ROWS - 1) / MD_ROWS), nblk2 = (int)((n + AX_ROWS - 1) / AX_ROWS);
-    // block dot kernel: 512 NCH rows per workgroup, CG columns per transpose reduction (option "gmres_dotv": 0 = 2 chunks x ss_cg
-    // columns; 1 = 1 chunk x ss_cg; 2 = 1 chunk x 2 ss_cg)
-    const int dotv = c->gmres_dotv;
-    // ("gmres_dotv" 3: S = 16 as two 8-column halves per workgroup over the same rows -- measured slower, 1.12 against 1.08 ms per
-    // sweep at cfg 3: the second half's loads do not all hit the L1)
-    const bool dot_split = S == 16 && dotv == 3;
-    const int dot_nch = dot_split ? 2 : (dotv == 0 ? 2 : 1), dot_cg = dot_split ? 4 : (dotv == 2 ? std::min(64 / S, 2 * ss_cg(S)) : ss_cg(S));
-    const int nblkd = dot_split ? (int)((n + 511) / 512) : (int)((n + 512 * dot_nch - 1) / (512 * dot_nch));
-    {
-        // the block kernels read whole 16-byte row pairs and rely on the padding rows [n, ldv) of every column being zero
-        // (and on finite data everywhere): a freshly (re)allocated basis, or one last used with another vector length, is cleared
-        const double* before = c->d_V.p;
-        FEDD_TRY(c->d_V.ensure((size_t)(m + 1) * ldv));
-        // (a buffer that another vector length used holds finite values everywhere: only its padding rows need the clearing)
-        if (c->d_V.p != before) FEDD_HIP(hipMemsetAsync(c->d_V.p, 0, c->d_V.cap * sizeof(double), c->stream));
-        else if (c->gm_V_ldv != ldv && ldv != n) FEDD_HIP(hipMemsetAsync(c->d_V.p, 0, (size_t)(m + 1) * ldv * sizeof(double), c->stream));
-        c->gm_V_ldv = ldv;
-    }
-    const int64_t nc = (std::max<int64_t>(c->n_rows, c->n_cols) * nr + 15) & ~(int64_t)15;
-    const bool ghosts = c->n_cols != c->n_rows || !c->halo.peers.empty();
-    FEDD_TRY(c->d_w.ensure(std::max<size_t>((size_t)2 * nc, c->d_w.cap)));   // x trial | A x trial
-    FEDD_TRY(c->d_Z.ensure((size_t)nc * (nr > 1 && ghosts ? 3 : 2)));      // (stacked, several ranks: + a copy with a ghost tail)
-    FEDD_TRY(c->d_part.ensure(std::max((size_t)(m + 1 + S) * S * (c->gmres_fuse != 0 ? std::max(nblkd, nblk2) : nblkd), (size_t)std::max(nblk, nblk2))));
-    FEDD_TRY(c->d_flags.ensure(16));
-    Off o;
+static int gmres_solve_sstep(fedd_ctx* c, const GmresCall& call, int s, int* its_out, double* relres_out) {
+    Frame f;
+    FEDD_TRY(f.setup(c, call, true));
+    const int nr = f.nr;
+    FEDD_CHECK(nr == 1 || (nr == MULTI_NR && call.use_prec && multi_rhs_ok(c)), "gmres: stacked solve with %d right-hand sides", nr);
+    const int64_t n = f.n, ldv = f.ldv;
+    const int m = f.m, nblk = f.nblk, nblk2 = f.nblk2, max_it = call.max_it;
+    const double rtol = call.rtol;
+    // block dot kernel: 1024 rows per workgroup (two 512-row chunks), ss_cg(S) columns per transpose reduction
+    constexpr int dot_cg = ss_cg(S);
+    const int nblkd = (int)((n + 1023) / 1024);
+    const Off o = f.o;
     Off3 o3;
-    int p = 0;
-    o.H = p; p += (m + 1) * m;
-    o.cs = p; p += m;
-    o.sn = p; p += m;
-    o.g = p; p += m + 1;
-    o.h1 = p; p += m + 2;
-    o.h2 = p; p += m + 2;
-    o.nrm = p; p += 4;
-    o.y = p; p += m;
-    o.misc = p; p += 8;
-    o3.Hraw = p; p += (m + 1) * m;
-    o3.P = p; p += (m + 1 + S) * S;
-    o3.C1 = p; p += m * S;
-    o3.Cc = p; p += m * S;
-    o3.cf1 = p; p += m * S;
-    o3.cf2 = p; p += m * S;
-    o3.R1 = p; p += S * S;
-    o3.R1i = p; p += S * S;
-    o3.ri1 = p; p += S * S;
-    o3.ri2 = p; p += S * S;
-    o3.th = p; p += S;
-    o3.res = p; p += S;
-    FEDD_TRY(c->d_small.ensure((size_t)p + 8));
-    double* Sx = c->d_small.p;
-    double* V = c->d_V.p;
-    double* xt = c->d_w.p;        // trial solution (ghost tail behind it)
-    double* axt = c->d_w.p + nc;  // A xt
-    double* z = c->d_Z.p;         // M^-1 v
-    double* r = c->d_Z.p + nc;    // residual / V y
+    o3.Hraw = f.p; f.p += (m + 1) * m;
+    o3.P = f.p; f.p += (m + 1 + S) * S;
+    o3.C1 = f.p; f.p += m * S;
+    o3.Cc = f.p; f.p += m * S;
+    o3.cf1 = f.p; f.p += m * S;
+    o3.cf2 = f.p; f.p += m * S;
+    o3.R1 = f.p; f.p += S * S;
+    o3.R1i = f.p; f.p += S * S;
+    o3.ri1 = f.p; f.p += S * S;
+    o3.ri2 = f.p; f.p += S * S;
+    o3.th = f.p; f.p += S;
+    o3.res = f.p; f.p += S;
+    FEDD_TRY(f.alloc(std::max((size_t)(m + 1 + S) * S * (c->gmres_fuse != 0 ? std::max(nblkd, nblk2) : nblkd), (size_t)std::max(nblk, nblk2)), true));
+    FEDD_TRY(c->d_flags.ensure(16));
+    double* Sx = f.S;
+    double* V = f.V;
+    double* xt = f.w0;    // trial solution (ghost tail behind it)
+    double* axt = f.w1;   // A xt
+    double* r = f.r;
+    double* d_x = call.x;
     int32_t* d_sa = c->d_flags.p + 12;   // (0 max scratch, 1 bad pivot, 2 DGKS gate, 3-5 coarse setup, 8-11 Schwarz setup)
-    const dim3 gn((unsigned)((n + 255) / 256)), blk(256);
-    hipStream_t st = c->stream;
+    const dim3 gn = f.gn, blk = f.blk;
+    hipStream_t st = f.st;
     const double chol_tol = c->gmres_chol_tol;
     // k_ss_pass2 keeps the S new Hessenberg columns in dynamic LDS (beside 18 KB of static block matrices): long restart cycles
     // go beyond the 64 KB a kernel gets without asking
@@ -1638,57 +1726,19 @@ static int gmres_solve_sstep(fedd_ctx* c, const double* d_b, double* d_x, double
     if (pass2_lds > 40 * 1024)
         FEDD_HIP(hipFuncSetAttribute((const void*)k_ss_pass2<S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pass2_lds));
 
-    auto norm2_into = [&](const double* v, double* out) -> int {
-        hipLaunchKernelGGL(k_multidot, dim3(nblk, 1), blk, 0, st, v, ldv, n, 0, v, c->d_part.p, nblk, (const int32_t*)nullptr);
-        hipLaunchKernelGGL(k_reduce_cols, dim3(1), blk, 0, st, (const double*)c->d_part.p, out, nblk, (const int32_t*)nullptr);
-        return allreduce_sum(c, out, 1);
-    };
-    // c->gm_mask != nullptr: the constrained system of the GDSW extension solves, A^ = D A D + (I - D), M^^-1 = D M^-1 D + (I - D)
-    // (see gmres_solve_dcgs2); monomial blocks only (the shift would have to reach the held rows too)
-    const double* mk = c->gm_mask;
-    // out = A M^-1 in - theta in  (basis columns: no ghost tail; the shift rides in the SpMV kernel's store)
-    auto apply_B = [&](const double* in, double* out, double theta) -> int {
-        if (nr > 1) {       // masks ride in the kernels' stores
-            double* src = const_cast<double*>(in);
-            if (ghosts) {
-                src = c->d_Z.p + 2 * nc;
-                FEDD_HIP(hipMemcpyAsync(src, in, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-            }
-            FEDD_TRY(schwarz_apply_multi(c, src, z, mk));
-            return spmm_owned(c, z, out, mk, z);
-        }
-        if (use_prec) FEDD_TRY(schwarz_apply(c, in, z, false));
-        if (mk) {
-            if (use_prec) hipLaunchKernelGGL(k_mask_mix, gn, blk, 0, st, mk, (const double*)z, in, z, n);
-            else FEDD_HIP(hipMemcpyAsync(z, in, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-            FEDD_TRY(spmv_owned(c, z, out, true));
-            hipLaunchKernelGGL(k_mask_mix, gn, blk, 0, st, mk, (const double*)out, (const double*)z, out, n);
-            return 0;
-        }
-        return spmv_owned(c, use_prec ? z : in, out, use_prec, theta != 0.0 ? in : nullptr, theta);
-    };
-
+    // the constrained system of the GDSW extension solves (Frame::mk) runs monomial blocks only: the shift would have to
+    // reach the held rows too
+    const double* mk = f.mk;
     FEDD_HIP(hipMemsetAsync(Sx + o3.th, 0, (size_t)S * sizeof(double), st));   // monomial block basis (shifts 0)
-    if (c->gm_x0 && !mk && nr == 1) {   // "Zero Initial Guess" = false (LinearSolver_def.hpp:76-78): d_x holds x_0, r_0 = b - A x_0
-        FEDD_TRY(spmv_owned(c, d_x, axt));
-        hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, d_b, -1.0, (const double*)axt, r, n);
-    } else {
-        FEDD_HIP(hipMemsetAsync(d_x, 0, (size_t)n * sizeof(double), st));  // "Zero Initial Guess" (LinearSolver_def.hpp:76-78)
-        FEDD_HIP(hipMemcpyAsync(r, d_b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
-    const bool project = cycle_projection(c, use_prec);
-    if (project) FEDD_TRY(coarse_project(c, d_b, d_x, r, 0, 2));
-    FEDD_TRY(norm2_into(r, Sx + o.nrm + 3));
-    FEDD_HIP(hipMemcpyAsync(c->h_pinned, Sx + o.nrm + 3, sizeof(double), hipMemcpyDeviceToHost, st));
-    FEDD_HIP(hipStreamSynchronize(st));
-    const double beta0 = std::sqrt(c->h_pinned[0]);
-    int its = 0;
-    double relres = beta0 > 0 ? 1.0 : 0.0;
-    if (!(beta0 > 0)) {
-        if (its_out) *its_out = 0;
-        if (relres_out) *relres_out = 0.0;
+    FEDD_TRY(f.start(axt, 0));
+    if (!(f.beta0 > 0)) {
+        f.report(its_out, relres_out);
         return 0;
     }
+    const double beta0 = f.beta0;
+    const bool project = f.project;
+    int& its = f.its;
+    double& relres = f.relres;
     hipEvent_t ev = nullptr;
     FEDD_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     struct EvGuard {
@@ -1704,44 +1754,20 @@ static int gmres_solve_sstep(fedd_ctx* c, const double* d_b, double* d_x, double
     double* hout = c->h_pinned + 16;                                  // host mirror of the block result
     double* hout_dev = c->h_pinned_dev ? c->h_pinned_dev + 16 : nullptr;
 
-    // xt = x + M^-1 V(:, 0:cols) y, r = b - A xt, ||r||^2 to the host: the true residual with `cols` columns of this cycle
+    // xt = x + M^-1 V(:, 0:cols) y, r = b - A xt, ||r|| to the host: the true residual with `cols` columns of this cycle
+    // (the residual that decides is formed with the parity CSR, see Frame::true_residual)
     // columns whose combination sum_c y_c V_c is already in r: written by the second update of a block that filled its restart
     // cycle (k_blockaxpy<S, true>), -1: none
     int precomb_cols = -1;
     auto trial = [&](int cols, double* true_abs) -> int {
         if (cols > 0) {
-            if (cols != precomb_cols) {
-                hipLaunchKernelGGL(k_backsolve, dim3(1), dim3(256), (size_t)(cols + 1) * sizeof(double), st, Sx, o, cols, m);
-                hipLaunchKernelGGL(k_combine, dim3((unsigned)((n + AX_ROWS - 1) / AX_ROWS)), blk, 0, st, (const double*)V, ldv, n, cols, (const double*)(Sx + o.y), r);
-            }
+            FEDD_TRY(f.add_correction(cols, xt, cols == precomb_cols));
             precomb_cols = -1;      // (r becomes the residual below)
-            if (nr > 1) {
-                FEDD_TRY(schwarz_apply_multi(c, r, z, mk));
-                hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, (const double*)d_x, 1.0, (const double*)z, xt, n);
-            } else if (use_prec) {
-                FEDD_TRY(schwarz_apply(c, r, z, true));
-                if (mk) hipLaunchKernelGGL(k_mask_mix, gn, blk, 0, st, mk, (const double*)z, (const double*)r, z, n);
-                hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, (const double*)d_x, 1.0, (const double*)z, xt, n);
-            } else {
-                hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, (const double*)d_x, 1.0, (const double*)r, xt, n);
-            }
         } else {
             FEDD_HIP(hipMemcpyAsync(xt, d_x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
         }
-        if (nr > 1) {
-            FEDD_TRY(spmm_owned(c, xt, axt, mk, xt));
-        } else {
-            // the residual that decides is formed with the parity CSR (every stored entry), like fedd_spmv, not with the
-            // compacted stream the Krylov process runs on (which leaves out sub-ulp cancellation noise)
-            FEDD_TRY(spmv_owned(c, xt, axt, true, nullptr, 0.0, 0));
-            if (mk) hipLaunchKernelGGL(k_mask_mix, gn, blk, 0, st, mk, (const double*)axt, (const double*)xt, axt, n);
-        }
-        hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, d_b, -1.0, (const double*)axt, r, n);
-        FEDD_TRY(norm2_into(r, Sx + o.nrm + 3));
-        FEDD_HIP(hipMemcpyAsync(c->h_pinned, Sx + o.nrm + 3, sizeof(double), hipMemcpyDeviceToHost, st));
-        FEDD_HIP(hipStreamSynchronize(st));
-        *true_abs = std::sqrt(std::max(c->h_pinned[0], 0.0));
-        return 0;
+        FEDD_TRY(f.true_residual(xt, axt, true, 0, false));
+        return f.read_norm(true_abs);
     };
     auto commit = [&]() -> int {   // x <- xt (r and ||r||^2 already belong to it)
         FEDD_HIP(hipMemcpyAsync(d_x, xt, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -1753,7 +1779,7 @@ static int gmres_solve_sstep(fedd_ctx* c, const double* d_b, double* d_x, double
     // claim fails its check and costs a restart, so tight tolerances take shorter blocks from the start.
     // (option "gmres_tol_blocks" 0 lifts the cap: runs that are held to an iteration count instead of a tolerance)
     const int s_tol = !c->gmres_tol_blocks || rtol >= 1e-9 ? 16 : (rtol >= 1e-11 ? 5 : 3);
-    const int s_goal = std::max(1, std::min(std::min(c->gmres_s, S), s_tol));
+    const int s_goal = std::max(1, std::min(std::min(s, S), s_tol));
     // Blocks longer than 8 need a better conditioned block basis than the monomial one (its condition grows tenfold every
     // two vectors, 1e7 at s = 8): the Newton basis w_i = (B - theta_i) w_{i-1} with the Ritz values of the first s_goal
     // Arnoldi steps as shifts, Leja-ordered (Bai, Hu, Reichel, "A Newton basis GMRES implementation", 1994).  Until those
@@ -1797,31 +1823,19 @@ static int gmres_solve_sstep(fedd_ctx* c, const double* d_b, double* d_x, double
             spec_done = 0;
             spec_k = -1;
             for (int i = i0; i < sa; ++i)
-                FEDD_TRY(apply_B(V + (int64_t)(k - 1 + i) * ldv, V + (int64_t)(k + i) * ldv, have_shifts ? theta[(size_t)i] : 0.0));
+                FEDD_TRY(f.apply(V + (int64_t)(k - 1 + i) * ldv, V + (int64_t)(k + i) * ldv, false, have_shifts ? theta[(size_t)i] : 0.0));
             {
                 ScopedTimer t(c, FEDD_T_ORTHO);
                 const int ncg = (k + sa + dot_cg - 1) / dot_cg;
                 const dim3 gd(nblkd, std::min(gy_dot, ncg));
-                auto launch_dot = [&](const dim3& g, const int32_t* dsa) {
-                    constexpr int CG0 = ss_cg(S), CG2 = (64 / S < 2 * CG0) ? 64 / S : 2 * CG0;
-                    if constexpr (S == 16) {
-                        if (dot_split) {
-                            hipLaunchKernelGGL((k_blockdot<S, 2, 4, 2>), g, blk, 0, st, (const double*)V, ldv, n, k, sa, dsa, c->d_part.p, nblkd);
-                            return;
-                        }
-                    }
-                    if (dotv == 0 || dotv == 4)
-                        hipLaunchKernelGGL((k_blockdot<S, 2, CG0>), g, blk, 0, st, (const double*)V, ldv, n, k, sa, dsa, c->d_part.p, nblkd);
-                    else if (dotv == 1)
-                        hipLaunchKernelGGL((k_blockdot<S, 1, CG0>), g, blk, 0, st, (const double*)V, ldv, n, k, sa, dsa, c->d_part.p, nblkd);
-                    else
-                        hipLaunchKernelGGL((k_blockdot<S, 1, CG2>), g, blk, 0, st, (const double*)V, ldv, n, k, sa, dsa, c->d_part.p, nblkd);
+                auto launch_dot = [&](const int32_t* dsa) {
+                    hipLaunchKernelGGL((k_blockdot<S, 2, dot_cg>), gd, blk, 0, st, (const double*)V, ldv, n, k, sa, dsa, c->d_part.p, nblkd);
                 };
                 const double dot_bytes = 8.0 * (double)n * (k + 2 * sa), upd_bytes = 8.0 * (double)n * (k + 2 * sa);
                 {
                     ScopedTimer td(c, FEDD_T_GS_DOT);
                     td.bytes(dot_bytes);
-                    launch_dot(gd, (const int32_t*)nullptr);
+                    launch_dot((const int32_t*)nullptr);
                 }
                 hipLaunchKernelGGL(k_reduce_cols, dim3((k + sa) * S), blk, 0, st, (const double*)c->d_part.p, Sx + o3.P, nblkd,
                                    (const int32_t*)nullptr);
@@ -1851,7 +1865,7 @@ static int gmres_solve_sstep(fedd_ctx* c, const double* d_b, double* d_x, double
                     {
                         ScopedTimer td(c, FEDD_T_GS_DOT);
                         td.bytes(dot_bytes);
-                        launch_dot(gd, (const int32_t*)d_sa);
+                        launch_dot((const int32_t*)d_sa);
                     }
                 }
                 hipLaunchKernelGGL(k_reduce_cols, dim3((k + sa) * S), blk, 0, st, (const double*)c->d_part.p, Sx + o3.P, fused ? nblk2 : nblkd,
@@ -1859,10 +1873,10 @@ static int gmres_solve_sstep(fedd_ctx* c, const double* d_b, double* d_x, double
                 FEDD_TRY(allreduce_sum(c, Sx + o3.P, (k + sa) * S));
                 hipLaunchKernelGGL(k_ss_pass2<S>, dim3(1), blk, pass2_lds, st, Sx, o, o3, k, sa, m,
                                    chol_tol, d_sa, hout_dev);
-                if (!hout_dev)
+                if (!hout_dev) {
                     FEDD_HIP(hipMemcpyAsync(hout, Sx + o.misc + 4, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-                if (!hout_dev)
                     FEDD_HIP(hipMemcpyAsync(hout + 2, Sx + o3.res, S * sizeof(double), hipMemcpyDeviceToHost, st));
+                }
                 FEDD_HIP(hipEventRecord(ev, st));
                 // a block that fills the restart cycle is followed by the solution update over all its columns: the second
                 // update forms that combination while it has the basis in hand (one read of the basis less per cycle)
@@ -1894,7 +1908,7 @@ static int gmres_solve_sstep(fedd_ctx* c, const double* d_b, double* d_x, double
                 const int room_next = std::min(m - (k_next - 1), max_it - its - (k_next - 1));
                 const int ns = std::min(std::min(c->gmres_spec, s_cur), room_next);
                 for (int i = 0; i < ns; ++i)
-                    FEDD_TRY(apply_B(V + (int64_t)(k_next - 1 + i) * ldv, V + (int64_t)(k_next + i) * ldv, have_shifts ? theta[(size_t)i] : 0.0));
+                    FEDD_TRY(f.apply(V + (int64_t)(k_next - 1 + i) * ldv, V + (int64_t)(k_next + i) * ldv, false, have_shifts ? theta[(size_t)i] : 0.0));
                 if (ns > 0) {
                     spec_done = ns;
                     spec_k = k_next;
@@ -2037,145 +2051,41 @@ static int gmres_solve_sstep(fedd_ctx* c, const double* d_b, double* d_x, double
             break;
         }
     }
-    FEDD_HIP(hipGetLastError());
-    FEDD_HIP(hipStreamSynchronize(st));
-    if (its_out) *its_out = its;
-    if (relres_out) *relres_out = relres;
-    return 0;
+    return f.finish(its_out, relres_out);
 }
 
-int gmres_solve(fedd_ctx* c, const double* d_b, double* d_x, double rtol, int max_it, int restart, int use_prec,
-                int* its_out, double* relres_out) {
-    c->gmres_floor = 0;
-    c->gmres_rec_relres = -1.0;
-    if (c->gmres_kind == 2) {
-        // block length: "gmres_s" 0 = by the vector length per rank -- 16-vector (Newton-basis) blocks where the sweeps over the
-        // basis dominate, 8-vector blocks on short vectors, where the longer blocks' fixed costs (two monomial blocks first,
-        // a 16 x 16 Cholesky per pass, one more vector per SpMV) are not paid back.  Measured: 1.03 M rows / 71 iterations (cfg 2)
-        // 11.8 ms with 8, 12.2 with 16; 1.26 M rows / 145 iterations (one GPU's share of cfg 3) 24.4 against 22.5; 9.9 M rows
-        // 122.5 against 108.0.  Every rank must take the same one: the decision uses the global row count
-        if (c->gmres_s == 0) {
-            double ng = (double)c->n_rows;
-            if (c->nranks > 1) {
-                FEDD_TRY(c->d_small.ensure(std::max<size_t>(16, c->d_small.cap)));
-                FEDD_HIP(hipMemcpyAsync(c->d_small.p, &ng, sizeof(double), hipMemcpyHostToDevice, c->stream));
-                FEDD_HIP(hipStreamSynchronize(c->stream));
-                FEDD_TRY(allreduce_sum(c, c->d_small.p, 1));
-                FEDD_HIP(hipMemcpyAsync(&ng, c->d_small.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-                FEDD_HIP(hipStreamSynchronize(c->stream));
-            }
-            c->gmres_s = ng / c->nranks >= 1.2e6 ? 16 : 8;
-            const int rc = gmres_solve(c, d_b, d_x, rtol, max_it, restart, use_prec, its_out, relres_out);
-            c->gmres_s_used = c->gmres_s;
-            c->gmres_s = 0;
-            return rc;
-        }
-        c->gmres_s_used = c->gmres_s;
-        // (the constrained solves run monomial blocks of at most eight vectors: the 8-column kernels)
-        if (c->gm_mask && c->gmres_s > 8) return gmres_solve_sstep<8>(c, d_b, d_x, rtol, max_it, restart, use_prec, its_out, relres_out);
-        // (cycles of more than 800 vectors: the 16-column block kernel's LDS image of its new Hessenberg columns does not fit)
-        if (c->gmres_s > 8 && std::min(restart, max_it) > 800)
-            return gmres_solve_sstep<8>(c, d_b, d_x, rtol, max_it, restart, use_prec, its_out, relres_out);
-        if (c->gmres_s <= 4) return gmres_solve_sstep<4>(c, d_b, d_x, rtol, max_it, restart, use_prec, its_out, relres_out);
-        if (c->gmres_s <= 8) return gmres_solve_sstep<8>(c, d_b, d_x, rtol, max_it, restart, use_prec, its_out, relres_out);
-        return gmres_solve_sstep<16>(c, d_b, d_x, rtol, max_it, restart, use_prec, its_out, relres_out);
-    }
-    if (c->gmres_kind == 0 || c->gmres_kind == 2) return gmres_solve_dcgs2(c, d_b, d_x, rtol, max_it, restart, use_prec, its_out, relres_out);
-    const int64_t n = c->n_rows;
-    const int m = std::min(restart, max_it);
-    const int64_t ldv = (n + 15) & ~(int64_t)15;  // 128-byte aligned basis columns
-    FEDD_CHECK(m + 2 <= 1024, "gmres: restart length above 1022 is not supported");
-    const int nblk = (int)((n + MD_ROWS - 1) / MD_ROWS), nblk2 = (int)((n + AX_ROWS - 1) / AX_ROWS);
-    FEDD_TRY(c->d_V.ensure((size_t)(m + 1) * ldv));
-    if (c->gm_V_ldv != ldv) c->gm_V_ldv = -1;
-    FEDD_TRY(c->d_w.ensure(std::max<size_t>((size_t)n, c->d_w.cap)));
-    FEDD_TRY(c->d_Z.ensure((size_t)n * 2));
-    FEDD_TRY(c->d_part.ensure(std::max((size_t)(m + 2) * nblk, (size_t)nblk2)));
-    Off o;
-    int p = 0;
-    o.H = p; p += (m + 1) * m;
-    o.cs = p; p += m;
-    o.sn = p; p += m;
-    o.g = p; p += m + 1;
-    o.h1 = p; p += m + 2;
-    o.h2 = p; p += m + 2;
-    o.nrm = p; p += 4;
-    o.y = p; p += m;
-    o.misc = p; p += 8;
-    FEDD_TRY(c->d_small.ensure((size_t)p + 8));
-    double* S = c->d_small.p;
+// GMRES with classical Gram-Schmidt in two passes (gmres_kind 1): fused multi-dot + multi-axpy twice, the second pass gated
+// by the DGKS test on the device.  The work vectors have no ghost tail here.
+static int gmres_solve_cgs2(fedd_ctx* c, const GmresCall& call, int* its_out, double* relres_out) {
+    Frame f;
+    FEDD_TRY(f.setup(c, call, false));
+    const int64_t n = f.n, ldv = f.ldv;
+    const int m = f.m, nblk = f.nblk, nblk2 = f.nblk2, max_it = call.max_it;
+    const Off o = f.o;
+    FEDD_TRY(f.alloc(std::max((size_t)(m + 2) * nblk, (size_t)nblk2), false));
     FEDD_TRY(c->d_flags.ensure(16));
     int32_t* gate = c->d_flags.p + 2;
-    double* V = c->d_V.p;
-    double* w = c->d_w.p;
-    double* z = c->d_Z.p;       // M^-1 v
-    double* r = c->d_Z.p + n;   // residual / u
-    const dim3 gn((unsigned)((n + 255) / 256)), blk(256);
-    hipStream_t st = c->stream;
+    double* S = f.S;
+    double* V = f.V;
+    double* w = f.w0;
+    double* r = f.r;
+    const dim3 gn = f.gn, blk = f.blk;
+    hipStream_t st = f.st;
 
-    auto norm2_into = [&](const double* v, double* out) -> int {  // out[0] = v.v (global)
-        hipLaunchKernelGGL(k_multidot, dim3(nblk, 1), blk, 0, st, v, ldv, n, 0, v, c->d_part.p, nblk, (const int32_t*)nullptr);
-        hipLaunchKernelGGL(k_reduce_cols, dim3(1), blk, 0, st, (const double*)c->d_part.p, out, nblk, (const int32_t*)nullptr);
-        return allreduce_sum(c, out, 1);
-    };
-    auto residual = [&]() -> int {  // r = b - A x
-        FEDD_TRY(spmv_owned(c, d_x, r));
-        hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, d_b, -1.0, (const double*)r, r, n);
-        return 0;
-    };
-
-    if (c->gm_x0) {   // "Zero Initial Guess" = false (LinearSolver_def.hpp:76-78): d_x holds x_0, r_0 = b - A x_0
-        FEDD_TRY(residual());
-    } else {
-        FEDD_HIP(hipMemsetAsync(d_x, 0, (size_t)n * sizeof(double), st));  // "Zero Initial Guess" (LinearSolver_def.hpp:76-78)
-        FEDD_HIP(hipMemcpyAsync(r, d_b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
-    const bool project = cycle_projection(c, use_prec);
-    if (project) FEDD_TRY(coarse_project(c, d_b, d_x, r, -1, 2));
-    FEDD_TRY(norm2_into(r, S + o.nrm + 3));
-    FEDD_HIP(hipMemcpyAsync(c->h_pinned, S + o.nrm + 3, sizeof(double), hipMemcpyDeviceToHost, st));
-    FEDD_HIP(hipStreamSynchronize(st));
-    const double beta0 = std::sqrt(c->h_pinned[0]);
-    int its = 0;
-    double relres = beta0 > 0 ? 1.0 : 0.0;
-    if (!(beta0 > 0)) {
-        if (its_out) *its_out = 0;
-        if (relres_out) *relres_out = 0.0;
+    FEDD_TRY(f.start(r, -1));
+    if (!(f.beta0 > 0)) {
+        f.report(its_out, relres_out);
         return 0;
     }
-    // The convergence test of iteration j is read on the host while iteration j + 1 is already
-    // queued (two pinned slots, one event each): the device never waits for the host round trip.
-    // An iteration queued past convergence only writes basis column j + 2, Hessenberg column
-    // j + 1 and g[j+1..j+2], none of which the update of x with k = j + 1 columns reads.
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    for (int q = 0; q < 2; ++q) FEDD_HIP(hipEventCreateWithFlags(&ev[q], hipEventDisableTiming));
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard() {
-            for (int q = 0; q < 2; ++q)
-                if (e[q]) (void)hipEventDestroy(e[q]);
-        }
-    } ev_guard{ev};
-    bool converged = false;
-    while (!converged && its < max_it) {
+    LaggedCheck lag(f, 1);
+    FEDD_TRY(lag.create());
+    int stop = 0;   // 1: converged or breakdown
+    while (!stop && f.its < max_it) {
         hipLaunchKernelGGL(k_cycle_init, dim3(1), dim3(1), 0, st, S, o, m, (const double*)(S + o.nrm + 3));
         hipLaunchKernelGGL(k_scale_to, gn, blk, 0, st, (const double*)r, (const double*)(S + o.misc + 1), V, n);
-        int k = 0;
-        int issued = its, checked = 0, queued = 0;  // iterations of this cycle: results read / queued
-        auto check = [&](int jj) -> int {           // 1 = stop (converged or breakdown), < 0 = error
-            if (hipEventSynchronize(ev[jj & 1]) != hipSuccess) return -1;
-            const double* hp = c->h_pinned + 4 * (jj & 1);
-            ++its;
-            ++checked;
-            k = jj + 1;
-            relres = hp[0] / beta0;
-            const bool breakdown = !(hp[2] > 0.0);   // ||w|| after both passes, behind the DGKS gate: a true breakdown
-            return (relres <= rtol || breakdown) ? 1 : 0;
-        };
-        for (int j = 0; j < m && issued < max_it; ++j) {
-            const double* vj = V + (int64_t)j * ldv;
-            if (use_prec) FEDD_TRY(schwarz_apply(c, vj, z));
-            FEDD_TRY(spmv_owned(c, use_prec ? z : vj, w));
+        lag.begin_cycle();
+        for (int j = 0; j < m && lag.issued < max_it && !stop; ++j) {
+            FEDD_TRY(f.apply(V + (int64_t)j * ldv, w));
             {
                 ScopedTimer t(c, FEDD_T_ORTHO);
                 // pass 1: h1 = V^T w, nrm[0] = w.w ; w -= V h1, nrm[1] = ||w||^2
@@ -2208,44 +2118,46 @@ int gmres_solve(fedd_ctx* c, const double* d_b, double* d_x, double rtol, int ma
                                (const int32_t*)gate, (const double*)(c->nranks > 1 ? nullptr : c->d_part.p), nblk2);
             hipLaunchKernelGGL(k_scale_to, gn, blk, 0, st, (const double*)w, (const double*)(S + o.misc + 1),
                                V + (int64_t)(j + 1) * ldv, n);
-            FEDD_HIP(hipMemcpyAsync(c->h_pinned + 4 * (j & 1), S + o.misc, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-            FEDD_HIP(hipEventRecord(ev[j & 1], st));
-            ++issued;
-            ++queued;
-            if (j > 0) {
-                const int rc = check(j - 1);
-                FEDD_CHECK(rc >= 0, "gmres: waiting for iteration %d failed", j - 1);
-                if (rc) {
-                    converged = true;
-                    break;
-                }
-            }
+            FEDD_TRY(lag.record(j, true, &stop));
         }
-        if (!converged && checked < queued) {
-            const int rc = check(queued - 1);
-            FEDD_CHECK(rc >= 0, "gmres: waiting for iteration %d failed", queued - 1);
-            converged = rc != 0;
-        }
-        // x += M^-1 (V y)
-        hipLaunchKernelGGL(k_backsolve, dim3(1), dim3(256), (size_t)(k + 1) * sizeof(double), st, S, o, k, m);
-        hipLaunchKernelGGL(k_combine, dim3((unsigned)((n + AX_ROWS - 1) / AX_ROWS)), blk, 0, st, (const double*)V, ldv, n, k, (const double*)(S + o.y), r);
-        if (use_prec) {
-            FEDD_TRY(schwarz_apply(c, r, z));
-            hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, (const double*)d_x, 1.0, (const double*)z, d_x, n);
-        } else {
-            hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, (const double*)d_x, 1.0, (const double*)r, d_x, n);
-        }
-        if (!converged && its < max_it) {
-            FEDD_TRY(residual());
-            if (project) FEDD_TRY(coarse_project(c, d_b, d_x, r, -1, 1));
-            FEDD_TRY(norm2_into(r, S + o.nrm + 3));
-        }
+        FEDD_TRY(lag.drain(&stop));
+        FEDD_TRY(f.add_correction(lag.cols, call.x));
+        if (!stop && f.its < max_it) FEDD_TRY(f.true_residual(call.x, r, false, -1, f.project));
     }
-    FEDD_HIP(hipGetLastError());
-    FEDD_HIP(hipStreamSynchronize(st));
-    if (its_out) *its_out = its;
-    if (relres_out) *relres_out = relres;
-    return 0;
+    return f.finish(its_out, relres_out);
+}
+
+int gmres_solve(fedd_ctx* c, const GmresCall& call, int* its_out, double* relres_out) {
+    c->gmres_floor = 0;
+    c->gmres_rec_relres = -1.0;
+    FEDD_CHECK(call.nr <= 1 || c->gmres_kind == 2, "gmres: a stacked solve (%d right-hand sides) needs the s-step solver (gmres_kind 2)", call.nr);
+    if (c->gmres_kind == 0) return gmres_solve_dcgs2(c, call, its_out, relres_out);
+    if (c->gmres_kind == 1) return gmres_solve_cgs2(c, call, its_out, relres_out);
+    // block length: "gmres_s" 0 = by the vector length per rank -- 16-vector (Newton-basis) blocks where the sweeps over the
+    // basis dominate, 8-vector blocks on short vectors, where the longer blocks' fixed costs (two monomial blocks first,
+    // a 16 x 16 Cholesky per pass, one more vector per SpMV) are not paid back.  Measured: 1.03 M rows / 71 iterations (cfg 2)
+    // 11.8 ms with 8, 12.2 with 16; 1.26 M rows / 145 iterations (one GPU's share of cfg 3) 24.4 against 22.5; 9.9 M rows
+    // 122.5 against 108.0.  Every rank must take the same one: the decision uses the global row count
+    int s = c->gmres_s;
+    if (s == 0) {
+        double ng = (double)c->n_rows;
+        if (c->nranks > 1) {
+            FEDD_TRY(c->d_small.ensure(std::max<size_t>(16, c->d_small.cap)));
+            FEDD_HIP(hipMemcpyAsync(c->d_small.p, &ng, sizeof(double), hipMemcpyHostToDevice, c->stream));
+            FEDD_HIP(hipStreamSynchronize(c->stream));
+            FEDD_TRY(allreduce_sum(c, c->d_small.p, 1));
+            FEDD_HIP(hipMemcpyAsync(&ng, c->d_small.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            FEDD_HIP(hipStreamSynchronize(c->stream));
+        }
+        s = ng / c->nranks >= 1.2e6 ? 16 : 8;
+    }
+    c->gmres_s_used = s;
+    // the 8-column kernels for longer blocks too: the constrained solves run monomial blocks of at most eight vectors; in
+    // cycles of more than 800 vectors the 16-column block kernel's LDS image of its new Hessenberg columns does not fit
+    if (s > 8 && (call.mask || std::min(call.restart, call.max_it) > 800)) s = 8;
+    if (s <= 4) return gmres_solve_sstep<4>(c, call, s, its_out, relres_out);
+    if (s <= 8) return gmres_solve_sstep<8>(c, call, s, its_out, relres_out);
+    return gmres_solve_sstep<16>(c, call, s, its_out, relres_out);
 }
 
 }  // namespace fedd

@@ -10,7 +10,7 @@
 //   k_apply_multi  Z = M^-1 R (restricted additive Schwarz): one wave per subdomain, Z_own[16 RT x 16] = Ainv[16 RT x n] R_sub[n x 16]
 //                  on the f64 matrix cores (v_mfma_f64_16x16x4_f64: M = owned rows, N = right-hand sides, K = subdomain dofs);
 //                  the N dimension that k_apply_mfma (schwarz.hip) fills with sixteen subdomains is filled with sixteen columns.
-// Both take the 0 / 1 mask of the constrained operator (gmres.hip, gm_mask) in their store:  out = mask ? result : alt.
+// Both take the 0 / 1 mask of the constrained operator (gmres.hip, GmresCall::mask) in their store:  out = mask ? result : alt.
 #include "fedd_internal.hpp"
 
 namespace fedd {

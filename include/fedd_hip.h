@@ -427,7 +427,7 @@ int fedd_gmres_fused_blocks(fedd_ctx* ctx, int* blocks);
  * (multiples of 16; 0 = one round of workgroups with the batch table, 32 / 64 / 96 / 128 by the number of subdomains without);
  * "apply_dbg" > 0 ablation bits of k_apply_mfma<4, 12> (development: wrong results by design), -1 = phase clocks of one wave of
  * k_apply_bt<4, 12> printed by the kernel (tools/apply_phases.py); "md2_gy" column groups in flight per row block of the
- * Gram-Schmidt dot sweep (0 = by vector length), "md2_nch" its 512-row chunks per workgroup (2 or 4; default 4);
+ * Gram-Schmidt dot sweep (0 = by vector length);
  * "gmres_hostwrite" 1 (default) = the solver's small kernel writes the three numbers of the host's lagged convergence test
  * into mapped pinned memory itself, 0 = an asynchronous copy per iteration;
  * "spmv_pattern" 1 (default) = column patterns for matrices beyond the Infinity Cache (fedd_spmv_patterns), 2 = for every

@@ -133,7 +133,7 @@ def test_two_level_misuse(fedd_lib, ctx):
 @pytest.mark.parametrize("dim,M,cells,kind", [(3, 12, 8, "gdsw"), (3, 12, 27, "gdsw"), (2, 24, 16, "gdsw"), (3, 9, 1, "gdsw"),
                                               (3, 12, 8, "rgdsw"), (3, 12, 27, "rgdsw"), (3, 16, 64, "rgdsw"),
                                               (2, 24, 16, "rgdsw"), (3, 9, 1, "rgdsw"), (3, 12, 2, "rgdsw")])
-def test_gdsw_coarse_matrix_and_apply(fedd_lib, dim, M, cells, kind):
+def test_gdsw_coarse_matrix_and_apply(fedd_lib, dim, M, cells, kind, gmres_kind=None):
     """FEDD_COARSE_GDSW / FEDD_COARSE_RGDSW against the oracle's CoarseGDSW (exact sparse interior solves): interface
     classification, coarse nodes and weights of the reduced space, harmonic extensions (device GMRES on the constrained
     operator, solved to 1e-13 here), K0^-1 and the operator.  (cells = 2: a slab decomposition, whose coarse nodes are
@@ -145,6 +145,8 @@ def test_gdsw_coarse_matrix_and_apply(fedd_lib, dim, M, cells, kind):
         c.schwarz_set_target(tgt, 1.0)
         c.schwarz_set_coarse(cells)
         c.set_option("gdsw_tol", 1e-13)
+        if gmres_kind is not None:
+            c.set_option("gmres_kind", gmres_kind)
         reduced = kind == "rgdsw"
         c.schwarz_setup(1, fedd_lib.COMBINE_RESTRICTED, two_level=1,
                         coarse_kind=fedd_lib.COARSE_RGDSW if reduced else fedd_lib.COARSE_GDSW)
@@ -168,6 +170,14 @@ def test_gdsw_coarse_matrix_and_apply(fedd_lib, dim, M, cells, kind):
         np.testing.assert_allclose(x, xd, rtol=0, atol=1e-10 * np.abs(xd).max())
     finally:
         c.close()
+
+
+@pytest.mark.parametrize("kind", ["gdsw", "rgdsw"])
+@pytest.mark.parametrize("gmres_kind", [0, 1])
+def test_gdsw_setup_under_one_vector_solvers(fedd_lib, kind, gmres_kind):
+    """The extension solves of the GDSW setup honour their constraint mask under every solver: the same case, assertions
+    and tolerances as test_gdsw_coarse_matrix_and_apply, with DCGS2 (0) and CGS2 (1) instead of the s-step default."""
+    test_gdsw_coarse_matrix_and_apply(fedd_lib, 3, 12, 8, kind, gmres_kind=gmres_kind)
 
 
 def test_gdsw_elasticity_and_iteration_counts(fedd_lib):
