@@ -887,14 +887,6 @@ extern "C" int fedd_set_option(fedd_ctx* c, const char* key, double value) {
     } else if (k == "schwarz_dedupe") c->sw_dedupe = (int)value;
     else if (k == "schwarz_fp_kind") { c->sw_fp_kind = (int)value; c->have_schwarz = false; }
     else if (k == "apply_span") c->apply_span = (int)value;
-    else if (k == "apply_dbg") {
-        // (the ablation instances schwarz_apply has, and -1 = phase clocks: any other positive value launched no kernel at all)
-        const int v = (int)value;
-        FEDD_CHECK((double)v == value && (v == -1 || v == 0 || v == 1 || v == 3 || v == 4 || v == 7 || v == 23 || v == 32 ||
-                                          v == 39 || v == 55),
-                   "fedd_set_option: apply_dbg %g (one of -1, 0, 1, 3, 4, 7, 23, 32, 39, 55)", value);
-        c->apply_dbg = v;
-    }
     else if (k == "apply_bt") c->apply_bt = (int)value;
     else if (k == "gdsw_block") c->gdsw_block = value != 0.0;
     else if (k == "gdsw_rotations") c->gdsw_rot = value != 0.0;
@@ -914,7 +906,12 @@ extern "C" int fedd_set_option(fedd_ctx* c, const char* key, double value) {
     else if (k == "asm_tiles") c->asm_tiles = (int)value;
     else if (k == "asm_u") c->asm_u = (int)value;
     else if (k == "asm_dbg") c->asm_dbg = (int)value;
-    else if (k == "apply_kind") c->apply_kind = (int)value;
+    else if (k == "apply_kind") {
+        // (the kernel families schwarz_apply has: any other value would be left to whatever its predicates happen to give)
+        FEDD_CHECK(value == 0 || value == 1 || value == 2 || value == 4 || value == 6,
+                   "fedd_set_option: apply_kind %g (one of 0, 1, 2, 4, 6)", value);
+        c->apply_kind = (int)value;
+    }
     else if (k == "inv_kind") c->inv_kind = (int)value;
     else if (k == "gmres_kind") {
         FEDD_CHECK(value == 0 || value == 1 || value == 2, "fedd_set_option: gmres_kind %g", value);

@@ -270,7 +270,7 @@ struct fedd_ctx {
     double sw_scale = 1.0;
     int sw_overlap = 1, sw_combine = 0;
     int64_t sw_nsub = 0, sw_max_size = 0, sw_max_own = 0, sw_inv_elems = 0;
-    int apply_kind = 0;                         // restricted apply: 0 = flat streaming kernel, 1 = strided (A/B)
+    int apply_kind = 0;                         // restricted apply: 0 = by the setup (matrix cores where inverses are shared, else flat), 1 = strided, 2 = flat without the compact LDS layout, 4 = matrix cores also below 4096 subdomains, 6 = chunk records instead of the batch table (A/B)
     int inv_kind = 0;                           // local inverses: 0 = scalar-pivot kernel (drops finished rows), 1 = MFMA block sweep, 2 = scalar-pivot, all rows (A/B)
     int ghost_overlap = 1;                      // subdomains may contain ghost dofs (identity rows): 1 = yes (A/B)
     int gmres_kind = 2;                         // Gram-Schmidt: 0 = delayed second pass (DCGS2), 1 = two passes (CGS2), 2 = s-step blocks (BCGS-PIP2)
@@ -298,8 +298,7 @@ struct fedd_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int64_t sw_nconf = 0;                       // subdomains whose dof list is their representative's list shifted (ids computed in the apply)
     int64_t sw_nint = -1;                       // subdomains without ghost dofs at the front of d_sw_order (-1: not split)
-    int apply_dbg = 0;                          // ablation bits of k_apply_mfma<4, 12> (development; wrong results by design)
-    int apply_span = 0;                         // grouped apply: subdomains per workgroup (0 = 64)
+    int apply_span = 0;                         // matrix-core apply: places per workgroup (0 = by subdomain count with chunk records, one round of workgroups with the batch table)
     int sw_dedupe = 1;                          // option "schwarz_dedupe": subdomains with the same local matrix share one slab
     int sw_fp_kind = 0;                         // option "schwarz_fp_kind": fingerprints from row hashes (0) or entry by entry (1)
     int64_t sw_nrep = 0;                        // distinct local matrices (= slabs) of the last setup

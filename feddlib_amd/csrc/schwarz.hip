@@ -1031,8 +1031,14 @@ __global__ __launch_bounds__(256) void k_apply_flat(const int32_t* __restrict__ 
 // order: fixed summation order => reproducible; no atomics (every owned dof belongs to one subdomain).
 // Without the sharing the slabs stream from HBM once per apply and the flat kernel above is the right one.
 typedef double ap_d4 __attribute__((ext_vector_type(4)));
+// XCD-contiguous ranges (neighbouring boxes gather overlapping parts of r: one L2): workgroups are dealt to the eight XCDs
+// round robin, so workgroup blockIdx.x takes the range whose number this returns -- consecutive ranges on one XCD
+__device__ __forceinline__ int xcd_contiguous_wg() {
+    const int nwg = gridDim.x, q_ = nwg >> 3, rem_ = nwg & 7, xcd_ = blockIdx.x & 7, within_ = blockIdx.x >> 3;
+    return (xcd_ < rem_ ? xcd_ * (q_ + 1) : rem_ * (q_ + 1) + (xcd_ - rem_) * q_) + within_;
+}
 constexpr int AM_MB = 16;
-template <int RT, int KW, int ABL = 0>   // owned rows <= 16 RT, columns <= 16 KW; ABL: ablation bits of tools/ab_apply.py (1 no gathers of r, 2 no stores of z, 4 no exchange of the partial tiles, 8 no products)
+template <int RT, int KW>   // owned rows <= 16 RT, columns <= 16 KW
 __global__ __launch_bounds__(256, (RT <= 2 && KW <= 10) ? 3 : ((RT <= 4 && KW <= 12) ? 2 : 1)) void k_apply_mfma(const int4* __restrict__ order, const int32_t* __restrict__ sub_dofs,
                                                     const int64_t* __restrict__ inv_ptr, const double* __restrict__ inv,
                                                     const double* __restrict__ r, double* __restrict__ z, int32_t nsub, int span) {
@@ -1043,9 +1049,7 @@ __global__ __launch_bounds__(256, (RT <= 2 && KW <= 10) ? 3 : ((RT <= 4 && KW <=
     __shared__ __attribute__((aligned(16))) int32_t soff[16 * KW];      // dof offsets of the current representative's list
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, lj = lane & 15, lk = lane >> 4;
     const int lm = tid >> 4, lc = tid & 15;     // id loads: subdomain lm of the batch, columns 4 lc + 64 u ...
-    // XCD-contiguous ranges (neighbouring boxes gather overlapping parts of r: one L2)
-    const int nwg = gridDim.x, q_ = nwg >> 3, rem_ = nwg & 7, xcd_ = blockIdx.x & 7, within_ = blockIdx.x >> 3;
-    const int wg = (xcd_ < rem_ ? xcd_ * (q_ + 1) : rem_ * (q_ + 1) + (xcd_ - rem_) * q_) + within_;
+    const int wg = xcd_contiguous_wg();
     const int32_t p_end = min(nsub, (wg + 1) * span);   // span = a multiple of 16
     int32_t p_chunk = wg * span;
     if (p_chunk >= p_end) return;
@@ -1152,7 +1156,7 @@ __global__ __launch_bounds__(256, (RT <= 2 && KW <= 10) ? 3 : ((RT <= 4 && KW <=
 #pragma unroll
             for (int kk = 0; kk < KW; ++kk) {
                 const int c = 4 * (w + 4 * kk) + lk;
-                bv[kk] = (ABL & 1) ? (double)(c + lj) : ((lj < mb && c < n) ? r[ids[buf][lj][c]] : 0.0);
+                bv[kk] = (lj < mb && c < n) ? r[ids[buf][lj][c]] : 0.0;
             }
 #pragma unroll
             for (int t = 0; t < RT; ++t) {
@@ -1188,12 +1192,9 @@ __global__ __launch_bounds__(256, (RT <= 2 && KW <= 10) ? 3 : ((RT <= 4 && KW <=
         for (int t = 0; t < RT; ++t) acc[t] = ap_d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int kk = 0; kk < KW; ++kk)
-            if ((ABL & 32) || 4 * (w + 4 * kk) < n) {     // (uniform over the wave)
+            if (4 * (w + 4 * kk) < n) {     // (uniform over the wave)
 #pragma unroll
-                for (int t = 0; t < RT; ++t) {
-                    if (ABL & 8) acc[t][kk & 3] += a[t][kk] * bv[kk];
-                    else acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t][kk], bv[kk], acc[t], 0, 0, 0);
-                }
+                for (int t = 0; t < RT; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t][kk], bv[kk], acc[t], 0, 0, 0);
             }
         // (uniform) the next batch's entries of r and its output rows (first dof + offset): the fragments of this batch are
         // spent, the gathers fly while the partial tiles are exchanged, added and stored
@@ -1204,7 +1205,7 @@ __global__ __launch_bounds__(256, (RT <= 2 && KW <= 10) ? 3 : ((RT <= 4 && KW <=
 #pragma unroll
             for (int kk = 0; kk < KW; ++kk) {
                 const int c = 4 * (w + 4 * kk) + lk;
-                bv[kk] = (ABL & 1) ? (double)(c + a0n) : ((lj < mb_n && c < n_n) ? r[a0n + soff[c]] : 0.0);
+                bv[kk] = (lj < mb_n && c < n_n) ? r[a0n + soff[c]] : 0.0;
             }
 #pragma unroll
             for (int t = 0; t < RT; ++t) {
@@ -1212,18 +1213,15 @@ __global__ __launch_bounds__(256, (RT <= 2 && KW <= 10) ? 3 : ((RT <= 4 && KW <=
                 od_p[t] = (lj < mb_n && i < nrow_n) ? a0n + soff[i] : -1;
             }
         }
-        if (!(ABL & 4)) {
 #pragma unroll
-            for (int t = 0; t < RT; ++t)
+        for (int t = 0; t < RT; ++t)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) part[w][t][q][lane] = acc[t][q];
-        }
-        if (!(ABL & 16)) __syncthreads();
+            for (int q = 0; q < 4; ++q) part[w][t][q][lane] = acc[t][q];
+        __syncthreads();
 #pragma unroll
         for (int t = 0; t < RT; ++t) {
-            const double sum = (ABL & 4) ? ((acc[t][0] + acc[t][1]) + acc[t][2]) + acc[t][3]
-                                         : ((part[0][t][w][lane] + part[1][t][w][lane]) + part[2][t][w][lane]) + part[3][t][w][lane];
-            if (od[t] >= 0 && (!(ABL & 2) || sum == 1.2345e300)) z[od[t]] = sum;
+            const double sum = ((part[0][t][w][lane] + part[1][t][w][lane]) + part[2][t][w][lane]) + part[3][t][w][lane];
+            if (od[t] >= 0) z[od[t]] = sum;
         }
         if (last) break;
         if (!direct_n) park_ids(buf ^ 1, v);
@@ -1232,7 +1230,7 @@ __global__ __launch_bounds__(256, (RT <= 2 && KW <= 10) ? 3 : ((RT <= 4 && KW <=
             hdr = hdr_n;
             hdr_n = p_chunk + 64 + lane < p_end ? order[p_chunk + 64 + lane] : none;
         }
-        if (!(ABL & 16)) __syncthreads();    // part and ids[buf] are rewritten by the next batch; ids[buf ^ 1] is complete
+        __syncthreads();    // part and ids[buf] are rewritten by the next batch; ids[buf ^ 1] is complete
         buf ^= 1;
         direct = direct_n;
         pos = pos_n;
@@ -1242,14 +1240,11 @@ __global__ __launch_bounds__(256, (RT <= 2 && KW <= 10) ? 3 : ((RT <= 4 && KW <=
     }
 }
 
-
-// The same batched product on a BATCH TABLE (round 4, the default when every subdomain conforms).  What bounds k_apply_mfma is
-// neither its gathers nor the matrix cores: with the gathers of r, the stores of z and the exchange of the partial tiles
-// taken out it still runs 103 of its 127 us at 214^3 cells, while its 48 matrix instructions per wave and batch alone
-// sustain 69-74 TFLOP/s on this chip (tools/microbench/mfma_f64.hip: 57 us for the same products).  The rest is the
-// instruction stream around them -- chunk records, ballots and bit scans to find the batch boundaries, predicated loads
-// compiled to one exec-mask branch each, the list path woven through the loop --, some 3 000 cycles per wave and batch,
-// which the two waves of a SIMD run through together instead of one under the other's matrix instructions.
+// The same batched product on a BATCH TABLE (the default when every subdomain conforms).  What bounds k_apply_mfma is
+// neither its gathers nor the matrix cores but the instruction stream around them -- chunk records, ballots and bit scans
+// to find the batch boundaries, predicated loads compiled to one exec-mask branch each, the list path woven through the
+// loop --, which the two waves of a SIMD run through together instead of one under the other's matrix instructions
+// (the ablations and phase clocks that said so: DESIGN_HISTORY.md, "Schwarz apply: the development kernels").
 // Here the batches are cut at setup (k_bt_*: one descriptor of 20 ints per batch: representative, sizes, subdomains in
 // the batch, subdomain of the inverse, the sixteen first dofs -- absent ones repeat the first), the control values of a
 // batch are wave-uniform scalars, every gather is unconditional (columns beyond the list read the first dof: their entries
@@ -1257,19 +1252,14 @@ __global__ __launch_bounds__(256, (RT <= 2 && KW <= 10) ? 3 : ((RT <= 4 && KW <=
 // of this batch that reads the register has been issued -- between the matrix instructions, not behind them.  Products
 // and summation order are those of k_apply_mfma: the same bits.
 constexpr int BT_W = 20;    // ints per batch descriptor: rep | n + (nrow << 10) | subdomains | subdomain of the inverse | first dofs [16]
-template <int RT, int KW, bool DBG = false>   // owned rows <= 16 RT, columns <= 16 KW; DBG: phase clocks of one wave (development)
+template <int RT, int KW>   // owned rows <= 16 RT, columns <= 16 KW
 __global__ __launch_bounds__(256, (RT <= 2 && KW <= 10) ? 3 : ((RT <= 4 && KW <= 12) ? 2 : 1)) void k_apply_bt(const int32_t* __restrict__ bt, const int32_t* __restrict__ sub_dofs,
                                                     const int64_t* __restrict__ inv_ptr, const double* __restrict__ inv,
                                                     const double* __restrict__ r, double* __restrict__ z, int32_t nbatch, int bspan) {
     __shared__ double part[4][RT][4][64];
-    long long t_begin = 0, t_loop = 0;
-    int n_reload = 0;
-    if (DBG) t_begin = __builtin_readcyclecounter();
     const int tid = threadIdx.x, lane = tid & 63, lj = lane & 15, lk = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // XCD-contiguous ranges (neighbouring boxes gather overlapping parts of r: one L2)
-    const int nwg = gridDim.x, q_ = nwg >> 3, rem_ = nwg & 7, xcd_ = blockIdx.x & 7, within_ = blockIdx.x >> 3;
-    const int wg = (xcd_ < rem_ ? xcd_ * (q_ + 1) : rem_ * (q_ + 1) + (xcd_ - rem_) * q_) + within_;
+    const int wg = xcd_contiguous_wg();
     int32_t b = wg * bspan;
     const int32_t b_end = min(nbatch, b + bspan);
     if (b >= b_end) return;
@@ -1322,12 +1312,7 @@ __global__ __launch_bounds__(256, (RT <= 2 && KW <= 10) ? 3 : ((RT <= 4 && KW <=
         for (int kk = 0; kk < KW; ++kk) bv[kk] = *reinterpret_cast<const double*>(rb + ((uint32_t)a0 * 8u + so_c[kk]));
         out_rows(h, a0, od);
     }
-    long long tk[6] = {0, 0, 0, 0, 0, 0};
-    int nbt = 0;
-    if (DBG) t_loop = __builtin_readcyclecounter();
     for (;;) {
-        long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0;
-        if (DBG) t0 = __builtin_readcyclecounter();
         const int32_t rp = __builtin_amdgcn_readfirstlane(h.x), packed = __builtin_amdgcn_readfirstlane(h.y);
         const int n = packed & 1023, nrow = (packed >> 10) & 1023;
         if (rp != cur) {    // (uniform) this lane's A fragments of the new inverse
@@ -1351,7 +1336,6 @@ __global__ __launch_bounds__(256, (RT <= 2 && KW <= 10) ? 3 : ((RT <= 4 && KW <=
                     if (!(c < n && 16 * t + lj < nrow)) a[t][kk] = 0.0;
             }
             cur = rp;
-            if (DBG) ++n_reload;
         }
         const bool more = b + 1 < b_end;    // (uniform; the last trip prepares its own batch once more and drops it)
         {
@@ -1366,7 +1350,6 @@ __global__ __launch_bounds__(256, (RT <= 2 && KW <= 10) ? 3 : ((RT <= 4 && KW <=
         const int32_t b2_ = min(b + 2, b_end - 1);
         const int4 h2 = bt4[(int64_t)b2_ * (BT_W / 4)];
         const int32_t a02 = bt[(int64_t)b2_ * BT_W + 4 + lj];
-        if (DBG) t1 = __builtin_readcyclecounter();
         ap_d4 acc[RT];
 #pragma unroll
         for (int t = 0; t < RT; ++t) acc[t] = ap_d4{0.0, 0.0, 0.0, 0.0};
@@ -1387,9 +1370,7 @@ __global__ __launch_bounds__(256, (RT <= 2 && KW <= 10) ? 3 : ((RT <= 4 && KW <=
         for (int t = 0; t < RT; ++t)
 #pragma unroll
             for (int q = 0; q < 4; ++q) part[w][t][q][lane] = acc[t][q];
-        if (DBG) t2 = __builtin_readcyclecounter();
         __syncthreads();
-        if (DBG) t3 = __builtin_readcyclecounter();
         double zs[RT];      // (all sums first: behind the predicate each tile's LDS reads and adds waited for the one before)
 #pragma unroll
         for (int t = 0; t < RT; ++t)
@@ -1397,14 +1378,6 @@ __global__ __launch_bounds__(256, (RT <= 2 && KW <= 10) ? 3 : ((RT <= 4 && KW <=
 #pragma unroll
         for (int t = 0; t < RT; ++t)
             if (od[t] != NO_ROW) *reinterpret_cast<double*>(zb + od[t]) = zs[t];
-        if (DBG) {
-            t4 = __builtin_readcyclecounter();
-            tk[0] += t1 - t0;
-            tk[1] += t2 - t1;
-            tk[2] += t3 - t2;
-            tk[3] += t4 - t3;
-            ++nbt;
-        }
         if (!more) break;
 #pragma unroll
         for (int t = 0; t < RT; ++t) od[t] = odn[t];
@@ -1414,13 +1387,6 @@ __global__ __launch_bounds__(256, (RT <= 2 && KW <= 10) ? 3 : ((RT <= 4 && KW <=
         a0n = a02;
         ++b;
         __syncthreads();    // part is rewritten by the next batch (two buffers and one barrier per batch: measured, no gain)
-        if (DBG) tk[4] += __builtin_readcyclecounter() - t4;
-    }
-    if (DBG && tid == 0 && (blockIdx.x % 31 == 0 || blockIdx.x + 8 >= gridDim.x)) {
-        const long long t_end = __builtin_readcyclecounter();
-        printf("[k_apply_bt] wg %4d (range %4d): begin %lld, prologue %lld, loop %lld ticks; %d batches, %d inverses; per batch: top %lld, products %lld, "
-               "barrier %lld, sum + stores %lld, rotate + barrier %lld\n", (int)blockIdx.x, wg, t_begin & 0xffffff, t_loop - t_begin, t_end - t_loop, nbt,
-               n_reload, tk[0] / nbt, tk[1] / nbt, tk[2] / nbt, tk[3] / nbt, tk[4] / max(nbt - 1, 1));
     }
 }
 
@@ -1467,179 +1433,6 @@ __global__ void k_bt_fill(const int4* __restrict__ rec, const int32_t* __restric
     for (int j = 0; j < AM_MB; ++j) d[4 + j] = j < mb ? rec[p + j].w : h.w;
 }
 
-// Warp-specialised form of the same batched product (round 4; option "apply_kind" 7 -- NOT the default: measured slower).
-// A workgroup of EIGHT waves, one per CU, persistent over up to 1024 places: waves 0-3 multiply -- wave w owns row tile w of the
-// shared inverse, its A fragments for all column steps in registers -- and waves 4-7 load: they gather the 16 subdomains'
-// restrictions of r three batches ahead (two register sets in flight) and park them in LDS as B[column][subdomain]
-// (double-buffered) together with the output row ids.  One barrier per batch, no partial tiles to add, the matrix-core loop is
-// back-to-back MFMAs behind software-pipelined LDS reads.  Measured at 214^3 cells / 166 375 subdomains: 224 us against the
-// 131 us of the K-split kernel above on the same box (33.9 against 46 us at 19 683 subdomains).  The counters say why
-// (tools/pmc_apply.sh, profiles/r04_pmc_apply.txt): both kernels do the same 3.7 M MFMA-busy cycles per SE and fetch 2.8-4.2 M
-// lines from L2 per apply -- r is re-fetched four to six times through the 16 KB L1s, 355-532 MB for the 80 MB vector -- and
-// the L1s spend 38 % (K-split) / 53 % (this kernel) of the time with their miss queues full (TCP_PENDING_STALL_CYCLES): the
-// apply is bound by outstanding L1 misses x L2/MALL latency per CU, and two independent workgroups per CU keep more of them
-// in flight than one workgroup with four loader waves.  Kept as an option for A/B; what would help either kernel is fetching
-// fewer lines (a workgroup owning a 3D block of boxes and staging the union of their overlap bricks once), not more overlap.
-// Dof ids: first dof + the representative's offsets for conforming subdomains (the loader lanes keep the offsets of their
-// columns in registers), the stored lists otherwise.
-constexpr int WS_SPAN = 1024;     // most places of a workgroup of the warp-specialised apply kernel
-template <int NK>    // column steps of 4: columns <= 4 NK; owned rows <= 64 (four row tiles)
-__global__ __launch_bounds__(512, 1) void k_apply_ws(const int4* __restrict__ order, const int32_t* __restrict__ sub_dofs,
-                                                     const int64_t* __restrict__ inv_ptr, const double* __restrict__ inv,
-                                                     const double* __restrict__ r, double* __restrict__ z, int32_t nsub, int span) {
-    constexpr int NC = 4 * NK, NG = NC / 16;    // columns, gathers per loader lane and batch
-    __shared__ double Bs[2][NC][16];
-    __shared__ int32_t ods[2][64][16];
-    __shared__ int4 rec[WS_SPAN];
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-    const bool loader = wv >= 4;
-    const int nwg = gridDim.x, q_ = nwg >> 3, rem_ = nwg & 7, xcd_ = blockIdx.x & 7, within_ = blockIdx.x >> 3;
-    const int wg = (xcd_ < rem_ ? xcd_ * (q_ + 1) : rem_ * (q_ + 1) + (xcd_ - rem_) * q_) + within_;
-    const int32_t p0 = wg * span, cnt = min(span, nsub - p0);
-    if (cnt <= 0) return;
-    for (int i = tid; i < cnt; i += 512) rec[i] = order[p0 + i];
-    __syncthreads();
-    // a batch = up to 16 consecutive places with the same representative and sizes (one LDS read and a ballot per wave)
-    auto batch_len = [&](int pos_) -> int {
-        if (pos_ >= cnt) return 0;
-        const int4 h0 = rec[pos_];
-        const int4 hl = rec[min(pos_ + min(lane, AM_MB - 1), cnt - 1)];
-        const uint64_t diff = __ballot(lane < AM_MB && (pos_ + lane >= cnt || hl.y != h0.y || hl.z != h0.z));
-        return diff ? (int)__builtin_ctzll(diff) : AM_MB;
-    };
-    if (loader) {
-        // batches are gathered THREE iterations before they are multiplied (two register sets in flight, parked one iteration
-        // ahead): a batch of gathers takes longer to come back than a batch of matrix-core products takes
-        const int lt = tid - 256, gj = lt & 15, gc = lt >> 4;   // subdomain gj of the batch, columns gc + 16 u
-        int32_t so[NG];
-        int32_t so_rep = -1;
-        auto gather = [&](int pos_, int mb_, double (&g)[NG], int32_t (&id4)[4]) {
-            const int4 h = rec[pos_ + min(gj, mb_ - 1)];
-            const int n_ = h.z & 1023, nrow_ = (h.z >> 10) & 1023;
-            const bool conf = (h.z >> 20) & 1;
-            const int32_t* __restrict__ row = sub_dofs + (int64_t)h.x * NMAX;
-            if (__builtin_amdgcn_readfirstlane(h.y) != so_rep) {        // (uniform: a batch has one representative)
-                const int32_t* __restrict__ ref = sub_dofs + (int64_t)h.y * NMAX;
-                const int32_t r0 = ref[0];
-#pragma unroll
-                for (int u = 0; u < NG; ++u) so[u] = gc + 16 * u < n_ ? ref[gc + 16 * u] - r0 : 0;
-                so_rep = __builtin_amdgcn_readfirstlane(h.y);
-            }
-#pragma unroll
-            for (int u = 0; u < NG; ++u) {
-                const int c = gc + 16 * u;
-                const bool on = gj < mb_ && c < n_;
-                const int32_t id = on ? (conf ? h.w + so[u] : row[c]) : 0;
-                g[u] = on ? r[id] : 0.0;
-                if (u < 4) id4[u] = (on && c < nrow_) ? id : -1;
-            }
-        };
-        auto park = [&](int buf_, const double (&g)[NG], const int32_t (&id4)[4]) {
-#pragma unroll
-            for (int u = 0; u < NG; ++u) Bs[buf_][gc + 16 * u][gj] = g[u];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) ods[buf_][gc + 16 * u][gj] = id4[u];
-        };
-        double gA[NG], gB[NG];
-        int32_t iA[4], iB[4];
-        // batches 0, 1, 2: 0 parked now, 1 in set B, 2 in set A
-        int pos = 0, mb = batch_len(0);
-        gather(pos, mb, gA, iA);
-        park(0, gA, iA);
-        pos += mb;
-        int mb1 = batch_len(pos);                   // batch i + 1 (in set B)
-        if (mb1 > 0) gather(pos, mb1, gB, iB);
-        pos += mb1;
-        int mb2 = mb1 > 0 ? batch_len(pos) : 0;     // batch i + 2 (in set A)
-        if (mb2 > 0) gather(pos, mb2, gA, iA);
-        pos += mb2;
-        __syncthreads();
-        int buf = 0;
-        for (;;) {
-            // iteration i (even): park batch i + 1 from set B, request batch i + 3 into set B
-            if (mb1 == 0) break;
-            park(buf ^ 1, gB, iB);
-            int mb3 = mb2 > 0 ? batch_len(pos) : 0;
-            if (mb3 > 0) gather(pos, mb3, gB, iB);
-            pos += mb3;
-            __syncthreads();
-            buf ^= 1;
-            // iteration i + 1 (odd): park batch i + 2 from set A, request batch i + 4 into set A
-            if (mb2 == 0) break;
-            park(buf ^ 1, gA, iA);
-            int mb4 = mb3 > 0 ? batch_len(pos) : 0;
-            if (mb4 > 0) gather(pos, mb4, gA, iA);
-            pos += mb4;
-            __syncthreads();
-            buf ^= 1;
-            mb1 = mb3;
-            mb2 = mb4;
-        }
-    } else {
-        const int w = wv, lj = lane & 15, lk = lane >> 4;
-        double a[NK];
-        int32_t cur = -1;
-        int pos_a = 0, mb_a = batch_len(0);
-        int pos_b = mb_a, mb_b = batch_len(pos_b);
-        __syncthreads();
-        int buf = 0;
-        for (;;) {
-            const int4 h = rec[pos_a];
-            const int n = h.z & 1023, nrow = (h.z >> 10) & 1023;
-            if (h.y != cur) {       // (uniform) this wave's row tile of the new inverse
-                const double* __restrict__ src = inv + inv_ptr[h.x];
-                const int i = 16 * w + lj;
-#pragma unroll
-                for (int s = 0; s < NK; ++s) {
-                    const int c = 4 * s + lk;
-                    const bool on = c < n && i < nrow;
-                    const double v = src[on ? c * nrow + i : 0];
-                    a[s] = on ? v : 0.0;
-                }
-                cur = h.y;
-            }
-            if (16 * w < nrow) {    // (uniform over the wave)
-                int32_t od[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) od[q] = ods[buf][16 * w + lk + 4 * q][lj];
-                ap_d4 acc[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] = ap_d4{0.0, 0.0, 0.0, 0.0};
-                // eight column steps at a time, the next eight B fragments requested before the current products (the scheduling
-                // barriers keep the compiler from hoisting all NK reads to the front, which spilled 300 registers)
-                double b[8], bn[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) b[u] = Bs[buf][4 * u + lk][lj];
-#pragma unroll
-                for (int s0 = 0; s0 < NK; s0 += 8) {
-                    if (s0 + 8 < NK) {
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) bn[u] = Bs[buf][4 * (s0 + 8 + u) + lk][lj];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u)
-                        acc[u & 3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s0 + u], b[u], acc[u & 3], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) b[u] = bn[u];
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (od[q] >= 0) z[od[q]] = (acc[0][q] + acc[1][q]) + (acc[2][q] + acc[3][q]);
-            }
-            if (mb_b == 0) break;
-            const int pos_c = pos_b + mb_b, mb_c = batch_len(pos_c);
-            __syncthreads();
-            buf ^= 1;
-            pos_a = pos_b;
-            mb_a = mb_b;
-            pos_b = pos_c;
-            mb_b = mb_c;
-        }
-    }
-}
-
 __global__ void k_count_mult(const int32_t* __restrict__ sub_n, const int32_t* __restrict__ sub_dofs, double* mult) {
     const int b = blockIdx.x;
     const int n = sub_n[b];
@@ -1649,6 +1442,52 @@ __global__ void k_count_mult(const int32_t* __restrict__ sub_n, const int32_t* _
 __global__ void k_div(double* __restrict__ z, const double* __restrict__ m, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) z[i] = z[i] / m[i];
+}
+
+// ---- launch of the restricted apply (host side) ----
+// The shapes of the matrix-core kernels, (row tiles, column steps per wave): a row takes subdomains of at most max_own = 16 RT
+// owned rows and max_size = 16 KW columns (fewer steps = fewer registers = more waves), on the batch table or on chunk records
+struct ApplyShape {
+    int64_t max_own, max_size;
+    void (*bt)(const int32_t*, const int32_t*, const int64_t*, const double*, const double*, double*, int32_t, int);
+    void (*mfma)(const int4*, const int32_t*, const int64_t*, const double*, const double*, double*, int32_t, int);
+};
+template <int RT, int KW>
+constexpr ApplyShape apply_shape_row() {
+    return {16 * RT, 16 * KW, k_apply_bt<RT, KW>, k_apply_mfma<RT, KW>};
+}
+constexpr ApplyShape APPLY_SHAPES[] = {apply_shape_row<2, 10>(), apply_shape_row<2, 16>(), apply_shape_row<4, 10>(),
+                                       apply_shape_row<4, 12>(), apply_shape_row<4, 16>(), apply_shape_row<6, 16>()};
+static_assert(NMAX <= 256, "the widest shapes take 16 column steps of 16: the setup admits no larger subdomain");
+
+// the first row that takes the largest subdomain (nullptr: more than 96 owned rows, no matrix-core kernel)
+const ApplyShape* apply_shape(int64_t max_own, int64_t max_size) {
+    for (const ApplyShape& s : APPLY_SHAPES)
+        if (max_own <= s.max_own && max_size <= s.max_size) return &s;
+    return nullptr;
+}
+
+// The kernel family of a restricted apply, by the outcome of the setup and option "apply_kind"
+enum class ApplyFamily { flat_compact, flat, strided, chunk_records, batch_table };
+struct ApplyChoice {
+    ApplyFamily family;
+    const ApplyShape* shape;    // (the matrix-core families)
+};
+ApplyChoice apply_family(const fedd_ctx* c, size_t park) {
+    const int kind = c->apply_kind;
+    const ApplyShape* shape = apply_shape(c->sw_max_own, c->sw_max_size);
+    // most subdomains share their inverse (schwarz_dedupe found few distinct local matrices): matrix-core kernel
+    // (a few thousand subdomains: their slabs stay in the caches and the flat kernel's shorter dependency chain wins;
+    // "apply_kind" 4 and 6 take it all the same)
+    const bool shared = c->sw_dedupe && c->sw_nrep * 4 <= c->sw_nsub && shape && kind != 1 && kind != 2 &&
+                        (c->sw_nsub >= 4096 || kind == 4 || kind == 6);
+    // the batch table: the setup built one when every subdomain conforms ("apply_kind" 6 keeps the chunk-record kernel)
+    const bool use_bt = c->sw_nbatch > 0 && kind != 6;
+    if (shared) return {use_bt ? ApplyFamily::batch_table : ApplyFamily::chunk_records, shape};
+    // flat streaming kernel while the product park of the largest slab fits 48 KB of LDS ("apply_kind" 1 and 6: strided)
+    if ((kind == 0 || kind == 2 || kind == 4) && park <= 48 * 1024)   // 2 = flat without the compact LDS layout (A/B)
+        return {c->sw_max_size <= 128 && kind != 2 ? ApplyFamily::flat_compact : ApplyFamily::flat, nullptr};
+    return {ApplyFamily::strided, nullptr};
 }
 
 }  // namespace
@@ -2119,17 +1958,40 @@ int schwarz_apply(fedd_ctx* c, const double* d_r_owned, double* d_z_owned, bool 
     }
     const dim3 blk(256);
     if (c->sw_combine == FEDD_COMBINE_RESTRICTED) {
-        // flat streaming kernel while the product park of the largest slab fits 48 KB of LDS
         const size_t park = (((size_t)c->sw_max_size * (size_t)c->sw_max_own + 1) & ~(size_t)1) * sizeof(double);
-        // most subdomains share their inverse (schwarz_dedupe found few distinct local matrices): matrix-core kernel
-        // (a few thousand subdomains: their slabs stay in the caches and the flat kernel's shorter dependency chain wins)
-        const bool shared = c->sw_dedupe && c->sw_nrep * 4 <= c->sw_nsub && c->sw_max_own <= 96 && c->apply_kind != 2 && c->apply_kind != 1 &&
-                            (c->sw_nsub >= 4096 || c->apply_kind == 4 || c->apply_kind == 6);
+        const ApplyChoice choice = apply_family(c, park);
         const int4* records = c->d_sw_order.p ? (const int4*)(c->d_sw_order.p + c->sw_order_off) : nullptr;
+        const int32_t *sub_n = c->d_sub_n.p, *sub_nown = c->d_sub_nown.p, *sub_dofs = c->d_sub_dofs.p;
+        const int64_t* inv_ptr = c->d_inv_ptr.p;
+        const double* inv = c->d_inv.p;
         // places [p0, p0 + count) of the order records (all subdomains: p0 = 0, count = sw_nsub)
         auto launch_range = [&](int64_t p0, int64_t count, bool permuted) {
             if (count <= 0) return;
-            if (shared) {
+            const int4* perm = permuted ? records : nullptr;
+            const int lds_stride = (int)((c->sw_max_size + 63) & ~63);
+            // (the batch table was cut at the split of the order and nowhere else)
+            const bool at_cut = p0 == 0 || p0 == c->sw_nint;
+            const ApplyFamily family = choice.family == ApplyFamily::batch_table && !at_cut ? ApplyFamily::chunk_records : choice.family;
+            switch (family) {
+            case ApplyFamily::batch_table: {
+                // the places [p0, p0 + count) are the batches [bt0, bt0 + btn)
+                const int64_t bt0 = p0 == 0 ? 0 : c->sw_nbatch_int;
+                const int64_t btn = (p0 == 0 && count == c->sw_nsub) ? c->sw_nbatch
+                                                                     : (p0 == 0 ? c->sw_nbatch_int : c->sw_nbatch - c->sw_nbatch_int);
+                if (btn <= 0) return;
+                // one round of workgroups: the loop over the batches is the whole kernel (prologue 2 %), so every slot of the
+                // chip -- 256 CUs x the workgroups the kernel's registers allow on one -- takes an equal share of the batches
+                // (214^3 cells, 64-node boxes, 10 417 batches: 6 per workgroup 129.6 us, 12: 126.8, 21 = one round: 119.9,
+                // 22: 123.8, 25: 136, 32: 162; 107^3 cells, 1 231 batches: 2: 30.1 us, 3 = one round: 25.1, 4: 33.6)
+                const int occ_bt = c->sw_max_own <= 32 ? 3 : 2;      // (by the registers of the shapes: 134 / 153 and 179 ... 256)
+                const int bspan = c->apply_span > 0 ? (c->apply_span + AM_MB - 1) / AM_MB
+                                                    : (int)std::max<int64_t>(1, (btn + 256 * occ_bt - 1) / (256 * occ_bt));
+                const int nwg_bt = (int)((btn + bspan - 1) / bspan);
+                hipLaunchKernelGGL(choice.shape->bt, dim3((unsigned)nwg_bt), blk, 0, c->stream, (const int32_t*)c->d_sw_bt.p + bt0 * BT_W,
+                                   sub_dofs, inv_ptr, inv, r, d_z_owned, (int32_t)btn, bspan);
+                break;
+            }
+            case ApplyFamily::chunk_records: {
                 // ranges of whole 64-place chunks (measured on the 214^3 grid, 389017 subdomains: 64: 195 us, 128: 187, 256: 191, 512: 233)
                 // (19683 subdomains, the share of one GPU of eight: 64: 40.8 us, 48: 37.0, 32: 34.9, 16: 36.2;
                 //  166375 subdomains of 64 nodes, the headline: 32: 157 us, 48: 144, 64: 142.5, 96: 138, 128: 146)
@@ -2137,100 +1999,19 @@ int schwarz_apply(fedd_ctx* c, const double* d_r_owned, double* d_z_owned, bool 
                                              : (count >= 256 * 1024 ? 128 : (count >= 128 * 1024 ? 96 : (count >= 48 * 1024 ? 64 : 32)));
                 span = std::max(16, (span + 15) / 16 * 16);     // whole 16-place batches
                 const int nwg = (int)((count + span - 1) / span);
-                // the batch table (every subdomain conforms; "apply_kind" 6 keeps the chunk-record kernel): the places [p0, p0 +
-                // count) are the batches [bt0, bt0 + btn) -- the table was cut at the split of the order
-                const bool use_bt = c->sw_nbatch > 0 && c->apply_kind != 6 && c->apply_kind != 7 && c->apply_dbg <= 0 &&
-                                    (p0 == 0 || p0 == c->sw_nint);
-                const int64_t bt0 = p0 == 0 ? 0 : c->sw_nbatch_int;
-                const int64_t btn = (p0 == 0 && count == c->sw_nsub) ? c->sw_nbatch
-                                                                     : (p0 == 0 ? c->sw_nbatch_int : c->sw_nbatch - c->sw_nbatch_int);
-                // one round of workgroups: the loop over the batches is the whole kernel (prologue 2 %), so every slot of the
-                // chip -- 256 CUs x the workgroups the kernel's registers allow on one -- takes an equal share of the batches
-                // (214^3 cells, 64-node boxes, 10 417 batches: 6 per workgroup 129.6 us, 12: 126.8, 21 = one round: 119.9,
-                // 22: 123.8, 25: 136, 32: 162; 107^3 cells, 1 231 batches: 2: 30.1 us, 3 = one round: 25.1, 4: 33.6)
-                const int occ_bt = c->sw_max_own <= 32 ? 3 : 2;      // (by the registers of the instantiations below: 134 / 153 and 179 ... 256)
-                const int bspan = c->apply_span > 0 ? std::max(1, span / AM_MB)
-                                                    : (int)std::max<int64_t>(1, (btn + 256 * occ_bt - 1) / (256 * occ_bt));
-                const int nwg_bt = (int)((btn + bspan - 1) / bspan);
-                if (use_bt && btn <= 0) return;
-#define APPLY_MFMA(RT, KW)                                                                                                   \
-    do {                                                                                                                     \
-        if (use_bt)                                                                                                          \
-            hipLaunchKernelGGL((k_apply_bt<RT, KW>), dim3((unsigned)nwg_bt), blk, 0, c->stream,                               \
-                               (const int32_t*)c->d_sw_bt.p + (int64_t)bt0 * BT_W, (const int32_t*)c->d_sub_dofs.p,          \
-                               (const int64_t*)c->d_inv_ptr.p, (const double*)c->d_inv.p, r, d_z_owned, (int32_t)btn, bspan); \
-        else                                                                                                                 \
-            hipLaunchKernelGGL((k_apply_mfma<RT, KW>), dim3((unsigned)nwg), blk, 0, c->stream, records + p0,                  \
-                               (const int32_t*)c->d_sub_dofs.p, (const int64_t*)c->d_inv_ptr.p, (const double*)c->d_inv.p, r, \
-                               d_z_owned, (int32_t)count, span);                                                             \
-    } while (0)
-                // (row tiles, column steps per wave) by the largest subdomain: fewer steps = fewer registers = more waves
-                const int64_t mx = c->sw_max_size;
-                // 33 ... 64 owned rows: the row tiles split over the waves, B through LDS (k_apply_ms); "apply_kind" 6 = K-split
-                if (c->apply_kind == 7 && c->sw_max_own > 32 && c->sw_max_own <= 64 && mx <= 256) {
-                    // one workgroup of eight waves per CU: whole rounds of 256 workgroups, at most WS_SPAN places each
-                    int span_ws = c->apply_span;
-                    if (span_ws <= 0) {
-                        const int64_t rounds = (count + 256 * WS_SPAN - 1) / (256 * WS_SPAN);
-                        span_ws = (int)((count + 256 * rounds - 1) / (256 * rounds));
-                    }
-                    span_ws = std::min(WS_SPAN, std::max(16, (span_ws + 15) / 16 * 16));
-                    const int nwg_ws = (int)((count + span_ws - 1) / span_ws);
-#define APPLY_WS(NK)                                                                                                          \
-    hipLaunchKernelGGL((k_apply_ws<NK>), dim3((unsigned)nwg_ws), dim3(512), 0, c->stream, records + p0, (const int32_t*)c->d_sub_dofs.p, \
-                       (const int64_t*)c->d_inv_ptr.p, (const double*)c->d_inv.p, r, d_z_owned, (int32_t)count, span_ws)
-                    if (mx <= 160) APPLY_WS(40);
-                    else if (mx <= 192) APPLY_WS(48);
-                    else APPLY_WS(64);
-#undef APPLY_WS
-                    return;
-                }
-                if (c->sw_max_own <= 32) {
-                    if (mx <= 160) APPLY_MFMA(2, 10);
-                    else APPLY_MFMA(2, 16);
-                } else if (c->sw_max_own <= 64) {
-                    if (mx <= 160) APPLY_MFMA(4, 10);
-                    else if (mx <= 192 && c->apply_dbg > 0) {
-#define APPLY_ABL(A)                                                                                                          \
-    case A:                                                                                                                  \
-        hipLaunchKernelGGL((k_apply_mfma<4, 12, A>), dim3((unsigned)nwg), blk, 0, c->stream, records + p0,                    \
-                           (const int32_t*)c->d_sub_dofs.p, (const int64_t*)c->d_inv_ptr.p, (const double*)c->d_inv.p, r,     \
-                           d_z_owned, (int32_t)count, span);                                                                 \
-        break;
-                        switch (c->apply_dbg) {     // (development: what bounds the kernel; results are wrong by design)
-                            APPLY_ABL(1) APPLY_ABL(3) APPLY_ABL(4) APPLY_ABL(7) APPLY_ABL(23) APPLY_ABL(32) APPLY_ABL(39) APPLY_ABL(55)
-                            default: break;
-                        }
-#undef APPLY_ABL
-                    } else if (mx <= 192 && use_bt && c->apply_dbg == -1) {     // (development: phase clocks of one wave)
-                        hipLaunchKernelGGL((k_apply_bt<4, 12, true>), dim3((unsigned)nwg_bt), blk, 0, c->stream,
-                                           (const int32_t*)c->d_sw_bt.p + (int64_t)bt0 * BT_W, (const int32_t*)c->d_sub_dofs.p,
-                                           (const int64_t*)c->d_inv_ptr.p, (const double*)c->d_inv.p, r, d_z_owned, (int32_t)btn, bspan);
-                    } else if (mx <= 192) APPLY_MFMA(4, 12);
-                    else APPLY_MFMA(4, 16);
-                } else {
-                    APPLY_MFMA(6, 16);
-                }
-#undef APPLY_MFMA
-                return;
+                hipLaunchKernelGGL(choice.shape->mfma, dim3((unsigned)nwg), blk, 0, c->stream, records + p0, sub_dofs, inv_ptr, inv, r,
+                                   d_z_owned, (int32_t)count, span);
+                break;
             }
-            const dim3 grid((unsigned)count);
-            const int4* perm = permuted ? records : nullptr;
-            if ((c->apply_kind == 0 || c->apply_kind == 2 || c->apply_kind == 4) && park <= 48 * 1024) {   // 2 = flat without the compact LDS layout (A/B)
-                if (c->sw_max_size <= 128 && c->apply_kind != 2)
-                    hipLaunchKernelGGL(k_apply_flat<true>, grid, blk, park, c->stream, (const int32_t*)c->d_sub_n.p,
-                                       (const int32_t*)c->d_sub_nown.p, (const int32_t*)c->d_sub_dofs.p,
-                                       (const int64_t*)c->d_inv_ptr.p, (const double*)c->d_inv.p, r, d_z_owned,
-                                       (c->sw_max_size + 63) & ~63, perm, (int32_t)p0);
-                else
-                    hipLaunchKernelGGL(k_apply_flat<false>, grid, blk, park, c->stream, (const int32_t*)c->d_sub_n.p,
-                                       (const int32_t*)c->d_sub_nown.p, (const int32_t*)c->d_sub_dofs.p,
-                                       (const int64_t*)c->d_inv_ptr.p, (const double*)c->d_inv.p, r, d_z_owned,
-                                       (c->sw_max_size + 63) & ~63, perm, (int32_t)p0);
-            } else {
-                hipLaunchKernelGGL(k_apply<true>, grid, blk, 0, c->stream, (const int32_t*)c->d_sub_n.p,
-                                   (const int32_t*)c->d_sub_nown.p, (const int32_t*)c->d_sub_dofs.p,
-                                   (const int64_t*)c->d_inv_ptr.p, (const double*)c->d_inv.p, r, d_z_owned, perm, (int32_t)p0);
+            case ApplyFamily::flat_compact:
+            case ApplyFamily::flat:
+                hipLaunchKernelGGL(family == ApplyFamily::flat_compact ? k_apply_flat<true> : k_apply_flat<false>, dim3((unsigned)count),
+                                   blk, park, c->stream, sub_n, sub_nown, sub_dofs, inv_ptr, inv, r, d_z_owned, lds_stride, perm, (int32_t)p0);
+                break;
+            case ApplyFamily::strided:
+                hipLaunchKernelGGL(k_apply<true>, dim3((unsigned)count), blk, 0, c->stream, sub_n, sub_nown, sub_dofs, inv_ptr, inv, r,
+                                   d_z_owned, perm, (int32_t)p0);
+                break;
             }
         };
         if (!overlap) {

@@ -39,15 +39,18 @@ def problem(fedd_lib, ctx, kind, dim, M):
     return m, A_bc, dim
 
 
-# (problem, dim, cells, nodes per box, overlap): owned rows / columns of the largest subdomain pick the kernel instance
-CASES = [("laplace", 3, 14, 27, 1),     # 27 + 74: two row tiles, ten column steps per wave
-         ("laplace", 3, 14, 8, 1),      # 8 + 56
-         ("laplace", 3, 26, 12, 2),     # two layers of overlap: 27 + 220 columns, sixteen steps
-         ("laplace", 3, 27, 64, 1),     # 64 + 144: four row tiles, sixteen steps
-         ("laplace", 2, 60, 27, 1),     # 2D boxes
-         ("linelas", 3, 16, 8, 1),      # 24 + 114
-         ("linelas", 2, 48, 27, 1),     # 50-odd owned rows: four row tiles
-         ("linelas", 2, 60, 36, 1)]     # 72 owned rows: six row tiles
+# (problem, dim, cells, nodes per box, overlap): owned rows / columns of the largest subdomain pick the row (row tiles RT, column
+# steps per wave KW) of the launch table of schwarz_apply: at most 16 RT owned rows and 16 KW columns.  Owned + overlap = columns
+# below are those of the oracle's bins and overlap layers (fo.schwarz_bins, fo.RAS); every row of the table is reached
+CASES = [("laplace", 3, 14, 27, 1),     # 27 + 74 = 101: (2, 10)
+         ("laplace", 3, 14, 8, 1),      # 8 + 38 = 46: (2, 10)
+         ("laplace", 3, 26, 12, 2),     # two layers of overlap: 27 + 220 = 247: (2, 16)
+         ("laplace", 3, 27, 64, 1),     # 64 + 122 = 186: (4, 12)
+         ("laplace", 2, 60, 27, 1),     # 2D boxes: 25 + 22 = 47: (2, 10)
+         ("laplace", 2, 62, 49, 4),     # 7 x 7 boxes, four layers: 49 + 156 = 205: (4, 16)
+         ("linelas", 3, 16, 8, 1),      # 24 + 114 = 138: (2, 10)
+         ("linelas", 2, 48, 27, 1),     # 50 + 44 = 94: (4, 10)
+         ("linelas", 2, 60, 36, 1)]     # 72 + 52 = 124: (6, 16)
 
 
 @pytest.mark.parametrize("kind,dim,M,target,overlap", CASES)

@@ -549,11 +549,35 @@ def test_whole_boxes_on_a_distorted_mesh_make_the_preconditioner_independent_of_
 
 
 # ---- options ----------------------------------------------------------------------------------------------------------------
-def test_apply_dbg_takes_only_the_values_it_has_kernels_for(fedd_lib, ctx):
-    """an unlisted positive value made schwarz_apply launch nothing and return the previous z"""
-    for v in (2, 5, 1000, -2, 0.5):
+def test_no_option_value_leaves_schwarz_apply_without_a_kernel(fedd_lib, ctx):
+    """No value of an option may make schwarz_apply return with z not written.  The development option apply_dbg (ablation
+    and phase-clock kernels; an unlisted value launched nothing and returned the previous z) is gone: every value is an
+    unknown key.  apply_kind takes the kernel families schwarz_apply has and nothing else, and each of them writes z: on the
+    smallest shared-inverse case of the suite (test_gpu_dedupe.CASES[0]) the apply of 2 r is twice the apply of r to the
+    bit (scaling by two is exact), which a kernel that did not run cannot give."""
+    for v in (2, 5, 1000, -2, 0.5) + (-1, 1, 3, 4, 7, 23, 32, 39, 55) + (0,):
         with pytest.raises(fedd_lib.FeddError, match="apply_dbg"):
             ctx.set_option("apply_dbg", v)
-    for v in (-1, 0, 1, 3, 4, 7, 23, 32, 39, 55):
-        ctx.set_option("apply_dbg", v)
-    ctx.set_option("apply_dbg", 0)
+    for v in (3, 5, 7, 8, -1, 0.5):
+        with pytest.raises(fedd_lib.FeddError, match="apply_kind"):
+            ctx.set_option("apply_kind", v)
+    kinds = (0, 1, 2, 4, 6)
+    for v in kinds:
+        ctx.set_option("apply_kind", v)
+    ctx.set_option("apply_kind", 0)
+    m = fedd_lib.structured_mesh(3, 1, 14)
+    _laplace_system(fedd_lib, ctx, m)
+    ctx.schwarz_set_target(27, 1.0)
+    ctx.set_option("schwarz_dedupe", 1)
+    ctx.schwarz_setup(1, fedd_lib.COMBINE_RESTRICTED)
+    info = ctx.schwarz_info()
+    assert info["n_unique"] * 4 <= info["n_subdomains"], info
+    r = np.random.default_rng(19).standard_normal(m["n_global"])
+    try:
+        for kind in kinds:
+            ctx.set_option("apply_kind", kind)
+            z = ctx.schwarz_apply(r)
+            assert np.all(z[_interior_rows(m)] != 0.0), kind
+            assert np.array_equal(ctx.schwarz_apply(2.0 * r), 2.0 * z), kind
+    finally:
+        ctx.set_option("apply_kind", 0)
