@@ -5,6 +5,8 @@
 //   Domain::buildMesh -> BCBuilder::addBC(zero Dirichlet on "Homogeneous Dirichlet Flag") ->
 //   LinElas(...) -> addRhsFunction -> addBoundaries -> addParemeterRhs(force, degree) ->
 //   initializeProblem -> assemble -> setBoundaries -> solve.
+// "Source Type" = "surface" in the problem file loads the surface elements with flag "Surface Flag" (default 3, the side
+// x = 1) with the traction ("Surface force", 0, 0) instead of the volume force (Problem_def.hpp:170-181, 219-254).
 // Output: iteration count and relative residual on stdout, the displacement as text (the reference
 // writes HDF5/XDMF through ExporterParaView and prints a Teuchos::StackedTimer report, both out of
 // scope here; a wall-clock time of the assemble + solve section is printed instead).
@@ -25,6 +27,10 @@ void zeroDirichlet3D(double* x, double* res, double t, const double* parameters)
 // parameters[0] is the time, parameters[1] the volume force
 void rhs2D(double* x, double* res, double* parameters) { res[0] = 0.; res[1] = parameters[1]; }
 void rhs3D(double* x, double* res, double* parameters) { res[0] = 0.; res[1] = parameters[1]; res[2] = 0.; }
+// "Source Type" = "surface": parameters[1] is the surface force (a traction along x), parameters[2] the flag of the loaded
+// surface elements, parameters[3] the flag of the element at hand (Problem::assembleSurfaceTerm puts it before the degree)
+void rhsSurface2D(double* x, double* res, double* parameters) { res[0] = parameters[3] == parameters[2] ? parameters[1] : 0.; res[1] = 0.; }
+void rhsSurface3D(double* x, double* res, double* parameters) { res[0] = parameters[3] == parameters[2] ? parameters[1] : 0.; res[1] = 0.; res[2] = 0.; }
 
 typedef default_sc SC;
 typedef default_lo LO;
@@ -90,14 +96,19 @@ static int run(int argc, char* argv[]) {
         bcFactory->addBC(dim == 2 ? zeroDirichlet2D : zeroDirichlet3D, zeroDirID, 0, domain, "Dirichlet", dim);
 
         LinElas<SC, LO, GO, NO> linElas(domain, discType, parameterListAll);
-        linElas.addRhsFunction(dim == 2 ? rhs2D : rhs3D);
+        // Problem::assembleSourceTerm reads "Source Type" itself (Problem_def.hpp:175-179); the load function goes with it
+        const bool surfaceLoad = parameterListAll->sublist("Parameter").get("Source Type", "volume") == "surface";
+        if (surfaceLoad) linElas.addRhsFunction(dim == 2 ? rhsSurface2D : rhsSurface3D);
+        else linElas.addRhsFunction(dim == 2 ? rhs2D : rhs3D);
         int its;
         const auto t0 = std::chrono::steady_clock::now();
         {
             linElas.addBoundaries(bcFactory);
-            const double force = parameterListAll->sublist("Parameter").get("Volume force", 0.);
+            const double force = surfaceLoad ? parameterListAll->sublist("Parameter").get("Surface force", 0.)
+                                             : parameterListAll->sublist("Parameter").get("Volume force", 0.);
             const double degree = 0;
             linElas.addParemeterRhs(force);
+            if (surfaceLoad) linElas.addParemeterRhs((double)parameterListAll->sublist("Parameter").get("Surface Flag", 3));
             linElas.addParemeterRhs(degree);
 
             fedd_timing_enable(domain->device()->ctx, 1);

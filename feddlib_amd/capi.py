@@ -51,6 +51,13 @@ SIGNATURES = {
     "fedd_mesh_partition_sizes": [C.c_int, C.c_int64, _i32p, C.c_int64, _i32p, C.c_int, C.c_int, C.c_int, _i64p, _i64p, _i64p, _i64p],
     "fedd_mesh_partition_extract": [C.c_int, C.c_int, C.c_int64, _i32p, C.c_int64, _f64p, _i32p, _i32p, C.c_int, C.c_int, C.c_int,
                                     _i32p, _f64p, _i64p, _i32p, _i32p, _i64p, _i32p, _i64p, _i32p, _i64p],
+    "fedd_mesh_boundary_faces": [C.c_int, C.c_int, C.c_int64, _i32p, C.c_int64, _i64p, _i32p],
+    "fedd_mesh_p2_surfaces": [C.c_int, C.c_int64, C.c_int64, _i32p, C.c_int64, _i32p, _i32p],
+    "fedd_mesh_structured_surfaces_sizes": [C.c_int, _ip, _ip, C.c_int, C.c_int, _i64p],
+    "fedd_mesh_structured_surfaces": [C.c_int, _ip, _ip, C.c_int, C.c_int, C.c_int, _i32p, _i32p],
+    "fedd_surface_set": [C.c_void_p, C.c_int, C.c_int64, _i32p, _i32p],
+    "fedd_assemble_surface": [C.c_void_p, C.c_int, C.c_int, _i32p, _f64p, C.c_int, C.c_int],
+    "fedd_assemble_surface_values": [C.c_void_p, C.c_int, _f64p, C.c_int, C.c_int],
     "fedd_fe_quadrature": [C.c_int, C.c_int, _ip, _f64p, _f64p],
     "fedd_fe_basis": [C.c_int, C.c_int, C.c_int, _f64p, _f64p],
     "fedd_mesh_set": [C.c_void_p, C.c_int, C.c_int, C.c_int64, _i32p, C.c_int64, _f64p, _i64p, C.c_int64,
@@ -309,6 +316,40 @@ def partitioned_mesh(m, part, nparts, rank, ghosts=1):
     return out
 
 
+def boundary_faces(dim, conn, n_node):
+    """the (dim-1)-faces that belong to exactly one element, [n, dim] with ascending vertex ids"""
+    conn = np.ascontiguousarray(conn, dtype=np.int32)
+    n = C.c_int64()
+    _chk(lib().fedd_mesh_boundary_faces(dim, conn.shape[1], conn.shape[0], _p(conn, _i32p), n_node, C.byref(n), None))
+    faces = np.zeros((n.value, dim), dtype=np.int32)
+    _chk(lib().fedd_mesh_boundary_faces(dim, conn.shape[1], conn.shape[0], _p(conn, _i32p), n_node, C.byref(n), _p(faces, _i32p)))
+    return faces
+
+
+def p2_surfaces(m, surf=None):
+    """P2 surface elements [n, 3 | 6] of the P1 surface elements `surf` (default m["surf"]) of the one-rank P1 mesh dict m,
+    numbered as p2_of_p1(m) numbers the mid nodes"""
+    dim = m["dim"]
+    conn = np.ascontiguousarray(m["conn"], dtype=np.int32)
+    s1 = np.ascontiguousarray(m["surf"] if surf is None else surf, dtype=np.int32).reshape(-1, dim)
+    s2 = np.zeros((s1.shape[0], 3 if dim == 2 else 6), dtype=np.int32)
+    _chk(lib().fedd_mesh_p2_surfaces(dim, m["xyz"].shape[0], conn.shape[0], _p(conn, _i32p), s1.shape[0], _p(s1, _i32p),
+                                     _p(s2, _i32p)))
+    return s2
+
+
+def structured_surfaces(dim, N, M, rank=0, flags_option=1, ghosts=False):
+    """(surf [n, dim] local repeated ids, flags [n]): the boundary faces of structured_mesh(dim, N, M, rank, ghosts=ghosts)"""
+    dec, cel = _decomp(dim, N), _decomp(dim, M)
+    n = C.c_int64()
+    _chk(lib().fedd_mesh_structured_surfaces_sizes(dim, _ints(dec), _ints(cel), rank, int(ghosts), C.byref(n)))
+    surf = np.zeros((n.value, dim), dtype=np.int32)
+    sflag = np.zeros(n.value, dtype=np.int32)
+    _chk(lib().fedd_mesh_structured_surfaces(dim, _ints(dec), _ints(cel), rank, flags_option, int(ghosts), _p(surf, _i32p),
+                                             _p(sflag, _i32p)))
+    return surf, sflag
+
+
 def fe_quadrature(dim, degree):
     """(points [nq, dim], weights [nq]) of the product's quadrature rule"""
     nq = C.c_int()
@@ -383,6 +424,7 @@ class Context:
                                        _p(xyz, _f64p), _p(gid_rep, _i64p), gid_uni.shape[0], _p(gid_uni, _i64p),
                                        _p(flag_uni, _i32p)))
         self.n_own = gid_uni.shape[0]
+        self._dim = dim
 
     def mesh_set_dict(self, m):
         self.mesh_set(m["dim"], m["conn"], m["xyz"], m["gid_rep"], m["gid_uni"], m["flag_uni"],
@@ -401,6 +443,25 @@ class Context:
     def assemble_rhs(self, f_const, extra_degree=0):
         f = np.ascontiguousarray(np.atleast_1d(f_const), dtype=np.float64)
         _chk(self._L.fedd_assemble_rhs(self._h, self.dofs, _p(f, _f64p), extra_degree))
+
+    def surface_set(self, surf, sflag):
+        """surface elements [n, nsn] (local repeated node ids) with their flags; n = 0 clears the set"""
+        s = np.ascontiguousarray(surf, dtype=np.int32)
+        f = np.ascontiguousarray(sflag, dtype=np.int32)
+        nsn = s.shape[1] if s.ndim == 2 and s.shape[1] else self._dim
+        _chk(self._L.fedd_surface_set(self._h, nsn, f.shape[0], _p(s, _i32p), _p(f, _i32p)))
+
+    def assemble_surface(self, g, flags=None, extra_degree=0, accumulate=False):
+        """rhs (+)= int g phi_i over the surface elements: g[dofs] on all of them, or g[len(flags), dofs] by flag"""
+        gg = np.ascontiguousarray(g, dtype=np.float64).ravel()
+        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.int32)
+        _chk(self._L.fedd_assemble_surface(self._h, self.dofs, 0 if fl is None else fl.shape[0], _p(fl, _i32p), _p(gg, _f64p),
+                                           extra_degree, int(accumulate)))
+
+    def assemble_surface_values(self, g_surf, extra_degree=0, accumulate=False):
+        """the same with one load per surface element, g_surf[n_surf, dofs]"""
+        gg = np.ascontiguousarray(g_surf, dtype=np.float64).ravel()
+        _chk(self._L.fedd_assemble_surface_values(self._h, self.dofs, _p(gg, _f64p), extra_degree, int(accumulate)))
 
     def dirichlet(self, flags, values=None, comp_mask=None):
         fl = np.ascontiguousarray(flags, dtype=np.int32)

@@ -208,6 +208,8 @@ static int mesh_set_impl(fedd_ctx* c, int dim, int nen, int64_t n_elem, const in
     c->p2_state = 0;     // ... and so do the gather lists of the P2 row sums
     c->adv_state = 0;    // ... and the pattern and lists of the advection matrices; the velocity belonged to the old nodes
     c->have_vel = false;
+    c->have_surf = false;   // ... and the surface elements
+    c->n_surf = 0;
     for (auto& id : c->adv_pattern_id) id = 0;
     c->d_adv_ke.release();   // the element-block scratch is sized by the mesh (the largest buffer of the advection path)
     ++c->mesh_id;
@@ -357,6 +359,42 @@ extern "C" int fedd_assemble_rhs(fedd_ctx* c, int dofs_per_node, const double* f
     FEDD_CHECK(f_const, "fedd_assemble_rhs: null f_const");
     FEDD_HIP(hipSetDevice(c->device));
     return assemble_rhs(c, dofs_per_node, f_const, extra_degree);
+}
+
+extern "C" int fedd_surface_set(fedd_ctx* c, int nsn, int64_t n_surf, const int32_t* surf, const int32_t* sflag) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(c->n_node > 0, "fedd_surface_set: call fedd_mesh_set first");
+    const bool okel = nsn == c->dim || (c->dim == 2 && nsn == 3) || (c->dim == 3 && nsn == 6);
+    FEDD_CHECK(okel, "fedd_surface_set: surface elements of a %dD mesh have %d (P1) or %d (P2) nodes, not %d", c->dim, c->dim,
+               c->dim == 2 ? 3 : 6, nsn);
+    FEDD_CHECK(n_surf >= 0 && n_surf * nsn < (int64_t)1 << 31, "fedd_surface_set: bad number of surface elements %lld", (long long)n_surf);
+    FEDD_CHECK(n_surf == 0 || (surf && sflag), "fedd_surface_set: null array");
+    FEDD_HIP(hipSetDevice(c->device));
+    return surface_set(c, nsn, n_surf, surf, sflag);
+}
+
+static int surface_entry(fedd_ctx* c, const char* who, int dofs, int n_flags, const int32_t* flags, const double* g,
+                         const double* g_surf, int extra_degree, int accumulate) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(c->have_pattern && !c->merged, "%s: call fedd_pattern_build first (the load vector of a block, not of a merged system)", who);
+    FEDD_CHECK(c->have_surf, "%s: call fedd_surface_set first", who);
+    FEDD_CHECK(dofs == c->dofs, "%s: dofs_per_node %d differs from the pattern's %d", who, dofs, c->dofs);
+    FEDD_CHECK(n_flags >= 0 && (n_flags == 0 || flags), "%s: null flag list", who);
+    FEDD_CHECK(g || g_surf || c->n_surf == 0, "%s: null load array", who);
+    FEDD_CHECK(extra_degree >= 0, "%s: negative extra degree", who);
+    FEDD_CHECK(accumulate == 0 || accumulate == 1, "%s: accumulate must be 0 or 1", who);
+    FEDD_HIP(hipSetDevice(c->device));
+    return assemble_surface(c, dofs, n_flags, flags, g, g_surf, extra_degree, accumulate);
+}
+
+extern "C" int fedd_assemble_surface(fedd_ctx* c, int dofs_per_node, int n_flags, const int32_t* flags, const double* g,
+                                     int extra_degree, int accumulate) {
+    FEDD_CHECK(g, "fedd_assemble_surface: null load array");
+    return surface_entry(c, "fedd_assemble_surface", dofs_per_node, n_flags, flags, g, nullptr, extra_degree, accumulate);
+}
+
+extern "C" int fedd_assemble_surface_values(fedd_ctx* c, int dofs_per_node, const double* g_surf, int extra_degree, int accumulate) {
+    return surface_entry(c, "fedd_assemble_surface_values", dofs_per_node, 0, nullptr, nullptr, g_surf, extra_degree, accumulate);
 }
 
 extern "C" int fedd_dirichlet(fedd_ctx* c, int n_bc, const int32_t* flags, const int32_t* comp_mask, const double* values) {

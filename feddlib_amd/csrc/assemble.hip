@@ -17,11 +17,13 @@
 // workgroup.
 #include "fedd_internal.hpp"
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <climits>
 #include <cmath>
 #include <thread>
+#include <unordered_map>
 
 namespace fedd {
 namespace {
@@ -2875,6 +2877,223 @@ int apply_dirichlet(fedd_ctx* c, int n_bc, const int32_t* flags, const int32_t* 
     t.stop();
     FEDD_HIP(hipGetLastError());
     c->have_schwarz = false;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Surface load vector: f_(i,d) = sum over the surface elements S that hold node i (as their local node li) of
+//   scaling_S * (sum_q w_q phi_q,li) * g_S[d],   scaling_S = |B[:,0]| (2D) or |B[:,0] x B[:,1]| (3D),
+// B = the vertex differences from vertex 0 (FE::assemblySurfaceIntegral[Flag] FE_def.hpp:4511-4691,
+// buildTransformationSurface :5406-5428, SmallMatrix::computeScaling SmallMatrix.hpp:360-378), counted once per local
+// volume element that holds the surface element (the reference walks the sub-elements of every element, :4550-4553).
+// Two phases like the volume load vector above: one lane per surface element for the scaling, then a gather over the
+// owned nodes' (surface element, local index) lists in list order -- no atomics, the sums do not depend on the launch shape.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// gmode 0: every element reads row 0 of the load table, 1: the row of its flag in flags[n_flags] (-1: none), 2: its own row
+template <int DIM>
+__global__ void k_surf_scaling(const int32_t* __restrict__ surf, int nsn, const double* __restrict__ xyz,
+                               const int32_t* __restrict__ weight, const int32_t* __restrict__ sflag, int64_t n_surf, int gmode,
+                               const int32_t* __restrict__ flags, int n_flags, double* __restrict__ scal, int32_t* __restrict__ gi) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_surf) return;
+    double X[DIM][DIM];
+#pragma unroll
+    for (int v = 0; v < DIM; ++v) {
+        const int32_t nd = surf[s * nsn + v];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) X[v][d] = xyz[(int64_t)nd * DIM + d];
+    }
+    double len;
+    if constexpr (DIM == 2) {
+        const double bx = X[1][0] - X[0][0], by = X[1][1] - X[0][1];
+        len = sqrt(bx * bx + by * by);
+    } else {
+        double u[3], v[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            u[d] = X[1][d] - X[0][d];
+            v[d] = X[2][d] - X[0][d];
+        }
+        const double c0 = u[1] * v[2] - u[2] * v[1], c1 = u[2] * v[0] - u[0] * v[2], c2 = u[0] * v[1] - u[1] * v[0];
+        len = sqrt(c0 * c0 + c1 * c1 + c2 * c2);
+    }
+    scal[s] = len * (double)weight[s];
+    int32_t row = gmode == 2 ? (int32_t)s : 0;
+    if (gmode == 1) {
+        row = -1;
+        const int32_t f = sflag[s];
+        for (int k = n_flags - 1; k >= 0; --k) row = flags[k] == f ? k : row;   // the first entry that names the flag
+    }
+    gi[s] = row;
+}
+
+// SURF_NPB owned nodes per workgroup: their pairs are one contiguous run of the adjacency, read coalesced (one lane per pair)
+// into an LDS park in windows of SURF_CAP pairs; then one lane per node adds its segment in adjacency order.
+constexpr int SURF_NPB = 64, SURF_CAP = 256;
+
+struct SurfArgs {
+    const int32_t* s2n_ptr;
+    const int32_t* s2n;
+    const double* scal;
+    const int32_t* gi;
+    const double* g;
+    double* rhs;
+    int32_t n_own;
+    int nsn, dofs, accumulate;
+    double base[6];  // sum_q w_q phi_q,i
+};
+
+__global__ __launch_bounds__(SURF_CAP) void k_surf_rhs(SurfArgs a) {
+    __shared__ double park[SURF_CAP];
+    __shared__ int32_t parkg[SURF_CAP];
+    const int32_t node0 = blockIdx.x * SURF_NPB;
+    const int32_t node1 = min(a.n_own, node0 + SURF_NPB);
+    const int32_t p0 = a.s2n_ptr[node0], p1 = a.s2n_ptr[node1];
+    const int tid = threadIdx.x;
+    const int32_t node = node0 + tid;
+    const bool mine = tid < SURF_NPB && node < node1;
+    const int32_t nb = mine ? a.s2n_ptr[node] : 0, ne = mine ? a.s2n_ptr[node + 1] : 0;
+    double sum[MAX_DOFS];
+#pragma unroll
+    for (int d = 0; d < MAX_DOFS; ++d) sum[d] = 0.0;
+    for (int32_t w0 = p0; w0 < p1; w0 += SURF_CAP) {
+        const int32_t w1 = min(p1, w0 + SURF_CAP);
+        if (w0 + tid < w1) {
+            const int32_t idx = a.s2n[w0 + tid];
+            const int32_t s = idx / a.nsn;
+            const int li = idx - s * a.nsn;
+            double b = 0.0;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) b = i == li ? a.base[i] : b;
+            park[tid] = a.scal[s] * b;
+            parkg[tid] = a.gi[s];
+        }
+        __syncthreads();
+        for (int32_t p = max(nb, w0); p < min(ne, w1); ++p) {
+            const int32_t row = parkg[p - w0];
+            if (row < 0) continue;
+            const double v = park[p - w0];
+#pragma unroll
+            for (int d = 0; d < MAX_DOFS; ++d)
+                if (d < a.dofs) sum[d] += v * a.g[(int64_t)row * a.dofs + d];
+        }
+        __syncthreads();
+    }
+    if (!mine || (a.accumulate && nb == ne)) return;   // accumulating: a node without surface elements keeps its value
+#pragma unroll
+    for (int d = 0; d < MAX_DOFS; ++d)
+        if (d < a.dofs) {
+            double* out = a.rhs + (int64_t)node * a.dofs + d;
+            *out = a.accumulate ? *out + sum[d] : sum[d];
+        }
+}
+
+struct FaceKeyHash {
+    size_t operator()(const std::array<int32_t, 3>& k) const {
+        uint64_t h = 0x9E3779B97F4A7C15ull;
+        for (int32_t v : k) h = (h ^ (uint64_t)(uint32_t)v) * 0xFF51AFD7ED558CCDull, h ^= h >> 32;
+        return (size_t)h;
+    }
+};
+
+}  // namespace
+
+int surface_set(fedd_ctx* c, int nsn, int64_t n_surf, const int32_t* surf, const int32_t* sflag) {
+    const int dim = c->dim;
+    c->have_surf = false;
+    c->n_surf = 0;
+    c->surf_nsn = nsn;
+    if (n_surf == 0) {
+        c->have_surf = true;
+        return 0;
+    }
+    const int64_t n_rep = (int64_t)c->h_col_of_rep.size();
+    std::vector<int32_t> surf2((size_t)(n_surf * nsn));
+    for (int64_t k = 0; k < n_surf * nsn; ++k) {
+        FEDD_CHECK(surf[k] >= 0 && surf[k] < n_rep, "fedd_surface_set: surface node id %d out of range", surf[k]);
+        surf2[k] = c->h_col_of_rep[surf[k]];
+    }
+    // weight: the local volume elements that hold all vertices of the surface element, through a map of the listed faces
+    typedef std::array<int32_t, 3> Key;
+    auto key_of = [dim](const int32_t* v) {
+        Key k = {v[0], v[1], dim == 3 ? v[2] : -1};
+        std::sort(k.begin(), k.begin() + dim);
+        return k;
+    };
+    std::unordered_map<Key, int32_t, FaceKeyHash> count;
+    count.reserve((size_t)n_surf * 2);
+    for (int64_t s = 0; s < n_surf; ++s) count.emplace(key_of(&surf2[s * nsn]), 0);
+    std::vector<int32_t> conn((size_t)(c->n_elem * c->nen));
+    FEDD_HIP(hipStreamSynchronize(c->stream));
+    if (!conn.empty()) FEDD_HIP(hipMemcpy(conn.data(), c->d_conn.p, conn.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    std::vector<char> on_surf((size_t)c->n_node, 0);   // (only elements with dim vertices on listed faces are looked up)
+    for (int64_t s = 0; s < n_surf; ++s)
+        for (int v = 0; v < dim; ++v) on_surf[surf2[s * nsn + v]] = 1;
+    for (int64_t e = 0; e < c->n_elem; ++e) {
+        int marked = 0;
+        for (int j = 0; j <= dim; ++j) marked += on_surf[conn[e * c->nen + j]];
+        if (marked < dim) continue;
+        for (int skip = 0; skip <= dim; ++skip) {
+            int32_t v[3] = {0, 0, 0};
+            int k = 0;
+            for (int j = 0; j <= dim; ++j)
+                if (j != skip) v[k++] = conn[e * c->nen + j];
+            auto it = count.find(key_of(v));
+            if (it != count.end()) ++it->second;
+        }
+    }
+    std::vector<int32_t> weight((size_t)n_surf);
+    for (int64_t s = 0; s < n_surf; ++s) weight[s] = count[key_of(&surf2[s * nsn])];
+    FEDD_TRY(c->d_surf.ensure(surf2.size()));
+    FEDD_TRY(c->d_sflag.ensure((size_t)n_surf));
+    FEDD_TRY(c->d_sweight.ensure((size_t)n_surf));
+    FEDD_HIP(hipMemcpy(c->d_surf.p, surf2.data(), surf2.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    FEDD_HIP(hipMemcpy(c->d_sflag.p, sflag, (size_t)n_surf * sizeof(int32_t), hipMemcpyHostToDevice));
+    FEDD_HIP(hipMemcpy(c->d_sweight.p, weight.data(), (size_t)n_surf * sizeof(int32_t), hipMemcpyHostToDevice));
+    int32_t max_deg = 0;
+    FEDD_TRY(build_node_lists(c, c->d_surf.p, n_surf * nsn, (int32_t)c->n_own, c->d_s2n_ptr, c->d_s2n, &max_deg));
+    FEDD_HIP(hipStreamSynchronize(c->stream));
+    c->n_surf = n_surf;
+    c->have_surf = true;
+    return 0;
+}
+
+int assemble_surface(fedd_ctx* c, int dofs, int n_flags, const int32_t* flags, const double* g, const double* g_surf,
+                     int extra_degree, int accumulate) {
+    SurfArgs a;
+    for (int i = 0; i < 6; ++i) a.base[i] = 0.0;
+    FEDD_TRY(fe_surface_base(c->dim, c->surf_nsn, extra_degree, a.base));
+    const int64_t n_surf = c->n_surf;
+    if (n_surf == 0 || c->n_own == 0) {   // the empty set: nothing to add; overwriting leaves the zero vector
+        if (!accumulate) FEDD_HIP(hipMemsetAsync(c->d_rhs.p, 0, (size_t)c->n_rows * sizeof(double), c->stream));
+        return 0;
+    }
+    const int gmode = g_surf ? 2 : (n_flags > 0 ? 1 : 0);
+    const size_t ng = (size_t)(gmode == 2 ? n_surf : (gmode == 1 ? n_flags : 1)) * dofs;
+    FEDD_TRY(c->d_sg.ensure(ng));
+    FEDD_TRY(c->d_sscal.ensure((size_t)n_surf));
+    FEDD_TRY(c->d_sgi.ensure((size_t)n_surf + (size_t)n_flags));
+    int32_t* d_flags = c->d_sgi.p + n_surf;
+    FEDD_HIP(hipStreamSynchronize(c->stream));   // an earlier launch may still read the tables
+    FEDD_HIP(hipMemcpy(c->d_sg.p, g_surf ? g_surf : g, ng * sizeof(double), hipMemcpyHostToDevice));
+    if (n_flags > 0) FEDD_HIP(hipMemcpy(d_flags, flags, (size_t)n_flags * sizeof(int32_t), hipMemcpyHostToDevice));
+    a.s2n_ptr = c->d_s2n_ptr.p; a.s2n = c->d_s2n.p; a.scal = c->d_sscal.p; a.gi = c->d_sgi.p; a.g = c->d_sg.p;
+    a.rhs = c->d_rhs.p; a.n_own = (int32_t)c->n_own; a.nsn = c->surf_nsn; a.dofs = dofs; a.accumulate = accumulate;
+    const dim3 sgrid((unsigned)((n_surf + 255) / 256)), block(256);
+    ScopedTimer t(c, FEDD_T_RHS);
+    if (c->dim == 2)
+        hipLaunchKernelGGL(k_surf_scaling<2>, sgrid, block, 0, c->stream, (const int32_t*)c->d_surf.p, c->surf_nsn,
+                           (const double*)c->d_xyz.p, (const int32_t*)c->d_sweight.p, (const int32_t*)c->d_sflag.p, n_surf, gmode,
+                           (const int32_t*)d_flags, n_flags, c->d_sscal.p, c->d_sgi.p);
+    else
+        hipLaunchKernelGGL(k_surf_scaling<3>, sgrid, block, 0, c->stream, (const int32_t*)c->d_surf.p, c->surf_nsn,
+                           (const double*)c->d_xyz.p, (const int32_t*)c->d_sweight.p, (const int32_t*)c->d_sflag.p, n_surf, gmode,
+                           (const int32_t*)d_flags, n_flags, c->d_sscal.p, c->d_sgi.p);
+    hipLaunchKernelGGL(k_surf_rhs, dim3((unsigned)((c->n_own + SURF_NPB - 1) / SURF_NPB)), dim3(SURF_CAP), 0, c->stream, a);
+    t.stop();
+    FEDD_HIP(hipGetLastError());
     return 0;
 }
 

@@ -25,6 +25,21 @@ static void push(std::vector<double>& pts, std::vector<double>& w, double x, dou
 int fe_quadrature(int dim, int degree, std::vector<double>& pts, std::vector<double>& w) {
     pts.clear();
     w.clear();
+    if (dim == 1) {  // rules on [0,1], :6031-6066 (boundary edges of 2D meshes); degrees 0 and 1 share a rule, 2 and 3 too
+        if (degree <= 1) {
+            pts.push_back(0.5);
+            w.push_back(1.);
+        } else if (degree <= 3) {
+            pts.push_back(-0.5 / std::sqrt(3.) + 0.5);
+            pts.push_back(0.5 / std::sqrt(3.) + 0.5);
+            w.push_back(.5);
+            w.push_back(.5);
+        } else {
+            set_error("1D quadrature only up to degree 3 (degree %d asked)", degree);
+            return 1;
+        }
+        return 0;
+    }
     if (degree <= 0) degree = 1;
     if (dim == 2) {
         if (degree == 3 || degree == 4) degree = 5;  // :6070-6071
@@ -91,15 +106,21 @@ int fe_quadrature(int dim, int degree, std::vector<double>& pts, std::vector<dou
         }
         return 0;
     }
-    set_error("quadrature: dimension must be 2 or 3");
+    set_error("quadrature: dimension must be 1, 2 or 3");
     return 1;
 }
 
 static void basis(int dim, int nen, const double* p, double* ph, double* g) {
-    const double x = p[0], y = p[1], z = dim == 3 ? p[2] : 0.0;
+    const double x = p[0], y = dim >= 2 ? p[1] : 0.0, z = dim == 3 ? p[2] : 0.0;
     auto G = [&](int i, int d) -> double& { return g[i * dim + d]; };
     for (int i = 0; i < nen * dim; ++i) g[i] = 0.0;
-    if (dim == 2 && nen == 3) {
+    if (dim == 1 && nen == 2) {  // line bases, :4962-4985; P2 node order end, end, mid
+        ph[0] = 1. - x; ph[1] = x;
+        G(0, 0) = -1; G(1, 0) = 1;
+    } else if (dim == 1) {
+        ph[0] = 1. - 3. * x + 2. * x * x; ph[1] = -x + 2. * x * x; ph[2] = 4. * x - 4. * x * x;
+        G(0, 0) = -3. + 4. * x; G(1, 0) = -1. + 4. * x; G(2, 0) = 4. - 8. * x;
+    } else if (dim == 2 && nen == 3) {
         ph[0] = 1. - x - y; ph[1] = x; ph[2] = y;
         G(0, 0) = -1; G(0, 1) = -1; G(1, 0) = 1; G(2, 1) = 1;
     } else if (dim == 2 && nen == 6) {
@@ -135,7 +156,8 @@ static void basis(int dim, int nen, const double* p, double* ph, double* g) {
 }
 
 int fe_tables(int dim, int nen, int degree, FeTables& out) {
-    const bool ok = (dim == 2 && (nen == 3 || nen == 6)) || (dim == 3 && (nen == 4 || nen == 10));
+    const bool ok = (dim == 1 && (nen == 2 || nen == 3)) || (dim == 2 && (nen == 3 || nen == 6)) ||
+                    (dim == 3 && (nen == 4 || nen == 10));
     if (!ok) {
         set_error("fe_tables: unsupported element (dim %d, %d nodes)", dim, nen);
         return 1;
@@ -149,6 +171,28 @@ int fe_tables(int dim, int nen, int degree, FeTables& out) {
     out.dphi.assign((size_t)out.nq * nen * dim, 0.0);
     for (int q = 0; q < out.nq; ++q)
         basis(dim, nen, &pts[(size_t)q * dim], &out.phi[(size_t)q * nen], &out.dphi[(size_t)q * nen * dim]);
+    return 0;
+}
+
+// Surface load vector on the (dim-1)-simplices of a dim-dimensional mesh with nsn nodes each: sum_q w_q phi_q,i at the
+// degree determineDegree(dim-1, FEType, Std) + extra_degree (FE_def.hpp:4530-4537, 5516-5562: P1 -> 1, P2 -> 2).
+int fe_surface_base(int dim, int nsn, int extra_degree, double* base) {
+    const bool p2 = (dim == 2 && nsn == 3) || (dim == 3 && nsn == 6);
+    if (!p2 && nsn != dim) {
+        set_error("surface elements of a %dD mesh have %d (P1) or %d (P2) nodes, not %d", dim, dim, dim == 2 ? 3 : 6, nsn);
+        return 1;
+    }
+    if (extra_degree < 0) {
+        set_error("surface integral: negative extra degree %d", extra_degree);
+        return 1;
+    }
+    FeTables tb;
+    if (fe_tables(dim - 1, nsn, (p2 ? 2 : 1) + extra_degree, tb)) return 1;
+    for (int i = 0; i < nsn; ++i) {
+        double s = 0.0;
+        for (int q = 0; q < tb.nq; ++q) s += tb.w[q] * tb.phi[(size_t)q * nsn + i];
+        base[i] = s;
+    }
     return 0;
 }
 

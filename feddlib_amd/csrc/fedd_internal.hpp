@@ -160,6 +160,16 @@ struct fedd_ctx {
     int max_deg = 0;
     bool have_adj = false;
 
+    // ---- surface elements (fedd_surface_set): boundary edges / triangles for the surface load vector ----
+    bool have_surf = false;                     // a set (possibly empty) has been given for the current mesh
+    int surf_nsn = 0;                           // nodes per surface element: dim (P1), 3 / 6 (P2 in 2D / 3D)
+    int64_t n_surf = 0;
+    fedd::DevBuf<int32_t> d_surf, d_sflag;      // [n_surf*nsn] column-local node ids, [n_surf] flags
+    fedd::DevBuf<int32_t> d_sweight;            // [n_surf] local volume elements that hold all vertices of the surface element
+    fedd::DevBuf<int32_t> d_s2n_ptr, d_s2n;     // owned node -> (surface element * nsn + local index), ascending: [n_own+1], [sum]
+    fedd::DevBuf<double> d_sscal, d_sg;         // per call: [n_surf] scaling * weight, the load table
+    fedd::DevBuf<int32_t> d_sgi;                // per call: [n_surf] row of the load table (-1: flag not asked for)
+
     // ---- CSR (dof level, owned rows) ----
     int dofs = 0, block_mode = 0;
     int64_t n_rows = 0, n_cols = 0, nnz = 0;
@@ -449,6 +459,8 @@ int radix_sort_pairs_i32(fedd_ctx* c, int32_t* keys[2], int32_t* vals[2], int32_
 
 // symbolic.hip
 int build_adjacency(fedd_ctx* c);
+int build_node_lists(fedd_ctx* c, const int32_t* d_conn, int64_t n_ent, int32_t n_nodes, DevBuf<int32_t>& ptr, DevBuf<int32_t>& lst,
+                     int32_t* max_deg);
 int build_pattern(fedd_ctx* c, int dofs, int block_mode);
 // the node-level pattern alone into buffers of the caller's (the system slot is not touched), and its closed-form expansion to dofs
 int build_node_pattern(fedd_ctx* c, DevBuf<int32_t>& nptr, DevBuf<int32_t>& ncol, int32_t* max_nn, int64_t* node_nnz);
@@ -457,6 +469,10 @@ int expand_node_pattern(fedd_ctx* c, const int32_t* nptr, const int32_t* ncol, i
 // assemble.hip
 int assemble_matrix(fedd_ctx* c, int form, const double* params);
 int assemble_rhs(fedd_ctx* c, int dofs, const double* f_const, int extra_degree);
+int surface_set(fedd_ctx* c, int nsn, int64_t n_surf, const int32_t* surf, const int32_t* sflag);
+// g_surf != nullptr: one load per surface element; else n_flags == 0: g[dofs] on every element, n_flags > 0: g[n_flags * dofs] by flag
+int assemble_surface(fedd_ctx* c, int dofs, int n_flags, const int32_t* flags, const double* g, const double* g_surf,
+                     int extra_degree, int accumulate);
 int apply_dirichlet(fedd_ctx* c, int n_bc, const int32_t* flags, const int32_t* comp_mask,
                     const double* values);
 int apply_dirichlet_nodes(fedd_ctx* c, int64_t n, const int32_t* nodes, const int32_t* comp_mask,
@@ -540,6 +556,7 @@ struct FeTables {
 };
 int fe_quadrature(int dim, int degree, std::vector<double>& pts, std::vector<double>& w);
 int fe_tables(int dim, int nen, int degree, FeTables& out);
+int fe_surface_base(int dim, int nsn, int extra_degree, double* base);   // sum_q w_q phi_q,i of the surface form, base[nsn]
 int fe_degree(int nen, int dim, bool grad);   // determineDegree building block: P1 Std 1/Grad 0, P2 2/1
 
 }  // namespace fedd

@@ -13,6 +13,7 @@
 // Layout: flat SoA arrays, no per-element objects.
 #include "fedd_internal.hpp"
 #include <algorithm>
+#include <array>
 #include <fstream>
 #include <map>
 #include <sstream>
@@ -193,6 +194,71 @@ extern "C" int fedd_mesh_p2_build(int dim, int64_t n_vert, int64_t n_elem, const
             const Edge key(std::min(u, v), std::max(u, v));
             const auto it = std::lower_bound(edges.begin(), edges.end(), key);
             conn_p2[e * nen2 + slot] = (int32_t)(n_vert + (it - edges.begin()));
+        }
+    }
+    return 0;
+}
+
+// The (dim-1)-faces of a simplex mesh that belong to exactly one element: what a mesh file lists as Edges (2D) / Triangles
+// (3D) when it lists its whole boundary.  Vertex ids ascend within a face, as the reference stores sub-elements
+// (MeshPartitioner_def.hpp:766-773, 809-810); faces come in lexicographic order.  Only the first dim + 1 nodes of an element
+// (its vertices) are read.  faces == NULL: count only.
+extern "C" int fedd_mesh_boundary_faces(int dim, int nen, int64_t n_elem, const int32_t* conn, int64_t n_node, int64_t* n_faces,
+                                        int32_t* faces) {
+    FEDD_CHECK((dim == 2 || dim == 3) && nen >= dim + 1 && n_elem >= 0 && (n_elem == 0 || conn) && n_faces,
+               "fedd_mesh_boundary_faces: bad arguments");
+    typedef std::array<int32_t, 3> Face;
+    std::vector<Face> all;
+    all.reserve((size_t)n_elem * (dim + 1));
+    for (int64_t e = 0; e < n_elem; ++e)
+        for (int skip = 0; skip <= dim; ++skip) {
+            Face f = {0, 0, 0};
+            int k = 0;
+            for (int v = 0; v <= dim; ++v) {
+                if (v == skip) continue;
+                const int32_t id = conn[e * nen + v];
+                FEDD_CHECK(id >= 0 && id < n_node, "fedd_mesh_boundary_faces: element node id %d out of range", id);
+                f[k++] = id;
+            }
+            std::sort(f.begin(), f.begin() + dim);
+            all.push_back(f);
+        }
+    std::sort(all.begin(), all.end());
+    int64_t n = 0;
+    for (size_t i = 0; i < all.size();) {
+        size_t j = i + 1;
+        while (j < all.size() && all[j] == all[i]) ++j;
+        if (j - i == 1) {
+            if (faces)
+                for (int k = 0; k < dim; ++k) faces[n * dim + k] = all[i][k];
+            ++n;
+        }
+        i = j;
+    }
+    *n_faces = n;
+    return 0;
+}
+
+// P2 surface elements from P1 ones: the dim vertices, then the mid nodes of the edges in the order of the product's line and
+// triangle bases -- 2D: mid(0,1); 3D: mid(0,1), mid(1,2), mid(0,2) -- numbered as fedd_mesh_p2_build numbers them (n_vert + rank
+// of the edge in the sorted list of the elements' edges).  The reference reaches the same node sets through the elements'
+// local surface lists (MeshUnstructured_def.hpp:459-557).  surf_p2[n_surf * (dim == 2 ? 3 : 6)].
+extern "C" int fedd_mesh_p2_surfaces(int dim, int64_t n_vert, int64_t n_elem, const int32_t* conn_p1, int64_t n_surf,
+                                     const int32_t* surf_p1, int32_t* surf_p2) {
+    FEDD_CHECK((dim == 2 || dim == 3) && conn_p1 && n_surf >= 0 && (n_surf == 0 || (surf_p1 && surf_p2)),
+               "fedd_mesh_p2_surfaces: bad arguments");
+    std::vector<Edge> edges;
+    collect_edges(dim, n_elem, conn_p1, edges);
+    const int nsn = dim == 2 ? 3 : 6, nle = dim == 2 ? 1 : 3;
+    for (int64_t s = 0; s < n_surf; ++s) {
+        for (int v = 0; v < dim; ++v) surf_p2[s * nsn + v] = surf_p1[s * dim + v];
+        for (int k = 0; k < nle; ++k) {
+            const int32_t u = surf_p1[s * dim + EDGE2[k][0]], v = surf_p1[s * dim + EDGE2[k][1]];
+            const Edge key(std::min(u, v), std::max(u, v));
+            const auto it = std::lower_bound(edges.begin(), edges.end(), key);
+            FEDD_CHECK(it != edges.end() && *it == key, "fedd_mesh_p2_surfaces: surface element %lld has an edge (%d, %d) that no element has",
+                       (long long)s, u, v);
+            surf_p2[s * nsn + dim + k] = (int32_t)(n_vert + (it - edges.begin()));
         }
     }
     return 0;

@@ -12,6 +12,7 @@
 // neighbour, which completes the rows of the ghost nodes within L - 1 layers as well ("row ghosts": the
 // Schwarz local matrices then hold true rows for nodes that belong to other ranks).
 #include "fedd_internal.hpp"
+#include <algorithm>
 #include <cmath>
 #include <limits>
 
@@ -347,5 +348,68 @@ extern "C" int fedd_mesh_structured_row_ghosts(int dim, const int* decomp, const
                 ++n;
             }
     if (n_out) *n_out = n;
+    return 0;
+}
+
+// Boundary faces of the rank's structured mesh, ghost elements included: every (dim-1)-face of a local element whose
+// vertices all lie on one side of the square / cube.  The reference builds no sub-elements for its structured meshes
+// (MeshStructured::buildSurfaceLinesSquare, MeshStructured_def.hpp:230-238, is an empty body), so the flag rule is this
+// library's: a face carries the flag setStructuredMeshFlags gives to the nodes strictly inside its side -- flags_option 0: 1
+// everywhere; flags_option 1: 2 on x = origin, 3 on x = origin + size, 1 on the other sides.  Decided on lattice indices,
+// not on coordinates.  Faces in element order, vertex ids (local repeated) ascending within a face.
+namespace {
+template <class F>
+void for_each_boundary_face(const Block& b, int flags_option, F&& f) {
+    const int dim = b.dim;
+    const unsigned all = (1u << (dim + 1)) - 1;
+    for_each_element(b, [&](const int* pr, const int* ps, const int* pt, bool) {
+        for (int d = 0; d < dim; ++d) {
+            // the vertices of the element on the lower / upper side in direction d, as bit masks: interior elements leave here
+            unsigned on[2] = {0, 0};
+            for (int v = 0; v <= dim; ++v) {
+                const int64_t g = (int64_t)(d == 0 ? pr[v] : (d == 1 ? ps[v] : pt[v])) + (int64_t)b.off[d] * b.M[d];
+                if (g == 0) on[0] |= 1u << v;
+                if (g == b.P[d] - 1) on[1] |= 1u << v;
+            }
+            for (int side = 0; side < 2; ++side)
+                for (int skip = 0; skip <= dim; ++skip)
+                    if ((on[side] | (1u << skip)) == all) f(pr, ps, pt, skip, flags_option == 1 && d == 0 ? (side ? 3 : 2) : 1);
+        }
+    });
+}
+}  // namespace
+
+extern "C" int fedd_mesh_structured_surfaces_sizes(int dim, const int* decomp, const int* cells, int rank,
+                                                   int with_ghost_elements, int64_t* n_surf) {
+    FEDD_CHECK(dim == 2 || dim == 3, "structured mesh: dimension must be 2 or 3");
+    FEDD_CHECK(n_surf, "fedd_mesh_structured_surfaces_sizes: null output");
+    Block b;
+    FEDD_TRY(make_block(dim, decomp, cells, rank, with_ghost_elements, b));
+    int64_t n = 0;
+    for_each_boundary_face(b, 0, [&](const int*, const int*, const int*, int, int) { ++n; });
+    *n_surf = n;
+    return 0;
+}
+
+extern "C" int fedd_mesh_structured_surfaces(int dim, const int* decomp, const int* cells, int rank, int flags_option,
+                                             int with_ghost_elements, int32_t* surf, int32_t* sflag) {
+    FEDD_CHECK(dim == 2 || dim == 3, "structured mesh: dimension must be 2 or 3");
+    FEDD_CHECK(flags_option == 0 || flags_option == 1, "structured mesh: flags option %d not supported", flags_option);
+    Block b;
+    FEDD_TRY(make_block(dim, decomp, cells, rank, with_ghost_elements, b));
+    Numbering num(b);
+    int64_t n = 0;
+    for_each_boundary_face(b, flags_option, [&](const int* pr, const int* ps, const int* pt, int skip, int flag) {
+        int32_t ids[3];
+        int k = 0;
+        for (int v = 0; v <= dim; ++v)
+            if (v != skip) ids[k++] = num.id(pr[v], ps[v], pt[v]);
+        for (int i = 1; i < dim; ++i)
+            for (int j = i; j > 0 && ids[j - 1] > ids[j]; --j) std::swap(ids[j - 1], ids[j]);
+        if (surf)
+            for (int i = 0; i < dim; ++i) surf[n * dim + i] = ids[i];
+        if (sflag) sflag[n] = flag;
+        ++n;
+    });
     return 0;
 }

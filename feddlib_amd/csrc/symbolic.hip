@@ -269,27 +269,37 @@ int build_adjacency(fedd_ctx* c) {      // once per mesh; its wall time is kept 
     return 0;
 }
 
+// node -> (entity, local index) lists of the first n_nodes nodes over a connectivity array of n_ent entries: counting sort by
+// node, every list ascending.  Shared by the element adjacency below and the surface-element adjacency of fedd_surface_set.
+int build_node_lists(fedd_ctx* c, const int32_t* d_conn, int64_t n_ent, int32_t n_nodes, DevBuf<int32_t>& ptr, DevBuf<int32_t>& lst,
+                     int32_t* max_deg) {
+    FEDD_TRY(ptr.ensure((size_t)n_nodes + 1));
+    FEDD_TRY(c->d_itmp0.ensure((size_t)n_nodes + 1));
+    int32_t* cnt = c->d_itmp0.p;
+    FEDD_HIP(hipMemsetAsync(cnt, 0, ((size_t)n_nodes + 1) * sizeof(int32_t), c->stream));
+    const int nb = (int)std::min<int64_t>(4096, std::max<int64_t>(1, (n_ent + 255) / 256));
+    if (n_ent > 0) hipLaunchKernelGGL(k_count_n2e, dim3(nb), dim3(256), 0, c->stream, d_conn, n_ent, n_nodes, cnt);
+    int32_t md = 0;
+    FEDD_TRY(reduce_max_i32(c, cnt, n_nodes, &md));
+    *max_deg = md;
+    int64_t total = 0;
+    FEDD_TRY(exclusive_scan_i32(c, cnt, ptr.p, n_nodes, &total));
+    FEDD_TRY(lst.ensure((size_t)total));
+    FEDD_HIP(hipMemcpyAsync(cnt, ptr.p, (size_t)n_nodes * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    if (n_ent > 0) {
+        hipLaunchKernelGGL(k_fill_n2e, dim3(nb), dim3(256), 0, c->stream, d_conn, n_ent, n_nodes, cnt, lst.p);
+        hipLaunchKernelGGL(k_sort_n2e, dim3((n_nodes + 255) / 256), dim3(256), 0, c->stream, ptr.p, n_nodes, lst.p);
+    }
+    FEDD_HIP(hipGetLastError());
+    return 0;
+}
+
 static int build_adjacency_impl(fedd_ctx* c) {
     const int64_t n_ent = c->n_elem * c->nen;
     const int32_t n_own = (int32_t)(c->n_own + c->n_rowg);   // every node that gets rows
-    FEDD_TRY(c->d_n2e_ptr.ensure((size_t)n_own + 1));
-    FEDD_TRY(c->d_itmp0.ensure((size_t)n_own + 1));
-    int32_t* cnt = c->d_itmp0.p;
-    FEDD_HIP(hipMemsetAsync(cnt, 0, ((size_t)n_own + 1) * sizeof(int32_t), c->stream));
-    const int nb = (int)std::min<int64_t>(4096, std::max<int64_t>(1, (n_ent + 255) / 256));
-    if (n_ent > 0) hipLaunchKernelGGL(k_count_n2e, dim3(nb), dim3(256), 0, c->stream, c->d_conn.p, n_ent, n_own, cnt);
     int32_t md = 0;
-    FEDD_TRY(reduce_max_i32(c, cnt, n_own, &md));
+    FEDD_TRY(build_node_lists(c, c->d_conn.p, n_ent, n_own, c->d_n2e_ptr, c->d_n2e, &md));
     c->max_deg = md;
-    int64_t total = 0;
-    FEDD_TRY(exclusive_scan_i32(c, cnt, c->d_n2e_ptr.p, n_own, &total));
-    FEDD_TRY(c->d_n2e.ensure((size_t)total));
-    FEDD_HIP(hipMemcpyAsync(cnt, c->d_n2e_ptr.p, (size_t)n_own * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
-    if (n_ent > 0) {
-        hipLaunchKernelGGL(k_fill_n2e, dim3(nb), dim3(256), 0, c->stream, c->d_conn.p, n_ent, n_own, cnt, c->d_n2e.p);
-        hipLaunchKernelGGL(k_sort_n2e, dim3((n_own + 255) / 256), dim3(256), 0, c->stream, c->d_n2e_ptr.p, n_own, c->d_n2e.p);
-    }
-    FEDD_HIP(hipGetLastError());
     c->have_adj = true;
     return 0;
 }
@@ -339,6 +349,7 @@ int build_pattern(fedd_ctx* c, int dofs, int block_mode) {
     // The per-lane lists live in LDS (cap x 64 ints per one-wave workgroup), and LDS decides how many waves a CU
     // holds: the bound above (73 for P1 tets) gives 8, a list of 32 entries 20.  Vertex-only elements are tried
     // with 32 first; a row that fills it (then the count may be cut off) sends the pass again with the full bound.
+    constexpr int PAT_CAP_LDS = 160 * 1024 / (64 * (int)sizeof(int32_t));   // longest per-lane list a one-wave workgroup can hold
     int cap = (nen == c->dim + 1) ? std::min(cap_full, 32) : cap_full;
   retry_with_full_lists:
     const size_t lds = (size_t)cap * 64 * sizeof(int32_t);
@@ -367,7 +378,11 @@ int build_pattern(fedd_ctx* c, int dofs, int block_mode) {
     int32_t max_nn = 0;
     FEDD_TRY(reduce_max_i32(c, nptr, n_own, &max_nn));
     if (max_nn >= cap && cap < cap_full) {
-        cap = cap_full;
+        // (the bound counts every node of every incident element; where it exceeds what LDS holds -- a node with hundreds of
+        // elements -- the largest list that fits is tried, and the rows decide)
+        FEDD_CHECK(cap < PAT_CAP_LDS, "pattern build: a node row with %d or more nodes exceeds the LDS list (%d incident elements)",
+                   max_nn, c->max_deg);
+        cap = std::min(cap_full, PAT_CAP_LDS);
         goto retry_with_full_lists;
     }
     int64_t node_nnz = 0;

@@ -412,6 +412,12 @@ public:
             if (nrg) feddCheck(fedd_mesh_structured_row_ghosts(dim, dec, cel, rank, ghosts, org, sz, flagsOption, &nrg, rowGhost.data(), rowGhostFlag.data()), "fedd_mesh_structured_row_ghosts");
         }
         finishMesh(grep, guni, dim + 1, ng, &rowGhost, &rowGhostFlag);
+        // the boundary faces of the rank's mesh, flagged like the nodes strictly inside their side (include/fedd_hip.h)
+        int64_t ns = 0;
+        feddCheck(fedd_mesh_structured_surfaces_sizes(dim, dec, cel, rank, ghosts, &ns), "fedd_mesh_structured_surfaces_sizes");
+        surf_.assign((size_t)ns * dim, 0); surfFlag_.assign((size_t)ns, 0); surfNsn_ = dim;
+        feddCheck(fedd_mesh_structured_surfaces(dim, dec, cel, rank, flagsOption, ghosts, surf_.data(), surfFlag_.data()), "fedd_mesh_structured_surfaces");
+        uploadSurfaces();
         if (size > 1) {     // owner of every repeated node (lowest rank whose block holds it), then the import plan
             std::vector<int32_t> owner(grep.size());
             feddCheck(fedd_mesh_structured_owner(dim, dec, cel, (int64_t)grep.size(), grep.data(), owner.data()), "fedd_mesh_structured_owner");
@@ -449,6 +455,8 @@ public:
         volumeID_ = volumeID;
         setMesh(dim, FEType, dim + 1, conn, xyz, gid, gid, vflag);
         flagRep_ = vflag;
+        surfNsn_ = dim;
+        uploadSurfaces();
     }
     void readAndPartitionMeshFile(const std::string& file, int dim, std::string FEType, int volumeID) {
         TEUCHOS_TEST_FOR_EXCEPTION(FEType != "P1", std::logic_error, "Domain::readMeshFile on several ranks: P1 meshes");
@@ -469,6 +477,18 @@ public:
                                               rowGhost.data(), rowGhostFlag.data(), egid.data()), "fedd_mesh_partition_extract");
         dim_ = dim; FEType_ = FEType; volumeID_ = volumeID;
         finishMesh(grep, guni, nen, nv, &rowGhost, &rowGhostFlag);
+        // the file's surface elements whose vertices are all in the rank's repeated map, in local repeated ids
+        std::vector<int32_t> repOfGlobal((size_t)nv, -1);
+        for (size_t i = 0; i < grep.size(); ++i) repOfGlobal[(size_t)grep[i]] = (int32_t)i;
+        surf_.clear(); surfFlag_.clear(); surfNsn_ = dim;
+        for (int64_t k = 0; k < ns; ++k) {
+            bool local = true;
+            for (int v = 0; v < dim; ++v) local = local && repOfGlobal[(size_t)surf[k * dim + v]] >= 0;
+            if (!local) continue;
+            for (int v = 0; v < dim; ++v) surf_.push_back(repOfGlobal[(size_t)surf[k * dim + v]]);
+            surfFlag_.push_back(sflag[k]);
+        }
+        uploadSurfaces();
         feddCheck(fedd_halo_set_owners(dev_->ctx, (int64_t)grep.size(), grep.data(), owner.data()), "fedd_halo_set_owners");
         dev_->finishHaloPlan();
     }
@@ -490,7 +510,21 @@ public:
         setMesh(dim, "P2", nen2, conn2, xyz2, gid, gid, flag2);
         flagRep_ = flag2;
         nP1_ = nv;
+        // P2 surface elements: the vertices, then the mid nodes in the order of the line / triangle bases
+        const int64_t ns = (int64_t)domainP1->surfFlag_.size();
+        surfNsn_ = dim == 2 ? 3 : 6;
+        surf_.assign((size_t)ns * surfNsn_, 0); surfFlag_ = domainP1->surfFlag_;
+        feddCheck(fedd_mesh_p2_surfaces(dim, nv, ne, domainP1->conn_.data(), ns, domainP1->surf_.data(), surf_.data()), "fedd_mesh_p2_surfaces");
+        uploadSurfaces();
     }
+    // surface elements of an externally built mesh (setMesh): nsn nodes each, local repeated ids
+    void setSurfaceElements(int nsn, const std::vector<int32_t>& surf, const std::vector<int32_t>& flags) {
+        surfNsn_ = nsn; surf_ = surf; surfFlag_ = flags;
+        uploadSurfaces();
+    }
+    int nodesPerSurfaceElement() const { return surfNsn_; }
+    const std::vector<int32_t>& surfaceElements() const { return surf_; }
+    const std::vector<int32_t>& surfaceFlags() const { return surfFlag_; }
     int64_t numberOfP1Nodes() const { return nP1_; }      // P2-of-P1 domain: its first nodes are the P1 nodes
 
     LO getApproxEntriesPerRow() const {      // Domain_def.hpp:176-198 (allocation hint only)
@@ -566,6 +600,9 @@ private:
             feddCheck(fedd_mesh_set(dev_->ctx, dim_, nen_, (int64_t)(conn_.size() / nen_), conn_.data(), (int64_t)grep.size(), xyz_.data(),
                                     grep.data(), (int64_t)guni.size(), guni.data(), flagUni_.data()), "fedd_mesh_set");
     }
+    void uploadSurfaces() {      // with the mesh: the boundary elements the surface load vectors integrate over
+        feddCheck(fedd_surface_set(dev_->ctx, surfNsn_, (int64_t)surfFlag_.size(), surf_.data(), surfFlag_.data()), "fedd_surface_set");
+    }
     vec2D_dbl_ptr_Type points(const std::vector<double>& xyz, size_t n, const std::vector<int32_t>* idx) const {
         vec2D_dbl_ptr_Type p = Teuchos::rcp(new vec2D_dbl_Type(n, vec_dbl_Type(dim_, 0.)));
         for (size_t i = 0; i < n; ++i) {
@@ -577,7 +614,7 @@ private:
     CommConstPtr_Type comm_;
     vec_dbl_Type coorRec;
     double length = 1., width = 1., height = 1.;
-    int dim_ = 0, n_ = 0, m_ = 0, flagsOption_ = 0, nen_ = 0;
+    int dim_ = 0, n_ = 0, m_ = 0, flagsOption_ = 0, nen_ = 0, surfNsn_ = 0;
     std::string FEType_;
     std::vector<int32_t> conn_, flagRep_, flagUni_, uniOfRep_, surf_, surfFlag_, rowGhostRep_, rowGhostFlag_;
     std::vector<double> xyz_;
@@ -675,7 +712,78 @@ public:
         feddCheck(fedd_assemble_rhs(ctx, dofs, f, degFunc), "fedd_assemble_rhs");
         feddCheck(fedd_rhs_get(ctx, a->raw().data()), "fedd_rhs_get");
     }
+    // FE::assemblySurfaceIntegral (FE_def.hpp:4511-4599): int_Gamma func . phi_i over every surface element of the domain.  The
+    // callback is evaluated once per surface element, at its first quadrature point, with the element's flag in
+    // funcParameter[size - 2]; the last entry is the degree of the function, and only constant functions are taken.  `a` lives
+    // on the unique (vec-field) map, as in assemblyRHS above.
+    void assemblySurfaceIntegral(int dim, std::string FEType, MultiVectorPtr_Type f, std::string fieldType, RhsFunc_Type func, std::vector<SC>& funcParameter) {
+        TEUCHOS_TEST_FOR_EXCEPTION(funcParameter.size() < 2, std::logic_error, "assemblySurfaceIntegral: the parameters need a slot for the surface flag before the degree.");
+        TEUCHOS_TEST_FOR_EXCEPTION(funcParameter[funcParameter.size() - 1] > 0., std::logic_error, "We only support constant functions for now.");
+        const int degFunc = (int)(funcParameter[funcParameter.size() - 1] + 1.e-14);
+        SC* params = funcParameter.data();
+        surfaceIntegral(dim, FEType, f, fieldType, degFunc, [&](double* x, double* res, int flag) {
+            params[funcParameter.size() - 2] = flag;
+            func(x, res, params);
+            return true;
+        });
+    }
+    // FE::assemblySurfaceIntegralFlag (FE_def.hpp:4601-4691): the same over the surface elements that carry the flag
+    // funcParameter[2]; funcParameter = {order, time, flag}
+    void assemblySurfaceIntegralFlag(int dim, std::string FEType, MultiVectorPtr_Type f, std::string fieldType, BC_func_Type func, std::vector<SC>& funcParameter) {
+        TEUCHOS_TEST_FOR_EXCEPTION(funcParameter.size() < 3, std::logic_error, "assemblySurfaceIntegralFlag: parameters are {order, time, flag}.");
+        TEUCHOS_TEST_FOR_EXCEPTION(funcParameter[0] != 0, std::logic_error, "We only support constant functions for now.");
+        SC* params = &funcParameter[1];
+        surfaceIntegral(dim, FEType, f, fieldType, 0, [&](double* x, double* res, int flag) {
+            if (params[1] != flag) return false;
+            func(x, res, params[0], params);
+            return true;
+        });
+    }
 private:
+    // eval(x, res, flag): the load of a surface element at the point x, false = the element is left out
+    template <class Eval>
+    void surfaceIntegral(int dim, const std::string& FEType, MultiVectorPtr_Type f, const std::string& fieldType, int degFunc, Eval eval) {
+        TEUCHOS_TEST_FOR_EXCEPTION(FEType != "P1" && FEType != "P2", std::logic_error, "Surface integrals are built for P1 and P2.");
+        TEUCHOS_TEST_FOR_EXCEPTION(f.is_null(), std::runtime_error, "MultiVector in assemblySurfaceIntegral is null.");
+        const UN loc = checkFE(dim, FEType);
+        auto dom = domainVec_[loc];
+        const int dofs = fieldType == "Scalar" ? 1 : (fieldType == "Vector" ? dim : 0);
+        TEUCHOS_TEST_FOR_EXCEPTION(dofs == 0, std::logic_error, "Invalid field type.");
+        TEUCHOS_TEST_FOR_EXCEPTION((size_t)f->getLocalLength() != (size_t)dom->getMapUnique()->getNodeNumElements() * dofs, std::logic_error,
+                                   "assemblySurfaceIntegral: the vector does not live on the unique map of a '" << fieldType << "' field.");
+        const int nsn = dom->nodesPerSurfaceElement();
+        const auto& surf = dom->surfaceElements();
+        const auto& sflag = dom->surfaceFlags();
+        const auto& xyz = dom->xyzRepeated();
+        // first quadrature point of the surface rule, degree determineDegree(dim-1, FEType, Std) + degFunc (:4530-4537)
+        int nq = 0;
+        const int deg = (FEType == "P2" ? 2 : 1) + degFunc;
+        feddCheck(fedd_fe_quadrature(dim - 1, deg, &nq, nullptr, nullptr), "fedd_fe_quadrature");
+        std::vector<double> q((size_t)nq * (dim - 1)), w((size_t)nq);
+        feddCheck(fedd_fe_quadrature(dim - 1, deg, &nq, q.data(), w.data()), "fedd_fe_quadrature");
+        std::vector<double> g(sflag.size() * dofs, 0.);
+        std::vector<double> valueFunc(dim, 0.), x(dim, 0.);
+        for (size_t s = 0; s < sflag.size(); ++s) {
+            // x = b + B q.  (The reference adds b once per column of B, :4570-4573 -- x = 2 b + B q in 3D --, which is wrong there
+            // and immaterial for the constant functions it admits.)
+            const int32_t n0 = surf[s * nsn];
+            for (int k = 0; k < dim; ++k) {
+                x[k] = xyz[(size_t)n0 * dim + k];
+                for (int l = 0; l < dim - 1; ++l) x[k] += (xyz[(size_t)surf[s * nsn + l + 1] * dim + k] - xyz[(size_t)n0 * dim + k]) * q[l];
+            }
+            if (!eval(x.data(), valueFunc.data(), sflag[s])) continue;
+            for (int d = 0; d < dofs; ++d) g[s * dofs + d] = valueFunc[d];
+        }
+        fedd_ctx* ctx = dom->device()->ctx;
+        int64_t nr = 0, nc = 0, nnz = 0;
+        if (fedd_csr_sizes(ctx, &nr, &nc, &nnz) != 0 || nr != (int64_t)f->getLocalLength()) {
+            int64_t dummy;                             // load vector before any matrix: build the matching pattern
+            feddCheck(fedd_pattern_build(ctx, dofs, dofs == 1 ? FEDD_BLOCK_SCALAR : FEDD_BLOCK_DIAG, &dummy), "fedd_pattern_build");
+            dom->device()->generation++;
+        }
+        feddCheck(fedd_assemble_surface_values(ctx, dofs, g.data(), degFunc, 0), "fedd_assemble_surface_values");
+        feddCheck(fedd_rhs_get(ctx, f->raw().data()), "fedd_rhs_get");
+    }
     void assembleInto(UN loc, int dofs, int mode, int form, const double* params, MatrixPtr_Type& A, bool callFillComplete) {
         TEUCHOS_TEST_FOR_EXCEPTION(A.is_null(), std::runtime_error, "Matrix is null.");
         auto dom = domainVec_.at(loc);
@@ -725,11 +833,14 @@ public:
             if (vecBlockID_[i] == block && vecBCType_[i].compare(0, 9, "Dirichlet") == 0) { loc = (int)i; return true; }
         return false;
     }
+    // (set() adds the "Neumann" entries, and so does setRHS(): call one of them on a right-hand side, not both, or the
+    // Neumann vector is added twice)
     // BCBuilder::set = setSystem + setRHS (BCBuilder_def.hpp:84-90).  The device call does both for
     // the diagonal block; the host evaluates the user function at every flagged unique node.
     void set(const BlockMatrixPtr_Type& blockMatrix, const BlockMultiVectorPtr_Type& blockMV, double t = 0.) const {
         TEUCHOS_TEST_FOR_EXCEPTION(blockMV->getNumVectors() > 1, std::runtime_error, "BCBuilder::setRHS() only for getNumVectors == 1.");
         for (UN block = 0; block < blockMatrix->size(); ++block) {
+            addNeumann(blockMV, (int)block, t);     // before the Dirichlet treatment, which overwrites
             int loc0;
             if (!blockHasDirichletBC((int)block, loc0)) continue;
             if (blockMatrix->size() > 1) {
@@ -834,10 +945,31 @@ public:
             dst = which == 0 ? values[k] : (which == 1 ? xi - values[k] : values[k] - xi);
         }
     }
-    void setRHS(const BlockMultiVectorPtr_Type& rhs, double t = 0.) const { setRows(rhs, rhs, t, 0); }
+    // (adds the "Neumann" entries like set(): not to be called on a right-hand side that set() has already treated)
+    void setRHS(const BlockMultiVectorPtr_Type& rhs, double t = 0.) const {
+        for (UN b = 0; b < rhs->size(); ++b) addNeumann(rhs, (int)b, t);
+        setRows(rhs, rhs, t, 0);
+    }
     void setVectorMinusBC(const BlockMultiVectorPtr_Type& v, const BlockMultiVectorPtr_Type& x, double t = 0.) const { setRows(v, x, t, 1); }
     void setBCMinusVector(const BlockMultiVectorPtr_Type& v, const BlockMultiVectorPtr_Type& x, double t = 0.) const { setRows(v, x, t, 2); }
 private:
+    // the "Neumann" entries of a block (BCBuilder::setRHS, BCBuilder_def.hpp:172-199): rhs += int_Gamma_flag g . phi_i, with
+    // funcParameter = {order 0, time, flag}.  The domain's device context computes it; a matrix of the same dofs stays untouched.
+    void addNeumann(const BlockMultiVectorPtr_Type& blockMV, int block, double t) const {
+        for (size_t i = 0; i < vecBCType_.size(); ++i) {
+            if (vecBCType_[i] != "Neumann" || vecBlockID_[i] != block) continue;
+            DomainPtr_Type domain = vecDomain_[i];
+            FE<SC, LO, GO, NO> feFactory;
+            feFactory.addFE(domain);
+            std::vector<SC> funcParameter(3, 0.);
+            funcParameter[1] = t;
+            funcParameter[2] = vecFlag_[i];
+            const int dim = (int)domain->getDimension(), dofs = vecDofs_[i];
+            auto aUnique = Teuchos::rcp(new MultiVector<SC, LO, GO, NO>(dofs > 1 ? domain->getMapVecFieldUnique() : domain->getMapUnique()));
+            feFactory.assemblySurfaceIntegralFlag(dim, domain->getFEType(), aUnique, dofs > 1 ? "Vector" : "Scalar", vecBC_func_[i], funcParameter);
+            blockMV->getBlockNonConst(block)->update(1., *aUnique, 1.);
+        }
+    }
     void setMerged(const BlockMatrixPtr_Type& blockMatrix, const BlockMultiVectorPtr_Type& blockMV, int block, double t) const {
         auto dev = blockMatrix->mergedDevice();
         TEUCHOS_TEST_FOR_EXCEPTION(dev.is_null(), std::runtime_error, "BCBuilder: the block system has not been merged on the device");
@@ -1045,8 +1177,22 @@ public:
         TEUCHOS_TEST_FOR_EXCEPTION(sourceTerm_.is_null(), std::runtime_error, "Initialize source term before you assemble it - sourceTerm pointer is null");
         sourceTerm_->putScalar(0.);
         std::string sourceType = parameterList_->sublist("Parameter").get("Source Type", "volume");
-        TEUCHOS_TEST_FOR_EXCEPTION(sourceType != "volume", std::logic_error, "only volume source terms are built");
-        assembleVolumeTerm(time);
+        if (sourceType == "volume") assembleVolumeTerm(time);
+        else if (sourceType == "surface") assembleSurfaceTerm(time);
+    }
+    void assembleSurfaceTerm(double time) const {                     // Problem_def.hpp:219-254
+        for (UN i = 0; i < sourceTerm_->size(); ++i) {
+            if (i < rhsFuncVec_.size() && rhsFuncVec_[i]) {
+                vec_dbl_Type funcParameter(1, 0.);
+                funcParameter[0] = time;
+                for (double p : parasSourceFunc_) funcParameter.push_back(p);
+                // one more slot: the surface flag of the element goes where the degree was, the degree moves to the end
+                funcParameter.push_back(funcParameter[funcParameter.size() - 1]);
+                // (always "Vector", as in the reference: a surface source of a scalar variable is rejected by the length check)
+                feFactory_->assemblySurfaceIntegral((int)getDomain((int)i)->getDimension(), getDomain((int)i)->getFEType(),
+                                                    sourceTerm_->getBlockNonConst(i), "Vector", rhsFuncVec_[i], funcParameter);
+            }
+        }
     }
     void assembleVolumeTerm(double time) const {                      // Problem_def.hpp:184-216
         for (UN i = 0; i < sourceTerm_->size(); ++i) {

@@ -141,6 +141,34 @@ int fedd_mesh_p2_build(int dim, int64_t n_vert, int64_t n_elem, const int32_t* c
                        const int32_t* vflag_p1, int64_t n_surf, const int32_t* surf, const int32_t* sflag,
                        int volume_id, int32_t* conn_p2, double* xyz_p2, int32_t* flag_p2);
 
+/* Surface elements (boundary edges in 2D, triangles in 3D), host side.
+ *   fedd_mesh_boundary_faces   the (dim-1)-faces that belong to exactly one of the n_elem elements (nen nodes each, the first
+ *                              dim + 1 the vertices): what a mesh file lists as Edges / Triangles.  Vertex ids ascend within a
+ *                              face, as the reference stores sub-elements (MeshPartitioner_def.hpp:766-773, 809-810); faces in
+ *                              lexicographic order.  faces = NULL: count only.
+ *   fedd_mesh_p2_surfaces      P2 surface elements from P1 ones: the dim vertices, then the mid nodes of the edges in the order of
+ *                              the line / triangle bases -- 2D: mid(0,1); 3D: mid(0,1), mid(1,2), mid(0,2) -- with the node ids
+ *                              fedd_mesh_p2_build gives them (n_vert + rank of the edge in the sorted edge list).  The reference
+ *                              reaches the same node sets through the elements' local surfaces (MeshUnstructured_def.hpp:459-557);
+ *                              only the assembled vector is normative, not the node order.  surf_p2[n_surf * (3 | 6)].
+ *   fedd_mesh_structured_surfaces[_sizes]
+ *                              the boundary faces of a rank's structured mesh (same arguments as fedd_mesh_structured_build,
+ *                              ghost elements included): every face of a local element that lies on a side of the square /
+ *                              cube, local repeated vertex ids ascending, in element order.  The reference builds no
+ *                              sub-elements for its structured meshes (MeshStructured::buildSurfaceLinesSquare,
+ *                              MeshStructured_def.hpp:230-238, has an empty body), so the flag rule is this library's: a face
+ *                              carries the flag setStructuredMeshFlags (:2974-3203) gives to the nodes strictly inside its side
+ *                              -- flags_option 0: 1 everywhere; flags_option 1: 2 on x = origin, 3 on x = origin + size, 1 on
+ *                              the other sides. */
+int fedd_mesh_boundary_faces(int dim, int nen, int64_t n_elem, const int32_t* conn, int64_t n_node, int64_t* n_faces,
+                             int32_t* faces /*[n_faces*dim], nullable*/);
+int fedd_mesh_p2_surfaces(int dim, int64_t n_vert, int64_t n_elem, const int32_t* conn_p1, int64_t n_surf,
+                          const int32_t* surf_p1, int32_t* surf_p2);
+int fedd_mesh_structured_surfaces_sizes(int dim, const int* decomp, const int* cells, int rank, int with_ghost_elements,
+                                        int64_t* n_surf);
+int fedd_mesh_structured_surfaces(int dim, const int* decomp, const int* cells, int rank, int flags_option,
+                                  int with_ghost_elements, int32_t* surf /*[n_surf*dim]*/, int32_t* sflag /*[n_surf]*/);
+
 /* ------------------------------------------------------------------------------------------------
  * element partitioner for unstructured meshes, host side: replaces MeshPartitioner::readAndPartitionMesh and the maps
  * it builds (feddlib/core/Mesh/MeshPartitioner_def.hpp:224-530; METIS_PartMeshDual :324, repeated map :358-397,
@@ -175,6 +203,10 @@ int fedd_mesh_partition_extract(int dim, int nen, int64_t n_elem, const int32_t*
  * tests against the reference's literals (tests/golden/ref_tables.json).
  * fedd_fe_quadrature: pts[nq*dim], w[nq] (call with NULL arrays for nq).  fedd_fe_basis: phi[nq*nen], dphi[nq*nen*dim].
  * ---------------------------------------------------------------------------------------------- */
+/* dim = 1: the rules on [0,1] (FE_def.hpp:6031-6066: degrees 0 ... 3, a higher degree is an error) and the line bases with 2 and
+ * 3 nodes (:4962-4985; P2 node order end, end, mid) that the boundary edges of a 2D mesh need; the boundary triangles of a 3D
+ * mesh use the dim = 2 tables.  The surface form integrates at degree determineDegree(dim - 1, FEType, Std) + extra_degree
+ * (:4530-4531, 5516-5562: P1 -> 1, P2 -> 2). */
 int fedd_fe_quadrature(int dim, int degree, int* nq, double* pts, double* w);
 int fedd_fe_basis(int dim, int nen, int degree, double* phi, double* dphi);
 
@@ -215,6 +247,31 @@ int fedd_assemble(fedd_ctx* ctx, int form, const double* params);
  * feddlib/problems/abstract/Problem_def.hpp:184-216): constant f per dof, quadrature degree
  * determineDegree(dim,FE,Std) + extra_degree. */
 int fedd_assemble_rhs(fedd_ctx* ctx, int dofs_per_node, const double* f_const, int extra_degree);
+
+/* Surface loads and Neumann terms: f_(i,d) += int_Gamma g_d phi_i over the surface elements of fedd_surface_set -- what
+ * FE::assemblySurfaceIntegral / assemblySurfaceIntegralFlag (FE_def.hpp:4511-4691) compute for Problem::assembleSourceTerm
+ * with "Source Type" = "surface" (Problem_def.hpp:170-181, 219-254) and for the "Neumann" entries of BCBuilder::setRHS
+ * (BCBuilder_def.hpp:172-199).  Per surface element S and local node li the contribution is
+ *   scaling_S * (sum_q w_q phi_q,li) * g[d],  scaling_S = |B[:,0]| in 2D, |B[:,0] x B[:,1]| in 3D, B = vertex differences from
+ * vertex 0 (buildTransformationSurface :5406-5428, SmallMatrix::computeScaling SmallMatrix.hpp:360-378), times the number of
+ * local volume elements that hold all vertices of S (1 on a boundary): the reference integrates a sub-element once per element
+ * that holds it (:4550-4553).  With at least one ghost layer every element at an owned node is local, so the owned rows are
+ * complete on any number of ranks without an exchange.  Like the reference (:4519, 4610) only constant loads are taken.
+ *   fedd_surface_set   surf[n_surf * nsn] local repeated node ids, nsn = dim (P1) or 3 / 6 (P2 in 2D / 3D: the vertices, then
+ *                      the mid nodes in the order of fedd_mesh_p2_surfaces), sflag[n_surf].  After fedd_mesh_set[_rows]; a later
+ *                      fedd_mesh_set drops the set.  n_surf = 0 is valid and clears it.
+ *   fedd_assemble_surface         g[n_flags * dofs]: the load of the elements that carry flags[k] (others contribute nothing);
+ *                                 n_flags = 0, flags = NULL: g[dofs] on every element.
+ *   fedd_assemble_surface_values  g_surf[n_surf * dofs]: one load per surface element.
+ * accumulate = 1 adds into the right-hand side (mv->update(1., *aUnique, 1.)); nodes without surface elements keep their value
+ * bit for bit.  accumulate = 0 overwrites it (assemblySurfaceIntegral after putScalar(0.)); such nodes get 0.  After
+ * fedd_pattern_build, owned rows only.  No atomics: each node sums its elements in ascending order, two calls agree bit for bit.
+ * Dirichlet rows: call fedd_dirichlet* afterwards; it overwrites, so where a Neumann and a Dirichlet flag meet on a node the
+ * Dirichlet value stands (the reference, in code it marks experimental, adds the Neumann vector after the Dirichlet values). */
+int fedd_surface_set(fedd_ctx* ctx, int nsn, int64_t n_surf, const int32_t* surf, const int32_t* sflag);
+int fedd_assemble_surface(fedd_ctx* ctx, int dofs_per_node, int n_flags, const int32_t* flags, const double* g,
+                          int extra_degree, int accumulate);
+int fedd_assemble_surface_values(fedd_ctx* ctx, int dofs_per_node, const double* g_surf, int extra_degree, int accumulate);
 
 /* BCBuilder::setSystem + setRHS for constant boundary values (BCBuilder_def.hpp:589-707, 93-170):
  * rows of nodes whose flag is in flags[] become unit rows (pattern kept), rhs <- values.
