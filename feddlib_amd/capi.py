@@ -17,7 +17,8 @@ COMBINE_RESTRICTED, COMBINE_AVERAGING, COMBINE_FULL = range(3)
 (T_SYMBOLIC, T_ASSEMBLE, T_RHS, T_DIRICHLET, T_SPMV, T_SCHWARZ_SETUP, T_SCHWARZ_APPLY, T_ORTHO, T_COARSE_SETUP,
  T_COARSE_APPLY, T_HALO, T_ALLREDUCE, T_SPMV_SETUP) = range(13)
 TIMER_NAMES = ["symbolic", "assemble", "rhs", "dirichlet", "spmv", "schwarz_setup", "schwarz_apply", "ortho",
-               "coarse_setup", "coarse_apply", "halo", "allreduce", "spmv_setup", "gs_dot", "gs_update", "gs_fused"]
+               "coarse_setup", "coarse_apply", "halo", "allreduce", "spmv_setup", "gs_dot", "gs_update", "gs_fused",
+               "full_park_mfma", "full_park", "full_gather", "cg_pq", "cg_xr", "cg_rz", "cg_p"]
 COARSE_Q1 = 1
 COARSE_GDSW = 2
 COARSE_RGDSW = 3
@@ -112,6 +113,10 @@ SIGNATURES = {
     "fedd_gmres_fused_blocks": [C.c_void_p, C.POINTER(C.c_int)],
     "fedd_gmres_x0": [C.c_void_p, _f64p, _f64p, C.c_double, C.c_int, C.c_int, C.c_int, _ip, _f64p],
     "fedd_gmres_status": [C.c_void_p, _ip, _f64p],
+    "fedd_cg": [C.c_void_p, _f64p, _f64p, C.c_double, C.c_int, C.c_int, _ip, _f64p],
+    "fedd_cg_x0": [C.c_void_p, _f64p, _f64p, C.c_double, C.c_int, C.c_int, _ip, _f64p],
+    "fedd_cg_info": [C.c_void_p, _ip, _ip],
+    "fedd_schwarz_full_info": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     "fedd_mesh_setup_info": [C.c_void_p, _f64p, _f64p, _ip, _i64p],
     "fedd_schwarz_coarse_apply": [C.c_void_p, _f64p, _f64p],
     "fedd_read_bandwidth": [C.c_void_p, C.c_int64, C.c_int, _f64p],
@@ -639,6 +644,34 @@ class Context:
         _chk(self._L.fedd_gmres_x0(self._h, _p(bb, _f64p), _p(x, _f64p), rtol, max_it, restart, int(use_prec),
                                    C.byref(its), C.byref(rel)))
         return (x if x is not None else self.solution_get()), its.value, rel.value
+
+    def cg(self, b=None, rtol=1e-8, max_it=1000, use_prec=True, want_x=True):
+        """preconditioned CG (symmetric positive definite systems; the preconditioner needs COMBINE_FULL)"""
+        bb = None if b is None else np.ascontiguousarray(b, dtype=np.float64)
+        nr = self.csr_sizes()[0]
+        x = np.zeros(nr) if want_x else None
+        its, rel = C.c_int(), C.c_double()
+        _chk(self._L.fedd_cg(self._h, _p(bb, _f64p), _p(x, _f64p), rtol, max_it, int(use_prec), C.byref(its), C.byref(rel)))
+        return x, its.value, rel.value
+
+    def cg_x0(self, x0=None, b=None, rtol=1e-8, max_it=1000, use_prec=True):
+        """CG from an initial guess; x0 None: from the vector the device holds"""
+        bb = None if b is None else np.ascontiguousarray(b, dtype=np.float64)
+        x = None if x0 is None else np.array(x0, dtype=np.float64, copy=True)
+        its, rel = C.c_int(), C.c_double()
+        _chk(self._L.fedd_cg_x0(self._h, _p(bb, _f64p), _p(x, _f64p), rtol, max_it, int(use_prec), C.byref(its), C.byref(rel)))
+        return (x if x is not None else self.solution_get()), its.value, rel.value
+
+    def cg_info(self):
+        a, b = C.c_int(), C.c_int()
+        _chk(self._L.fedd_cg_info(self._h, C.byref(a), C.byref(b)))
+        return {"replacements": a.value, "breakdown": b.value}
+
+    def schwarz_full_info(self):
+        """subdomains the symmetric apply parks on the matrix cores / with the one-workgroup kernel"""
+        a, b = C.c_int64(), C.c_int64()
+        _chk(self._L.fedd_schwarz_full_info(self._h, C.byref(a), C.byref(b)))
+        return {"n_mfma": a.value, "n_plain": b.value}
 
     def mesh_setup_info(self):
         a, t, st, nt = C.c_double(), C.c_double(), C.c_int(), C.c_int64()

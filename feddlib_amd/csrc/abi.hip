@@ -847,6 +847,61 @@ extern "C" int fedd_gmres_x0(fedd_ctx* c, const double* b_owned, double* x_owned
     return gmres_entry(c, "fedd_gmres_x0", true, b_owned, x_owned, rtol, max_it, restart, use_prec, its_out, relres_out);
 }
 
+static int cg_entry(fedd_ctx* c, const char* who, bool x0, const double* b_owned, double* x_owned, double rtol, int max_it,
+                    int use_prec, int* its_out, double* relres_out) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(c->have_pattern, "%s: no matrix", who);
+    FEDD_CHECK(rtol > 0 && max_it >= 1, "%s: bad rtol/max_it", who);
+    FEDD_CHECK(c->nranks == 1, "%s: a context with more than one rank (summing the overlap contributions across ranks needs an export-add that is not built)", who);
+    FEDD_CHECK(!c->merged, "%s: a merged block system is not symmetric positive definite; use fedd_gmres", who);
+    if (use_prec) {
+        FEDD_CHECK(c->have_schwarz, "%s: preconditioner requested but fedd_schwarz_setup was not called", who);
+        FEDD_CHECK(!c->sw_big_active, "%s: the large-subdomain path (schwarz_big) has no symmetric apply", who);
+        FEDD_CHECK(c->sw_combine == FEDD_COMBINE_FULL, "%s: preconditioner not symmetric: use FEDD_COMBINE_FULL", who);
+        FEDD_CHECK(c->sw_levels != FEDD_LEVELS_MULTIPLICATIVE, "%s: FEDD_LEVELS_MULTIPLICATIVE is not symmetric: use FEDD_LEVELS_ADDITIVE", who);
+    }
+    FEDD_HIP(hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->n_rows * sizeof(double);
+    if (b_owned) FEDD_HIP(hipMemcpyAsync(c->d_rhs.p, b_owned, bytes, hipMemcpyHostToDevice, c->stream));
+    if (x0 && x_owned) FEDD_HIP(hipMemcpyAsync(c->d_x.p, x_owned, bytes, hipMemcpyHostToDevice, c->stream));
+    CgCall call{c->d_rhs.p, c->d_x.p, rtol, max_it, use_prec};
+    call.x0 = x0;
+    const int rc = cg_solve(c, call, its_out, relres_out);
+    if (x_owned) {
+        FEDD_HIP(hipMemcpyAsync(x_owned, c->d_x.p, bytes, hipMemcpyDeviceToHost, c->stream));
+        FEDD_HIP(hipStreamSynchronize(c->stream));
+    }
+    return rc;
+}
+
+extern "C" int fedd_cg(fedd_ctx* c, const double* b_owned, double* x_owned, double rtol, int max_it, int use_prec, int* its_out,
+                       double* relres_out) {
+    return cg_entry(c, "fedd_cg", false, b_owned, x_owned, rtol, max_it, use_prec, its_out, relres_out);
+}
+
+extern "C" int fedd_cg_x0(fedd_ctx* c, const double* b_owned, double* x_owned, double rtol, int max_it, int use_prec, int* its_out,
+                          double* relres_out) {
+    return cg_entry(c, "fedd_cg_x0", true, b_owned, x_owned, rtol, max_it, use_prec, its_out, relres_out);
+}
+
+extern "C" int fedd_cg_info(fedd_ctx* c, int* replacements, int* breakdown) {
+    FEDD_CHECK(c, "fedd_cg_info: null context");
+    if (replacements) *replacements = c->cg_replacements;
+    if (breakdown) *breakdown = c->cg_breakdown;
+    return 0;
+}
+
+extern "C" int fedd_schwarz_full_info(fedd_ctx* c, int64_t* n_mfma, int64_t* n_plain) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(c->have_schwarz, "fedd_schwarz_full_info: no preconditioner");
+    FEDD_HIP(hipSetDevice(c->device));
+    if (c->sym_ready && c->sym_kind_built != c->apply_full_kind) c->sym_ready = false;
+    FEDD_TRY(schwarz_sym_setup(c));
+    if (n_mfma) *n_mfma = c->sw_full_nmfma;
+    if (n_plain) *n_plain = c->sw_full_nplain;
+    return 0;
+}
+
 extern "C" int fedd_mesh_setup_info(fedd_ctx* c, double* adjacency_ms, double* tiles_ms, int* tiles_state, int64_t* n_tiles) {
     FEDD_CHECK(c, "fedd_mesh_setup_info: null context");
     if (adjacency_ms) *adjacency_ms = c->have_adj ? c->adj_build_ms : 0.0;
@@ -924,6 +979,11 @@ extern "C" int fedd_set_option(fedd_ctx* c, const char* key, double value) {
         c->gdsw_tol = value;
     } else if (k == "schwarz_dedupe") c->sw_dedupe = (int)value;
     else if (k == "schwarz_fp_kind") { c->sw_fp_kind = (int)value; c->have_schwarz = false; }
+    else if (k == "apply_gather") c->apply_gather = value != 0.0;
+    else if (k == "apply_full_kind") {
+        FEDD_CHECK(value == 0 || value == 1 || value == 2, "fedd_set_option: apply_full_kind %g (one of 0, 1, 2)", value);
+        c->apply_full_kind = (int)value;
+    }
     else if (k == "apply_span") c->apply_span = (int)value;
     else if (k == "apply_bt") c->apply_bt = (int)value;
     else if (k == "gdsw_block") c->gdsw_block = value != 0.0;

@@ -330,6 +330,24 @@ struct fedd_ctx {
     fedd::DevBuf<int32_t> d_big_nblk;           // 64-blocks per subdomain
     fedd::DevBuf<int32_t> d_big_ids, d_big_pos; // subdomains taken by the batched dense inversion (compacted ids)
 
+    // ---- symmetric apply without floating-point atomics (schwarz_sym.hip): park + gather ----
+    int apply_gather = 0;                       // option "apply_gather": 1 = fedd_schwarz_apply / GMRES take the park + gather kernels for Full and Averaging
+    int apply_full_kind = 0;                    // option "apply_full_kind": 0 = matrix cores where a representative is shared, 1 = k_full_park only, 2 = matrix cores asked for
+    bool sym_force = false;                     // fedd_cg is running: the park + gather kernels whatever "apply_gather" says
+    bool sym_ready = false;                     // the structures below belong to the current preconditioner
+    int sym_kind_built = 0;                     // ... and to this value of "apply_full_kind"
+    bool sw_full_records = false;               // k_full_park walks d_sw_fplain (else every subdomain)
+    int64_t sw_sum_n = 0;                       // sum of the subdomain sizes = entries of the park
+    int64_t sw_full_nbatch = 0, sw_full_nmfma = 0, sw_full_nplain = 0;   // matrix-core batches; subdomains by park kernel
+    fedd::DevBuf<int32_t> d_sw_off;             // [nsub + 1] offset of every subdomain in the park
+    fedd::DevBuf<int32_t> d_sw_tptr, d_sw_tsrc; // transpose of sub_dofs: [n_cols + 1] list starts, [sum n_i] park positions, ascending per dof
+    fedd::DevBuf<double> d_sw_park;             // [sum n_i] y_i = A_i^-1 R_i r
+    fedd::DevBuf<int32_t> d_sw_fbatch, d_sw_fplain;   // (first place, places) per matrix-core batch; subdomains of k_full_park
+
+    // ---- CG (cg.hip) ----
+    fedd::DevBuf<double> d_cg;                  // r, z, p, q and the slots of the dot partials
+    int cg_replacements = 0, cg_breakdown = 0;  // of the last fedd_cg: residual replacements, breakdown word (FEDD_CG_BREAKDOWN_*)
+
     // ---- coarse level (two-level Schwarz) ----
     int sw_two_level = 0;
     int sw_levels = FEDD_LEVELS_ADDITIVE;       // fedd_schwarz_set_level_combination, read at apply time
@@ -500,6 +518,9 @@ int read_bandwidth(fedd_ctx* c, int64_t bytes, int reps, double* gbs);     // re
 // schwarz.hip
 int schwarz_setup(fedd_ctx* c);
 int schwarz_apply(fedd_ctx* c, const double* d_r_owned, double* d_z_owned, bool r_has_tail = false);
+// schwarz_sym.hip: Full / Averaging combine by park + gather (no floating-point atomics, fixed summation order)
+int schwarz_sym_setup(fedd_ctx* c);
+int schwarz_apply_sym(fedd_ctx* c, const double* d_r_cols, double* d_z_owned);
 int bounding_box(fedd_ctx* c, int64_t n_nodes, double lo[3], double hi[3], double* d_scratch = nullptr);   // of d_xyz[0, n_nodes)
 int global_box(fedd_ctx* c, int64_t n_own, double lo[3], double hi[3], double* n_global);   // over all ranks
 
@@ -546,6 +567,16 @@ struct GmresCall {
 };
 int gmres_solve(fedd_ctx* c, const GmresCall& call, int* its_out, double* relres_out);
 int allreduce_sum(fedd_ctx* c, double* d_buf, int n);
+
+// cg.hip
+struct CgCall {
+    const double* b;                // right-hand side (device, owned rows)
+    double* x;                      // solution; the initial guess if x0
+    double rtol;
+    int max_it, use_prec;
+    bool x0 = false;
+};
+int cg_solve(fedd_ctx* c, const CgCall& call, int* its_out, double* relres_out);
 
 // FE tables (fe_tables.cpp): reference-simplex quadrature and basis values
 struct FeTables {

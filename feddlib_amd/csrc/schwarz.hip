@@ -1579,6 +1579,7 @@ int schwarz_slab_offsets(fedd_ctx* c, int64_t nsub, int restricted) {
 }
 
 int schwarz_setup(fedd_ctx* c) {
+    c->sym_ready = false;       // (schwarz_sym.hip: its lists belong to the setup they were built for)
     if (schwarz_use_big(c)) return schwarz_setup_big(c);
     c->sw_big_active = false;
     c->have_coarse = false;
@@ -2043,6 +2044,11 @@ int schwarz_apply(fedd_ctx* c, const double* d_r_owned, double* d_z_owned, bool 
         // are not stored here, so those entries of the local solutions are not Schwarz corrections),
         // and the multiplicity counts this rank's subdomains only; no exchange is needed.
         double* z = c->d_ycol.p;
+        if (c->apply_gather || c->sym_force) {      // park + gather (schwarz_sym.hip): no atomics, fixed summation order
+            ScopedTimer t(c, FEDD_T_SCHWARZ_APPLY);
+            FEDD_TRY(schwarz_apply_sym(c, r, d_z_owned));
+            t.stop();
+        } else {
         FEDD_HIP(hipMemsetAsync(z, 0, (size_t)c->n_cols * sizeof(double), c->stream));
         {
             ScopedTimer t(c, FEDD_T_SCHWARZ_APPLY);
@@ -2055,6 +2061,7 @@ int schwarz_apply(fedd_ctx* c, const double* d_r_owned, double* d_z_owned, bool 
             hipLaunchKernelGGL(k_div, dim3((unsigned)((c->n_rows + 255) / 256)), blk, 0, c->stream, z,
                                (const double*)c->d_mult.p, c->n_rows);
         FEDD_HIP(hipMemcpyAsync(d_z_owned, z, (size_t)c->n_rows * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        }
     }
     if (levels_mult(c)) FEDD_TRY(coarse_apply_mult(c, d_z_owned));    // z = (I - Pc A) M1^-1 r
     else if (c->have_coarse) FEDD_TRY(coarse_apply_add(c, d_r_owned, d_z_owned));

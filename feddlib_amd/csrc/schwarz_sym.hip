@@ -1,0 +1,298 @@
+// Symmetric one-level Schwarz apply without floating-point atomics (FEDD_COMBINE_FULL / FEDD_COMBINE_AVERAGING):
+//   z = sum_i R_i^T A_i^-1 R_i r   [ / multiplicity ]
+// in two phases.  PARK: y_i = A_i^-1 (R_i r), all n_i rows, contiguously at the subdomain's offset in sw_park[sum n_i]
+// (k_full_park: one workgroup per subdomain, the general path; k_full_park_mfma: up to sixteen subdomains that share an
+// inverse per workgroup, on the f64 matrix cores).  GATHER: a lane per owned dof adds the parked entries of its dof in the
+// order of a list that was sorted at setup (k_full_gather).  Every sum has a fixed order: two applies of the same r give the
+// same bits, which the atomicAdd combine of k_apply<false> (schwarz.hip) does not.
+//
+// Setup (schwarz_sym_setup, at first use after a fedd_schwarz_setup with a non-restricted combine): the transpose of
+// sub_dofs -- sw_tptr[n_cols + 1] = start of every column-local dof's list, sw_tsrc[sum n_i] = its park positions
+// (subdomain offset + local index), ascending -- by count -> scan -> fill -> per-dof sort of the short lists (integer
+// atomics in count and fill; the sort fixes the order), and the split of the apply order into matrix-core batches and
+// plain subdomains.
+#include "fedd_internal.hpp"
+
+#include <algorithm>
+
+namespace fedd {
+namespace {
+
+constexpr int NMAX = SCHWARZ_NMAX;
+constexpr int FP_MB = 16;       // subdomains per matrix-core batch = columns of the B operand
+constexpr int FP_LD = 17;       // leading dimension of the gathered restrictions in LDS (doubles)
+
+typedef double fp_d4 __attribute__((ext_vector_type(4)));
+
+// ---- setup: transpose of sub_dofs ----
+__global__ void k_sym_count(const int32_t* __restrict__ sub_n, const int32_t* __restrict__ sub_dofs, int32_t n_cols,
+                            int32_t* __restrict__ cnt) {
+    const int b = blockIdx.x;
+    const int n = sub_n[b];
+    for (int k = threadIdx.x; k < n; k += blockDim.x) {
+        const int32_t d = sub_dofs[(int64_t)b * NMAX + k];
+        if (d >= 0 && d < n_cols) atomicAdd(&cnt[d], 1);
+    }
+}
+
+__global__ void k_sym_fill(const int32_t* __restrict__ sub_n, const int32_t* __restrict__ sub_dofs, const int32_t* __restrict__ off,
+                           int32_t n_cols, int32_t* __restrict__ cursor, int32_t* __restrict__ tsrc) {
+    const int b = blockIdx.x;
+    const int n = sub_n[b];
+    const int32_t o = off[b];
+    for (int k = threadIdx.x; k < n; k += blockDim.x) {
+        const int32_t d = sub_dofs[(int64_t)b * NMAX + k];
+        if (d >= 0 && d < n_cols) tsrc[atomicAdd(&cursor[d], 1)] = o + k;
+    }
+}
+
+// insertion sort of every dof's list (a handful of entries: the subdomains that overlap in one dof)
+__global__ void k_sym_sort(const int32_t* __restrict__ tptr, int32_t n_cols, int32_t* __restrict__ tsrc) {
+    const int32_t d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= n_cols) return;
+    const int32_t beg = tptr[d], end = tptr[d + 1];
+    for (int32_t i = beg + 1; i < end; ++i) {
+        const int32_t v = tsrc[i];
+        int32_t j = i - 1;
+        while (j >= beg && tsrc[j] > v) {
+            tsrc[j + 1] = tsrc[j];
+            --j;
+        }
+        tsrc[j + 1] = v;
+    }
+}
+
+// ---- park, general path: k_apply<false> of schwarz.hip with a coalesced store in place of the atomics ----
+// thread (r, s) accumulates row r over the columns c == s (mod S); the S partial sums of a row are added in order
+__global__ __launch_bounds__(256) void k_full_park(const int32_t* __restrict__ sub_n, const int32_t* __restrict__ sub_dofs,
+                                                   const int64_t* __restrict__ inv_ptr, const double* __restrict__ inv,
+                                                   const int32_t* __restrict__ off, const double* __restrict__ r,
+                                                   double* __restrict__ park, const int32_t* __restrict__ list) {
+    __shared__ double rsub[NMAX];
+    __shared__ double part[256];
+    const int b = list ? list[blockIdx.x] : (int)blockIdx.x, tid = threadIdx.x;
+    const int n = sub_n[b];
+    if (n <= 0 || n > NMAX) return;
+    for (int c = tid; c < n; c += 256) rsub[c] = r[sub_dofs[(int64_t)b * NMAX + c]];
+    __syncthreads();
+    const int S = 256 / n;
+    const int rr = tid % n, s = tid / n;
+    double acc = 0.0;
+    if (s < S) {
+        const double* __restrict__ slab = inv + inv_ptr[b] + rr;
+        int c = s;
+        for (; c + 3 * S < n; c += 4 * S) {
+            const double a0 = slab[(int64_t)c * n];
+            const double a1 = slab[(int64_t)(c + S) * n];
+            const double a2 = slab[(int64_t)(c + 2 * S) * n];
+            const double a3 = slab[(int64_t)(c + 3 * S) * n];
+            acc += a0 * rsub[c] + a1 * rsub[c + S] + a2 * rsub[c + 2 * S] + a3 * rsub[c + 3 * S];
+        }
+        for (; c < n; c += S) acc += slab[(int64_t)c * n] * rsub[c];
+    }
+    part[tid] = acc;
+    __syncthreads();
+    if (tid < n) {
+        double sum = 0.0;
+        for (int q = 0; q < S; ++q) sum += part[q * n + tid];
+        park[(int64_t)off[b] + tid] = sum;
+    }
+}
+
+// ---- park, matrix cores: one workgroup per batch of up to sixteen consecutive places of the order records that share a
+// representative (hence n and the inverse).  The restrictions of r are gathered into LDS as R[n_pad][16] (columns beyond the
+// batch and entries beyond n are zero); wave w takes the 16-row tiles w, w + 4, ... of the inverse and walks K in steps of 4
+// with v_mfma_f64_16x16x4_f64: lane (i = lane & 15, k = lane >> 4) holds A[16 t + i][4 s + k] from the slab (column-major,
+// L2-resident: few representatives), lane (k, j = lane & 15) holds R[4 s + k][j] from LDS; result register q of lane (k, j)
+// is row 16 t + k + 4 q of subdomain j.  Rows and columns beyond n are padded by multiplying zeros of R against clamped
+// (valid, finite) entries of A; nothing branches per element, and the loads of four K steps are issued together. ----
+__global__ __launch_bounds__(256) void k_full_park_mfma(const int2* __restrict__ batch, const int4* __restrict__ rec,
+                                                        const int32_t* __restrict__ sub_dofs, const int64_t* __restrict__ inv_ptr,
+                                                        const double* __restrict__ inv, const int32_t* __restrict__ off,
+                                                        const double* __restrict__ r, double* __restrict__ park) {
+    __shared__ double R[NMAX * FP_LD];
+    __shared__ int32_t s_sub[FP_MB], s_off[FP_MB];
+    const int tid = threadIdx.x, lane = tid & 63, lj = lane & 15, lk = lane >> 4;
+    const int w = tid >> 6;
+    const int2 bt = batch[blockIdx.x];
+    const int p0 = bt.x, mb = bt.y;
+    const int4 h = rec[p0];
+    const int rep = h.y, n = h.z & 1023;
+    if (n <= 0 || n > NMAX || mb <= 0 || mb > FP_MB) return;    // (uniform)
+    const int n_pad = (n + 15) & ~15;
+    if (tid < FP_MB) {
+        const int sidx = tid < mb ? rec[p0 + tid].x : -1;
+        s_sub[tid] = sidx;
+        s_off[tid] = sidx >= 0 ? off[sidx] : 0;
+    }
+    __syncthreads();
+    // gather: consecutive lanes read consecutive entries of one subdomain's list
+    for (int idx = tid; idx < n_pad * FP_MB; idx += 256) {
+        const int j = idx / n_pad, k = idx - j * n_pad;
+        const int sidx = s_sub[j];
+        double v = 0.0;
+        if (sidx >= 0 && k < n) v = r[sub_dofs[(int64_t)sidx * NMAX + k]];
+        R[k * FP_LD + j] = v;
+    }
+    __syncthreads();
+    const double* __restrict__ slab = inv + inv_ptr[rep];
+    const int nt = n_pad >> 4, nstep = n_pad >> 2;
+    const int my_off = s_off[lj];
+    const bool my_col = lj < mb;
+    for (int t = w; t < nt; t += 4) {
+        const int i = min(16 * t + lj, n - 1);      // (rows beyond n: clamped, never stored)
+        const double* __restrict__ arow = slab + i;
+        fp_d4 acc = {0.0, 0.0, 0.0, 0.0};
+        for (int s = 0; s < nstep; s += 4) {
+            // (columns beyond n: a clamped entry of A against a zero of R)
+            const double a0 = arow[(int64_t)min(4 * s + lk, n - 1) * n];
+            const double a1 = arow[(int64_t)min(4 * s + 4 + lk, n - 1) * n];
+            const double a2 = arow[(int64_t)min(4 * s + 8 + lk, n - 1) * n];
+            const double a3 = arow[(int64_t)min(4 * s + 12 + lk, n - 1) * n];
+            const double b0 = R[(4 * s + lk) * FP_LD + lj];
+            const double b1 = R[(4 * s + 4 + lk) * FP_LD + lj];
+            const double b2 = R[(4 * s + 8 + lk) * FP_LD + lj];
+            const double b3 = R[(4 * s + 12 + lk) * FP_LD + lj];
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b2, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a3, b3, acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int row = 16 * t + lk + 4 * q;
+            if (my_col && row < n) park[(int64_t)my_off + row] = acc[q];     // absent columns / padding rows: not stored
+        }
+    }
+}
+
+// ---- gather: a lane per owned dof; the sources of four trips are loaded together and added in list order ----
+__global__ __launch_bounds__(256) void k_full_gather(const int32_t* __restrict__ tptr, const int32_t* __restrict__ tsrc,
+                                                     const double* __restrict__ park, int32_t n_rows, int averaging,
+                                                     double* __restrict__ z) {
+    const int32_t d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= n_rows) return;       // (ghost columns are not written)
+    const int32_t beg = tptr[d], len = tptr[d + 1] - beg;
+    double s = 0.0;
+    for (int32_t k = 0; k < len; k += 4) {
+        const int32_t i0 = tsrc[beg + k];
+        const int32_t i1 = tsrc[beg + min(k + 1, len - 1)];
+        const int32_t i2 = tsrc[beg + min(k + 2, len - 1)];
+        const int32_t i3 = tsrc[beg + min(k + 3, len - 1)];
+        const double v0 = park[i0], v1 = park[i1], v2 = park[i2], v3 = park[i3];
+        s += v0;
+        if (k + 1 < len) s += v1;
+        if (k + 2 < len) s += v2;
+        if (k + 3 < len) s += v3;
+    }
+    if (averaging && len > 1) s = s / (double)len;
+    z[d] = s;
+}
+
+}  // namespace
+
+int schwarz_sym_setup(fedd_ctx* c) {
+    if (c->sym_ready) return 0;
+    FEDD_CHECK(c->have_schwarz && !c->sw_big_active && c->sw_combine != FEDD_COMBINE_RESTRICTED,
+               "symmetric Schwarz apply: needs a fedd_schwarz_setup with FEDD_COMBINE_FULL or FEDD_COMBINE_AVERAGING on the small-subdomain path");
+    const int64_t nsub = c->sw_nsub;
+    const int32_t n_cols = (int32_t)std::max(c->n_cols, c->n_rows);
+    const dim3 blk(256);
+    hipStream_t st = c->stream;
+    // offsets of the subdomains in the park
+    int64_t total = 0;
+    FEDD_TRY(c->d_sw_off.ensure((size_t)nsub + 1));
+    FEDD_TRY(exclusive_scan_i32(c, c->d_sub_n.p, c->d_sw_off.p, nsub, &total));
+    FEDD_CHECK(total > 0 && total < ((int64_t)1 << 31), "symmetric Schwarz apply: %lld park entries", (long long)total);
+    c->sw_sum_n = total;
+    FEDD_TRY(c->d_sw_park.ensure((size_t)total));
+    FEDD_TRY(c->d_sw_tptr.ensure((size_t)n_cols + 1));
+    FEDD_TRY(c->d_sw_tsrc.ensure((size_t)total));
+    FEDD_TRY(c->d_itmp0.ensure((size_t)n_cols + 1));
+    FEDD_HIP(hipMemsetAsync(c->d_sw_tptr.p, 0, ((size_t)n_cols + 1) * sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_sym_count, dim3((unsigned)nsub), dim3(64), 0, st, (const int32_t*)c->d_sub_n.p,
+                       (const int32_t*)c->d_sub_dofs.p, n_cols, c->d_sw_tptr.p);
+    int64_t listed = 0;
+    FEDD_TRY(exclusive_scan_i32(c, c->d_sw_tptr.p, c->d_sw_tptr.p, (int64_t)n_cols, &listed));
+    FEDD_CHECK(listed == total, "symmetric Schwarz apply: %lld of %lld subdomain entries name a dof of this rank", (long long)listed,
+               (long long)total);
+    FEDD_HIP(hipMemcpyAsync(c->d_itmp0.p, c->d_sw_tptr.p, (size_t)n_cols * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_sym_fill, dim3((unsigned)nsub), dim3(64), 0, st, (const int32_t*)c->d_sub_n.p,
+                       (const int32_t*)c->d_sub_dofs.p, (const int32_t*)c->d_sw_off.p, n_cols, c->d_itmp0.p, c->d_sw_tsrc.p);
+    hipLaunchKernelGGL(k_sym_sort, dim3((unsigned)((n_cols + 255) / 256)), blk, 0, st, (const int32_t*)c->d_sw_tptr.p, n_cols,
+                       c->d_sw_tsrc.p);
+    // matrix-core batches: runs of consecutive places of the order records with one representative, cut into sixteens; a
+    // representative with a single member, and everything when the inverses are not shared, goes through k_full_park
+    std::vector<int32_t> batches, plain;
+    c->sw_full_records = false;
+    const bool records = c->sw_dedupe && c->d_sw_order.p && c->sw_nrep > 0 && c->sw_nrep < nsub && c->apply_full_kind != 1;
+    if (records) {
+        std::vector<int32_t> rec((size_t)nsub * 4);
+        FEDD_HIP(hipMemcpyAsync(rec.data(), c->d_sw_order.p + c->sw_order_off, rec.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        FEDD_HIP(hipStreamSynchronize(st));
+        for (int64_t p = 0; p < nsub;) {
+            int64_t q = p + 1;
+            while (q < nsub && rec[4 * q + 1] == rec[4 * p + 1] && (rec[4 * q + 2] & 1023) == (rec[4 * p + 2] & 1023)) ++q;
+            if (q - p >= 2) {
+                for (int64_t b = p; b < q; b += FP_MB) {
+                    batches.push_back((int32_t)b);
+                    batches.push_back((int32_t)std::min<int64_t>(FP_MB, q - b));
+                }
+            } else {
+                plain.push_back(rec[4 * p]);
+            }
+            p = q;
+        }
+        c->sw_full_records = true;
+    }
+    c->sw_full_nbatch = (int64_t)batches.size() / 2;
+    c->sw_full_nplain = records ? (int64_t)plain.size() : nsub;
+    c->sw_full_nmfma = nsub - c->sw_full_nplain;
+    if (records) {
+        FEDD_TRY(c->d_sw_fbatch.ensure(batches.size() + 2));
+        FEDD_TRY(c->d_sw_fplain.ensure(plain.size() + 1));
+        if (!batches.empty())
+            FEDD_HIP(hipMemcpyAsync(c->d_sw_fbatch.p, batches.data(), batches.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (!plain.empty())
+            FEDD_HIP(hipMemcpyAsync(c->d_sw_fplain.p, plain.data(), plain.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    }
+    FEDD_HIP(hipStreamSynchronize(st));     // (the host vectors leave scope)
+    FEDD_HIP(hipGetLastError());
+    c->sym_kind_built = c->apply_full_kind;
+    c->sym_ready = true;
+    return 0;
+}
+
+// z_owned = sum_i R_i^T A_i^-1 R_i r [ / multiplicity ]; r with its ghost entries in place (column numbering)
+int schwarz_apply_sym(fedd_ctx* c, const double* r, double* d_z_owned) {
+    if (c->sym_ready && c->sym_kind_built != c->apply_full_kind) c->sym_ready = false;   // option "apply_full_kind" changed
+    FEDD_TRY(schwarz_sym_setup(c));
+    const dim3 blk(256);
+    hipStream_t st = c->stream;
+    const int32_t *sub_n = c->d_sub_n.p, *sub_dofs = c->d_sub_dofs.p, *off = c->d_sw_off.p;
+    const int64_t* inv_ptr = c->d_inv_ptr.p;
+    const double* inv = c->d_inv.p;
+    if (c->sw_full_nbatch > 0) {
+        ScopedTimer t(c, FEDD_T_FULL_PARK_MFMA);
+        hipLaunchKernelGGL(k_full_park_mfma, dim3((unsigned)c->sw_full_nbatch), blk, 0, st, (const int2*)c->d_sw_fbatch.p,
+                           (const int4*)(c->d_sw_order.p + c->sw_order_off), sub_dofs, inv_ptr, inv, off, r, c->d_sw_park.p);
+        t.stop();
+    }
+    if (c->sw_full_nplain > 0) {
+        ScopedTimer t(c, FEDD_T_FULL_PARK);
+        hipLaunchKernelGGL(k_full_park, dim3((unsigned)c->sw_full_nplain), blk, 0, st, sub_n, sub_dofs, inv_ptr, inv, off, r,
+                           c->d_sw_park.p, (const int32_t*)(c->sw_full_records ? c->d_sw_fplain.p : nullptr));
+        t.stop();
+    }
+    {
+        ScopedTimer t(c, FEDD_T_FULL_GATHER);
+        t.bytes(16.0 * (double)c->sw_sum_n + 16.0 * (double)c->n_rows);     // sources and their park entries; list starts and z
+        hipLaunchKernelGGL(k_full_gather, dim3((unsigned)((c->n_rows + 255) / 256)), blk, 0, st, (const int32_t*)c->d_sw_tptr.p,
+                           (const int32_t*)c->d_sw_tsrc.p, (const double*)c->d_sw_park.p, (int32_t)c->n_rows,
+                           c->sw_combine == FEDD_COMBINE_AVERAGING ? 1 : 0, d_z_owned);
+        t.stop();
+    }
+    return 0;
+}
+
+}  // namespace fedd

@@ -1290,6 +1290,11 @@ int LinearSolver<SC, LO, GO, NO>::solve(Problem_Type* problem, BlockMultiVectorP
     // same keys the reference's XML files use (laplace/parametersSolver.xml, parametersPrec.xml)
     auto& belos = pl->sublist("ThyraSolver").sublist("Linear Solver Types").sublist("Belos");
     const std::string solverType = belos.get("Solver Type", "Block GMRES");
+    // Stratimikos hands the string to Belos; of its solvers "Block GMRES" (fedd_gmres) and "Block CG" / "Pseudo Block CG"
+    // (fedd_cg, block size 1) are built.  Anything else is an error, not a GMRES run on an empty sublist
+    const bool useCg = solverType == "Block CG" || solverType == "Pseudo Block CG";
+    TEUCHOS_TEST_FOR_EXCEPTION(!useCg && solverType != "Block GMRES", std::logic_error,
+                               "Solver Type \"" + solverType + "\" is not built (Block GMRES, Block CG, Pseudo Block CG are)");
     auto& gm = belos.sublist("Solver Types").sublist(solverType);
     const double tol = gm.get("Convergence Tolerance", 1e-8);
     const int maxIt = gm.get("Maximum Iterations", 100);
@@ -1302,6 +1307,12 @@ int LinearSolver<SC, LO, GO, NO>::solve(Problem_Type* problem, BlockMultiVectorP
     if (combine.empty()) combine = ovl.get("Overlapping Operator Combination", "Restricted");
     const int cmb = combine == "Averaging" ? FEDD_COMBINE_AVERAGING : (combine == "Full" ? FEDD_COMBINE_FULL : FEDD_COMBINE_RESTRICTED);
     const bool usePrec = precType != "None";
+    // CG needs a symmetric preconditioner (the words of fedd_cg's own error)
+    TEUCHOS_TEST_FOR_EXCEPTION(useCg && usePrec && problem->getUserPreconditioner().is_null() && cmb != FEDD_COMBINE_FULL, std::logic_error,
+                               solverType + ": preconditioner not symmetric: use FEDD_COMBINE_FULL (\"Combine Values in Overlap\" = \"Full\")");
+    TEUCHOS_TEST_FOR_EXCEPTION(useCg && !problem->getUserPreconditioner().is_null(), std::logic_error,
+                               solverType + ": user preconditioner operators run with Block GMRES only");
+    TEUCHOS_TEST_FOR_EXCEPTION(useCg && blocks, std::logic_error, solverType + ": a merged block system is not symmetric positive definite; use Block GMRES");
     if (usePrec && type != "MonolithicConstPrec") {
         // "TwoLevel" = true (parametersPrec.xml:17) switches the coarse level on.  The coarse space is
         // this library's lattice space, not FROSch's GDSW: say so.
@@ -1360,7 +1371,13 @@ int LinearSolver<SC, LO, GO, NO>::solve(Problem_Type* problem, BlockMultiVectorP
         lastRelativeResidual = rel;
         return its;
     }
-    if (!blocks) {
+    if (useCg) {
+        TEUCHOS_TEST_FOR_EXCEPTION(multiplicative, std::logic_error, solverType + ": FEDD_LEVELS_MULTIPLICATIVE is not symmetric: use \"Level Combination\" = \"Additive\"");
+        if (!zeroGuess)
+            feddCheck(fedd_cg_x0(ctx, b->getBlock(0)->raw().data(), x->getBlockNonConst(0)->raw().data(), tol, maxIt, usePrec ? 1 : 0, &its, &rel), "fedd_cg_x0");
+        else
+            feddCheck(fedd_cg(ctx, b->getBlock(0)->raw().data(), x->getBlockNonConst(0)->raw().data(), tol, maxIt, usePrec ? 1 : 0, &its, &rel), "fedd_cg");
+    } else if (!blocks) {
         if (multiplicative && problem->getUserPreconditioner().is_null())
             feddCheck(fedd_schwarz_coarse_apply(ctx, b->getBlock(0)->raw().data(), x->getBlockNonConst(0)->raw().data()), "fedd_schwarz_coarse_apply");
         if (multiplicative || !zeroGuess)

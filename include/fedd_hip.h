@@ -78,7 +78,14 @@ enum fedd_timer {
     FEDD_T_GS_DOT   = 13, /* Gram-Schmidt sweep 1 alone: the multi-dot kernel over the Krylov basis (inside ORTHO)   */
     FEDD_T_GS_UPDATE= 14, /* Gram-Schmidt sweep 2 alone: the multi-axpy kernel over the Krylov basis (inside ORTHO)  */
     FEDD_T_GS_FUSED = 15, /* s-step solver: first update and second dot of a block in one sweep, k_blockfuse (inside ORTHO) */
-    FEDD_T_COUNT    = 16
+    FEDD_T_FULL_PARK_MFMA = 16, /* symmetric Schwarz apply: k_full_park_mfma (inside SCHWARZ_APPLY) */
+    FEDD_T_FULL_PARK = 17,      /* ... k_full_park                                       */
+    FEDD_T_FULL_GATHER = 18,    /* ... k_full_gather                                     */
+    FEDD_T_CG_PQ    = 19, /* CG sweeps: k_cg_pq                                */
+    FEDD_T_CG_XR    = 20, /* ... k_cg_xr                                       */
+    FEDD_T_CG_RZ    = 21, /* ... k_cg_rz                                       */
+    FEDD_T_CG_P     = 22, /* ... k_cg_p                                        */
+    FEDD_T_COUNT    = 23
 };
 
 /* ------------------------------------------------------------------------------------------------
@@ -426,6 +433,12 @@ int fedd_schwarz_sizes(fedd_ctx* ctx, int64_t* sum_sizes, int64_t* sum_owned);
 /* subdomains whose dof list is their representative's list shifted by a constant (every box of a class on a structured mesh):
  * the matrix-core apply computes their dof ids from the representative's offsets and does not read their lists */
 int fedd_schwarz_conforming(fedd_ctx* ctx, int64_t* n_conforming);
+/* The symmetric apply without floating-point atomics (FEDD_COMBINE_FULL / FEDD_COMBINE_AVERAGING; options "apply_gather" and
+ * "apply_full_kind" below; fedd_cg always uses it): every subdomain parks y_i = A_i^-1 R_i r, a lane per owned dof then adds the
+ * parked entries of its dof in the fixed order of a list sorted at setup, so two applies of one r give the same bits.  This call
+ * builds the lists if they are not built yet and tells how many subdomains the matrix-core park kernel takes (those that share
+ * their inverse with another subdomain, in batches of up to sixteen) and how many the one-workgroup-per-subdomain kernel. */
+int fedd_schwarz_full_info(fedd_ctx* ctx, int64_t* n_mfma, int64_t* n_plain);
 
 /* right-preconditioned restarted GMRES (replaces Thyra::solve on the Belos "Block GMRES"
  * LOWS, feddlib/problems/Solver/LinearSolver_def.hpp:72-135; parametersSolver.xml:5-15).
@@ -442,6 +455,35 @@ int fedd_gmres(fedd_ctx* ctx, const double* b_owned, double* x_owned, double rto
  * (for a guess that fedd_schwarz_coarse_apply made, the projection changes nothing in exact arithmetic). */
 int fedd_gmres_x0(fedd_ctx* ctx, const double* b_owned, double* x_owned, double rtol, int max_it,
                   int restart, int use_prec, int* its_out, double* relres_out);
+/* Preconditioned conjugate gradients for systems that are symmetric positive definite on their free dofs (Laplace, linear
+ * elasticity): Belos "Block CG" / "Pseudo Block CG" with block size 1.  Arguments and NULL conventions are those of fedd_gmres /
+ * fedd_gmres_x0 without `restart`.  The algorithm (normative):
+ *   1. den = ||b - A x_0|| for the caller's x_0 (fedd_cg: x_0 = 0), Belos' default scaling as in fedd_gmres_x0.  (fedd_cg_x0: a
+ *      guess with ||b - A x_0|| <= 1e-13 (||b|| + ||A x_0||) is at the rounding floor of the product and is returned as it is,
+ *      0 iterations.)
+ *   2. Dirichlet lift: x_0[d] <- b[d] on every Dirichlet row d.  Those rows are identity rows (rows are zeroed, not columns), so
+ *      r is then exactly 0 there, z, p and q stay 0 there, and the iteration runs on A_II, which is symmetric.
+ *   3. r = b - A x, z = M^-1 r (or z = r), p = mask z, rho = r.z            (mask: 0 on the Dirichlet rows, 1 elsewhere)
+ *   4. loop: q = A p; alpha = rho / (p.q); x += alpha p; r -= alpha q; stop if ||r|| <= rtol den; z = M^-1 r; rho' = r.z;
+ *      beta = rho' / rho; p = mask (z + beta p)
+ * The test runs on the device; the returned x is exactly the iterate that met it and its_out its index.  Every claim of
+ * convergence is checked against ||b - A x|| (the product fedd_gmres checks with): if it fails, r is replaced by the true
+ * residual, z, p and rho start again and the loop continues; after three replacements in a row without progress the solve
+ * stops.  relres_out is always the true relative residual.  p.q <= 0, rho <= 0 or a non-finite value is a breakdown: the call
+ * returns an error that names it.  The preconditioner must be symmetric: FEDD_COMBINE_FULL (applied by the park + gather kernels,
+ * whatever "apply_gather" says), one level or with the additive coarse level.  Errors before any work: FEDD_COMBINE_RESTRICTED /
+ * FEDD_COMBINE_AVERAGING ("not symmetric: use FEDD_COMBINE_FULL"), FEDD_LEVELS_MULTIPLICATIVE, a merged block system, the
+ * large-subdomain path, and a context with more than one rank (summing the overlap contributions across ranks needs an
+ * export-add of the ghost entries that does not exist yet: the follow-up). */
+int fedd_cg(fedd_ctx* ctx, const double* b_owned, double* x_owned, double rtol, int max_it, int use_prec, int* its_out,
+            double* relres_out);
+int fedd_cg_x0(fedd_ctx* ctx, const double* b_owned, double* x_owned, double rtol, int max_it, int use_prec, int* its_out,
+               double* relres_out);
+/* the last fedd_cg / fedd_cg_x0: residual replacements, and the breakdown word (0 = none); outputs may be NULL */
+#define FEDD_CG_BREAKDOWN_PQ 1          /* p.Ap <= 0 */
+#define FEDD_CG_BREAKDOWN_RHO 2         /* r.z <= 0 */
+#define FEDD_CG_BREAKDOWN_NONFINITE 3   /* a dot product was not finite */
+int fedd_cg_info(fedd_ctx* ctx, int* replacements, int* breakdown);
 /* The structures that depend on the mesh alone are built once per mesh, at the first call that needs them, and reused by every
  * later assembly: the node -> element adjacency (fedd_pattern_build) and the element-major tile structures of the assembly
  * kernel (fedd_assemble, P1 forms).  Their wall time (ms, device synchronised before and after) is not part of a steady-state
@@ -467,7 +509,11 @@ int fedd_gmres_info(fedd_ctx* ctx, int* kind, int* s, int* blocks, int* cut_bloc
 /* blocks of the last s-step solve orthogonalised with three sweeps instead of four (option "gmres_fuse": k_blockfuse) */
 int fedd_gmres_fused_blocks(fedd_ctx* ctx, int* blocks);
 
-/* tuning knobs (A/B tests), 0 is the default of each: "spmv_kind" 0 = CSR-window (CSR-stream when a row has more than 256 entries), 1 = row-per-lane-group, 2 = CSR-stream;
+/* "apply_gather" 0 (default) = fedd_schwarz_apply and GMRES keep the atomicAdd combine for Full and Averaging, 1 = they use the
+ * park + gather kernels (bitwise reproducible); "apply_full_kind" 0 = the matrix-core park kernel for subdomains that share their
+ * inverse, the one-workgroup kernel for the rest, 1 = the one-workgroup kernel only, 2 = the matrix-core kernel wherever an
+ * inverse is shared (an error at the apply if the setup kept no shared inverses, "schwarz_dedupe" 0).
+ * tuning knobs (A/B tests), 0 is the default of each: "spmv_kind" 0 = CSR-window (CSR-stream when a row has more than 256 entries), 1 = row-per-lane-group, 2 = CSR-stream;
  * "pat_hash" 1 (default) = node pattern of vertex-only elements merged through a hash table of list positions (symbolic.hip), 0 = ordered insertion;
  * "asm_tiles" 1 (default) = the P1 Laplace / vector-Laplace / elasticity forms are assembled element-major over tiles of ~27 nodes
  * (every element of a tile evaluated once, contributions gathered per CSR slot from lists built once per mesh), 0 = the pair
