@@ -97,6 +97,7 @@ SIGNATURES = {
     "fedd_schwarz_apply": [C.c_void_p, _f64p, _f64p],
     "fedd_schwarz_apply_device": [C.c_void_p, C.c_int],
     "fedd_schwarz_info": [C.c_void_p, _i64p, _i64p, _i64p],
+    "fedd_schwarz_reuse_info": [C.c_void_p, _ip, _i64p],
     "fedd_schwarz_unique": [C.c_void_p, _i64p],
     "fedd_schwarz_sizes": [C.c_void_p, _i64p, _i64p],
     "fedd_schwarz_conforming": [C.c_void_p, _i64p],
@@ -617,6 +618,12 @@ class Context:
             if self._L.fedd_schwarz_conforming(self._h, C.byref(nc)) == 0:
                 out.update(n_conforming=nc.value)
         return out
+
+    def schwarz_reuse_info(self):
+        """whether the last schwarz_setup kept the box structure of the one before, and how many setups of this context have"""
+        a, n = C.c_int(), C.c_int64()
+        _chk(self._L.fedd_schwarz_reuse_info(self._h, C.byref(a), C.byref(n)))
+        return {"last_reused": bool(a.value), "n_reused": n.value}
 
     def schwarz_apply(self, r):
         r = np.ascontiguousarray(r, dtype=np.float64)

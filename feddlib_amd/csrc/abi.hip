@@ -213,6 +213,8 @@ static int mesh_set_impl(fedd_ctx* c, int dim, int nen, int64_t n_elem, const in
     for (auto& id : c->adv_pattern_id) id = 0;
     c->d_adv_ke.release();   // the element-block scratch is sized by the mesh (the largest buffer of the advection path)
     ++c->mesh_id;
+    ++c->mesh_gen;          // the Schwarz structure (schwarz.hip) belongs to the old nodes
+    c->pat_repeatable = false;
     c->halo.reset();
 
     // column-local numbering: owned nodes in unique-map order, then ghosts sorted by global id
@@ -452,7 +454,11 @@ extern "C" int fedd_assemble_div(fedd_ctx* c, int64_t n_pressure_nodes, int slot
     FEDD_CHECK(slot_b != slot_bt, "fedd_assemble_div: B and B^T need different slots");
     FEDD_CHECK(c->n_node > 0, "fedd_assemble_div: call fedd_mesh_set first");
     FEDD_HIP(hipSetDevice(c->device));
-    return assemble_div(c, n_pressure_nodes, slot_b, slot_bt);
+    ++c->pattern_gen;       // the system slot becomes the scratch node pattern
+    const int rc = assemble_div(c, n_pressure_nodes, slot_b, slot_bt);
+    ++c->pattern_gen;
+    c->pat_repeatable = false;
+    return rc;
 }
 
 extern "C" int fedd_block_merge(fedd_ctx* c, int slot_a, int slot_bt, int slot_b, int slot_c) {
@@ -460,6 +466,8 @@ extern "C" int fedd_block_merge(fedd_ctx* c, int slot_a, int slot_bt, int slot_b
     CHECK_SLOT(slot_a);
     FEDD_CHECK(slot_bt < fedd::MAX_AUX && slot_b < fedd::MAX_AUX && slot_c < fedd::MAX_AUX, "fedd_block_merge: slot out of range");
     FEDD_HIP(hipSetDevice(c->device));
+    ++c->pattern_gen;       // (a merge that only moves values bumps too: a missed reuse is cheap, a wrong one is not)
+    c->pat_repeatable = false;
     FEDD_TRY(block_merge(c, slot_a, slot_bt, slot_b, slot_c));
     c->have_pattern = true;
     return 0;
@@ -786,6 +794,13 @@ extern "C" int fedd_schwarz_info(fedd_ctx* c, int64_t* n_sub, int64_t* max_size,
     return 0;
 }
 
+extern "C" int fedd_schwarz_reuse_info(fedd_ctx* c, int* last_reused, int64_t* n_reused) {
+    FEDD_CHECK(c, "fedd_schwarz_reuse_info: null context");
+    if (last_reused) *last_reused = c->have_schwarz ? c->sw_last_reused : 0;
+    if (n_reused) *n_reused = c->sw_reuse_count;
+    return 0;
+}
+
 extern "C" int fedd_schwarz_apply(fedd_ctx* c, const double* r_owned, double* z_owned) {
     NEED_DEVICE(c);
     FEDD_CHECK(c->have_schwarz && r_owned && z_owned, "fedd_schwarz_apply: no preconditioner / null pointer");
@@ -991,7 +1006,7 @@ extern "C" int fedd_set_option(fedd_ctx* c, const char* key, double value) {
     else if (k == "gmres_fuse") c->gmres_fuse = (int)value;
     else if (k == "multi_ch") c->multi_ch = (int)value;
     else if (k == "spmv_col16") { c->spmv_col16 = value != 0.0; c->cs_valid = false; }
-    else if (k == "pat_hash") c->pat_hash = value != 0.0;
+    else if (k == "pat_hash") { c->pat_hash = value != 0.0; c->pat_repeatable = false; }
     else if (k == "md2_gy") c->md2_gy = (int)value;
     else if (k == "gmres_hostwrite") c->h_pinned_dev = value != 0 ? c->h_pinned_map : nullptr;
     else if (k == "spmv_pattern") { c->spmv_pattern = (int)value; c->cs_valid = false; }
@@ -1032,6 +1047,7 @@ extern "C" int fedd_set_option(fedd_ctx* c, const char* key, double value) {
         c->gmres_chol_tol = value;
     }
     else if (k == "ghost_overlap") c->ghost_overlap = (int)value;
+    else if (k == "schwarz_reuse") c->sw_reuse = value != 0.0;
     else FEDD_CHECK(false, "fedd_set_option: unknown key '%s'", key);
     return 0;
 }

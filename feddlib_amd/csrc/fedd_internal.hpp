@@ -298,7 +298,31 @@ struct fedd_ctx {
     fedd::DevBuf<int32_t> d_bin_ptr, d_bin_nodes;   // [nsub+1], [n_own]
     fedd::DevBuf<int32_t> d_sub_n, d_sub_nown;  // [nsub] total / owned dofs of each subdomain
     fedd::DevBuf<int32_t> d_sub_dofs;           // [nsub*NMAX] local dof ids (owned first)
-    fedd::DevBuf<int64_t> d_inv_ptr;            // [nsub+1] offsets into d_inv (elements)
+    // structure stage of the setup (lattice, bins, dof lists: the five buffers above, d_fbin_* and the sizes sw_nsub, sw_max_size,
+    // sw_max_own, sw_max_size_all): a function of the node coordinates, the matrix graph and the parameters of SwStructKey, kept
+    // from setup to setup while those stand (option "schwarz_reuse", default 1; 0 = built by every setup)
+    uint64_t mesh_gen = 0;                      // bumped by whatever can change coordinates, node counts, ghost layout, owners or halo
+    uint64_t pattern_gen = 0;                   // bumped by whatever writes d_rowptr / d_colind, except a fedd_pattern_build that repeats
+                                                // the one the pattern came from (same mesh_gen, dofs per node, block mode)
+    bool pat_repeatable = false;                // the system pattern is the output of build_pattern on pat_mesh_gen (and nothing wrote it since)
+    uint64_t pat_mesh_gen = 0;
+    struct SwStructKey {
+        uint64_t mesh_gen = 0, pattern_gen = 0;
+        int64_t n_own = 0, n_rows = 0, n_rows_ext = 0, merged_nA = 0;
+        double scale = 0.0;
+        int target = 0, overlap = 0, box_kind = 0, whole_boxes = 0, ghost_overlap = 0, merged = 0, dofs = 0, dim = 0, nranks = 0;
+        bool operator==(const SwStructKey& o) const {
+            return mesh_gen == o.mesh_gen && pattern_gen == o.pattern_gen && n_own == o.n_own && n_rows == o.n_rows &&
+                   n_rows_ext == o.n_rows_ext && merged_nA == o.merged_nA && scale == o.scale && target == o.target &&
+                   overlap == o.overlap && box_kind == o.box_kind && whole_boxes == o.whole_boxes &&
+                   ghost_overlap == o.ghost_overlap && merged == o.merged && dofs == o.dofs && dim == o.dim && nranks == o.nranks;
+        }
+    } sw_struct_key;
+    bool sw_struct_valid = false;               // the kept structure belongs to sw_struct_key (false after the large-subdomain path)
+    int sw_reuse = 1;                           // option "schwarz_reuse"
+    int sw_last_reused = 0;                     // the last setup kept the structure
+    int64_t sw_reuse_count = 0;                 // setups that kept it since the context was made
+    fedd::DevBuf<int64_t> d_inv_ptr;           // [nsub+1] offsets into d_inv (elements)
     fedd::DevBuf<double> d_inv;                 // per subdomain [n_i][rp_i] column-major slab
     fedd::DevBuf<double> d_mult;                // [n_cols] multiplicity (averaging)
     bool have_schwarz = false;

@@ -94,6 +94,7 @@ extern "C" int fedd_halo_set_owners(fedd_ctx* c, int64_t n_rep, const int64_t* g
     FEDD_CHECK(n_rep == 0 || (gid_rep && owner_rep), "fedd_halo_set_owners: null array");
     HaloPlan& h = c->halo;
     h.reset();
+    ++c->mesh_gen;      // owners and halo are part of what the Schwarz structure was built on
     const int64_t ng = c->n_node - c->n_own;
     std::unordered_map<int64_t, int32_t> ghost;  // gid -> ghost node id
     ghost.reserve((size_t)ng * 2);
@@ -145,6 +146,7 @@ extern "C" int fedd_halo_requests_set(fedd_ctx* c, const int64_t* count_from_ran
     FEDD_CHECK(c && count_from_rank, "fedd_halo_requests_set: null");
     HaloPlan& h = c->halo;
     FEDD_CHECK((int)h.req_count.size() == c->nranks, "fedd_halo_requests_set: call fedd_halo_set_owners first");
+    ++c->mesh_gen;
     std::unordered_map<int64_t, int32_t> own;
     own.reserve((size_t)c->n_own * 2);
     for (int64_t i = 0; i < c->n_own; ++i) own.emplace(c->h_node_gid[i], (int32_t)i);

@@ -1578,12 +1578,41 @@ int schwarz_slab_offsets(fedd_ctx* c, int64_t nsub, int restricted) {
     return 0;
 }
 
-int schwarz_setup(fedd_ctx* c) {
-    c->sym_ready = false;       // (schwarz_sym.hip: its lists belong to the setup they were built for)
-    if (schwarz_use_big(c)) return schwarz_setup_big(c);
-    c->sw_big_active = false;
-    c->have_coarse = false;
-    ScopedTimer timer(c, FEDD_T_SCHWARZ_SETUP);
+namespace {
+
+// nodes per box: the caller's, or 27 for scalar problems and 27 / dofs for node-interleaved vector problems
+// (the dense local solver takes 256 dofs including the overlap)
+int schwarz_target(const fedd_ctx* c) {
+    return c->sw_target > 0 ? c->sw_target : (c->merged ? 27 : std::max(1, 27 / std::max(1, c->dofs)));
+}
+
+// what the structure stage reads beside d_xyz, d_rowptr / d_colind and d_dof_node (whose writers move the two generations)
+fedd_ctx::SwStructKey schwarz_struct_key(const fedd_ctx* c) {
+    fedd_ctx::SwStructKey k;
+    k.mesh_gen = c->mesh_gen;
+    k.pattern_gen = c->pattern_gen;
+    k.n_own = c->n_own;
+    k.n_rows = c->n_rows;
+    k.n_rows_ext = c->n_rows_ext;
+    k.merged_nA = c->merged ? c->merged_nA : 0;
+    k.scale = c->sw_scale;
+    k.target = c->sw_target;
+    k.overlap = c->sw_overlap;
+    k.box_kind = c->box_kind;
+    k.whole_boxes = c->whole_boxes;
+    k.ghost_overlap = c->ghost_overlap;
+    k.merged = c->merged ? 1 : 0;
+    k.dofs = c->dofs;
+    k.dim = c->dim;
+    k.nranks = c->nranks;
+    return k;
+}
+
+// Structure stage of the setup: box lattice, bins and overlapping dof lists -> d_bin_ptr, d_bin_nodes, d_node_bin, d_fbin_*,
+// d_sub_n, d_sub_nown, d_sub_dofs, sw_nsub, sw_max_size, sw_max_own, sw_max_size_all.
+// Reads coordinates, the matrix graph and the parameters of SwStructKey, never a matrix value.  (d_itmp0..2 are its scratch
+// and free afterwards.)
+int schwarz_structure(fedd_ctx* c) {
     const int32_t n_own = (int32_t)c->n_own;
     const int dim = c->dim, dofs = c->dofs;
     const int32_t n_rows = (int32_t)c->n_rows;
@@ -1606,9 +1635,7 @@ int schwarz_setup(fedd_ctx* c) {
     // regular grid of boxes with about sw_target nodes each (same formula as the oracle)
     double V = 1.0;
     for (int d = 0; d < dim; ++d) V *= (L[d] > 0 ? L[d] : 1.0);
-    // default target: 27 nodes for scalar problems, 27 / dofs for node-interleaved vector problems
-    // (the dense local solver takes 256 dofs including the overlap)
-    const int target = c->sw_target > 0 ? c->sw_target : (c->merged ? 27 : std::max(1, 27 / std::max(1, dofs)));
+    const int target = schwarz_target(c);
     // If a subdomain comes out larger than the dense local solver takes (NMAX dofs with the overlap), the lattice is
     // refined (box edge x 0.85) and the lists are built again: every rank takes the same decision (several
     // ranks: the largest size is all-reduced), so the lattice stays one lattice.
@@ -1713,7 +1740,52 @@ int schwarz_setup(fedd_ctx* c) {
         const int32_t limit = c->sw_target > 0 ? NMAX : 160;
         if (c->sw_max_size_all <= limit || attempt >= 8) break;
     }
-    max_n = std::max(max_n, c->sw_max_size_all);
+    return 0;
+}
+
+}  // namespace
+
+int schwarz_setup(fedd_ctx* c) {
+    c->sym_ready = false;       // (schwarz_sym.hip: its lists belong to the setup they were built for)
+    if (schwarz_use_big(c)) {
+        c->sw_struct_valid = false;     // (that path writes the bins and lists of its own bisection)
+        c->sw_last_reused = 0;
+        return schwarz_setup_big(c);
+    }
+    c->sw_big_active = false;
+    c->have_coarse = false;
+    ScopedTimer timer(c, FEDD_T_SCHWARZ_SETUP);
+    const int32_t n_rows = (int32_t)c->n_rows;
+    const int32_t n_stored = (int32_t)c->n_rows_ext;   // rows the local matrices can read (owned + row ghosts)
+    // ---- structure stage: kept from the last setup while mesh, pattern and parameters are the ones it was built for.  The key
+    // holds no hash and nothing is compared on the device: the generations count the calls that can change the inputs.
+    // With several ranks the stage holds collectives, so every rank keeps it or none does: one all-reduce of the flags
+    // (the smallest decides) takes the place of the two collectives of the build ----
+    const fedd_ctx::SwStructKey key = schwarz_struct_key(c);
+    bool reuse = c->sw_reuse && c->sw_struct_valid && c->sw_struct_key == key;
+    if (c->nranks > 1) {     // (also with the option off on this rank: the others wait in this all-reduce)
+        // (min through the sum transport: the count of the ranks that can keep theirs)
+        double ok = reuse ? 1.0 : 0.0;
+        FEDD_TRY(c->d_dtmp0.ensure(std::max<size_t>(1, c->d_dtmp0.cap)));
+        FEDD_HIP(hipMemcpyAsync(c->d_dtmp0.p, &ok, sizeof(double), hipMemcpyHostToDevice, c->stream));
+        FEDD_TRY(allreduce_sum(c, c->d_dtmp0.p, 1));
+        FEDD_HIP(hipMemcpyAsync(&ok, c->d_dtmp0.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        FEDD_HIP(hipStreamSynchronize(c->stream));
+        reuse = ok > (double)c->nranks - 0.5;
+    }
+    if (reuse) {
+        ++c->sw_reuse_count;
+    } else {
+        c->sw_struct_valid = false;     // (a build that fails on the way leaves nothing to keep)
+        FEDD_TRY(schwarz_structure(c));
+        c->sw_struct_key = key;
+        c->sw_struct_valid = true;
+    }
+    c->sw_last_reused = reuse ? 1 : 0;
+    const int64_t nsub = c->sw_nsub;
+    const int32_t max_own = (int32_t)c->sw_max_own;
+    const int target = schwarz_target(c);
+    const int32_t max_n = std::max((int32_t)c->sw_max_size, c->sw_max_size_all);
     const dim3 blk(256);
     FEDD_CHECK(max_n <= NMAX,
                "schwarz setup: an overlapping subdomain has %d dofs, the dense local solver takes at most %d; "

@@ -390,6 +390,12 @@ int build_pattern(fedd_ctx* c, int dofs, int block_mode) {
     const int64_t mult = scalar ? 1 : (block_mode == FEDD_BLOCK_FULL ? (int64_t)dofs * dofs : dofs);
     const int64_t nnz = node_nnz * mult;
     FEDD_CHECK(nnz < ((int64_t)1 << 31), "pattern build: %lld nonzeros exceed 32-bit local offsets", (long long)nnz);
+    // the same build on the same mesh writes the same pattern: only then the pattern generation stands (schwarz.hip keeps the
+    // box structure of a pattern it has seen)
+    const bool repeat = c->pat_repeatable && c->have_pattern && !c->merged && c->pat_mesh_gen == c->mesh_gen && c->dofs == dofs &&
+                        c->block_mode == block_mode;
+    c->pat_repeatable = false;
+    if (!repeat) ++c->pattern_gen;
     c->dofs = dofs;
     c->block_mode = block_mode;
     c->n_rows = c->n_own * dofs;
@@ -446,6 +452,8 @@ int build_pattern(fedd_ctx* c, int dofs, int block_mode) {
     c->have_schwarz = false;
     c->spmv_rows_ready = false;
     c->merged = false;
+    c->pat_repeatable = true;
+    c->pat_mesh_gen = c->mesh_gen;
     return 0;
 }
 

@@ -423,6 +423,13 @@ int fedd_schwarz_coarse_get(fedd_ctx* ctx, double* k0_inverse);
 int fedd_schwarz_apply(fedd_ctx* ctx, const double* r_owned, double* z_owned);
 int fedd_schwarz_apply_device(fedd_ctx* ctx, int reps);
 int fedd_schwarz_info(fedd_ctx* ctx, int64_t* n_subdomains, int64_t* max_size, int64_t* inverse_bytes);
+/* The setup has a structure stage (box lattice, bins, overlapping dof lists: a function of the node coordinates, the matrix
+ * graph and the setup parameters) and a numeric stage (everything that reads matrix values), as FROSch's initialize() /
+ * compute().  The structure is kept from one fedd_schwarz_setup to the next while the mesh, the pattern (a repeated
+ * fedd_pattern_build with the same arguments on the same mesh counts as the same pattern), target, scale, overlap and the box
+ * options stand; with several ranks all ranks keep it or none does.  Option "schwarz_reuse" = 0 builds it in every setup.
+ * last_reused: 1 if the last setup kept the structure; n_reused: setups that kept it since the context was made. */
+int fedd_schwarz_reuse_info(fedd_ctx* ctx, int* last_reused, int64_t* n_reused);
 /* number of DISTINCT local matrices of the last setup: subdomains whose principal submatrices agree (to 2^-44 of each row's
  * largest entry; option "schwarz_dedupe", default 1) share one stored inverse, which fedd_schwarz_info's inverse_bytes
  * counts once.  On the structured cube of the headline a few hundred of the 389 017 subdomains are distinct. */
@@ -566,6 +573,9 @@ int fedd_gmres_fused_blocks(fedd_ctx* ctx, int* blocks);
  * compacted stream (tests and measurements of those kernels);
  * "schwarz_dedupe" 1 (default) = subdomains with the same local matrix share one inverse (see fedd_schwarz_unique), 0 = every
  * subdomain is inverted and stored on its own;
+ * "schwarz_reuse" 1 (default) = fedd_schwarz_setup keeps the box lattice, the bins and the overlapping dof lists of the setup
+ * before while mesh, pattern and parameters stand (see fedd_schwarz_reuse_info), 0 = they are built by every setup (the same
+ * preconditioner bit for bit; the A/B switch).  With several ranks a rank that has it off makes every rank build;
  * "schwarz_fp_kind" 0 (default) = the fingerprints of that sharing are built from one hash per matrix ROW (column offsets and
  * quantised values of all its entries) and the rows' positions in the subdomain, 1 = entry by entry over the entries inside the
  * subdomain (the round-2 form; finds the same classes on the structured grids, four times slower);
