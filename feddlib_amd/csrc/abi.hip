@@ -982,8 +982,14 @@ extern "C" int fedd_set_option(fedd_ctx* c, const char* key, double value) {
     else if (k == "spmv_classes") { c->spmv_classes = (int)value; c->cs_valid = false; }
     else if (k == "spmv_keep_dictionary") c->spmv_keep_dict = (int)value;
     else if (k == "spmv_classes_cover") { c->spmv_cls_cover = (int)value; c->cs_valid = false; }
-    else if (k == "asm_tiles_host") { c->asm_tiles_host = (int)value; c->tl_state = 0; }
-    else if (k == "asm_p2_elem") c->asm_p2_elem = (int)value;
+    else if (k == "asm_tiles_host") {
+        FEDD_CHECK(value == 0 || value == 1, "fedd_set_option: asm_tiles_host %g (0 or 1)", value);
+        c->asm_tiles_host = (int)value;
+        c->tl_state = 0;
+    } else if (k == "asm_p2_elem") {
+        FEDD_CHECK(value == 0 || value == 1 || value == 2, "fedd_set_option: asm_p2_elem %g (one of 0, 1, 2)", value);
+        c->asm_p2_elem = (int)value;
+    }
     else if (k == "asm_zero_eps") {
         FEDD_CHECK(value >= 0.0, "fedd_set_option: asm_zero_eps %g", value);
         c->asm_zero_eps = value;
@@ -1015,10 +1021,14 @@ extern "C" int fedd_set_option(fedd_ctx* c, const char* key, double value) {
     else if (k == "halo_overlap") { c->halo_overlap = (int)value; c->have_schwarz = false; }
     else if (k == "schwarz_big") c->sw_big = (int)value;
     else if (k == "schwarz_big_target") c->sw_big_target = (int)value;
-    else if (k == "asm_kind") c->asm_kind = (int)value;
-    else if (k == "asm_tiles") c->asm_tiles = (int)value;
-    else if (k == "asm_u") c->asm_u = (int)value;
-    else if (k == "asm_dbg") c->asm_dbg = (int)value;
+    else if (k == "asm_kind") {
+        // (the dispatches launch_assemble has: 0 = default, 2 = the pair sweep always, 3 = slot-addressed where it fits)
+        FEDD_CHECK(value == 0 || value == 2 || value == 3, "fedd_set_option: asm_kind %g (one of 0, 2, 3)", value);
+        c->asm_kind = (int)value;
+    } else if (k == "asm_tiles") {
+        FEDD_CHECK(value == 0 || value == 1, "fedd_set_option: asm_tiles %g (0 or 1)", value);
+        c->asm_tiles = (int)value;
+    }
     else if (k == "apply_kind") {
         // (the kernel families schwarz_apply has: any other value would be left to whatever its predicates happen to give)
         FEDD_CHECK(value == 0 || value == 1 || value == 2 || value == 4 || value == 6,

@@ -190,10 +190,8 @@ struct fedd_ctx {
     int asm_lds_kb = 37;                        // LDS budget of the assembly kernel's contribution park (KB): 4 workgroups per CU
     int box_kind = 0;                           // Schwarz boxes: 0 = one lattice over all ranks' nodes, 1 = per-rank lattice
     int spmv_kind = 0;                          // 0 = CSR-window / automatic, 1 = row-per-lane-group, 2 = CSR-stream
-    int asm_dbg = 0;                            // ablation switches of the assembly kernel (development)
-    int asm_u = 1;                              // slot-addressed assembly: pairs per lane with their loads in flight together (P1)
-    int asm_kind = 0;                           // 0 = slot-addressed pair-parallel assembly, 2 = pair-parallel with slot sweep, 1 = lane-per-row gather
-    // element-major tile structures of the current mesh (assemble.hip build_tiles): 0 = not built, 1 = ready, -1 = mesh does not fit
+    int asm_kind = 0;                           // option "asm_kind": 0 = the default dispatch (assemble.hip launch_assemble), 2 = the pair sweep always, 3 = slot-addressed where it fits
+    // element-major tile structures of the current mesh (assemble_tiles.hip build_tiles): 0 = not built, 1 = ready, -1 = mesh does not fit
     int asm_p2_elem = 1;                        // option "asm_p2_elem": P2 scalar forms take their element matrices from k_elem_matrix (one element per wavefront); 0 = pair kernels alone
     int p2_state = 0;                           // gather lists of the P2 row sums (assemble.hip k_p2_lists): 0 = not built, 1 = ready, -1 = not applicable
     fedd::DevBuf<uint16_t> d_p2_soff, d_p2_src; // per node-level nonzero the start of its sources; the sources (adjacency entry << 4 | local column)
@@ -204,7 +202,7 @@ struct fedd_ctx {
     int tl_state = 0, asm_tiles = 1;            // option "asm_tiles": the P1 Laplace / elasticity forms take the element-major tile kernel (0: pair kernels)
     int64_t tl_ntile = 0;
     int tl_max_el = 0, tl_max_ext = 0, tl_max_blob = 0;
-    fedd::DevBuf<uint32_t> tl_hdr, tl_blob;     // per-tile headers (16 bytes each) and blobs (assemble.hip TileHdr)
+    fedd::DevBuf<uint32_t> tl_hdr, tl_blob;     // per-tile headers (16 bytes each) and blobs (assemble_tiles.hip TileHdr)
     fedd::DevBuf<uint32_t> tl_shape;            // [tl_ntile] first word of the shape part every tile reads (its own or an earlier tile's)
     int tl_nshared = 0;                         // tiles that read the shape of an earlier tile
     fedd::DevBuf<int32_t> d_pat_stash;          // pattern build: merged node lists of the count pass, [k][node]
@@ -523,6 +521,11 @@ int apply_dirichlet_rows(fedd_ctx* c, int64_t n, const int32_t* rows, const doub
 int assemble_div(fedd_ctx* c, int64_t n_pressure_nodes, int slot_b, int slot_bt);
 int velocity_set(fedd_ctx* c, const double* u_rep);
 int assemble_advection(fedd_ctx* c, int kind, double scale, int slot_add, int slot_out);
+
+// assemble_tiles.hip: the element-major tile path (P1 simplices; kform = Laplace or elasticity of assemble_common.hpp).
+// Returns -1, without error, when the mesh does not fit the tiles.
+struct AsmArgs;
+int assemble_tiles(fedd_ctx* c, int kform, const AsmArgs& a, int ntab);
 
 // blocks.hip
 int matrix_store(fedd_ctx* c, int slot);

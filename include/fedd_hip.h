@@ -524,9 +524,9 @@ int fedd_gmres_fused_blocks(fedd_ctx* ctx, int* blocks);
  * "pat_hash" 1 (default) = node pattern of vertex-only elements merged through a hash table of list positions (symbolic.hip), 0 = ordered insertion;
  * "asm_tiles" 1 (default) = the P1 Laplace / vector-Laplace / elasticity forms are assembled element-major over tiles of ~27 nodes
  * (every element of a tile evaluated once, contributions gathered per CSR slot from lists built once per mesh), 0 = the pair
- * kernels; "asm_kind" 4 = tiles whatever "asm_tiles" says, 0 = pair-parallel assembly (slot-addressed accumulation for the block forms -- elasticity, B / B^T --, slot sweep for
- * the scalar forms), 1 = lane-per-row gather, 2 = slot sweep always, 3 = slot-addressed always; "asm_u" pairs per lane whose
- * loads are in flight together in the slot-addressed kernel (P1; default 1); "asm_dbg" ablation switches (development); "apply_kind" 0 = restricted Schwarz
+ * kernels (0 or 1, any other value is an error); "asm_kind" 0 (default) = tiles where "asm_tiles" and the form allow, else pair-parallel
+ * assembly (slot-addressed accumulation for the block forms -- elasticity, B / B^T --, slot sweep for the scalar forms), 2 = slot
+ * sweep always, 3 = slot-addressed wherever it fits (2 and 3 never take the tiles; any other value is an error); "apply_kind" 0 = restricted Schwarz
  * apply by the setup's outcome (batched matrix-core kernel when at most a quarter of at least 4096 subdomains have distinct
  * local matrices -- on the batch table of the setup, k_apply_bt, when every subdomain conforms to its representative, on chunk
  * records, k_apply_mfma, otherwise --, else the flat streaming kernel), 1 = strided, 2 = flat without the compact LDS layout,
@@ -591,9 +591,10 @@ int fedd_gmres_fused_blocks(fedd_ctx* ctx, int* blocks);
  * divergence blocks (fedd_assemble_div, :2002-2004, 2032-2034); 0 (default) = off;
  * "asm_p2_elem" 1 (default) = the P2 scalar forms (Laplace, vector Laplace, mass) evaluate every element once, one element per
  * wavefront with the reference gradients and quadrature weights staged in LDS (k_elem_matrix), and the rows are summed from
- * those element matrices; 0 = the pair kernels alone re-derive the row of every (row, element) pair;
+ * those element matrices through gather lists built once per mesh; 2 = the element matrices, the rows summed by the pair kernels;
+ * 0 = the pair kernels alone re-derive the row of every (row, element) pair (any other value is an error);
  * "asm_tiles_host" 1 = the tile structures of the assembly kernel are built by the round-3 host builder instead of the device
- * kernels (A/B and tests; see fedd_mesh_setup_info). */
+ * kernels (A/B and tests; see fedd_mesh_setup_info), 0 (default) = on the device (any other value is an error). */
 int fedd_set_option(fedd_ctx* ctx, const char* key, double value);
 
 /* device-time accounting (HIP events on the context's stream around each kernel class) */

@@ -1,4 +1,4 @@
-"""Element-major tile assembly (asm_kind 4) against the pair kernels (asm_kind 0 with asm_tiles 0): values, reproducibility, time.
+"""Element-major tile assembly (asm_tiles 1) against the pair kernels (asm_tiles 0): values, reproducibility, time.
 usage: ab_tiles.py [cells of the big Laplace cube] [cells of the big elasticity cube]   (development aid)"""
 import os
 import sys
@@ -12,8 +12,8 @@ from feddlib_amd import capi  # noqa: E402
 GOLD = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 
 
-def assemble(c, form, dofs, mode, params=None, kind=0):
-    c.set_option("asm_kind", kind)
+def assemble(c, form, dofs, mode, params=None, tiles=0):
+    c.set_option("asm_tiles", tiles)
     c.pattern_build(dofs, mode)
     c.assemble(form, params)
     return c.csr_get()[2].copy()
@@ -23,8 +23,8 @@ def compare(name, m, form, dofs, mode, params=None):
     c = capi.Context(device=0)
     c.mesh_set_dict(m)
     v0 = assemble(c, form, dofs, mode, params, 0)
-    v4 = assemble(c, form, dofs, mode, params, 4)
-    v4b = assemble(c, form, dofs, mode, params, 4)
+    v4 = assemble(c, form, dofs, mode, params, 1)
+    v4b = assemble(c, form, dofs, mode, params, 1)
     scale = np.abs(v0).max()
     print("%-44s nnz %9d  max |tiles - pairs| / max|a| %.2e  identical %s  reproducible %s" % (
         name, v0.shape[0], np.abs(v4 - v0).max() / scale, bool(np.array_equal(v4, v0)), bool(np.array_equal(v4, v4b))), flush=True)
@@ -46,8 +46,8 @@ for M, form, dofs, mode, params, name in big:
     m = capi.structured_mesh(3, 1, M)
     c = capi.Context(device=0)
     c.mesh_set_dict(m)
-    for kind in (0, 4, 0, 4):
-        c.set_option("asm_kind", kind)
+    for tiles in (0, 1, 0, 1):
+        c.set_option("asm_tiles", tiles)
         t0 = time.perf_counter()
         c.pattern_build(dofs, mode)
         c.assemble(form, params)
@@ -60,5 +60,5 @@ for M, form, dofs, mode, params, name in big:
         c.sync()
         ms = c.timing_get()["assemble"][0] / 3
         c.timing_enable(0)
-        print("%s %d^3 cells asm_kind %d: %.3f ms per assembly (first call incl. pattern and structures %.2f s)" % (name, M, kind, ms, first), flush=True)
+        print("%s %d^3 cells asm_tiles %d: %.3f ms per assembly (first call incl. pattern and structures %.2f s)" % (name, M, tiles, ms, first), flush=True)
     c.close()

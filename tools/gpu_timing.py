@@ -64,7 +64,7 @@ def main():
         out.append(rec)
         print(json.dumps(rec), flush=True)
     # kernel micro-timings on resident data
-    for kind in (1, 0):
+    for kind in (2, 3, 0):      # the pair sweep, the slot-addressed kernel, the default (tiles)
         c.set_option("asm_kind", kind)
         c.pattern_build(1, capi.BLOCK_SCALAR)
         c.assemble(capi.FORM_LAPLACE); c.sync()
