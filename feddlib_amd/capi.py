@@ -18,7 +18,7 @@ COMBINE_RESTRICTED, COMBINE_AVERAGING, COMBINE_FULL = range(3)
  T_COARSE_APPLY, T_HALO, T_ALLREDUCE, T_SPMV_SETUP) = range(13)
 TIMER_NAMES = ["symbolic", "assemble", "rhs", "dirichlet", "spmv", "schwarz_setup", "schwarz_apply", "ortho",
                "coarse_setup", "coarse_apply", "halo", "allreduce", "spmv_setup", "gs_dot", "gs_update", "gs_fused",
-               "full_park_mfma", "full_park", "full_gather", "cg_pq", "cg_xr", "cg_rz", "cg_p"]
+               "full_park_mfma", "full_park", "full_gather", "cg_pq", "cg_xr", "cg_rz", "cg_p", "newmark_state", "block_apply"]
 COARSE_Q1 = 1
 COARSE_GDSW = 2
 COARSE_RGDSW = 3
@@ -79,6 +79,16 @@ SIGNATURES = {
     "fedd_matrix_get": [C.c_void_p, C.c_int, _i64p, _i32p, _f64p],
     "fedd_velocity_set": [C.c_void_p, _f64p],
     "fedd_assemble_advection": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int],
+    "fedd_matrix_combine": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double],
+    "fedd_matrix_combine_current": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, _ip],
+    "fedd_matrix_apply": [C.c_void_p, C.c_int, C.c_double, _f64p, _f64p],
+    "fedd_newmark_begin": [C.c_void_p],
+    "fedd_newmark_set": [C.c_void_p, _f64p, _f64p, _f64p],
+    "fedd_newmark_get": [C.c_void_p, _f64p, _f64p, _f64p],
+    "fedd_newmark_advance": [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double],
+    "fedd_rhs_axpy": [C.c_void_p, C.c_double, _f64p],
+    "fedd_solution_set": [C.c_void_p, _f64p],
+    "fedd_dirichlet_rhs": [C.c_void_p, C.c_int, _i32p, _i32p, _f64p],
     "fedd_csr_sizes": [C.c_void_p, _i64p, _i64p, _i64p],
     "fedd_csr_get": [C.c_void_p, _i64p, _i32p, _f64p, _i64p],
     "fedd_rhs_get": [C.c_void_p, _f64p],
@@ -518,6 +528,73 @@ class Context:
     def assemble_advection(self, kind, scale=1.0, slot_add=-1, slot_out=4):
         """slot_out <- scale * (N | W | N + W)(u) + M[slot_add], FULL velocity pattern (fedd_assemble_advection)"""
         _chk(self._L.fedd_assemble_advection(self._h, kind, float(scale), slot_add, slot_out))
+
+    def matrix_combine(self, slot_m, cm, slot_a, ca):
+        """system matrix <- (cm * M[slot_m]) + (ca * A[slot_a]) on the pattern of slot_a (TimeProblem::combineSystems)"""
+        _chk(self._L.fedd_matrix_combine(self._h, slot_m, float(cm), slot_a, float(ca)))
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _chk(self._L.fedd_matrix_sizes(self._h, slot_a, C.byref(a), C.byref(b), C.byref(c)))
+        self.dofs = max(1, a.value // max(1, self.n_own))
+
+    def matrix_combine_current(self, slot_m, cm, slot_a, ca):
+        """True while the system matrix still is that combine (Dirichlet rows apart): nothing to rebuild"""
+        k = C.c_int()
+        _chk(self._L.fedd_matrix_combine_current(self._h, slot_m, float(cm), slot_a, float(ca), C.byref(k)))
+        return bool(k.value)
+
+    def matrix_apply(self, slot, x, alpha=1.0):
+        """y = alpha * M[slot] x (Matrix::apply on a stored block)"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _chk(self._L.fedd_matrix_sizes(self._h, slot, C.byref(a), C.byref(b), C.byref(c)))
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape[0] != b.value:
+            raise FeddError("matrix_apply: x has %d entries, the block %d columns" % (x.shape[0], b.value))
+        y = np.zeros(a.value)
+        _chk(self._L.fedd_matrix_apply(self._h, slot, float(alpha), _p(x, _f64p), _p(y, _f64p)))
+        return y
+
+    def newmark_begin(self):
+        """u_n <- the current solution, v = w = 0; the next advance is the first step"""
+        _chk(self._L.fedd_newmark_begin(self._h))
+
+    def newmark_set(self, u_n=None, v=None, w=None):
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (u_n, v, w)]
+        nr = self.csr_sizes()[0]
+        for a in arrs:
+            if a is not None and a.shape[0] != nr:
+                raise FeddError("newmark_set: vector of %d entries, the system has %d rows" % (a.shape[0], nr))
+        _chk(self._L.fedd_newmark_set(self._h, *[_p(a, _f64p) for a in arrs]))
+
+    def newmark_get(self):
+        """(u_n, v, w) of the Newmark state"""
+        nr = self.csr_sizes()[0]
+        out = [np.zeros(nr) for _ in range(3)]
+        _chk(self._L.fedd_newmark_get(self._h, *[_p(a, _f64p) for a in out]))
+        return tuple(out)
+
+    def newmark_advance(self, slot_m, dt, beta, gamma, coeff=1.0):
+        """updateSolutionNewmarkPreviousStep + updateNewmarkRhs: the state moves to the solved step, rhs <- coeff * M t"""
+        _chk(self._L.fedd_newmark_advance(self._h, slot_m, float(dt), float(beta), float(gamma), float(coeff)))
+
+    def rhs_axpy(self, alpha, f):
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        if f.shape[0] != self.csr_sizes()[0]:
+            raise FeddError("rhs_axpy: vector length differs from the system's rows")
+        _chk(self._L.fedd_rhs_axpy(self._h, float(alpha), _p(f, _f64p)))
+
+    def solution_set(self, x):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape[0] != self.csr_sizes()[0]:
+            raise FeddError("solution_set: vector length differs from the system's rows")
+        _chk(self._L.fedd_solution_set(self._h, _p(x, _f64p)))
+
+    def dirichlet_rhs(self, flags, values=None, comp_mask=None):
+        """the right-hand-side half of dirichlet(): the rows are unit rows already, the matrix is not touched"""
+        fl = np.ascontiguousarray(flags, dtype=np.int32)
+        n = fl.shape[0]
+        v = np.zeros(n * self.dofs) if values is None else np.ascontiguousarray(values, dtype=np.float64).ravel()
+        m = None if comp_mask is None else np.ascontiguousarray(comp_mask, dtype=np.int32).ravel()
+        _chk(self._L.fedd_dirichlet_rhs(self._h, n, _p(fl, _i32p), _p(m, _i32p), _p(v, _f64p)))
 
     def csr_sizes(self):
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()

@@ -213,6 +213,9 @@ static int mesh_set_impl(fedd_ctx* c, int dim, int nen, int64_t n_elem, const in
     for (auto& id : c->adv_pattern_id) id = 0;
     c->d_adv_ke.release();   // the element-block scratch is sized by the mesh (the largest buffer of the advection path)
     ++c->mesh_id;
+    ++c->sys_value_gen;
+    c->comb_valid = false;
+    c->nm_n = -1;           // the Newmark state belonged to the old rows
     ++c->mesh_gen;          // the Schwarz structure (schwarz.hip) belongs to the old nodes
     c->pat_repeatable = false;
     c->halo.reset();
@@ -338,6 +341,7 @@ extern "C" int fedd_pattern_build(fedd_ctx* c, int dofs_per_node, int block_mode
     FEDD_CHECK((dofs_per_node == 1) == (block_mode == FEDD_BLOCK_SCALAR),
                "fedd_pattern_build: block mode SCALAR <=> one dof per node");
     FEDD_HIP(hipSetDevice(c->device));
+    ++c->sys_value_gen;
     {
         ScopedTimer t(c, FEDD_T_SYMBOLIC);
         if (!c->have_adj) FEDD_TRY(build_adjacency(c));
@@ -351,6 +355,7 @@ extern "C" int fedd_assemble(fedd_ctx* c, int form, const double* params) {
     NEED_DEVICE(c);
     FEDD_CHECK(c->have_pattern, "fedd_assemble: call fedd_pattern_build first");
     FEDD_HIP(hipSetDevice(c->device));
+    ++c->sys_value_gen;
     return assemble_matrix(c, form, params);
 }
 
@@ -444,6 +449,7 @@ extern "C" int fedd_matrix_scale(fedd_ctx* c, int slot, double alpha) {
         FEDD_CHECK(c->have_pattern, "fedd_matrix_scale: no system matrix");
     }
     FEDD_HIP(hipSetDevice(c->device));
+    if (slot < 0) ++c->sys_value_gen;
     return matrix_scale(c, slot, alpha);
 }
 
@@ -455,6 +461,7 @@ extern "C" int fedd_assemble_div(fedd_ctx* c, int64_t n_pressure_nodes, int slot
     FEDD_CHECK(c->n_node > 0, "fedd_assemble_div: call fedd_mesh_set first");
     FEDD_HIP(hipSetDevice(c->device));
     ++c->pattern_gen;       // the system slot becomes the scratch node pattern
+    ++c->sys_value_gen;
     const int rc = assemble_div(c, n_pressure_nodes, slot_b, slot_bt);
     ++c->pattern_gen;
     c->pat_repeatable = false;
@@ -467,6 +474,7 @@ extern "C" int fedd_block_merge(fedd_ctx* c, int slot_a, int slot_bt, int slot_b
     FEDD_CHECK(slot_bt < fedd::MAX_AUX && slot_b < fedd::MAX_AUX && slot_c < fedd::MAX_AUX, "fedd_block_merge: slot out of range");
     FEDD_HIP(hipSetDevice(c->device));
     ++c->pattern_gen;       // (a merge that only moves values bumps too: a missed reuse is cheap, a wrong one is not)
+    ++c->sys_value_gen;
     c->pat_repeatable = false;
     FEDD_TRY(block_merge(c, slot_a, slot_bt, slot_b, slot_c));
     c->have_pattern = true;

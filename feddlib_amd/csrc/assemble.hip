@@ -1034,6 +1034,8 @@ int assemble_div(fedd_ctx* c, int64_t n_p, int slot_b, int slot_bt) {
     B.valid = BT.valid = true;
     B.pattern_id = ++c->pattern_counter;
     BT.pattern_id = ++c->pattern_counter;
+    B.value_id = ++c->value_counter;
+    BT.value_id = ++c->value_counter;
     B.block_mode = BT.block_mode = -1;
     c->have_pattern = false;  // the system slot only holds the scratch node pattern now
     c->have_schwarz = false;
@@ -1375,6 +1377,7 @@ int assemble_advection(fedd_ctx* c, int kind, double scale, int slot_add, int sl
     else if (dim == 3 && nen == 4) FEDD_TRY((advection_kind<3, 4>(c, kind, scale, add, out)));
     else FEDD_TRY((advection_kind<3, 10>(c, kind, scale, add, out)));
     out.valid = true;
+    out.value_id = ++c->value_counter;
     return 0;
 }
 

@@ -108,6 +108,9 @@ int matrix_store(fedd_ctx* c, int slot) {
     m.max_row_nnz = c->max_row_nnz;
     m.valid = true;
     m.pattern_id = ++c->pattern_counter;
+    m.value_id = ++c->value_counter;
+    c->sys_pattern_id = m.pattern_id;       // the system slot and this slot now hold the same pattern (timestep.hip)
+    c->sys_pattern_gen = c->pattern_gen;
     m.dofs = c->dofs;
     m.block_mode = c->merged ? -1 : c->block_mode;
     m.mesh_id = c->mesh_id;
@@ -121,6 +124,7 @@ int matrix_scale(fedd_ctx* c, int slot, double alpha) {
     if (n > 0) hipLaunchKernelGGL(k_scale, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, v, n, alpha);
     FEDD_HIP(hipGetLastError());
     if (slot < 0) c->have_schwarz = false;
+    else c->aux[slot].value_id = ++c->value_counter;
     return 0;
 }
 

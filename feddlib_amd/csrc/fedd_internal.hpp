@@ -106,6 +106,7 @@ struct DevCsr {
     int dofs = 0, block_mode = -1;  // velocity-space matrices (fedd_matrix_store of a fedd_pattern_build pattern, fedd_assemble_advection): dofs per node and
     uint64_t mesh_id = 0;           // FEDD_BLOCK_* of the pattern, and the fedd_ctx::mesh_id it was built on; block_mode -1 = another origin
     uint64_t pattern_id = 0;    // drawn from fedd_ctx::pattern_counter whenever rowptr / colind are rewritten: equal ids = same pattern
+    uint64_t value_id = 0;      // drawn from fedd_ctx::value_counter by every writer of val: equal ids = same contents (timestep.hip)
 };
 constexpr int MAX_AUX = 5;      // A, B, B^T, C and the linearised velocity block F = A + rho (N | N + W) of Navier-Stokes
 
@@ -252,6 +253,7 @@ struct fedd_ctx {
     fedd::DevCsr aux[fedd::MAX_AUX];            // stored blocks (A, B, B^T, C, F) of a mixed problem
     uint64_t pattern_counter = 0;               // source of DevCsr::pattern_id
     uint64_t mesh_id = 0;                       // counts the fedd_mesh_set calls: which mesh a stored pattern belongs to
+    uint64_t value_counter = 0;                 // source of DevCsr::value_id
     int merge_slots[4] = {-2, -2, -2, -2};      // the slots and pattern ids the merged system matrix was built from: a merge of the
     uint64_t merge_ids[4] = {0, 0, 0, 0};       // same patterns moves values only (blocks.hip)
 
@@ -369,6 +371,19 @@ struct fedd_ctx {
     // ---- CG (cg.hip) ----
     fedd::DevBuf<double> d_cg;                  // r, z, p, q and the slots of the dot partials
     int cg_replacements = 0, cg_breakdown = 0;  // of the last fedd_cg: residual replacements, breakdown word (FEDD_CG_BREAKDOWN_*)
+
+    // ---- Newmark time stepping (timestep.hip; one rank) ----
+    fedd::DevBuf<double> d_nm_un, d_nm_v, d_nm_w;   // [n_rows] u_n, velocity, acceleration of the last completed step
+    fedd::DevBuf<double> d_nm_t;                // [n_rows] the vector M is applied to for the right-hand side
+    int64_t nm_n = -1;                          // length the state was allocated and zeroed for (-1: none)
+    bool nm_first = true;                       // the next fedd_newmark_advance is the first step: v and w stay
+    uint64_t sys_pattern_id = 0;                // the system slot holds the pattern with this DevCsr::pattern_id (copied by
+    uint64_t sys_pattern_gen = 0;               // fedd_matrix_store / fedd_matrix_combine) ... while pattern_gen still has this value
+    uint64_t sys_value_gen = 0;                 // bumped by every entry that rewrites the system matrix' values (Dirichlet rows excepted)
+    bool comb_valid = false;                    // the last fedd_matrix_combine: slots, coefficients, the slots' value ids
+    int comb_slot_m = -1, comb_slot_a = -1;     // and the sys_value_gen it left
+    double comb_cm = 0.0, comb_ca = 0.0;
+    uint64_t comb_id_m = 0, comb_id_a = 0, comb_sys_gen = 0;
 
     // ---- coarse level (two-level Schwarz) ----
     int sw_two_level = 0;

@@ -1255,6 +1255,8 @@ public:
     CommConstPtr_Type getComm() const { return comm_; }
     void addParemeterRhs(double para) { parasSourceFunc_.push_back(para); }
     double getLastRelativeResidual() const { return lastRelativeResidual_; }
+    BCConstPtr_Type getBCFactory() const { return bcFactory_; }      // what TimeProblem reads (fedd_time.hpp)
+    FEFacPtr_Type getFEFactory() const { return feFactory_; }
 
     int dim_;
     mutable CommConstPtr_Type comm_;

@@ -85,7 +85,9 @@ enum fedd_timer {
     FEDD_T_CG_XR    = 20, /* ... k_cg_xr                                       */
     FEDD_T_CG_RZ    = 21, /* ... k_cg_rz                                       */
     FEDD_T_CG_P     = 22, /* ... k_cg_p                                        */
-    FEDD_T_COUNT    = 23
+    FEDD_T_NEWMARK  = 23, /* Newmark state update: k_newmark (timestep.hip)             */
+    FEDD_T_BLOCK_APPLY = 24, /* y = alpha M x on a stored block: k_block_apply          */
+    FEDD_T_COUNT    = 25
 };
 
 /* ------------------------------------------------------------------------------------------------
@@ -318,6 +320,75 @@ int fedd_assemble_div(fedd_ctx* ctx, int64_t n_pressure_nodes, int slot_b, int s
 int fedd_block_merge(fedd_ctx* ctx, int slot_a, int slot_bt, int slot_b, int slot_c);
 int fedd_matrix_sizes(fedd_ctx* ctx, int slot, int64_t* n_rows, int64_t* n_cols, int64_t* nnz);
 int fedd_matrix_get(fedd_ctx* ctx, int slot, int64_t* rowptr, int32_t* colind, double* val);
+
+/* ------------------------------------------------------------------------------------------------
+ * Newmark time stepping for linear single-block problems (unsteady linear elasticity), one rank like the block slots it uses:
+ * what DAESolverInTime::advanceInTimeLinearNewmark (feddlib/problems/Solver/DAESolverInTime_def.hpp:519-607) does per step with
+ * Tpetra vectors and matrix additions.  On a context with more than one rank every entry below is an error that says so; on a
+ * host-only context they fail with "needs a GPU context".  No multiplication is fused with an addition in any of them.
+ *
+ *   fedd_matrix_combine   system matrix <- (cm * M[slot_m]) + (ca * A[slot_a]): TimeProblem::combineSystems
+ *                         (feddlib/problems/abstract/TimeProblem_def.hpp:359-408: systemMass_->addMatrix(massParameters_,
+ *                         combined, 0) followed by system->addMatrix(timeParameters_, combined, 1)).  The two products are
+ *                         rounded separately and then added, as the two addMatrix calls do.  The result has the pattern of
+ *                         slot_a, structural zeros included.  slot_m holds a matrix of the same mesh with the same pattern
+ *                         (same block mode of fedd_pattern_build) or the DIAG node-block pattern where slot_a has the FULL one
+ *                         (mass against elasticity; an entry M does not have counts as 0.0).  Errors: an empty slot, slots stored
+ *                         before the last fedd_mesh_set, FULL into DIAG and every other pairing.  When the system slot already
+ *                         holds slot_a's pattern (a fedd_matrix_store into slot_a or an earlier combine put it there and nothing
+ *                         rewrote it since) only values move and the pattern generation stands, so the next fedd_schwarz_setup
+ *                         keeps its structure stage (fedd_schwarz_reuse_info).  Right-hand side and solution are NOT reset
+ *                         (unlike fedd_block_merge) unless their length changes; Dirichlet marks are: the rows are real rows
+ *                         again until fedd_dirichlet* is called.
+ *   fedd_matrix_combine_current
+ *                         *current = 1 while the system matrix still is that combine: same slots and coefficients, neither slot
+ *                         written since (fedd_matrix_store, fedd_matrix_scale, fedd_assemble_div, fedd_assemble_advection each
+ *                         count as a write), the system matrix not rebuilt by anything else.  Dirichlet rows do not count: a time
+ *                         loop that finds 1 skips the combine, fedd_dirichlet and both solver setups and calls
+ *                         fedd_dirichlet_rhs only.  The reference combines and builds its preconditioner in every step
+ *                         (DAESolverInTime_def.hpp:565); the results are the same.  Needs no device.
+ *   fedd_matrix_apply     y = alpha * (M[slot] x), host pointers (x[n_cols], y[n_rows]): Matrix::apply on a stored block, i.e.
+ *                         BlockMatrix::apply with a coefficient (TimeProblem_def.hpp:413, 519).  A group of lanes per row; each
+ *                         lane adds its products in ascending column order and the lane sums meet in a fixed tree: two calls
+ *                         agree bit for bit.  The same kernel forms the Newmark right-hand side on device vectors.
+ *   fedd_newmark_begin    u_n <- the current solution, v = w = 0 (the start values of TimeProblem_def.hpp:913-926); the next
+ *                         fedd_newmark_advance is the first step.
+ *   fedd_newmark_set/get  the state vectors u_n, v (velocity), w (acceleration), host pointers of the system's length, any of
+ *                         them NULL (tests, restarts).  A state that was set counts as a state after some step: the next advance
+ *                         is not a first step.
+ *   fedd_newmark_advance  TimeProblem::updateSolutionNewmarkPreviousStep (:875-981) followed by updateNewmarkRhs (:473-524).
+ *                         With u = the current solution (the result u_{n+1} of the step just solved) and the coefficients,
+ *                         evaluated in double precision exactly as written,
+ *                             cuu = 1.0 / ((dt * dt) * beta)      cuv = 1.0 / (dt * beta)        cuw = (0.5 - beta) / beta
+ *                             cvu = gamma / (dt * beta)            cvv = 1.0 - (gamma / beta)     cvw = (dt * (beta - (0.5 * gamma))) / beta
+ *                         every row does, each product and each sum rounded on its own, in this order (NORMATIVE):
+ *                             unless this is the first step:   d  = u - u_n
+ *                                                              v' = ((cvu * d) + (cvv * v)) + (cvw * w)
+ *                                                              w' = ((cuu * d) - (cuv * v)) - (cuw * w)        (the old v)
+ *                             first step:                      v' = v,  w' = w
+ *                             u_n <- u
+ *                             t   = ((cuu * u) + (cuv * v')) + (cuw * w')
+ *                         in ONE kernel that reads u, u_n, v, w and writes u_n, v, w, t once (56 bytes per row), and then
+ *                             rhs <- coeff * (M[slot_m] t)          (the kernel of fedd_matrix_apply)
+ *                         Errors: dt <= 0, beta <= 0, an empty slot, a slot of another size or mesh, no state.
+ *   fedd_rhs_axpy         rhs += alpha * f, host pointer: DAESolverInTime::addSourceTermToRHS (DAESolverInTime_def.hpp:1444-1450).
+ *                         fedd_assemble_rhs overwrites the right-hand side, so a loop assembles the load once, reads it back and
+ *                         adds it here with the step's factor.
+ *   fedd_solution_set     the device's solution vector <- x (the counterpart of fedd_solution_get: initial values, restarts, tests)
+ *   fedd_dirichlet_rhs    the right-hand-side half of fedd_dirichlet (BCBuilder::setRHS, BCBuilder_def.hpp:93-170): rhs <- values
+ *                         on the flagged rows; the matrix, whose rows an earlier fedd_dirichlet made unit rows, is not touched, so
+ *                         the preconditioner and the solver's SpMV setup stand.
+ * ---------------------------------------------------------------------------------------------- */
+int fedd_matrix_combine(fedd_ctx* ctx, int slot_m, double cm, int slot_a, double ca);
+int fedd_matrix_combine_current(fedd_ctx* ctx, int slot_m, double cm, int slot_a, double ca, int* current);
+int fedd_matrix_apply(fedd_ctx* ctx, int slot, double alpha, const double* x_owned, double* y_owned);
+int fedd_newmark_begin(fedd_ctx* ctx);
+int fedd_newmark_set(fedd_ctx* ctx, const double* u_n, const double* v, const double* w);
+int fedd_newmark_get(fedd_ctx* ctx, double* u_n, double* v, double* w);
+int fedd_newmark_advance(fedd_ctx* ctx, int slot_m, double dt, double beta, double gamma, double coeff);
+int fedd_rhs_axpy(fedd_ctx* ctx, double alpha, const double* f_owned);
+int fedd_solution_set(fedd_ctx* ctx, const double* x_owned);
+int fedd_dirichlet_rhs(fedd_ctx* ctx, int n_bc, const int32_t* flags, const int32_t* comp_mask, const double* values);
 
 /* ------------------------------------------------------------------------------------------------
  * steady Navier-Stokes (one rank, like the block system it feeds): the matrices NavierStokes::reAssemble builds in every
