@@ -18,7 +18,7 @@ COMBINE_RESTRICTED, COMBINE_AVERAGING, COMBINE_FULL = range(3)
  T_COARSE_APPLY, T_HALO, T_ALLREDUCE, T_SPMV_SETUP) = range(13)
 TIMER_NAMES = ["symbolic", "assemble", "rhs", "dirichlet", "spmv", "schwarz_setup", "schwarz_apply", "ortho",
                "coarse_setup", "coarse_apply", "halo", "allreduce", "spmv_setup", "gs_dot", "gs_update", "gs_fused",
-               "full_park_mfma", "full_park", "full_gather", "cg_pq", "cg_xr", "cg_rz", "cg_p", "newmark_state", "block_apply"]
+               "full_park_mfma", "full_park", "full_gather", "cg_pq", "cg_xr", "cg_rz", "cg_p", "newmark_state", "block_apply", "multistep_state"]
 COARSE_Q1 = 1
 COARSE_GDSW = 2
 COARSE_RGDSW = 3
@@ -86,6 +86,11 @@ SIGNATURES = {
     "fedd_newmark_set": [C.c_void_p, _f64p, _f64p, _f64p],
     "fedd_newmark_get": [C.c_void_p, _f64p, _f64p, _f64p],
     "fedd_newmark_advance": [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double],
+    "fedd_multistep_begin": [C.c_void_p, C.c_int],
+    "fedd_multistep_advance": [C.c_void_p, C.c_int, C.c_int, _f64p],
+    "fedd_multistep_set": [C.c_void_p, C.c_int, _f64p],
+    "fedd_multistep_get": [C.c_void_p, C.c_int, _f64p],
+    "fedd_multistep_info": [C.c_void_p, _ip, _ip],
     "fedd_rhs_axpy": [C.c_void_p, C.c_double, _f64p],
     "fedd_solution_set": [C.c_void_p, _f64p],
     "fedd_dirichlet_rhs": [C.c_void_p, C.c_int, _i32p, _i32p, _f64p],
@@ -575,6 +580,35 @@ class Context:
     def newmark_advance(self, slot_m, dt, beta, gamma, coeff=1.0):
         """updateSolutionNewmarkPreviousStep + updateNewmarkRhs: the state moves to the solved step, rhs <- coeff * M t"""
         _chk(self._L.fedd_newmark_advance(self._h, slot_m, float(dt), float(beta), float(gamma), float(coeff)))
+
+    def multistep_begin(self, order):
+        """`order` (1 or 2) zeroed history vectors of the current system's length, count = 0"""
+        _chk(self._L.fedd_multistep_begin(self._h, int(order)))
+
+    def multistep_advance(self, slot_m, coeff):
+        """updateSolutionMultiPreviousStep + updateMultistepRhs: the current solution enters the history,
+        rhs <- [M (coeff[0] u + coeff[1] u_0) ; 0]; coeff already divided by dt, len(coeff) = n_use"""
+        cf = np.ascontiguousarray(np.atleast_1d(coeff), dtype=np.float64)
+        _chk(self._L.fedd_multistep_advance(self._h, slot_m, cf.shape[0], _p(cf, _f64p)))
+
+    def multistep_info(self):
+        """(order, count): order 0 = no history"""
+        o, k = C.c_int(), C.c_int()
+        _chk(self._L.fedd_multistep_info(self._h, C.byref(o), C.byref(k)))
+        return o.value, k.value
+
+    def multistep_set(self, k, u_k):
+        u_k = np.ascontiguousarray(u_k, dtype=np.float64)
+        if self.multistep_info()[0] > 0 and u_k.shape[0] != self.csr_sizes()[0]:
+            raise FeddError("multistep_set: vector of %d entries, the system has %d rows" % (u_k.shape[0], self.csr_sizes()[0]))
+        _chk(self._L.fedd_multistep_set(self._h, int(k), _p(u_k, _f64p)))
+
+    def multistep_get(self, k):
+        if self.multistep_info()[0] <= 0:       # the length of the host buffer comes from the history: none, no copy
+            raise FeddError("multistep_get: no multistep history (fedd_multistep_begin first; a fedd_mesh_set releases it)")
+        out = np.zeros(self.csr_sizes()[0])
+        _chk(self._L.fedd_multistep_get(self._h, int(k), _p(out, _f64p)))
+        return out
 
     def rhs_axpy(self, alpha, f):
         f = np.ascontiguousarray(f, dtype=np.float64)

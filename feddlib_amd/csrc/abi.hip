@@ -216,6 +216,11 @@ static int mesh_set_impl(fedd_ctx* c, int dim, int nen, int64_t n_elem, const in
     ++c->sys_value_gen;
     c->comb_valid = false;
     c->nm_n = -1;           // the Newmark state belonged to the old rows
+    c->ms_order = c->ms_count = 0;   // ... and so did the multistep history, whose buffers go with it
+    c->ms_n = -1;
+    c->d_ms_u[0].release();
+    c->d_ms_u[1].release();
+    c->d_ms_t.release();
     ++c->mesh_gen;          // the Schwarz structure (schwarz.hip) belongs to the old nodes
     c->pat_repeatable = false;
     c->halo.reset();

@@ -108,7 +108,8 @@ struct DevCsr {
     uint64_t pattern_id = 0;    // drawn from fedd_ctx::pattern_counter whenever rowptr / colind are rewritten: equal ids = same pattern
     uint64_t value_id = 0;      // drawn from fedd_ctx::value_counter by every writer of val: equal ids = same contents (timestep.hip)
 };
-constexpr int MAX_AUX = 5;      // A, B, B^T, C and the linearised velocity block F = A + rho (N | N + W) of Navier-Stokes
+constexpr int MAX_AUX = 7;      // A, B, B^T, C, the linearised velocity block F = A + rho (N | N + W) of Navier-Stokes, and of its time loop
+                                // the velocity mass matrix (5) and the time-combined constant velocity block (cm M) + (ca A) (6)
 
 // regular lattice of the coarse level: g cells and np = g + 1 points per direction (1 point in
 // directions beyond dim), over the global bounding box [lo, lo + L]
@@ -250,7 +251,7 @@ struct fedd_ctx {
     fedd::DevBuf<double> d_cs_clsval;           // [classes][8] values of a class
     fedd::DevBuf<int32_t> d_cs_clsi;            // slot of row [n] | table min row | class of slot | counters
     fedd::DevBuf<uint64_t> d_cs_clskey;         // table keys
-    fedd::DevCsr aux[fedd::MAX_AUX];            // stored blocks (A, B, B^T, C, F) of a mixed problem
+    fedd::DevCsr aux[fedd::MAX_AUX];            // stored blocks (A, B, B^T, C, F, M, A') of a mixed problem
     uint64_t pattern_counter = 0;               // source of DevCsr::pattern_id
     uint64_t mesh_id = 0;                       // counts the fedd_mesh_set calls: which mesh a stored pattern belongs to
     uint64_t value_counter = 0;                 // source of DevCsr::value_id
@@ -269,7 +270,7 @@ struct fedd_ctx {
     fedd::DevBuf<double> d_adv_tab;             // quadrature tables of N, then of W where its rule differs (w | phi | dphi each)
     int adv_nq[2] = {0, 0}, adv_tab_off_w = 0;
     fedd::DevBuf<double> d_adv_ke;              // [n_elem][nen][nen][1 | dim * dim] element blocks of the assembly in progress
-    uint64_t adv_pattern_id[fedd::MAX_AUX] = {0, 0, 0, 0, 0};   // pattern id of the slots that hold the FULL pattern written here
+    uint64_t adv_pattern_id[fedd::MAX_AUX] = {};   // pattern id of the slots that hold the FULL pattern written here
     bool merged = false;                        // system matrix = merged blocks (dof -> node map below)
     int64_t merged_nA = 0;                      // rows of block row 0
     int merged_dofsA = 1;                       // dofs per node of block row 0
@@ -377,6 +378,11 @@ struct fedd_ctx {
     fedd::DevBuf<double> d_nm_t;                // [n_rows] the vector M is applied to for the right-hand side
     int64_t nm_n = -1;                          // length the state was allocated and zeroed for (-1: none)
     bool nm_first = true;                       // the next fedd_newmark_advance is the first step: v and w stay
+    // ---- multistep (BDF) history (timestep.hip; one rank): buffers of their own, released by fedd_mesh_set ----
+    fedd::DevBuf<double> d_ms_u[2];             // [ms_n] u_0 (the last recorded solution), u_1 (the one before; order 2 only)
+    fedd::DevBuf<double> d_ms_t;                // [ms_n] the combination M is applied to for the right-hand side
+    int ms_order = 0, ms_count = 0;             // 0 = no history (fedd_multistep_begin); vectors recorded so far (<= ms_order)
+    int64_t ms_n = -1;                          // length of the system at fedd_multistep_begin
     uint64_t sys_pattern_id = 0;                // the system slot holds the pattern with this DevCsr::pattern_id (copied by
     uint64_t sys_pattern_gen = 0;               // fedd_matrix_store / fedd_matrix_combine) ... while pattern_gen still has this value
     uint64_t sys_value_gen = 0;                 // bumped by every entry that rewrites the system matrix' values (Dirichlet rows excepted)

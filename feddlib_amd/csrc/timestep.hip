@@ -7,11 +7,15 @@
 //   DAESolverInTime::addSourceTermToRHS               feddlib/problems/Solver/DAESolverInTime_def.hpp:1444-1450
 // as sequenced by DAESolverInTime::advanceInTimeLinearNewmark (:519-607).
 //
-// Three kernels:
+// Four kernels:
 //   k_combine_*   system <- cm M + ca A, one lane per stored entry of A; the position of M's entry inside A's row is closed form
 //                 (both patterns expand from the same node-level pattern, symbolic.hip k_expand_pattern)
 //   k_block_apply y = alpha M x on a stored block: G lanes per row, loads of four trips in flight, fixed shuffle tree
 //   k_newmark     the vector part of a step in one pass: reads u, u_n, v, w, writes u_n, v, w, t (56 bytes per row)
+//   k_multistep   the history of a BDF loop on a merged (velocity, pressure) system in one pass: reads u and u_0, writes u_0, u_1
+//                 and t = coeff[0] u (+ coeff[1] u_0) (40 bytes per row), zeroes the pressure rows of the right-hand side
+//                 (TimeProblem::updateSolutionMultiPreviousStep :833-849, updateMultistepRhs :417-438, as sequenced by
+//                 DAESolverInTime::advanceInTimeNonLinearMultistep, DAESolverInTime_def.hpp:1209-1333)
 // The normative operation order is in include/fedd_hip.h; no product is fused with a sum anywhere in this file, so the
 // combine and the state update can be restated bit for bit on the host.
 #include "fedd_internal.hpp"
@@ -147,6 +151,62 @@ __global__ __launch_bounds__(256) void k_newmark(const double* __restrict__ u, d
             w[i] = d;
         }
         t[i] = e;
+    }
+}
+
+// ---- multistep (BDF) history ---------------------------------------------------------------------------------------------------
+// One row pair of fedd_multistep_advance, in the operation order of include/fedd_hip.h.  NUSE = coefficients in use, SHIFT2 =
+// the old u_0 moves to u_1 (order 2 with a recorded vector).  The old u_0 is read where NUSE == 2 or SHIFT2 asks for it and
+// nowhere else: a first step, and every step of an order-1 history, neither reads u_0 nor writes u_1.
+template <int NUSE, bool SHIFT2>
+__device__ __forceinline__ double ms_row(double c0, double c1, double u, double old0) {
+    (void)c1;
+    (void)old0;
+    if (NUSE == 2) {
+        const double p0 = c0 * u;
+        const double p1 = c1 * old0;
+        return p0 + p1;
+    }
+    return c0 * u;
+}
+
+// Pure stream like k_newmark: 16-byte accesses over the row pairs, one scalar tail row when n is odd.  The zero fill of
+// rhs[n_m, n) rides along: a pair that lies at or above n_m stores 16 bytes, the pair n_m cuts (n_m odd) stores its upper row
+// alone, so every 16-byte store is pair-aligned and none crosses n_m; rows below n_m are k_block_apply's.
+template <int NUSE, bool SHIFT2>
+__global__ __launch_bounds__(256) void k_multistep(const double* __restrict__ u, double* __restrict__ h0, double* __restrict__ h1,
+                                                   double* __restrict__ t, double* __restrict__ rhs, int64_t n, int64_t n_m, double c0,
+                                                   double c1) {
+    constexpr bool HAVE0 = NUSE == 2 || SHIFT2;
+    const int64_t n2 = n >> 1;
+    const double2* __restrict__ u2 = reinterpret_cast<const double2*>(u);
+    double2* __restrict__ h02 = reinterpret_cast<double2*>(h0);
+    double2* __restrict__ h12 = reinterpret_cast<double2*>(h1);
+    double2* __restrict__ t2 = reinterpret_cast<double2*>(t);
+    double2* __restrict__ rhs2 = reinterpret_cast<double2*>(rhs);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (int64_t)gridDim.x * blockDim.x) {
+        const double2 a = u2[i];
+        double2 o = a, e;
+        if (HAVE0) o = h02[i];
+        e.x = ms_row<NUSE, SHIFT2>(c0, c1, a.x, o.x);
+        e.y = ms_row<NUSE, SHIFT2>(c0, c1, a.y, o.y);
+        if (SHIFT2) h12[i] = o;
+        h02[i] = a;
+        t2[i] = e;
+        const int64_t r = 2 * i;
+        if (r >= n_m) rhs2[i] = make_double2(0.0, 0.0);
+        else if (r + 1 >= n_m) rhs[r + 1] = 0.0;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t i = n - 1;
+        const double a = u[i];
+        double o = a;
+        if (HAVE0) o = h0[i];
+        const double e = ms_row<NUSE, SHIFT2>(c0, c1, a, o);
+        if (SHIFT2) h1[i] = o;
+        h0[i] = a;
+        t[i] = e;
+        if (i >= n_m) rhs[i] = 0.0;
     }
 }
 
@@ -425,6 +485,113 @@ extern "C" int fedd_newmark_advance(fedd_ctx* c, int slot_m, double dt, double b
     }
     c->nm_first = false;
     return block_apply_device(c, M, coeff, c->d_nm_t.p, c->d_rhs.p);
+}
+
+// ---- multistep (BDF) history: include/fedd_hip.h "BDF time stepping" -------------------------------------------------------------
+#define NEED_MULTISTEP(c, who)                                                                                   \
+    FEDD_CHECK((c)->ms_order > 0 && (c)->d_ms_u[0].p && (c)->d_ms_t.p,                                           \
+               "%s: no multistep history (fedd_multistep_begin first; a fedd_mesh_set releases it)", who)
+
+extern "C" int fedd_multistep_begin(fedd_ctx* c, int order) {
+    FEDD_CHECK(order == 1 || order == 2, "fedd_multistep_begin: order must be 1 or 2 (got %d)", order);
+    NEED_DEVICE(c);
+    ONE_RANK(c, "fedd_multistep_begin");
+    FEDD_CHECK(c->have_pattern, "fedd_multistep_begin: no system (fedd_block_merge, fedd_pattern_build or fedd_matrix_combine first)");
+    FEDD_HIP(hipSetDevice(c->device));
+    const size_t n = (size_t)c->n_rows;
+    c->ms_order = c->ms_count = 0;
+    for (int k = 0; k < 2; ++k) {
+        if (k < order) {
+            FEDD_TRY(c->d_ms_u[k].ensure(n));
+            FEDD_HIP(hipMemsetAsync(c->d_ms_u[k].p, 0, n * sizeof(double), c->stream));
+        } else {
+            c->d_ms_u[k].release();
+        }
+    }
+    FEDD_TRY(c->d_ms_t.ensure(n));   // (not zeroed: k_multistep writes all n rows before k_block_apply reads them)
+    c->ms_n = (int64_t)n;
+    c->ms_order = order;
+    return 0;
+}
+
+extern "C" int fedd_multistep_info(fedd_ctx* c, int* order, int* count) {
+    FEDD_CHECK(c, "fedd_multistep_info: null context");
+    if (order) *order = c->ms_order;
+    if (count) *count = c->ms_count;
+    return 0;
+}
+
+extern "C" int fedd_multistep_set(fedd_ctx* c, int k, const double* u_k) {
+    NEED_DEVICE(c);
+    ONE_RANK(c, "fedd_multistep_set");
+    NEED_MULTISTEP(c, "fedd_multistep_set");
+    FEDD_CHECK(k >= 0 && k < c->ms_order, "fedd_multistep_set: k must be 0 .. order - 1 = %d (got %d)", c->ms_order - 1, k);
+    FEDD_CHECK(u_k, "fedd_multistep_set: null pointer");
+    FEDD_HIP(hipSetDevice(c->device));
+    FEDD_HIP(hipMemcpyAsync(c->d_ms_u[k].p, u_k, (size_t)c->ms_n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    FEDD_HIP(hipStreamSynchronize(c->stream));   // the host buffer is the caller's
+    c->ms_count = std::max(c->ms_count, k + 1);  // a vector that was given is a state after some step (restart)
+    return 0;
+}
+
+extern "C" int fedd_multistep_get(fedd_ctx* c, int k, double* u_k) {
+    NEED_DEVICE(c);
+    ONE_RANK(c, "fedd_multistep_get");
+    NEED_MULTISTEP(c, "fedd_multistep_get");
+    FEDD_CHECK(k >= 0 && k < c->ms_order, "fedd_multistep_get: k must be 0 .. order - 1 = %d (got %d)", c->ms_order - 1, k);
+    FEDD_CHECK(u_k, "fedd_multistep_get: null pointer");
+    FEDD_HIP(hipSetDevice(c->device));
+    FEDD_HIP(hipStreamSynchronize(c->stream));
+    FEDD_HIP(hipMemcpy(u_k, c->d_ms_u[k].p, (size_t)c->ms_n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int fedd_multistep_advance(fedd_ctx* c, int slot_m, int n_use, const double* coeff) {
+    FEDD_CHECK(n_use >= 1, "fedd_multistep_advance: n_use must be at least 1 (got %d)", n_use);
+    FEDD_CHECK(coeff, "fedd_multistep_advance: null coefficient array");
+    NEED_DEVICE(c);
+    ONE_RANK(c, "fedd_multistep_advance");
+    CHECK_SLOT(slot_m);
+    NEED_MULTISTEP(c, "fedd_multistep_advance");
+    FEDD_CHECK(c->have_pattern, "fedd_multistep_advance: no system");
+    FEDD_CHECK(c->n_rows == c->ms_n,
+               "fedd_multistep_advance: the system has %lld rows, the history was begun on %lld (fedd_multistep_begin again)",
+               (long long)c->n_rows, (long long)c->ms_n);
+    FEDD_CHECK(n_use <= std::min(c->ms_count + 1, c->ms_order),
+               "fedd_multistep_advance: n_use %d exceeds min(count + 1, order) = %d (order %d, %d vectors recorded)", n_use,
+               std::min(c->ms_count + 1, c->ms_order), c->ms_order, c->ms_count);
+    const DevCsr& M = c->aux[slot_m];
+    FEDD_CHECK(M.valid, "fedd_multistep_advance: slot %d is empty", slot_m);
+    FEDD_CHECK(M.mesh_id == c->mesh_id, "fedd_multistep_advance: slot %d holds a matrix of an earlier mesh", slot_m);
+    FEDD_CHECK(M.n_rows <= c->n_rows && M.n_cols <= c->n_rows,
+               "fedd_multistep_advance: slot %d holds a %lld x %lld matrix, more rows or columns than the system's %lld", slot_m,
+               (long long)M.n_rows, (long long)M.n_cols, (long long)c->n_rows);
+    FEDD_HIP(hipSetDevice(c->device));
+    const int64_t n = c->n_rows, n_m = M.n_rows;
+    const bool shift2 = c->ms_order == 2 && c->ms_count >= 1;
+    if (n > 0) {
+        ScopedTimer t(c, FEDD_T_MULTISTEP);
+        const unsigned grid = (unsigned)std::min<int64_t>(2048, std::max<int64_t>(1, ((n >> 1) + 255) / 256));
+        const double c0 = coeff[0], c1 = n_use == 2 ? coeff[1] : 0.0;
+        const double* u = c->d_x.p;
+        double *h0 = c->d_ms_u[0].p, *h1 = c->d_ms_u[1].p, *tt = c->d_ms_t.p, *rhs = c->d_rhs.p;
+        double row_bytes;       // the byte model of the instance launched (DESIGN section 4 "BDF")
+        if (n_use == 2) {       // needs order 2 and a recorded vector: the shift is on
+            row_bytes = 40.0;   // reads u, u_0; writes u_0, u_1, t
+            hipLaunchKernelGGL((k_multistep<2, true>), dim3(grid), dim3(256), 0, c->stream, u, h0, h1, tt, rhs, n, n_m, c0, c1);
+        } else if (shift2) {
+            row_bytes = 40.0;
+            hipLaunchKernelGGL((k_multistep<1, true>), dim3(grid), dim3(256), 0, c->stream, u, h0, h1, tt, rhs, n, n_m, c0, c1);
+        } else {
+            row_bytes = 24.0;   // reads u; writes u_0, t
+            hipLaunchKernelGGL((k_multistep<1, false>), dim3(grid), dim3(256), 0, c->stream, u, h0, h1, tt, rhs, n, n_m, c0, c1);
+        }
+        t.bytes(row_bytes * (double)n + 8.0 * (double)(n - n_m));   // + the zero fill of the pressure rows
+        t.stop();
+        FEDD_HIP(hipGetLastError());
+    }
+    c->ms_count = std::min(c->ms_count + 1, c->ms_order);
+    return block_apply_device(c, M, 1.0, c->d_ms_t.p, c->d_rhs.p);
 }
 
 extern "C" int fedd_rhs_axpy(fedd_ctx* c, double alpha, const double* f_owned) {

@@ -1206,6 +1206,12 @@ public:
         }
     }
     bool hasSourceTerm() const { return !sourceTerm_.is_null(); }
+    // a right-hand-side function was added (what the reference's hasSourceTerm_ flag records, Problem_def.hpp addRhsFunction)
+    bool hasRhsFunction() const {
+        for (const auto& f : rhsFuncVec_)
+            if (f) return true;
+        return false;
+    }
     int solve(BlockMultiVectorPtr_Type rhs = Teuchos::null) {         // Problem_def.hpp:257-295
         if (verbose_) std::cout << "-- Solve System ..." << std::endl;
         LinearSolver<SC, LO, GO, NO> linSolver;
@@ -1704,7 +1710,7 @@ public:
             }
             feddCheck(fedd_velocity_set(dev->ctx, u_rep_.data()), "fedd_velocity_set");
         }
-        feddCheck(fedd_assemble_advection(dev->ctx, type == "Newton" ? FEDD_ADV_NEWTON : FEDD_ADV_N, density, 0, 4), "fedd_assemble_advection");
+        feddCheck(fedd_assemble_advection(dev->ctx, type == "Newton" ? FEDD_ADV_NEWTON : FEDD_ADV_N, density, baseSlot_, 4), "fedd_assemble_advection");
         MatrixPtr_Type ANW(new Matrix_Type(domV->getMapVecFieldUnique(), domV->getDimension() * domV->getApproxEntriesPerRow()));
         ANW->bindSlot(dev, 4);
         ANW->fillComplete(domV->getMapVecFieldUnique(), domV->getMapVecFieldUnique());
@@ -1736,19 +1742,31 @@ public:
         if (standard) this->bcFactory_->setVectorMinusBC(this->residualVec_, this->solution_, time);
         else this->bcFactory_->setBCMinusVector(this->residualVec_, this->solution_, time);
     }
+    // the slot reAssemble hands to fedd_assemble_advection as slot_add: 0 = A (steady); a time loop sets 6, the time-combined
+    // constant block (cm M) + (ca A) (TimeProblem::combineSystems, fedd_time.hpp)
+    void setVelocityBaseSlot(int slot) const { baseSlot_ = slot; }
+    int getVelocityBaseSlot() const { return baseSlot_; }
 private:
     mutable MatrixPtr_Type A_;
     mutable std::vector<double> u_rep_;
-    mutable int slotC_ = -1;
+    mutable int slotC_ = -1, baseSlot_ = 0;
 };
 
 // NonLinearSolver (feddlib/problems/Solver/NonLinearSolver_def.hpp:274-391): solveFixedPoint and solveNewton, line by line --
 // residual first ("reverse"), "Criterion" = Residual | Update, relNonLinTol, MaxNonLinIts, "Cancel MaxNonLinIts".  What the
 // reference's parameter files can ask for beyond that is refused with the key named.
+template <class SC, class LO, class GO, class NO>
+class TimeProblem;      // fedd_time.hpp
+
 template <class SC = default_sc, class LO = default_lo, class GO = default_go, class NO = default_no>
 class NonLinearSolver {
 public:
     typedef NonLinearProblem<SC, LO, GO, NO> NonLinearProblem_Type;
+    typedef TimeProblem<SC, LO, GO, NO> TimeProblem_Type;
+    // the TimeProblem overloads of NonLinearSolver_def.hpp (solveFixedPoint :394-452, solveNewton :459-531); defined in
+    // fedd_time.hpp, which a caller of this overload includes anyway (DAESolverInTime)
+    void solve(TimeProblem_Type& problem, double time);
+    int lastNonLinIts = 0;          // nonlinear iterations of the last time-problem solve
     NonLinearSolver() : type_("") {}
     NonLinearSolver(std::string type) : type_(type) {}
     void solve(NonLinearProblem_Type& problem) {

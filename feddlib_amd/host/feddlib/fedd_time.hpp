@@ -1,11 +1,17 @@
-// Time stepping of the facade: TimeSteppingTools, TimeProblem, DAESolverInTime -- the subset the reference's unsteadyLinElas
-// test runs (feddlib/problems/tests/unsteadyLinElas/main.cpp): Newmark only, linear only, one block, one rank.
+// Time stepping of the facade: TimeSteppingTools, TimeProblem, DAESolverInTime -- the subsets the reference's unsteadyLinElas
+// and unsteadyNavierStokes tests run (feddlib/problems/tests/unsteadyLinElas/main.cpp, unsteadyNavierStokes/main.cpp):
+// "Newmark" on a linear one-block problem, and "Multistep" (BDF1 / BDF2) on Navier-Stokes (two variables, time definition
+// [[1,1],[0,0]]); one rank.
 //   TimeSteppingTools   feddlib/problems/Solver/TimeSteppingTools.cpp (the keys the Newmark path reads)
 //   TimeProblem         feddlib/problems/abstract/TimeProblem_def.hpp (assembleMassSystem :599-663, combineSystems :359-408,
 //                       updateNewmarkRhs :473-524, updateSolutionNewmarkPreviousStep :875-981)
-//   DAESolverInTime     feddlib/problems/Solver/DAESolverInTime_def.hpp (advanceInTimeLinearNewmark :519-607)
-// Everything else these classes do in the reference (multi-stage and multi-step schemes, adaptive steps, nonlinear loops, FSI)
-// is an error here that names what is built.
+//                       nonlinear: updateSolutionMultiPreviousStep :833-849, updateMultistepRhs :417-438,
+//                       calculateNonLinResidualVec :693-738, setBoundariesSystem / solveUpdate / solveAndUpdate :767-803
+//   DAESolverInTime     feddlib/problems/Solver/DAESolverInTime_def.hpp (advanceInTimeLinearNewmark :519-607,
+//                       advanceInTimeNonLinearMultistep :1209-1333)
+//   NonLinearSolver::solve(TimeProblem&, time)   NonLinearSolver_def.hpp:394-531
+// Everything else these classes do in the reference (single-step / Butcher-table schemes, adaptive steps, "Extrapolation", NOX,
+// source terms in the nonlinear loop, FSI) is an error here that names what is built.
 #pragma once
 #include "fedd_facade.hpp"
 
@@ -40,6 +46,16 @@ public:
         beta_ = pl_->get("beta", 0.25);
         gamma_ = pl_->get("gamma", 0.5);
         TEUCHOS_TEST_FOR_EXCEPTION(dt_ <= 0., std::logic_error, "Timestepping Parameter: dt must be positive");
+        bdf_ = pl_->get("BDF", 1);
+        if (class_ == "Multistep") checkBDF();
+    }
+    // TimeSteppingTools.cpp:493-515: {M u_new / dt, A u_new, M u_n / dt (, M u_{n-1} / dt)}
+    int getBDFNumber() const { checkBDF(); return bdf_; }
+    double getInformationBDF(int i) const {
+        checkBDF();
+        static const double one[3] = {1., 1., 1.}, two[4] = {1.5, 1.0, 2.0, -0.5};
+        TEUCHOS_TEST_FOR_EXCEPTION(i < 0 || i + 1 > bdf_ + 2, std::logic_error, "Wrong bdf table access!");
+        return bdf_ == 1 ? one[i] : two[i];
     }
     std::string getClass() const { return class_; }
     double get_dt() const { return dt_; }
@@ -54,8 +70,13 @@ public:
         if (printInfo && comm_->getRank() == 0) std::cout << "-- time step " << step_ << " done, t = " << t_ << " --" << std::endl;
     }
 private:
+    void checkBDF() const {
+        TEUCHOS_TEST_FOR_EXCEPTION(bdf_ != 1 && bdf_ != 2, std::logic_error,
+                                   "Timestepping Parameter \"BDF\" = " + std::to_string(bdf_) + " is not built (1 and 2 are)");
+    }
     ParameterListPtr_Type pl_;
     Teuchos::RCP<const Teuchos::Comm<int>> comm_;
+    int bdf_ = 1;
     std::string class_;
     double dt_ = 0., tEnd_ = 0., beta_ = 0.25, gamma_ = 0.5, t_ = 0.;
     int step_ = 0;
@@ -74,20 +95,45 @@ public:
     typedef typename Problem_Type::BlockMatrixPtr_Type BlockMatrixPtr_Type;
     typedef typename Problem_Type::BlockMultiVectorPtr_Type BlockMultiVectorPtr_Type;
     typedef Teuchos::RCP<const Teuchos::Comm<int>> CommConstPtr_Type;
+    typedef NonLinearProblem<SC, LO, GO, NO> NonLinearProblem_Type;
+    typedef NavierStokes<SC, LO, GO, NO> NavierStokes_Type;
     static constexpr int SLOT_MASS = 0, SLOT_SYSTEM = 1;
+    // nonlinear path (Navier-Stokes occupies slots 0 .. 4): velocity mass, time-combined constant velocity block
+    static constexpr int SLOT_NL_A = 0, SLOT_NL_MASS = 5, SLOT_NL_COMBINED = 6;
 
     TimeProblem(Problem_Type& problem, CommConstPtr_Type comm) : problem_(&problem), comm_(comm) {
-        TEUCHOS_TEST_FOR_EXCEPTION(comm->getSize() != 1, std::logic_error, "TimeProblem: one rank only (the Newmark device layer is one rank)");
-        TEUCHOS_TEST_FOR_EXCEPTION((dynamic_cast<NonLinearProblem<SC, LO, GO, NO>*>(problem_) != nullptr), std::logic_error,
-                                   "TimeProblem: nonlinear problems are not built; linear \"Newmark\" is");
+        TEUCHOS_TEST_FOR_EXCEPTION(comm->getSize() != 1, std::logic_error, "TimeProblem: one rank only (the time-stepping device layer is one rank)");
+        nl_ = dynamic_cast<NonLinearProblem_Type*>(problem_);
+        ns_ = dynamic_cast<NavierStokes_Type*>(problem_);
+        TEUCHOS_TEST_FOR_EXCEPTION(nl_ != nullptr && ns_ == nullptr, std::logic_error,
+                                   "TimeProblem: NavierStokes is the nonlinear problem that is built");
     }
+    bool isNonLinear() const { return nl_ != nullptr; }
     void setTimeDef(const SmallMatrix<int>& def) {
-        TEUCHOS_TEST_FOR_EXCEPTION(def.size() != 1, std::logic_error, "TimeProblem::setTimeDef: only a 1 x 1 definition is built (one block, \"Newmark\")");
+        if (nl_) {
+            TEUCHOS_TEST_FOR_EXCEPTION(def.size() != 2 || def[0][0] != 1 || def[0][1] != 1 || def[1][0] != 0 || def[1][1] != 0, std::logic_error,
+                                       "TimeProblem::setTimeDef: a nonlinear problem takes the 2 x 2 definition [[1,1],[0,0]] (velocity, pressure)");
+        } else {
+            TEUCHOS_TEST_FOR_EXCEPTION(def.size() != 1, std::logic_error, "TimeProblem::setTimeDef: only a 1 x 1 definition is built (one block, \"Newmark\")");
+        }
         timeStepDef_ = def;
     }
     // TimeProblem::assembleMassSystem (:599-663): FE::assemblyMass on the variable's space, scaled by "Density" (:605, 620).
     // The problem's own matrix, still in the device's system slot after Problem::assemble, moves to slot 1 first.
     void assembleMassSystem() {
+        if (nl_) {      // the vector mass on the velocity space x "Density" into slot 5; the system slot is scratch until the next reAssemble
+            dev_ = problem_->getDomain(0)->device();
+            const int dim = (int)problem_->getDomain(0)->getDimension();
+            const double density = problem_->getParameterList()->sublist("Parameter").get("Density", 1.);
+            MatrixPtr_Type M = Teuchos::rcp(new Matrix_Type(problem_->getDomain(0)->getMapVecFieldUnique(), problem_->getDomain(0)->getApproxEntriesPerRow()));
+            problem_->getFEFactory()->assemblyMass(dim, problem_->getFEType(0), "Vector", M);
+            M->scale(density);
+            feddCheck(fedd_matrix_store(dev_->ctx, SLOT_NL_MASS), "fedd_matrix_store");
+            M->bindSlot(dev_, SLOT_NL_MASS);
+            systemMass_.reset(new BlockMatrix_Type(2));
+            systemMass_->addBlock(M, 0, 0);
+            return;
+        }
         auto sys = problem_->getSystem();
         TEUCHOS_TEST_FOR_EXCEPTION(sys.is_null() || sys->size() != 1 || !sys->blockExists(0, 0), std::logic_error,
                                    "TimeProblem: a single-block problem, assembled (Problem::assemble), is needed");
@@ -110,15 +156,41 @@ public:
         systemMass_->addBlock(M, 0, 0);
     }
     void setTimeParameters(const SmallMatrix<double>& massParameters, const SmallMatrix<double>& timeParameters) {
+        if (nl_) {
+            TEUCHOS_TEST_FOR_EXCEPTION(massParameters.size() != 2 || timeParameters.size() != 2, std::logic_error, "TimeProblem: 2 x 2 parameters for a nonlinear problem");
+            TEUCHOS_TEST_FOR_EXCEPTION(timeParameters[0][1] != 1. || timeParameters[1][0] != 1. || timeParameters[1][1] != 1., std::logic_error,
+                                       "TimeProblem::setTimeParameters: off-diagonal and pressure-row problem coefficients other than 1.0 are not built (BDF gives 1.0)");
+            TEUCHOS_TEST_FOR_EXCEPTION(massParameters[0][1] != 0. || massParameters[1][0] != 0. || massParameters[1][1] != 0., std::logic_error,
+                                       "TimeProblem::setTimeParameters: mass coefficients outside the velocity block are not built (the time definition is [[1,1],[0,0]])");
+            massParameters_ = massParameters;
+            timeParameters_ = timeParameters;
+            return;
+        }
         TEUCHOS_TEST_FOR_EXCEPTION(massParameters.size() != 1 || timeParameters.size() != 1, std::logic_error, "TimeProblem: 1 x 1 parameters only");
         massParameters_ = massParameters;
         timeParameters_ = timeParameters;
     }
     // TimeProblem::combineSystems (:359-408) -> fedd_matrix_combine.  The reference combines in every step; here the combined
     // matrix is rebuilt only when the coefficients or either matrix changed since the last combine (same results)
+    // Nonlinear: slot 6 <- (cm * M[5]) + (ca * A[0]) when (cm, ca) changed -- once per coefficient set, twice in a BDF2 run --, the
+    // base slot of NavierStokes::reAssemble becomes 6, and one reAssemble puts the merged time system into the system slot.
+    // The reference adds the matrices in every nonlinear iteration; the sums are the same.
     void combineSystems() {
         TEUCHOS_TEST_FOR_EXCEPTION(systemMass_.is_null(), std::logic_error, "TimeProblem::combineSystems: call assembleMassSystem first");
         const double cm = massParameters_[0][0], ca = timeParameters_[0][0];
+        if (nl_) {
+            if (nlCombined_ && cm == nlCm_ && ca == nlCa_) return;
+            int cur = 0;
+            feddCheck(fedd_matrix_combine_current(dev_->ctx, SLOT_NL_MASS, cm, SLOT_NL_A, ca, &cur), "fedd_matrix_combine_current");
+            if (!cur) feddCheck(fedd_matrix_combine(dev_->ctx, SLOT_NL_MASS, cm, SLOT_NL_A, ca), "fedd_matrix_combine");
+            feddCheck(fedd_matrix_store(dev_->ctx, SLOT_NL_COMBINED), "fedd_matrix_store");
+            dev_->generation++;
+            nlCombined_ = true; nlCm_ = cm; nlCa_ = ca;
+            ++combines_;
+            ns_->setVelocityBaseSlot(SLOT_NL_COMBINED);
+            nl_->reAssemble("FixedPoint");
+            return;
+        }
         int current = 0;
         feddCheck(fedd_matrix_combine_current(dev_->ctx, SLOT_MASS, cm, SLOT_SYSTEM, ca, &current), "fedd_matrix_combine_current");
         if (current && !systemCombined_.is_null()) return;
@@ -150,6 +222,52 @@ public:
         feddCheck(fedd_newmark_advance(dev_->ctx, SLOT_MASS, dt, beta, gamma, coeff.at(0)), "fedd_newmark_advance");
         feddCheck(fedd_rhs_get(dev_->ctx, problem_->getRhs()->getBlockNonConst(0)->raw().data()), "fedd_rhs_get");
     }
+    // updateSolutionMultiPreviousStep (:833-849) and updateMultistepRhs (:417-438) are ONE device call, fedd_multistep_advance:
+    // the first only records, the second launches (history shift, rhs <- [M t; 0]) and brings the right-hand side to the host.
+    void updateSolutionMultiPreviousStep(int nmbSteps) {
+        TEUCHOS_TEST_FOR_EXCEPTION(!nl_, std::logic_error, "TimeProblem::updateSolutionMultiPreviousStep: the multistep path is built for nonlinear problems");
+        pendMs_ = true; pendSteps_ = nmbSteps;
+    }
+    void updateMultistepRhs(vec_dbl_Type& coeff, int nmbToUse) {
+        TEUCHOS_TEST_FOR_EXCEPTION(!pendMs_, std::logic_error, "TimeProblem::updateMultistepRhs: call updateSolutionMultiPreviousStep first");
+        TEUCHOS_TEST_FOR_EXCEPTION(nmbToUse < 1 || nmbToUse > pendSteps_ || (int)coeff.size() < nmbToUse, std::logic_error,
+                                   "TimeProblem::updateMultistepRhs: more coefficients asked for than steps recorded or coefficients given");
+        pendMs_ = false;
+        combineSystems();                                   // the merged time system: the history is as long as it
+        std::vector<double> x = flatSolution();
+        feddCheck(fedd_solution_set(dev_->ctx, x.data()), "fedd_solution_set");     // fedd_block_merge has reset it
+        if (!msBegan_) {
+            feddCheck(fedd_multistep_begin(dev_->ctx, pendSteps_), "fedd_multistep_begin");
+            msBegan_ = true;
+        }
+        feddCheck(fedd_multistep_advance(dev_->ctx, SLOT_NL_MASS, nmbToUse, coeff.data()), "fedd_multistep_advance");
+        feddCheck(fedd_rhs_get(dev_->ctx, x.data()), "fedd_rhs_get");
+        size_t off = 0;
+        auto rhs = problem_->getRhs();
+        for (UN b = 0; b < rhs->size(); ++b) {
+            auto& r = rhs->getBlockNonConst(b)->raw();
+            std::copy(x.begin() + off, x.begin() + off + r.size(), r.begin());
+            off += r.size();
+        }
+    }
+    // the nonlinear problem's own entries on the time system: NavierStokes::reAssemble adds the advection to slot 6, so its
+    // merged system IS (cm M + ca A + rho (N | N + W), B^T; B, C) and its residual b - S x (one fedd_spmv) already holds the
+    // mass term the reference adds afterwards (:693-738, up to rounding); Dirichlet rows through setBCMinusVector / setVectorMinusBC
+    void assemble(std::string type) const { needNl("assemble"); nl_->assemble(type); }
+    void reAssemble(std::string type) const { needNl("reAssemble"); nl_->reAssemble(type); }
+    void calculateNonLinResidualVec(std::string type = "standard", double time = 0.) {
+        needNl("calculateNonLinResidualVec");
+        combineSystems();
+        nl_->calculateNonLinResidualVec(type, time);
+    }
+    double calculateResidualNorm() const { needNl("calculateResidualNorm"); return nl_->calculateResidualNorm(); }
+    void setBoundariesSystem() const { needNl("setBoundariesSystem"); nl_->setBoundariesSystem(); }
+    void setBoundariesRHS(double time = .0) const { needNl("setBoundariesRHS"); nl_->setBoundariesRHS(time); }
+    int solveUpdate() { needNl("solveUpdate"); return nl_->solveUpdate(); }
+    int solveAndUpdate(const std::string& criterion, double& criterionValue) { needNl("solveAndUpdate"); return nl_->solveAndUpdate(criterion, criterionValue); }
+    bool getVerbose() const { return problem_->getVerbose(); }
+    BlockMultiVectorPtr_Type getRhs() const { return problem_->getRhs(); }
+    ParameterListPtr_Type getParameterList() const { return problem_->getParameterList(); }
     void updateTime(double time) { time_ = time; }
     void assembleSourceTerm(double time) { problem_->assembleSourceTerm(time); }
     bool hasSourceTerm() const { return problem_->hasSourceTerm(); }
@@ -194,7 +312,21 @@ public:
     double getLastRelativeResidual() const { return lastRelativeResidual_; }
     int numberOfCombines() const { return combines_; }
 private:
+    void needNl(const char* who) const {
+        TEUCHOS_TEST_FOR_EXCEPTION(!nl_, std::logic_error, std::string("TimeProblem::") + who + ": the wrapped problem is linear");
+    }
+    std::vector<double> flatSolution() const {
+        std::vector<double> x;
+        auto sol = problem_->getSolution();
+        for (UN b = 0; b < sol->size(); ++b) x.insert(x.end(), sol->getBlock(b)->raw().begin(), sol->getBlock(b)->raw().end());
+        return x;
+    }
     Problem_Type* problem_;
+    NonLinearProblem_Type* nl_ = nullptr;
+    NavierStokes_Type* ns_ = nullptr;
+    bool nlCombined_ = false, msBegan_ = false, pendMs_ = false;
+    double nlCm_ = 0., nlCa_ = 0.;
+    int pendSteps_ = 0;
     CommConstPtr_Type comm_;
     DeviceContextPtr dev_;
     SmallMatrix<int> timeStepDef_;
@@ -204,6 +336,58 @@ private:
     double pendDt_ = 0., pendBeta_ = 0., pendGamma_ = 0., time_ = 0., lastRelativeResidual_ = 0.;
     int combines_ = 0;
 };
+
+// NonLinearSolver::solve(TimeProblem&, time): the TimeProblem overloads of the reference's fixed-point and Newton loops
+// (NonLinearSolver_def.hpp:394-452, 459-531), line by line
+template <class SC, class LO, class GO, class NO>
+void NonLinearSolver<SC, LO, GO, NO>::solve(TimeProblem_Type& problem, double time) {
+    TEUCHOS_TEST_FOR_EXCEPTION(type_ != "FixedPoint" && type_ != "Newton", std::logic_error,
+                               "\"Linearization\" = \"" + type_ + "\" is not built for time problems (FixedPoint and Newton are; Extrapolation and NOX are not)");
+    TEUCHOS_TEST_FOR_EXCEPTION(!problem.isNonLinear(), std::logic_error, "NonLinearSolver: the time problem wraps a linear problem");
+    const bool newton = type_ == "Newton";
+    const bool verbose = problem.getVerbose();
+    problem.setBoundariesRHS(time);
+    TEUCHOS_TEST_FOR_EXCEPTION(problem.getRhs()->getNumVectors() != 1, std::logic_error, "We need to change the code for numVectors>1.");
+    const char* name = newton ? "Newton" : "Fixed Point";
+    double gmresIts = 0., residual0 = 1., residual = 1.;
+    auto& par = problem.getParameterList()->sublist("Parameter");
+    const double tol = par.get("relNonLinTol", 1.0e-6);
+    int nlIts = 0;
+    const int maxNonLinIts = par.get("MaxNonLinIts", 10);
+    double criterionValue = 1.;
+    const std::string criterion = par.get("Criterion", "Residual");
+    while (nlIts < maxNonLinIts) {
+        problem.calculateNonLinResidualVec("reverse", time);
+        if (criterion == "Residual") residual = problem.calculateResidualNorm();
+        if (nlIts == 0) residual0 = residual;
+        if (!newton) {                      // :423-427: the linearised matrix is combined with the mass matrix, then the boundary rows
+            problem.combineSystems();
+            problem.setBoundariesSystem();
+        }
+        if (criterion == "Residual") {
+            criterionValue = residual / residual0;
+            if (verbose) std::cout << "### " << name << " iteration : " << nlIts << "  relative nonlinear residual : " << criterionValue << std::endl;
+            if (criterionValue < tol) break;
+        }
+        if (newton) {                       // :495-498
+            problem.assemble("Newton");
+            problem.setBoundariesSystem();
+        }
+        gmresIts += problem.solveAndUpdate(criterion, criterionValue);
+        nlIts++;
+        if (criterion == "Update") {
+            if (verbose) std::cout << "### " << name << " iteration : " << nlIts << "  residual of update : " << criterionValue << std::endl;
+            if (criterionValue < tol) break;
+        }
+    }
+    gmresIts /= std::max(nlIts, 1);
+    lastNonLinIts = nlIts;
+    if (verbose)
+        std::cout << "### Total " << (newton ? "Newton iteration" : "FPI") << " : " << nlIts << "  with average gmres its : " << gmresIts << std::endl;
+    if (par.get("Cancel MaxNonLinIts", false))
+        TEUCHOS_TEST_FOR_EXCEPTION(nlIts == maxNonLinIts, std::runtime_error,
+                                   "Maximum nonlinear Iterations reached. Problem might have converged in the last step. Still we cancel here.");
+}
 
 template <class SC = default_sc, class LO = default_lo, class GO = default_go, class NO = default_no>
 class DAESolverInTime {
@@ -216,9 +400,8 @@ public:
     DAESolverInTime(ParameterListPtr_Type& parameterList, CommConstPtr_Type comm) : parameterList_(parameterList), comm_(comm) {}
     void defineTimeStepping(const SmallMatrix<int>& def) { timeStepDef_ = def; }
     void setProblem(Problem_Type& problem) {
-        TEUCHOS_TEST_FOR_EXCEPTION((dynamic_cast<NonLinearProblem<SC, LO, GO, NO>*>(&problem) != nullptr), std::logic_error,
-                                   "DAESolverInTime: time stepping of nonlinear problems is not built; the class \"Newmark\" on a linear problem is");
         problem_ = &problem;
+        nonLinear_ = dynamic_cast<NonLinearProblem<SC, LO, GO, NO>*>(&problem) != nullptr;
         problemTime_.reset(new TimeProblem_Type(problem, comm_));
     }
     void setupTimeStepping() {                                          // DAESolverInTime_def.hpp: setupTimeStepping
@@ -232,15 +415,75 @@ public:
     void advanceInTime() {
         TEUCHOS_TEST_FOR_EXCEPTION(timeSteppingTool_.is_null(), std::logic_error, "DAESolverInTime: call setupTimeStepping first");
         checkClass();
-        advanceInTimeLinearNewmark();
+        if (nonLinear_) advanceInTimeNonLinearMultistep();
+        else advanceInTimeLinearNewmark();
     }
+    const std::vector<int>& nonLinearIterations() const { return nlItsPerStep_; }
     Teuchos::RCP<TimeProblem_Type> getTimeProblem() const { return problemTime_; }
     int stepsDone() const { return timeSteppingTool_.is_null() ? 0 : timeSteppingTool_->currentStep(); }
 private:
     void checkClass() const {
-        const std::string cls = parameterList_->sublist("Timestepping Parameter").get("Class", "Newmark");
-        TEUCHOS_TEST_FOR_EXCEPTION(cls != "Newmark", std::logic_error,
-                                   "Timestepping Parameter \"Class\" = \"" + cls + "\" is not built (Singlestep, Multistep and External are not); \"Newmark\" on a linear problem is");
+        // "Newmark" + linear and "Multistep" + nonlinear are built; the reference's default class is "Singlestep"
+        const std::string cls = parameterList_->sublist("Timestepping Parameter").get("Class", nonLinear_ ? "Singlestep" : "Newmark");
+        const bool ok = nonLinear_ ? cls == "Multistep" : cls == "Newmark";
+        TEUCHOS_TEST_FOR_EXCEPTION(!ok, std::logic_error,
+                                   "Timestepping Parameter \"Class\" = \"" + cls + "\" on a " + (nonLinear_ ? "nonlinear" : "linear") +
+                                       " problem is not built (Singlestep and External are not); \"Newmark\" on a linear problem and \"Multistep\" (BDF 1, 2) on a nonlinear problem are");
+        if (nonLinear_) {
+            const std::string lin = parameterList_->sublist("General").get("Linearization", "FixedPoint");
+            TEUCHOS_TEST_FOR_EXCEPTION(lin != "FixedPoint" && lin != "Newton", std::logic_error,
+                                       "\"Linearization\" = \"" + lin + "\" is not built for time problems (FixedPoint and Newton are; Extrapolation and NOX are not)");
+        }
+    }
+    // DAESolverInTime::advanceInTimeNonLinearMultistep (:1209-1333), in the reference's order
+    void advanceInTimeNonLinearMultistep() {
+        const bool print = parameterList_->sublist("General").get("ParaViewExport", false);
+        if (print) exportTimestep();
+        const int size = timeStepDef_.size();
+        const double dt = timeSteppingTool_->get_dt();
+        const int nmbBDF = timeSteppingTool_->getBDFNumber();
+        vec_dbl_Type coeffPrevSteps((size_t)nmbBDF);
+        for (int i = 0; i < nmbBDF; ++i) coeffPrevSteps[(size_t)i] = timeSteppingTool_->getInformationBDF(i + 2) / dt;
+        SmallMatrix<double> massCoeff(size), problemCoeff(size);
+        for (int i = 0; i < size; ++i)
+            for (int j = 0; j < size; ++j) {
+                massCoeff[i][j] = (timeStepDef_[i][j] > 0 && i == j) ? timeSteppingTool_->getInformationBDF(0) / dt : 0.;
+                problemCoeff[i][j] = timeStepDef_[i][j] > 0 ? timeSteppingTool_->getInformationBDF(1) : 1.;
+            }
+        problemTime_->setTimeParameters(massCoeff, problemCoeff);
+        const std::string linearization = parameterList_->sublist("General").get("Linearization", "FixedPoint");
+        while (timeSteppingTool_->continueTimeStepping()) {
+            const bool firstStep = timeSteppingTool_->currentTime() == 0.;
+            if (firstStep) {                                            // BDF1 for the first time step
+                SmallMatrix<double> tmpMassCoeff(size), tmpProblemCoeff(size);
+                for (int i = 0; i < size; ++i)
+                    for (int j = 0; j < size; ++j) {
+                        tmpMassCoeff[i][j] = (timeStepDef_[i][j] > 0 && i == j) ? 1. / dt : 0.;
+                        tmpProblemCoeff[i][j] = 1.;
+                    }
+                problemTime_->setTimeParameters(tmpMassCoeff, tmpProblemCoeff);
+            }
+            problemTime_->updateSolutionMultiPreviousStep(nmbBDF);
+            const double time = timeSteppingTool_->currentTime() + dt;
+            problemTime_->updateTime(time);
+            if (firstStep) {
+                vec_dbl_Type tmpCoeffPrevSteps(1, 1. / dt);
+                problemTime_->updateMultistepRhs(tmpCoeffPrevSteps, 1);
+            } else {
+                problemTime_->updateMultistepRhs(coeffPrevSteps, nmbBDF);
+            }
+            // :1303-1304; the source vector of this facade exists from initializeProblem on, so the question is whether a function fills it
+            TEUCHOS_TEST_FOR_EXCEPTION(problem_->hasRhsFunction(), std::logic_error, "Check sourceterm.");
+            NonLinearSolver<SC, LO, GO, NO> nlSolver(linearization);
+            nlSolver.solve(*problemTime_, time);
+            nlItsPerStep_.push_back(nlSolver.lastNonLinIts);
+            if (firstStep) problemTime_->setTimeParameters(massCoeff, problemCoeff);   // the desired BDF parameters from now on
+            timeSteppingTool_->advanceTime(true);
+            if (print) exportTimestep();
+        }
+        comm_->barrier();
+        if (print && !exporter_.is_null()) exporter_->closeExporter();
+        if (print && !exporterP_.is_null()) exporterP_->closeExporter();
     }
     // DAESolverInTime::advanceInTimeLinearNewmark (:519-607), in the reference's order
     void advanceInTimeLinearNewmark() {
@@ -284,8 +527,16 @@ private:
             exportSolution_ = problem_->getSolution()->getBlock(0);
             const int dofs = problem_->getDofsPerNode(0);
             exporter_->addVariable(exportSolution_, problem_->getVariableName(0), dofs > 1 ? "Vector" : "Scalar", dofs, dom->getMapUnique());
+            if (nonLinear_) {                                           // velocity and pressure per step
+                exporterP_.reset(new Exporter_Type());
+                auto domP = problem_->getDomain(1);
+                exporterP_->setup(problem_->getVariableName(1), domP->getMesh(), problem_->getFEType(1));
+                exportSolutionP_ = problem_->getSolution()->getBlock(1);
+                exporterP_->addVariable(exportSolutionP_, problem_->getVariableName(1), "Scalar", 1, domP->getMapUnique());
+            }
         }
         exporter_->save(timeSteppingTool_->currentTime());
+        if (!exporterP_.is_null()) exporterP_->save(timeSteppingTool_->currentTime());
     }
     ParameterListPtr_Type parameterList_;
     CommConstPtr_Type comm_;
@@ -293,8 +544,10 @@ private:
     Problem_Type* problem_ = nullptr;
     Teuchos::RCP<TimeProblem_Type> problemTime_;
     Teuchos::RCP<TimeSteppingTools> timeSteppingTool_;
-    Teuchos::RCP<Exporter_Type> exporter_;
-    Teuchos::RCP<const MultiVector<SC, LO, GO, NO>> exportSolution_;
+    Teuchos::RCP<Exporter_Type> exporter_, exporterP_;
+    Teuchos::RCP<const MultiVector<SC, LO, GO, NO>> exportSolution_, exportSolutionP_;
+    bool nonLinear_ = false;
+    std::vector<int> nlItsPerStep_;
 };
 
 }  // namespace FEDD

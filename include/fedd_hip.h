@@ -87,7 +87,8 @@ enum fedd_timer {
     FEDD_T_CG_P     = 22, /* ... k_cg_p                                        */
     FEDD_T_NEWMARK  = 23, /* Newmark state update: k_newmark (timestep.hip)             */
     FEDD_T_BLOCK_APPLY = 24, /* y = alpha M x on a stored block: k_block_apply          */
-    FEDD_T_COUNT    = 25
+    FEDD_T_MULTISTEP = 25, /* BDF history update: k_multistep (timestep.hip)              */
+    FEDD_T_COUNT    = 26
 };
 
 /* ------------------------------------------------------------------------------------------------
@@ -300,8 +301,9 @@ int fedd_dirichlet_rows(fedd_ctx* ctx, int64_t n, const int32_t* rows, const dou
 
 /* ------------------------------------------------------------------------------------------------
  * mixed / block problems (one rank for now).  Blocks live in numbered slots beside the system matrix.
- *   fedd_matrix_store     copy the system matrix into `slot` (0..4; Stokes uses 0..3 = A, B, B^T, C, Navier-Stokes adds 4 = the
- *                         linearised velocity block of fedd_assemble_advection)
+ *   fedd_matrix_store     copy the system matrix into `slot` (0..6; Stokes uses 0..3 = A, B, B^T, C, Navier-Stokes adds 4 = the
+ *                         linearised velocity block of fedd_assemble_advection, its time loop 5 = the velocity mass matrix and
+ *                         6 = the time-combined constant velocity block (cm * M) + (ca * A), "BDF time stepping" below)
  *   fedd_matrix_scale     Matrix::scale (Stokes_def.hpp:83-85,102); slot < 0 = system matrix
  *   fedd_assemble_div     FE::assemblyDivAndDivT (FE_def.hpp:1932-2057): velocity = the mesh's element,
  *                         pressure = P1 on the vertices = the first n_pressure_nodes node ids; B -> slot_b
@@ -389,6 +391,56 @@ int fedd_newmark_advance(fedd_ctx* ctx, int slot_m, double dt, double beta, doub
 int fedd_rhs_axpy(fedd_ctx* ctx, double alpha, const double* f_owned);
 int fedd_solution_set(fedd_ctx* ctx, const double* x_owned);
 int fedd_dirichlet_rhs(fedd_ctx* ctx, int n_bc, const int32_t* flags, const int32_t* comp_mask, const double* values);
+
+/* ------------------------------------------------------------------------------------------------
+ * BDF time stepping for nonlinear block problems (unsteady Navier-Stokes), one rank: the vector part of the reference's
+ * "Class" = "Multistep" loop, DAESolverInTime::advanceInTimeNonLinearMultistep (DAESolverInTime_def.hpp:1209-1333) with the
+ * BDF tables of TimeSteppingTools.cpp:493-515.  Error conventions as for Newmark: "needs a GPU context" on a host-only context,
+ * an error that says so on more than one rank.  No multiplication is fused with an addition.
+ *
+ * The matrices need no entry of their own: the velocity mass matrix is stored in slot 5, the constant velocity block
+ * A' = (cm * M) + (ca * A) is a fedd_matrix_combine of slots 5 and 0 followed by a fedd_matrix_store into slot 6 (both DIAG, so
+ * only values move), once per coefficient set, i.e. twice in a BDF2 run (BDF1 for the first step, BDF2 afterwards).  Every
+ * nonlinear iteration then calls fedd_assemble_advection(kind, rho, slot_add = 6, slot_out = 4) and the values-only
+ * fedd_block_merge of slots 4, 2, 1, C.
+ *
+ *   n   = the length of the current system (the merged one: velocity dofs, then pressure dofs)
+ *   n_m = the rows of M[slot_m], the velocity block; n_m <= n
+ *   u   = the device's current solution vector; the caller sets it with fedd_solution_set, because fedd_block_merge resets it
+ *
+ *   fedd_multistep_begin    allocates `order` (1 or 2) history vectors u_0, u_1 of length n, zeroed, and sets count = 0.  Does
+ *                           not read the solution.  The vectors are buffers of their own: they survive fedd_block_merge,
+ *                           fedd_assemble_advection, fedd_matrix_combine and fedd_dirichlet*; the next fedd_mesh_set* releases
+ *                           them.
+ *   fedd_multistep_advance  TimeProblem::updateSolutionMultiPreviousStep (TimeProblem_def.hpp:833-849: the first call fills [0],
+ *                           the second grows the list, later calls shift) followed by updateMultistepRhs (:417-438).
+ *                           coeff[0 .. n_use) are the caller's coefficients, already divided by dt.  ONE streaming kernel does on
+ *                           every row of the system, each product and each sum rounded on its own, in this order (NORMATIVE):
+ *                               old0 = u_0                                   (only if count >= 1)
+ *                               u_1 <- old0                                  (only if order == 2 and count >= 1)
+ *                               u_0 <- u
+ *                               t   = coeff[0] * u                           (n_use == 1)
+ *                               t   = (coeff[0] * u) + (coeff[1] * old0)     (n_use == 2)
+ *                           and after it
+ *                               count = min(count + 1, order)
+ *                               rhs[0 .. n_m) <- M[slot_m] t                 (the kernel of fedd_matrix_apply, alpha = 1.0)
+ *                               rhs[n_m .. n) <- 0.0                         (updateMultistepRhs zeroes the right-hand side and
+ *                                                                             adds mass terms only where massParameters_ != 0)
+ *                           A full BDF2 step reads u, u_0 and writes u_0, u_1, t: 40 bytes per row; a first step 24.
+ *                           The reference forms sum_i coeff_i * (M u_i) with one apply per history vector; here M is applied ONCE
+ *                           to the combination -- a deliberate difference at rounding level.
+ *                           Errors: no history (fedd_multistep_begin first), n_use < 1 or n_use > min(count + 1, order), an empty
+ *                           slot, a slot of an earlier mesh, a slot with more rows than the system, a system whose length has
+ *                           changed since fedd_multistep_begin.
+ *   fedd_multistep_set/get  history vector k = 0 .. order - 1, host pointer of length n (tests, restarts).  A vector that was set
+ *                           counts as a state after some step: count = max(count, k + 1).
+ *   fedd_multistep_info     order (0: no history) and count.  Needs no device.
+ * ---------------------------------------------------------------------------------------------- */
+int fedd_multistep_begin(fedd_ctx* ctx, int order);
+int fedd_multistep_advance(fedd_ctx* ctx, int slot_m, int n_use, const double* coeff);
+int fedd_multistep_set(fedd_ctx* ctx, int k, const double* u_k);
+int fedd_multistep_get(fedd_ctx* ctx, int k, double* u_k);
+int fedd_multistep_info(fedd_ctx* ctx, int* order, int* count);
 
 /* ------------------------------------------------------------------------------------------------
  * steady Navier-Stokes (one rank, like the block system it feeds): the matrices NavierStokes::reAssemble builds in every
