@@ -113,6 +113,8 @@ SIGNATURES = {
     "fedd_schwarz_apply_device": [C.c_void_p, C.c_int],
     "fedd_schwarz_info": [C.c_void_p, _i64p, _i64p, _i64p],
     "fedd_schwarz_reuse_info": [C.c_void_p, _ip, _i64p],
+    "fedd_pattern_reuse_info": [C.c_void_p, _ip, _i64p],
+    "fedd_spmv_reuse_info": [C.c_void_p, _ip, _i64p],
     "fedd_schwarz_unique": [C.c_void_p, _i64p],
     "fedd_schwarz_sizes": [C.c_void_p, _i64p, _i64p],
     "fedd_schwarz_conforming": [C.c_void_p, _i64p],
@@ -734,6 +736,18 @@ class Context:
         """whether the last schwarz_setup kept the box structure of the one before, and how many setups of this context have"""
         a, n = C.c_int(), C.c_int64()
         _chk(self._L.fedd_schwarz_reuse_info(self._h, C.byref(a), C.byref(n)))
+        return {"last_reused": bool(a.value), "n_reused": n.value}
+
+    def pattern_reuse_info(self):
+        """whether the last pattern_build kept the pattern arrays of the one before, and how many builds of this context have"""
+        a, n = C.c_int(), C.c_int64()
+        _chk(self._L.fedd_pattern_reuse_info(self._h, C.byref(a), C.byref(n)))
+        return {"last_reused": bool(a.value), "n_reused": n.value}
+
+    def spmv_reuse_info(self):
+        """whether the solver's SpMV stream in use was kept from the matrix before (verified, not built), and how often it was"""
+        a, n = C.c_int(), C.c_int64()
+        _chk(self._L.fedd_spmv_reuse_info(self._h, C.byref(a), C.byref(n)))
         return {"last_reused": bool(a.value), "n_reused": n.value}
 
     def schwarz_apply(self, r):

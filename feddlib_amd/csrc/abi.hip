@@ -814,6 +814,20 @@ extern "C" int fedd_schwarz_reuse_info(fedd_ctx* c, int* last_reused, int64_t* n
     return 0;
 }
 
+extern "C" int fedd_pattern_reuse_info(fedd_ctx* c, int* last_reused, int64_t* n_reused) {
+    FEDD_CHECK(c, "fedd_pattern_reuse_info: null context");
+    if (last_reused) *last_reused = c->have_pattern ? c->pat_last_reused : 0;
+    if (n_reused) *n_reused = c->pat_reuse_count;
+    return 0;
+}
+
+extern "C" int fedd_spmv_reuse_info(fedd_ctx* c, int* last_reused, int64_t* n_reused) {
+    FEDD_CHECK(c, "fedd_spmv_reuse_info: null context");
+    if (last_reused) *last_reused = c->cs_valid ? c->cs_last_reused : 0;
+    if (n_reused) *n_reused = c->cs_reuse_count;
+    return 0;
+}
+
 extern "C" int fedd_schwarz_apply(fedd_ctx* c, const double* r_owned, double* z_owned) {
     NEED_DEVICE(c);
     FEDD_CHECK(c->have_schwarz && r_owned && z_owned, "fedd_schwarz_apply: no preconditioner / null pointer");
@@ -986,15 +1000,15 @@ extern "C" int fedd_set_option(fedd_ctx* c, const char* key, double value) {
     else if (k == "spmv_drop_tol") {
         FEDD_CHECK(value >= 0.0 && value < 1.0, "fedd_set_option: spmv_drop_tol %g", value);
         c->spmv_drop_tol = value;
-        c->cs_valid = false;
+        c->cs_valid = c->cs_key.valid = false;
     } else if (k == "spmv_compact") {
         c->spmv_compact = (int)value;
-        c->cs_valid = false;
+        c->cs_valid = c->cs_key.valid = false;
     }
     else if (k == "spmv_exact_public") c->spmv_exact_public = (int)value;
-    else if (k == "spmv_classes") { c->spmv_classes = (int)value; c->cs_valid = false; }
+    else if (k == "spmv_classes") { c->spmv_classes = (int)value; c->cs_valid = c->cs_key.valid = false; }
     else if (k == "spmv_keep_dictionary") c->spmv_keep_dict = (int)value;
-    else if (k == "spmv_classes_cover") { c->spmv_cls_cover = (int)value; c->cs_valid = false; }
+    else if (k == "spmv_classes_cover") { c->spmv_cls_cover = (int)value; c->cs_valid = c->cs_key.valid = false; }
     else if (k == "asm_tiles_host") {
         FEDD_CHECK(value == 0 || value == 1, "fedd_set_option: asm_tiles_host %g (0 or 1)", value);
         c->asm_tiles_host = (int)value;
@@ -1024,13 +1038,13 @@ extern "C" int fedd_set_option(fedd_ctx* c, const char* key, double value) {
     else if (k == "gdsw_rotations") c->gdsw_rot = value != 0.0;
     else if (k == "gmres_fuse") c->gmres_fuse = (int)value;
     else if (k == "multi_ch") c->multi_ch = (int)value;
-    else if (k == "spmv_col16") { c->spmv_col16 = value != 0.0; c->cs_valid = false; }
+    else if (k == "spmv_col16") { c->spmv_col16 = value != 0.0; c->cs_valid = c->cs_key.valid = false; }
     else if (k == "pat_hash") { c->pat_hash = value != 0.0; c->pat_repeatable = false; }
     else if (k == "md2_gy") c->md2_gy = (int)value;
     else if (k == "gmres_hostwrite") c->h_pinned_dev = value != 0 ? c->h_pinned_map : nullptr;
-    else if (k == "spmv_pattern") { c->spmv_pattern = (int)value; c->cs_valid = false; }
-    else if (k == "spmv_pat_nu") { c->spmv_pat_nu = (int)value; c->cs_valid = false; }
-    else if (k == "spmv_win_nu") { c->spmv_win_nu = (int)value; c->cs_valid = false; }
+    else if (k == "spmv_pattern") { c->spmv_pattern = (int)value; c->cs_valid = c->cs_key.valid = false; }
+    else if (k == "spmv_pat_nu") { c->spmv_pat_nu = (int)value; c->cs_valid = c->cs_key.valid = false; }
+    else if (k == "spmv_win_nu") { c->spmv_win_nu = (int)value; c->cs_valid = c->cs_key.valid = false; }
     else if (k == "halo_overlap") { c->halo_overlap = (int)value; c->have_schwarz = false; }
     else if (k == "schwarz_big") c->sw_big = (int)value;
     else if (k == "schwarz_big_target") c->sw_big_target = (int)value;
@@ -1071,6 +1085,8 @@ extern "C" int fedd_set_option(fedd_ctx* c, const char* key, double value) {
     }
     else if (k == "ghost_overlap") c->ghost_overlap = (int)value;
     else if (k == "schwarz_reuse") c->sw_reuse = value != 0.0;
+    else if (k == "pattern_reuse") c->pat_reuse = value != 0.0;
+    else if (k == "spmv_reuse") c->spmv_reuse = value != 0.0;
     else FEDD_CHECK(false, "fedd_set_option: unknown key '%s'", key);
     return 0;
 }

@@ -242,6 +242,18 @@ struct fedd_ctx {
     int32_t cs_pat_tab_n = -1, cs_pat_tab_npat = 0, cs_pat_tab_nexpl = 0, cs_pat_tab_len = 0;   // the column-pattern dictionary on the device: rows, patterns, explicit rows, longest pattern of the build it comes from (kept while the next matrix still matches it)
     int spmv_cls_cover = 90;                    // option "spmv_classes_cover": the classes are used when they cover at least this percentage of the rows
     int spmv_keep_dict = 0;                     // option "spmv_keep_dictionary": 1 = the previous matrix' pattern dictionary and row classes are kept while the new stream matches them bit for bit (one verifying pass instead of the build: time loops that reassemble the same operator); 0 (default) = built per matrix
+    // the stream, its dictionary, classes and row lists are kept from matrix to matrix while this key stands (option "spmv_reuse";
+    // spmv.hip spmv_reuse_try): written by a build, dropped by every option setter that invalidates the stream
+    struct CsKey {
+        bool valid = false;
+        uint64_t pattern_gen = 0;
+        int64_t n = 0, n_cols = 0, nnz = 0;
+        double drop_tol = 0.0;
+        bool cls_tried = false;                 // the build ran the class stage: its outcome follows the VALUES, so the keep must find them unchanged
+    } cs_key;
+    int spmv_reuse = 1;                         // option "spmv_reuse"
+    int cs_last_reused = 0;                     // the stream in use was kept, not built
+    int64_t cs_reuse_count = 0;
     int32_t cs_nbnd = -1;                       // rows of the compacted stream that read ghost columns (-1: not listed)
     fedd::DevBuf<int32_t> d_cs_bnd;             // flags / positions [n + 2] | the rows
     int cs_cls_len = 8;                         // stride of the class table (8, 16 or 48 values)
@@ -307,6 +319,9 @@ struct fedd_ctx {
                                                 // the one the pattern came from (same mesh_gen, dofs per node, block mode)
     bool pat_repeatable = false;                // the system pattern is the output of build_pattern on pat_mesh_gen (and nothing wrote it since)
     uint64_t pat_mesh_gen = 0;
+    int pat_reuse = 1;                          // option "pattern_reuse": a build_pattern that repeats keeps d_rowptr / d_colind (0: writes them again)
+    int pat_last_reused = 0;                    // the last build_pattern kept them
+    int64_t pat_reuse_count = 0;                // builds that kept them since the context was made
     struct SwStructKey {
         uint64_t mesh_gen = 0, pattern_gen = 0;
         int64_t n_own = 0, n_rows = 0, n_rows_ext = 0, merged_nA = 0;
@@ -442,7 +457,7 @@ struct fedd_ctx {
     fedd::DevBuf<int64_t> d_scan[3];            // block sums of the device scan, one per level
     fedd::DevBuf<int32_t> d_rs_hist;            // radix sort: digit histograms [256][tiles]
     fedd::DevBuf<double> d_dtmp0;
-    fedd::DevBuf<int32_t> d_flags;              // [16] device flags: 0 max scratch, 1 bad pivot, 2 DGKS gate, 3-5 coarse setup, 8-11 Schwarz setup counters, 12 s-step block length
+    fedd::DevBuf<int32_t> d_flags;              // [16] device flags: 0 max scratch, 1 bad pivot, 2 DGKS gate, 3-5 coarse setup, 8-11 Schwarz setup counters, 12 s-step block length, 13 SpMV stream keep
 
     fedd::HaloPlan halo;
 

@@ -526,7 +526,7 @@ __global__ __launch_bounds__(256) void k_pat_table(const unsigned long long* __r
 // wrong product); n_expl counts the rows that keep explicit columns
 __global__ void k_pat_rows(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, int32_t n,
                            const int32_t* __restrict__ slot_of, const int32_t* __restrict__ pat_of_slot,
-                           const int32_t* __restrict__ plen, const int32_t* __restrict__ pdelta, uint16_t* __restrict__ pat,
+                           const int32_t* __restrict__ plen, const int32_t* __restrict__ pdelta, uint16_t* pat,
                            int32_t* __restrict__ n_expl, const uint16_t* prev, int32_t n_prev_pat) {
     // 8 lanes per row (consecutive lanes read consecutive column ids)
     // prev != nullptr (may be pat itself): the candidate of a row is its id of the PREVIOUS matrix' dictionary (slot_of /
@@ -848,6 +848,92 @@ __global__ __launch_bounds__(256) void k_cls_verify(const int32_t* __restrict__ 
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The stream of the matrix before, kept (option "spmv_reuse").  A driver that assembles again on the same graph -- the bench, a
+// Newton step, a time step -- would have spmv_compact_build read the assembled matrix twice, write the stream and read that
+// several times more for a dictionary, classes and row lists that come out as they are.  This kernel walks the ASSEMBLED rows
+// once instead, eight lanes per row (consecutive lanes, consecutive entries), applies the drop rule of cs_window_flags and
+// checks what a build would put into the stream against what the stream holds: the number of kept entries of the row against
+// its stream row, every kept column against the row's pattern offsets (pat != nullptr and the row has a pattern) or against
+// the stream's column, and
+//   REFRESH = false   every kept value, bit for bit, against the row's class entry (cls != nullptr and the row has a class: the
+//                     table is L2 resident) or against the stream's value.  Nothing is written: when no row differs the
+//                     stream IS the one a build would write, and so is everything built from it.
+//   REFRESH = true    the kept values are written to their places in the stream (same graph, new numbers).  For streams whose
+//                     build ran no class stage: everything else it decides follows the columns alone.
+// Any difference ends up in *n_bad, and the caller builds (a half-refreshed stream is overwritten by k_cs_fill).  A row's loads
+// fly together and the differences are OR-ed, no short-circuit (see k_cls_rows); the second round of loads -- what to compare
+// with -- needs the positions, i.e. the row's threshold, i.e. its values.
+// ------------------------------------------------------------------------------------------------
+template <bool REFRESH>
+__global__ __launch_bounds__(256) void k_cs_reuse(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                  const double* __restrict__ val, int32_t n, double tol,
+                                                  const int32_t* __restrict__ cs_rowptr, const int32_t* __restrict__ cs_col,
+                                                  double* cs_val, const uint16_t* __restrict__ pat,
+                                                  const int32_t* __restrict__ pdelta, const uint32_t* __restrict__ cls,
+                                                  const double* __restrict__ cls_val, int cl, int32_t* __restrict__ n_bad) {
+    constexpr int NV = 4;                   // chunks of eight entries held in registers; longer rows read their tail twice
+    const int e = threadIdx.x & 7;
+    const int gsh = threadIdx.x & 56;       // first lane of the row's group in its wave
+    uint32_t bad = 0;
+    for (int64_t r64 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 3; r64 < n; r64 += ((int64_t)gridDim.x * blockDim.x) >> 3) {
+        const int32_t r = (int32_t)r64;
+        const int32_t b = rowptr[r], len = rowptr[r + 1] - b;
+        const int32_t cb = cs_rowptr[r], clen = cs_rowptr[r + 1] - cb;
+        const uint16_t pid = pat ? pat[r] : SPAT_EXPL;
+        const uint32_t w = cls ? cls[r] : CLS_NONE;
+        double v[NV];
+        int32_t cc[NV];
+#pragma unroll
+        for (int u = 0; u < NV; ++u) {
+            const int32_t j = e + 8 * u;
+            v[u] = j < len ? __builtin_nontemporal_load(val + b + j) : 0.0;
+            cc[u] = j < len ? __builtin_nontemporal_load(colind + b + j) : 0;
+        }
+        double mx = 0.0;                    // (the maximum does not depend on the order; fmax passes a NaN by, as there)
+#pragma unroll
+        for (int u = 0; u < NV; ++u) mx = fmax(mx, fabs(v[u]));
+        for (int32_t j = e + 8 * NV; j < len; j += 8) mx = fmax(mx, fabs(val[b + j]));
+        for (int off = 4; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off, 8));
+        const double thr = tol * mx;
+        const bool dict = pid != SPAT_EXPL, classed = w != CLS_NONE;
+        // (a row with a pattern has at most SPAT_L stream entries and one with a class at most cl: its build verified that)
+        const int32_t lim = min(clen, min(dict ? SPAT_L : clen, classed ? cl : clen));
+        const int32_t* __restrict__ dl = pdelta + (dict ? (int)pid : 0) * SPAT_L;
+        const double* tv = classed ? cls_val + (size_t)(w >> 8) * cl : cs_val + cb;
+        int32_t base = 0;                   // kept entries of the row before this chunk
+        auto chunk = [&](int32_t j, double vj, int32_t cj) {
+            const bool keep = j < len && !(fabs(vj) <= thr);
+            const uint32_t m8 = (uint32_t)(__ballot(keep) >> gsh) & 0xffu;
+            const int32_t pos = base + __popc(m8 & ((1u << e) - 1u));
+            base += __popc(m8);
+            if (keep) {
+                const bool in = pos < lim;
+                const int32_t q = in ? pos : 0;
+                const int32_t want = dict ? r + dl[q] : cs_col[cb + q];
+                bad |= (uint32_t)(want ^ cj) | (in ? 0u : 1u);
+                if (REFRESH) {
+                    if (in) cs_val[cb + pos] = vj;
+                } else {
+                    const long long d = __double_as_longlong(vj) ^ __double_as_longlong(tv[q]);
+                    bad |= (uint32_t)d | (uint32_t)(d >> 32);
+                }
+            }
+        };
+#pragma unroll
+        for (int u = 0; u < NV; ++u) chunk(e + 8 * u, v[u], cc[u]);
+        for (int32_t j0 = 8 * NV; j0 < len; j0 += 8) {      // (uniform over the row's lanes)
+            const int32_t j = j0 + e;
+            const double vj = j < len ? val[b + j] : 0.0;
+            const int32_t cj = j < len ? colind[b + j] : 0;
+            chunk(j, vj, cj);
+        }
+        bad |= base != clen ? 1u : 0u;
+    }
+    const uint64_t any = __ballot(bad != 0u);
+    if (any && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(any)) atomicOr(n_bad, 1);
+}
+
 // SpMV over row classes: a lane per row, RPT rows per lane 256 apart; a classed row reads its 4-byte (class, pattern) word, the
 // column pattern (LDS) and the class's values (table), and x at row + offset (consecutive lanes = consecutive rows: coalesced); the other
 // rows take their entries from the compacted stream.  Products and sums separate and in entry order: the bits of k_spmv_pat
@@ -1006,8 +1092,53 @@ static int spmv_window_rows(fedd_ctx* c) {
     return 0;
 }
 
+// The matrix changed, its graph and the options did not (cs_key): one pass over the assembled rows instead of the build, see
+// k_cs_reuse.  *kept = false: some row differs (or there is nothing to keep), the caller builds.
+static int spmv_reuse_try(fedd_ctx* c, bool* kept) {
+    *kept = false;
+    const fedd_ctx::CsKey& k = c->cs_key;
+    if (!c->spmv_reuse || !k.valid) return 0;
+    if (k.pattern_gen != c->pattern_gen || k.n != c->n_rows || k.n_cols != c->n_cols || k.nnz != c->nnz || k.drop_tol != c->spmv_drop_tol)
+        return 0;
+    const int32_t n = (int32_t)c->n_rows;
+    const bool dict = c->cs_npat > 0, classes = dict && c->cs_ncls > 0;
+    const int32_t* pdelta = dict ? c->d_cs_pati.p + n + 2 * SPAT_TS + SPAT_P : nullptr;
+    ScopedTimer ts(c, FEDD_T_SPMV_SETUP);
+    FEDD_TRY(c->d_flags.ensure(16));
+    int32_t* flag = c->d_flags.p + 13;
+    FEDD_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), c->stream));
+    const dim3 grid((unsigned)std::min<int64_t>(((int64_t)n * 8 + 255) / 256, 8192)), blk(256);
+#define CS_REUSE(REFRESH_)                                                                                                            \
+    hipLaunchKernelGGL(k_cs_reuse<REFRESH_>, grid, blk, 0, c->stream, (const int32_t*)c->d_rowptr.p, (const int32_t*)c->d_colind.p,    \
+                       (const double*)c->d_val.p, n, c->spmv_drop_tol, (const int32_t*)c->d_cs_rowptr.p, (const int32_t*)c->d_cs_col.p, \
+                       c->d_cs_val.p, dict ? (const uint16_t*)c->d_cs_pat.p : (const uint16_t*)nullptr, pdelta,                        \
+                       classes ? (const uint32_t*)c->d_cs_cls.p : (const uint32_t*)nullptr,                                            \
+                       classes ? (const double*)c->d_cs_clsval.p : (const double*)nullptr, c->cs_cls_len, flag)
+    // (a build that ran the class stage decided by the values: they have to be the same; else they are written)
+    if (k.cls_tried) CS_REUSE(false);
+    else CS_REUSE(true);
+#undef CS_REUSE
+    int32_t h_bad = 0;
+    FEDD_HIP(hipMemcpyAsync(&h_bad, flag, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    FEDD_HIP(hipStreamSynchronize(c->stream));
+    ts.stop();
+    FEDD_HIP(hipGetLastError());
+    if (h_bad) return 0;
+    c->cs_valid = true;
+    c->cs_last_reused = 1;
+    ++c->cs_reuse_count;
+    *kept = true;
+    return 0;
+}
+
 // (re)build the compacted stream after the matrix changed; part of the solver's first SpMV
 static int spmv_compact_build(fedd_ctx* c) {
+    bool kept = false;
+    FEDD_TRY(spmv_reuse_try(c, &kept));
+    if (kept) return 0;
+    c->cs_key.valid = false;
+    c->cs_last_reused = 0;
+    bool cls_tried = false;
     const int32_t n = (int32_t)c->n_rows;
     const int32_t nb = (int32_t)(c->nnz / SP_CHUNK + 1);
     FEDD_TRY(spmv_window_rows(c));
@@ -1116,6 +1247,7 @@ static int spmv_compact_build(fedd_ctx* c) {
         c->cs_ncls = 0;
         c->cs_cls_rows = 0;
         if (c->cs_npat > 0 && c->spmv_classes) {
+            cls_tried = true;
             FEDD_TRY(c->d_cs_cls.ensure((size_t)n + 1));
             const int cl = c->cs_pat_len <= 8 ? 8 : (c->cs_pat_len <= 16 ? 16 : SPAT_L);       // table stride
             c->cs_cls_len = cl;
@@ -1207,6 +1339,14 @@ static int spmv_compact_build(fedd_ctx* c) {
     ts.stop();
     FEDD_HIP(hipGetLastError());
     c->cs_valid = true;
+    // what the next matrix has to share with this one for the stream to be kept (spmv_reuse_try)
+    c->cs_key.pattern_gen = c->pattern_gen;
+    c->cs_key.n = c->n_rows;
+    c->cs_key.n_cols = c->n_cols;
+    c->cs_key.nnz = c->nnz;
+    c->cs_key.drop_tol = c->spmv_drop_tol;
+    c->cs_key.cls_tried = cls_tried;
+    c->cs_key.valid = true;
     return 0;
 }
 

@@ -341,6 +341,24 @@ int expand_node_pattern(fedd_ctx* c, const int32_t* nptr, const int32_t* ncol, i
 
 int build_pattern(fedd_ctx* c, int dofs, int block_mode) {
     c->cs_valid = false;   // the solver's compacted SpMV stream follows the matrix values
+    // The same build on the same mesh writes the same pattern (every writer of d_rowptr / d_colind clears pat_repeatable): the
+    // pattern generation stands (schwarz.hip keeps the box structure of a pattern it has seen, spmv.hip its stream), and with
+    // option "pattern_reuse" the arrays stand too -- every kernel, reduction, scan and copy below would rewrite them with the
+    // integers they hold.  What is left of the call is what it promises beside the pattern: zeroed values and vectors.
+    const bool repeat = c->pat_repeatable && c->have_pattern && !c->merged && c->pat_mesh_gen == c->mesh_gen && c->dofs == dofs &&
+                        c->block_mode == block_mode;
+    c->pat_last_reused = 0;
+    if (repeat && c->pat_reuse) {
+        FEDD_HIP(hipMemsetAsync(c->d_val.p, 0, (size_t)c->nnz_ext * sizeof(double), c->stream));
+        FEDD_HIP(hipMemsetAsync(c->d_rhs.p, 0, (size_t)c->n_rows_ext * sizeof(double), c->stream));
+        FEDD_HIP(hipMemsetAsync(c->d_x.p, 0, (size_t)c->n_rows * sizeof(double), c->stream));
+        FEDD_HIP(hipMemsetAsync(c->d_xcol.p, 0, (size_t)c->n_cols * sizeof(double), c->stream));
+        FEDD_HIP(hipMemsetAsync(c->d_isdir.p, 0, (size_t)c->n_rows_ext * sizeof(int32_t), c->stream));
+        c->have_schwarz = false;
+        c->pat_last_reused = 1;
+        ++c->pat_reuse_count;
+        return 0;
+    }
     const int32_t n_own = (int32_t)(c->n_own + c->n_rowg);   // every node that gets rows (owned, then row ghosts)
     const int nen = c->nen;
     // upper bound for the distinct columns of one node row
@@ -390,10 +408,6 @@ int build_pattern(fedd_ctx* c, int dofs, int block_mode) {
     const int64_t mult = scalar ? 1 : (block_mode == FEDD_BLOCK_FULL ? (int64_t)dofs * dofs : dofs);
     const int64_t nnz = node_nnz * mult;
     FEDD_CHECK(nnz < ((int64_t)1 << 31), "pattern build: %lld nonzeros exceed 32-bit local offsets", (long long)nnz);
-    // the same build on the same mesh writes the same pattern: only then the pattern generation stands (schwarz.hip keeps the
-    // box structure of a pattern it has seen)
-    const bool repeat = c->pat_repeatable && c->have_pattern && !c->merged && c->pat_mesh_gen == c->mesh_gen && c->dofs == dofs &&
-                        c->block_mode == block_mode;
     c->pat_repeatable = false;
     if (!repeat) ++c->pattern_gen;
     c->dofs = dofs;

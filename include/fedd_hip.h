@@ -249,6 +249,13 @@ int fedd_mesh_set_rows(fedd_ctx* ctx, int dim, int nen, int64_t n_elem, const in
 /* symbolic CSR on the owned (unique-map) rows: what Tpetra's dynamic insert + fillComplete
  * discover (feddlib/core/LinearAlgebra/Matrix_def.hpp:88-92,192-199). */
 int fedd_pattern_build(fedd_ctx* ctx, int dofs_per_node, int block_mode, int64_t* nnz_out);
+/* A fedd_pattern_build that repeats the one the system pattern came from -- same mesh, dofs per node, block mode and "pat_hash",
+ * and nothing wrote the pattern since (fedd_block_merge, fedd_assemble_div, a fedd_matrix_combine that brings another pattern,
+ * fedd_mesh_set*) -- keeps the arrays on the device and does only what the call promises beside them: values, right-hand side,
+ * solution and Dirichlet marks zeroed, solver setups dropped, nnz returned.  Option "pattern_reuse" = 0 builds every time (the
+ * same integers; the A/B switch).  last_reused: 1 if the last build kept the pattern; n_reused: builds that kept it since the
+ * context was made.  Needs no device; outputs may be NULL. */
+int fedd_pattern_reuse_info(fedd_ctx* ctx, int* last_reused, int64_t* n_reused);
 
 /* numeric assembly into the pattern; FE::assemblyXxx + fillComplete (file:line per form above). */
 int fedd_assemble(fedd_ctx* ctx, int form, const double* params);
@@ -699,6 +706,9 @@ int fedd_gmres_fused_blocks(fedd_ctx* ctx, int* blocks);
  * "schwarz_reuse" 1 (default) = fedd_schwarz_setup keeps the box lattice, the bins and the overlapping dof lists of the setup
  * before while mesh, pattern and parameters stand (see fedd_schwarz_reuse_info), 0 = they are built by every setup (the same
  * preconditioner bit for bit; the A/B switch).  With several ranks a rank that has it off makes every rank build;
+ * "pattern_reuse" 1 (default) = a fedd_pattern_build that repeats the last one keeps the pattern arrays (see
+ * fedd_pattern_reuse_info), 0 = every call builds them; "spmv_reuse" 1 (default) = the solver's SpMV stream is verified
+ * against the reassembled matrix in one pass and kept (see fedd_spmv_reuse_info), 0 = built for every matrix;
  * "schwarz_fp_kind" 0 (default) = the fingerprints of that sharing are built from one hash per matrix ROW (column offsets and
  * quantised values of all its entries) and the rows' positions in the subdomain, 1 = entry by entry over the entries inside the
  * subdomain (the round-2 form; finds the same classes on the structured grids, four times slower);
@@ -750,6 +760,13 @@ int fedd_spmv_patterns(fedd_ctx* ctx, int64_t* n_patterns, int64_t* n_rows_expli
  * verifying pass instead of the build -- for drivers that reassemble the same operator); default 0: built for every matrix.
  * Option "spmv_classes_cover" (default 90): the percentage of the rows the classes must cover to be used. */
 int fedd_spmv_classes(fedd_ctx* ctx, int64_t* n_classes, int64_t* n_rows_in_classes, int64_t* nnz_streamed_rest);
+/* The solver's stream is kept from one matrix to the next while the pattern, the sizes and the SpMV options stand (option
+ * "spmv_reuse", default 1): the first SpMV after the matrix changed walks the ASSEMBLED rows once, applies the drop rule and
+ * checks every kept entry against what the stream already holds -- count and columns always; with row classes in use also
+ * the values, bit for bit (nothing is written: the stream is the one a build would produce); without classes the values are
+ * written to their places (same graph, new numbers: Newton steps, time loops).  Any mismatch runs the full build.
+ * last_reused: 1 if the stream in use was kept; n_reused: keeps since the context was made.  Outputs may be NULL. */
+int fedd_spmv_reuse_info(fedd_ctx* ctx, int* last_reused, int64_t* n_reused);
 /* bytes per column index of the solver's SpMV stream: 0 = column patterns in use (above), 2 = 16-bit offsets from a base per
  * window of the stream (option "spmv_col16", default 1; 10 instead of 12 bytes per entry) in every window whose columns span less
  * than 65536 -- any mesh numbered with some locality; entries_with_32bit_columns (nullable) = the entries of the windows that
