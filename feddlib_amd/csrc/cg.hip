@@ -178,6 +178,7 @@ const char* breakdown_name(int w) {
     case FEDD_CG_BREAKDOWN_PQ: return "p.Ap <= 0";
     case FEDD_CG_BREAKDOWN_RHO: return "r.z <= 0";
     case FEDD_CG_BREAKDOWN_NONFINITE: return "non-finite value";
+    case FEDD_CG_BREAKDOWN_NONSYMMETRIC: return "operator not symmetric";
     default: return "none";
     }
 }
@@ -279,6 +280,31 @@ int cg_solve(fedd_ctx* c, const CgCall& call, int* its_out, double* relres_out) 
     }
     hipLaunchKernelGGL(k_cg_set, dim3(1), dim3(1), 0, st, S, (int)S_TOL2, tol * tol);
     FEDD_TRY(restart_direction());
+    // The recurrences hold for A = A^T on the free rows only; on another matrix they neither break down nor converge (the
+    // residual grows for as long as the budget lasts), so the first direction probes it, once per solve: with q = A p,
+    // q.q = p.A^T A p and p.(A q) = p.A A p agree for a symmetric matrix (p, and with it q, vanishes on the unit Dirichlet
+    // rows).  Rounding and the last bits in which a_ij and a_ji differ stay below 1e-14 ||p|| ||A q||; 1e-8 is asked.
+    // (z is free here: the loop forms it again before it reads it.)
+    {
+        FEDD_TRY(spmv_owned(c, p, q, false, nullptr, 0.0, -1));
+        FEDD_TRY(spmv_owned(c, q, z, false, nullptr, 0.0, -1));
+        double qq = 0.0, paq = 0.0, pp = 0.0, zz = 0.0;
+        hipLaunchKernelGGL(k_cg_rz, gb, blk, 0, st, (const double*)q, (const double*)q, n, (const double*)S, part);
+        hipLaunchKernelGGL(k_cg_rz, gb, blk, 0, st, (const double*)p, (const double*)z, n, (const double*)S, part_x);
+        FEDD_TRY(read2(part, part_x, &qq, &paq));
+        hipLaunchKernelGGL(k_cg_rz, gb, blk, 0, st, (const double*)p, (const double*)p, n, (const double*)S, part);
+        hipLaunchKernelGGL(k_cg_rz, gb, blk, 0, st, (const double*)z, (const double*)z, n, (const double*)S, part_x);
+        FEDD_TRY(read2(part, part_x, &pp, &zz));
+        const double scale = std::sqrt(std::max(pp, 0.0)) * std::sqrt(std::max(zz, 0.0));
+        if (std::isfinite(qq) && std::isfinite(paq) && std::isfinite(scale) && std::fabs(qq - paq) > 1e-8 * scale) {
+            c->cg_breakdown = FEDD_CG_BREAKDOWN_NONSYMMETRIC;
+            if (relres_out) *relres_out = relres;
+            FEDD_CHECK(false, "fedd_cg: breakdown (%s): p.A(Ap) = %.6e against (Ap).(Ap) = %.6e on the first direction; conjugate "
+                              "gradients need a symmetric positive definite matrix on the free rows -- nonsymmetric systems "
+                              "(advection, Navier-Stokes) are solved with fedd_gmres",
+                       breakdown_name(FEDD_CG_BREAKDOWN_NONSYMMETRIC), paq, qq);
+        }
+    }
 
     hipEvent_t ev[CG_LAG + 1];
     for (auto& e : ev) e = nullptr;

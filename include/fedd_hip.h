@@ -620,6 +620,7 @@ int fedd_cg_x0(fedd_ctx* ctx, const double* b_owned, double* x_owned, double rto
 #define FEDD_CG_BREAKDOWN_PQ 1          /* p.Ap <= 0 */
 #define FEDD_CG_BREAKDOWN_RHO 2         /* r.z <= 0 */
 #define FEDD_CG_BREAKDOWN_NONFINITE 3   /* a dot product was not finite */
+#define FEDD_CG_BREAKDOWN_NONSYMMETRIC 4 /* the matrix is not symmetric on its free rows (probed on the first direction) */
 int fedd_cg_info(fedd_ctx* ctx, int* replacements, int* breakdown);
 /* The structures that depend on the mesh alone are built once per mesh, at the first call that needs them, and reused by every
  * later assembly: the node -> element adjacency (fedd_pattern_build) and the element-major tile structures of the assembly
