@@ -25,6 +25,8 @@ COARSE_RGDSW = 3
 LEVELS_ADDITIVE = 0         # FROSch "Level Combination" (fedd_schwarz_set_level_combination)
 LEVELS_MULTIPLICATIVE = 1
 ADV_N, ADV_W, ADV_NEWTON = range(3)     # fedd_assemble_advection
+HYPER_NEOHOOKE, HYPER_MOONEY_RIVLIN, HYPER_STVK = range(3)   # fedd_assemble_hyperelastic: model
+HYPER_TANGENT, HYPER_FORCE = 1, 2                            # ... what (or-ed)
 
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
@@ -79,6 +81,8 @@ SIGNATURES = {
     "fedd_matrix_get": [C.c_void_p, C.c_int, _i64p, _i32p, _f64p],
     "fedd_velocity_set": [C.c_void_p, _f64p],
     "fedd_assemble_advection": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int],
+    "fedd_assemble_hyperelastic": [C.c_void_p, C.c_int, _f64p, C.c_int, C.c_int],
+    "fedd_hyperelastic_force_get": [C.c_void_p, _f64p],
     "fedd_matrix_combine": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double],
     "fedd_matrix_combine_current": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, _ip],
     "fedd_matrix_apply": [C.c_void_p, C.c_int, C.c_double, _f64p, _f64p],
@@ -535,6 +539,17 @@ class Context:
     def assemble_advection(self, kind, scale=1.0, slot_add=-1, slot_out=4):
         """slot_out <- scale * (N | W | N + W)(u) + M[slot_add], FULL velocity pattern (fedd_assemble_advection)"""
         _chk(self._L.fedd_assemble_advection(self._h, kind, float(scale), slot_add, slot_out))
+
+    def assemble_hyperelastic(self, model, params, what=HYPER_TANGENT | HYPER_FORCE):
+        """tangent -> system matrix (FULL pattern, dim dofs per node) and / or force vector of the material at the displacement
+        given by velocity_set (fedd_assemble_hyperelastic); params: {E, nu} | {E, nu, C} | {lambda, mu}"""
+        p = np.ascontiguousarray(params, dtype=np.float64).ravel()
+        _chk(self._L.fedd_assemble_hyperelastic(self._h, int(model), _p(p, _f64p), p.shape[0], int(what)))
+
+    def hyperelastic_force_get(self):
+        f = np.zeros(self.n_own * self._dim, dtype=np.float64)
+        _chk(self._L.fedd_hyperelastic_force_get(self._h, _p(f, _f64p)))
+        return f
 
     def matrix_combine(self, slot_m, cm, slot_a, ca):
         """system matrix <- (cm * M[slot_m]) + (ca * A[slot_a]) on the pattern of slot_a (TimeProblem::combineSystems)"""

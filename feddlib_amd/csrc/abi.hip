@@ -208,6 +208,7 @@ static int mesh_set_impl(fedd_ctx* c, int dim, int nen, int64_t n_elem, const in
     c->p2_state = 0;     // ... and so do the gather lists of the P2 row sums
     c->adv_state = 0;    // ... and the pattern and lists of the advection matrices; the velocity belonged to the old nodes
     c->have_vel = false;
+    c->hy_lists = c->have_hy_f = false;   // ... and the lists and the force vector of the hyperelastic path
     c->have_surf = false;   // ... and the surface elements
     c->n_surf = 0;
     for (auto& id : c->adv_pattern_id) id = 0;
@@ -503,6 +504,23 @@ extern "C" int fedd_assemble_advection(fedd_ctx* c, int kind, double scale, int 
     FEDD_CHECK(c->n_node > 0, "fedd_assemble_advection: call fedd_mesh_set first");
     FEDD_HIP(hipSetDevice(c->device));
     return assemble_advection(c, kind, scale, slot_add, slot_out);
+}
+
+extern "C" int fedd_assemble_hyperelastic(fedd_ctx* c, int model, const double* params, int n_params, int what) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(c->n_node > 0, "fedd_assemble_hyperelastic: call fedd_mesh_set first");
+    FEDD_HIP(hipSetDevice(c->device));
+    return assemble_hyperelastic(c, model, params, n_params, what);
+}
+
+extern "C" int fedd_hyperelastic_force_get(fedd_ctx* c, double* f_owned) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(f_owned, "fedd_hyperelastic_force_get: null pointer");
+    FEDD_CHECK(c->have_hy_f, "fedd_hyperelastic_force_get: no fedd_assemble_hyperelastic call with FEDD_HYPER_FORCE on this mesh yet");
+    FEDD_HIP(hipSetDevice(c->device));
+    FEDD_HIP(hipStreamSynchronize(c->stream));
+    FEDD_HIP(hipMemcpy(f_owned, c->d_hy_f.p, (size_t)c->n_own * c->dim * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 extern "C" int fedd_matrix_sizes(fedd_ctx* c, int slot, int64_t* n_rows, int64_t* n_cols, int64_t* nnz) {

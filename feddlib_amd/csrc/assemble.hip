@@ -1316,6 +1316,30 @@ int advection_kind(fedd_ctx* c, int kind, double scale, const DevCsr* add, DevCs
 
 }  // namespace
 
+int build_gather_lists(fedd_ctx* c, const int32_t* rowptr, const int32_t* colind, int dofs, int full, uint16_t* soff, uint16_t* src,
+                       const char* who) {
+    const int64_t nn = c->n_own;
+    FEDD_TRY(c->d_flags.ensure(16));
+    int32_t* bad = c->d_flags.p + 6;
+    FEDD_HIP(hipMemsetAsync(bad, 0, sizeof(int32_t), c->stream));
+    const int nwg = (int)std::max<int64_t>(1, std::min<int64_t>((nn + 3) / 4, 256 * 32));
+    auto go = [&](auto nen) {
+        hipLaunchKernelGGL(k_p2_lists<decltype(nen)::value>, dim3((unsigned)nwg), dim3(256), 0, c->stream, (const int32_t*)c->d_conn.p,
+                           (const int32_t*)c->d_n2e_ptr.p, (const int32_t*)c->d_n2e.p, rowptr, colind, dofs, full, (int32_t)nn, soff,
+                           src, bad);
+    };
+    if (c->nen == 3) go(std::integral_constant<int, 3>());
+    else if (c->nen == 4) go(std::integral_constant<int, 4>());
+    else if (c->nen == 6) go(std::integral_constant<int, 6>());
+    else go(std::integral_constant<int, 10>());
+    int32_t h_bad = 0;
+    FEDD_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    FEDD_HIP(hipStreamSynchronize(c->stream));
+    FEDD_HIP(hipGetLastError());
+    FEDD_CHECK(!h_bad, "%s: a node with more than 4095 incident elements does not fit the gather lists", who);
+    return 0;
+}
+
 // what NavierStokes::u_rep_ holds (NavierStokes_def.hpp:282-321), brought to the column-local numbering of the mesh
 int velocity_set(fedd_ctx* c, const double* u_rep) {
     FEDD_CHECK(c->nranks == 1, "fedd_velocity_set: one rank only for now");

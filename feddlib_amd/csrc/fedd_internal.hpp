@@ -283,6 +283,17 @@ struct fedd_ctx {
     int adv_nq[2] = {0, 0}, adv_tab_off_w = 0;
     fedd::DevBuf<double> d_adv_ke;              // [n_elem][nen][nen][1 | dim * dim] element blocks of the assembly in progress
     uint64_t adv_pattern_id[fedd::MAX_AUX] = {};   // pattern id of the slots that hold the FULL pattern written here
+    // ---- hyperelastic tangent and forces (hyperelastic.hip assemble_hyperelastic; one rank): u is d_vel, the element blocks
+    //      pass through d_adv_ke, the tangent goes into the system matrix ----
+    bool hy_lists = false;                      // the gather lists and tables below belong to hy_mesh_id / hy_pattern_gen
+    uint64_t hy_mesh_id = 0, hy_pattern_gen = 0;
+    fedd::DevBuf<uint16_t> d_hy_soff, d_hy_src; // gather lists of the node-level nonzeros of the system's FULL pattern (k_p2_lists)
+    fedd::DevBuf<double> d_hy_tab;              // w | dphi of the rule determineDegree(Grad, Grad)
+    int hy_nq = 0;
+    fedd::DevBuf<double> d_hy_fe;               // [n_elem][nen][dim] element forces of the assembly in progress
+    fedd::DevBuf<double> d_hy_f;                // [n_own * dim] the force vector of the last call that asked for it
+    bool have_hy_f = false;
+    fedd::DevBuf<int32_t> d_hy_flag;            // [1] smallest element with det F <= 0 at a quadrature point (INT32_MAX: none)
     bool merged = false;                        // system matrix = merged blocks (dof -> node map below)
     int64_t merged_nA = 0;                      // rows of block row 0
     int merged_dofsA = 1;                       // dofs per node of block row 0
@@ -557,6 +568,13 @@ int apply_dirichlet_rows(fedd_ctx* c, int64_t n, const int32_t* rows, const doub
 int assemble_div(fedd_ctx* c, int64_t n_pressure_nodes, int slot_b, int slot_bt);
 int velocity_set(fedd_ctx* c, const double* u_rep);
 int assemble_advection(fedd_ctx* c, int kind, double scale, int slot_add, int slot_out);
+// k_p2_lists on a pattern of the caller's (rows of the first dof of every owned node; full: FULL blocks, else scalar / DIAG):
+// soff [node-level nnz + 2], src [adjacency entries * nen + 2]; `who` names the caller in the error text
+int build_gather_lists(fedd_ctx* c, const int32_t* rowptr, const int32_t* colind, int dofs, int full, uint16_t* soff, uint16_t* src,
+                       const char* who);
+
+// hyperelastic.hip
+int assemble_hyperelastic(fedd_ctx* c, int model, const double* params, int n_params, int what);
 
 // assemble_tiles.hip: the element-major tile path (P1 simplices; kform = Laplace or elasticity of assemble_common.hpp).
 // Returns -1, without error, when the mesh does not fit the tiles.

@@ -455,6 +455,7 @@ public:
         volumeID_ = volumeID;
         setMesh(dim, FEType, dim + 1, conn, xyz, gid, gid, vflag);
         flagRep_ = vflag;
+        elemFlag_ = eflag;
         surfNsn_ = dim;
         uploadSurfaces();
     }
@@ -509,6 +510,7 @@ public:
         for (size_t i = 0; i < gid.size(); ++i) gid[i] = (int64_t)i;
         setMesh(dim, "P2", nen2, conn2, xyz2, gid, gid, flag2);
         flagRep_ = flag2;
+        elemFlag_ = domainP1->elemFlag_;
         nP1_ = nv;
         // P2 surface elements: the vertices, then the mid nodes in the order of the line / triangle bases
         const int64_t ns = (int64_t)domainP1->surfFlag_.size();
@@ -525,6 +527,8 @@ public:
     int nodesPerSurfaceElement() const { return surfNsn_; }
     const std::vector<int32_t>& surfaceElements() const { return surf_; }
     const std::vector<int32_t>& surfaceFlags() const { return surfFlag_; }
+    // element flags of a mesh read from a file on one rank (FiniteElement::getFlag); empty: no element carries a flag
+    const std::vector<int32_t>& elementFlags() const { return elemFlag_; }
     int64_t numberOfP1Nodes() const { return nP1_; }      // P2-of-P1 domain: its first nodes are the P1 nodes
 
     LO getApproxEntriesPerRow() const {      // Domain_def.hpp:176-198 (allocation hint only)
@@ -616,7 +620,7 @@ private:
     double length = 1., width = 1., height = 1.;
     int dim_ = 0, n_ = 0, m_ = 0, flagsOption_ = 0, nen_ = 0, surfNsn_ = 0;
     std::string FEType_;
-    std::vector<int32_t> conn_, flagRep_, flagUni_, uniOfRep_, surf_, surfFlag_, rowGhostRep_, rowGhostFlag_;
+    std::vector<int32_t> conn_, flagRep_, flagUni_, uniOfRep_, surf_, surfFlag_, rowGhostRep_, rowGhostFlag_, elemFlag_;
     std::vector<double> xyz_;
     int volumeID_ = 10;
     int64_t nP1_ = 0;
@@ -921,6 +925,13 @@ public:
     // BCBuilder::setSystem alone on a merged block system (BCBuilder_def.hpp:589-707): unit rows, no right-hand side
     void setSystem(const BlockMatrixPtr_Type& blockMatrix, const BlockMultiVectorPtr_Type& layout) const {
         auto dev = blockMatrix->mergedDevice();
+        if (blockMatrix->size() == 1 && dev.is_null()) {
+            // one block (nonlinear elasticity): the unit rows of set() on the resident matrix; the right-hand side stays as it is
+            BlockMultiVectorPtr_Type scratch(new BlockMultiVector_Type(1));
+            scratch->addBlock(Teuchos::rcp(new MultiVector<SC, LO, GO, NO>(layout->getBlock(0)->getMap(), 1)), 0);
+            set(blockMatrix, scratch, 0.);
+            return;
+        }
         TEUCHOS_TEST_FOR_EXCEPTION(dev.is_null(), std::runtime_error, "BCBuilder: the block system has not been merged on the device");
         std::vector<int32_t> rows;
         std::vector<double> values;
@@ -1750,6 +1761,117 @@ private:
     mutable MatrixPtr_Type A_;
     mutable std::vector<double> u_rep_;
     mutable int slotC_ = -1, baseSlot_ = 0;
+};
+
+// NonLinElasticity (feddlib/problems/specific/NonLinElasticity_def.hpp:16-120, 251-271): one vector block; every
+// "Newton-Residual" reassembly is one device pass (fedd_assemble_hyperelastic) for the tangent, which becomes the system matrix,
+// and the internal force, which becomes the residual vector.  "Newton" is a no-op, as in the reference (:112-117).
+// The source term enters twice, as in the reference: assemble("") adds it to rhs_ (:61-62) and calculateNonLinResidualVec
+// subtracts rhs_ AND sourceTerm_ (:254-263), so the residual is f(u) - 2 * source on the free rows.  Restated, not corrected.
+// Per-flag materials ("E1" / "E2" / "Mu1" / "Mu2" on elements flagged 1 / 2, FE_def.hpp:1164-1174) are not built: an error
+// where such elements exist and the parameter differs from the base one.
+template <class SC = default_sc, class LO = default_lo, class GO = default_go, class NO = default_no>
+class NonLinElasticity : public NonLinearProblem<SC, LO, GO, NO> {
+public:
+    typedef NonLinearProblem<SC, LO, GO, NO> NonLinearProblem_Type;
+    typedef Problem<SC, LO, GO, NO> Problem_Type;
+    typedef typename Problem_Type::DomainConstPtr_Type DomainConstPtr_Type;
+    typedef typename Problem_Type::Matrix_Type Matrix_Type;
+    typedef typename Problem_Type::MatrixPtr_Type MatrixPtr_Type;
+    typedef typename Problem_Type::BlockMatrix_Type BlockMatrix_Type;
+    typedef typename Problem_Type::BlockMultiVectorPtr_Type BlockMultiVectorPtr_Type;
+    NonLinElasticity(const DomainConstPtr_Type& domain, std::string FEType, ParameterListPtr_Type parameterList)
+        : NonLinearProblem_Type(parameterList, domain->getComm()) {
+        this->addVariable(domain, FEType, "u", (int)domain->getDimension());
+        this->dim_ = (int)this->getDomain(0)->getDimension();
+        C_ = this->parameterList_->sublist("Parameter").get("C", 1.);
+    }
+    void info() override { this->infoProblem(); this->infoNonlinProblem(); }
+    void assemble(std::string type = "") const override {
+        if (type != "") { reAssemble(type); return; }
+        if (this->verbose_) std::cout << "-- Assembly nonlinear elasticity ... " << std::flush;
+        TEUCHOS_TEST_FOR_EXCEPTION(this->comm_->getSize() > 1, std::logic_error, "NonLinElasticity: one rank in this build");
+        auto dom = this->getDomain(0);
+        auto dev = dom->device();
+        int64_t nnz = 0;
+        feddCheck(fedd_pattern_build(dev->ctx, this->dim_, FEDD_BLOCK_FULL, &nnz), "fedd_pattern_build");   // assemblyEmptyMatrix
+        dev->generation++;
+        MatrixPtr_Type A(new Matrix_Type(dom->getMapVecFieldUnique(), dom->getDimension() * dom->getApproxEntriesPerRow()));
+        A->bind(dev, this->dim_);
+        this->system_.reset(new BlockMatrix_Type(1));
+        this->system_->addBlock(A, 0, 0);
+        this->assembleSourceTerm(0.);
+        this->addToRhs(this->sourceTerm_);
+        this->setBoundariesRHS();
+        this->solution_->putScalar(0.);
+        if (this->verbose_) std::cout << "done -- " << std::endl;
+        reAssemble("Newton-Residual");
+    }
+    void reAssemble(std::string type) const override {
+        auto& par = this->parameterList_->sublist("Parameter");
+        const std::string model = par.get("Material model", "Neo-Hooke");
+        if (this->verbose_) std::cout << "-- Reassembly nonlinear elasticity with material model " << model << " (" << type << ") ... " << std::flush;
+        if (type == "Newton-Residual") {
+            auto dom = this->getDomain(0);
+            auto dev = dom->device();
+            const int dim = this->dim_;
+            const double nu = par.get("Poisson Ratio", 0.4), mu = par.get("Mu", 2.0e+6);
+            const bool stvk = model == "Saint Venant-Kirchhoff";
+            TEUCHOS_TEST_FOR_EXCEPTION(!stvk && model != "Neo-Hooke" && model != "Mooney-Rivlin", std::logic_error,
+                                       "Material model \"" + model + "\" is not built (Neo-Hooke, Mooney-Rivlin, Saint Venant-Kirchhoff are)");
+            TEUCHOS_TEST_FOR_EXCEPTION(dim == 2 && !stvk, std::logic_error, "Only Saint Venant-Kirchhoff in 2D.");
+            const double E = stvk ? mu * 2. * (1. + nu) : par.get("E", 3.0e+6);     // FE_def.hpp:883-891
+            for (int32_t flag : dom->elementFlags()) {
+                if (flag != 1 && flag != 2) continue;
+                const std::string base = stvk ? "Mu" : "E", key = base + (flag == 1 ? "1" : "2");
+                const double other = par.get(key, stvk ? 2.0e+6 : 3.0e+6);
+                TEUCHOS_TEST_FOR_EXCEPTION(other != (stvk ? mu : E), std::logic_error,
+                                           "NonLinElasticity: the mesh has elements with flag " + std::to_string(flag) + " and \"" + key +
+                                           "\" differs from \"" + base + "\": per-flag materials are not built (one material per assembly is)");
+            }
+            double p[3] = {E, nu, C_};
+            const int np = model == "Mooney-Rivlin" ? 3 : 2;
+            const int id = model == "Neo-Hooke" ? FEDD_HYPER_NEOHOOKE : (stvk ? FEDD_HYPER_STVK : FEDD_HYPER_MOONEY_RIVLIN);
+            if (stvk) { p[0] = (nu * E) / ((1 + nu) * (1 - 2 * nu)); p[1] = mu; }   // lambda, mue (:894)
+            // u_rep_->importFromVector(u)
+            auto mapRep = dom->getMapRepeated();
+            auto mapUni = dom->getMapUnique();
+            const auto& u = this->solution_->getBlock(0)->raw();
+            u_rep_.assign((size_t)mapRep->getNodeNumElements() * dim, 0.);
+            for (LO i = 0; i < mapRep->getNodeNumElements(); ++i) {
+                const LO k = mapUni->getLocalElement(mapRep->getGlobalElement(i));
+                for (int d = 0; d < dim; ++d) u_rep_[(size_t)i * dim + d] = u[(size_t)k * dim + d];
+            }
+            feddCheck(fedd_velocity_set(dev->ctx, u_rep_.data()), "fedd_velocity_set");
+            feddCheck(fedd_assemble_hyperelastic(dev->ctx, id, p, np, FEDD_HYPER_TANGENT | FEDD_HYPER_FORCE), "fedd_assemble_hyperelastic");
+            feddCheck(fedd_hyperelastic_force_get(dev->ctx, this->residualVec_->getBlockNonConst(0)->raw().data()), "fedd_hyperelastic_force_get");
+            dev->generation++;
+            MatrixPtr_Type W(new Matrix_Type(dom->getMapVecFieldUnique(), dom->getDimension() * dom->getApproxEntriesPerRow()));
+            W->bind(dev, dim);
+            this->system_->addBlock(W, 0, 0);
+        } else {
+            TEUCHOS_TEST_FOR_EXCEPTION(type != "Newton", std::logic_error, "NonLinElasticity::reAssemble: unknown type " + type + " (Newton-Residual and Newton are built)");
+        }
+        if (this->verbose_) std::cout << "done -- " << std::endl;
+    }
+    void reAssembleExtrapolation(std::vector<BlockMultiVectorPtr_Type> previousSolutions) {
+        (void)previousSolutions;
+        TEUCHOS_TEST_FOR_EXCEPTION(true, std::logic_error, "Only Newton implemented for nonlinear material models! (NOX and extrapolation are not built)");
+    }
+    void calculateNonLinResidualVec(std::string type = "standard", double time = 0.) const override {
+        reAssemble("Newton-Residual");
+        const bool standard = type == "standard";
+        TEUCHOS_TEST_FOR_EXCEPTION(!standard && type != "reverse", std::runtime_error, "Unknown type for residual computation.");
+        auto& r = this->residualVec_->getBlockNonConst(0)->raw();
+        const auto& f = this->rhs_->getBlock(0)->raw();
+        const auto& s = this->sourceTerm_->getBlock(0)->raw();
+        // :254-263: standard r <- r - rhs - source; reverse r <- rhs - r + source
+        for (size_t i = 0; i < r.size(); ++i) r[i] = standard ? (r[i] - f[i]) - s[i] : (f[i] - r[i]) + s[i];
+        this->bcFactory_->setBCMinusVector(this->residualVec_, this->solution_, time);
+    }
+private:
+    mutable std::vector<double> u_rep_;
+    double C_;
 };
 
 // NonLinearSolver (feddlib/problems/Solver/NonLinearSolver_def.hpp:274-391): solveFixedPoint and solveNewton, line by line --

@@ -475,6 +475,51 @@ int fedd_multistep_info(fedd_ctx* ctx, int* order, int* count);
 int fedd_velocity_set(fedd_ctx* ctx, const double* u_rep);
 int fedd_assemble_advection(fedd_ctx* ctx, int kind, double scale, int slot_add, int slot_out);
 
+/* ------------------------------------------------------------------------------------------------
+ * nonlinear elasticity (one rank, like the advection path): tangent and internal forces of a hyperelastic material for the
+ * displacement u, FE::assemblyElasticityJacobianAndStressAceFEM (feddlib/core/FE/FE_def.hpp:837-1291; element loops :1123-1267
+ * in 3D, :928-1066 in 2D), which NonLinElasticity::reAssemble("Newton-Residual") calls in every Newton step
+ * (feddlib/problems/specific/NonLinElasticity_def.hpp:89-103).
+ *   u   is what fedd_velocity_set uploaded: u_rep[n_rep * dim], node-wise interleaved on the repeated map (the buffer is the
+ *       nodal vector field of the context; for this entry it holds NonLinElasticity::u_rep_, :69-71, 90-92).
+ *   Per element T and quadrature point p of the rule determineDegree(dim, FEType, FEType, Grad, Grad) (:856; P1 one point, P2
+ *   degree 2), in this order:
+ *       g_i = B^-T grad phi_i(x_p)                         transformed gradients
+ *       F   = I + sum_i u_i (x) g_i                        nodes in element order, (:1143-1156)
+ *       P(F), A[i][j][k][l] = dP_ij / dF_kl                the material, both multiplied by w_p at once
+ *       H_j[d1][k][d2] = sum_l A[d1][k][d2][l] g_j,l
+ *       K_(i,d1),(j,d2) += sum_k g_i,k H_j[d1][k][d2]      summed over p, then multiplied by |det B|   (:1200-1222, 1258-1262)
+ *       f_(i,d)         += sum_k P_dk g_i,k                summed over p, then multiplied by |det B|   (:1229-1243, 1251-1253)
+ *   The element blocks are then added to their rows in the order of the node -> element adjacency.  No floating-point atomics:
+ *   two calls on the same input agree bit for bit, and tangent-only / force-only calls give the bits of the combined call.
+ *   Materials (one per call), with C = F^T F, I1 = tr C, I2 = (I1^2 - tr C^2) / 2, J = det F; the reference's generated routines
+ *   nh3d, mr3d, stvk3d, stvk2d (:6969-7803) evaluate the same functions:
+ *       FEDD_HYPER_NEOHOOKE       params {E, nu}:     mu = E / (2 (1 + nu)), lambda = E nu / ((1 + nu)(1 - 2 nu)),
+ *                                 psi = mu / 2 (I1 - 3) - mu ln J + lambda / 2 (ln J)^2
+ *       FEDD_HYPER_MOONEY_RIVLIN  params {E, nu, C}:  mu as above, kappa = E / (3 (1 - 2 nu)),
+ *                                 psi = (1 - C) mu / 2 (I1 - 3) + C mu / 2 (I2 - 3) - mu (1 + C) ln J + kappa / 2 (ln J)^2
+ *       FEDD_HYPER_STVK           params {lambda, mu} (the caller derives them as :887-896 does):
+ *                                 P = F (lambda tr(E) I + 2 mu E), E = (C - I) / 2
+ *   In 2D only FEDD_HYPER_STVK exists (:903); the other two are an error there.
+ *   what  FEDD_HYPER_TANGENT: K overwrites the values of the system matrix, which must have the pattern of
+ *         fedd_pattern_build(dim, FEDD_BLOCK_FULL) -- the one FEDD_FORM_LINELAS fills -- so fedd_dirichlet, fedd_schwarz_setup,
+ *         fedd_gmres and the reuse keys work as after fedd_assemble (Dirichlet rows are to be set again, the preconditioner to be
+ *         set up again).  FEDD_HYPER_FORCE: f goes into a device vector of the owned rows, read by fedd_hyperelastic_force_get.
+ *         Both: one pass over the elements.
+ *   Inverted elements: where J <= 0 at a quadrature point and the material takes ln J (Neo-Hooke, Mooney-Rivlin) the call
+ *   returns non-zero and fedd_last_error names the first such element; the system matrix and the force vector are NOT written
+ *   then (the element pass ends before the rows are summed).  Saint Venant-Kirchhoff is a polynomial in F and is evaluated for
+ *   any F, as in the reference.
+ *   The gather lists of the row sums are built at the first call on a pattern (timer FEDD_T_SYMBOLIC) and kept; later calls move
+ *   values only (FEDD_T_ASSEMBLE).  Memory: the element blocks pass through the scratch of fedd_assemble_advection,
+ *   8 * n_elem * nen^2 * dim^2 bytes (7.2 KB per P2 tetrahedron), and the element forces through 8 * n_elem * nen * dim bytes.
+ * ---------------------------------------------------------------------------------------------- */
+enum fedd_hyper_model { FEDD_HYPER_NEOHOOKE = 0, FEDD_HYPER_MOONEY_RIVLIN = 1, FEDD_HYPER_STVK = 2 };
+#define FEDD_HYPER_TANGENT 1
+#define FEDD_HYPER_FORCE 2
+int fedd_assemble_hyperelastic(fedd_ctx* ctx, int model, const double* params, int n_params, int what);
+int fedd_hyperelastic_force_get(fedd_ctx* ctx, double* f_owned);
+
 /* read-back for Tpetra::CrsMatrix fill / parity (Matrix::getLocalRowView analog). col_gid maps
  * a local column index to its global dof id. */
 int fedd_csr_sizes(fedd_ctx* ctx, int64_t* n_rows, int64_t* n_cols, int64_t* nnz);
