@@ -55,6 +55,15 @@ int main(int argc, char* argv[]) {
     try {
         Teuchos::RCP<const Teuchos::Comm<int> > comm = Teuchos::rcp(new Teuchos::Comm<int>(0, 1));
         ParameterListPtr_Type parameterListProblem = Teuchos::getParametersFromXmlFile(xmlProblemFile);
+        // the preconditioner's parameter file follows the method, as feddlib/problems/tests/stokes/main.cpp:171-179 does:
+        // Diagonal / Triangular read parametersPrecBlock.xml beside the file given (or the file given, if it is that one)
+        std::string precMethod = parameterListProblem->sublist("General").get("Preconditioner Method", "Monolithic");
+        TEUCHOS_TEST_FOR_EXCEPTION(precMethod != "Monolithic" && precMethod != "Diagonal" && precMethod != "Triangular", std::logic_error,
+                                   "\"Preconditioner Method\" = \"" << precMethod << "\" is not built (Monolithic, Diagonal and Triangular are; Teko and FaCSI are not)");
+        if (precMethod != "Monolithic" && xmlPrecFile.find("parametersPrecBlock.xml") == std::string::npos) {
+            const size_t slash = xmlPrecFile.find_last_of('/');
+            xmlPrecFile = (slash == std::string::npos ? std::string() : xmlPrecFile.substr(0, slash + 1)) + "parametersPrecBlock.xml";
+        }
         ParameterListPtr_Type parameterListPrec = Teuchos::getParametersFromXmlFile(xmlPrecFile);
         ParameterListPtr_Type parameterListSolver = Teuchos::getParametersFromXmlFile(xmlSolverFile);
 
@@ -64,9 +73,6 @@ int main(int argc, char* argv[]) {
         std::string meshType = parameterListProblem->sublist("Parameter").get("Mesh Type", "structured");
         int volumeID = parameterListProblem->sublist("Parameter").get("Volume ID", 0);
         std::string bcType = parameterListProblem->sublist("Parameter").get("BC Type", "parabolic");
-        std::string precMethod = parameterListProblem->sublist("General").get("Preconditioner Method", "Monolithic");
-        TEUCHOS_TEST_FOR_EXCEPTION(precMethod != "Monolithic", std::logic_error,
-                                   "Preconditioner Method " << precMethod << ": only Monolithic is built (Teko and the block preconditioners are out of scope)");
         TEUCHOS_TEST_FOR_EXCEPTION(meshType != "unstructured", std::logic_error, "this driver reads unstructured meshes");
         TEUCHOS_TEST_FOR_EXCEPTION(discVelocity != "P2", std::logic_error, "this driver builds P2 / P1");
 

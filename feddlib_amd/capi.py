@@ -18,7 +18,7 @@ COMBINE_RESTRICTED, COMBINE_AVERAGING, COMBINE_FULL = range(3)
  T_COARSE_APPLY, T_HALO, T_ALLREDUCE, T_SPMV_SETUP) = range(13)
 TIMER_NAMES = ["symbolic", "assemble", "rhs", "dirichlet", "spmv", "schwarz_setup", "schwarz_apply", "ortho",
                "coarse_setup", "coarse_apply", "halo", "allreduce", "spmv_setup", "gs_dot", "gs_update", "gs_fused",
-               "full_park_mfma", "full_park", "full_gather", "cg_pq", "cg_xr", "cg_rz", "cg_p", "newmark_state", "block_apply", "multistep_state"]
+               "full_park_mfma", "full_park", "full_gather", "cg_pq", "cg_xr", "cg_rz", "cg_p", "newmark_state", "block_apply", "multistep_state", "blockprec_bt"]
 COARSE_Q1 = 1
 COARSE_GDSW = 2
 COARSE_RGDSW = 3
@@ -27,6 +27,7 @@ LEVELS_MULTIPLICATIVE = 1
 ADV_N, ADV_W, ADV_NEWTON = range(3)     # fedd_assemble_advection
 HYPER_NEOHOOKE, HYPER_MOONEY_RIVLIN, HYPER_STVK = range(3)   # fedd_assemble_hyperelastic: model
 HYPER_TANGENT, HYPER_FORCE = 1, 2                            # ... what (or-ed)
+BLOCKPREC_DIAGONAL, BLOCKPREC_TRIANGULAR = 1, 2              # fedd_block_prec_attach: kind
 
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
@@ -152,6 +153,10 @@ SIGNATURES = {
     "fedd_halo_requests_set": [C.c_void_p, _i64p, _i64p],
     "fedd_halo_exchange_setup": [C.c_void_p],
     "fedd_comm_set_host_callbacks": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "fedd_matrix_import": [C.c_void_p, C.c_void_p, C.c_int],
+    "fedd_block_prec_attach": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int],
+    "fedd_block_prec_detach": [C.c_void_p],
+    "fedd_block_prec_info": [C.c_void_p, _ip, _f64p, _ip, _i64p],
 }
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, _i32p, _i64p, _f64p, _i64p, _f64p, C.c_int)
@@ -574,6 +579,30 @@ class Context:
         y = np.zeros(a.value)
         _chk(self._L.fedd_matrix_apply(self._h, slot, float(alpha), _p(x, _f64p), _p(y, _f64p)))
         return y
+
+    def matrix_import(self, src, slot):
+        """system matrix <- the block in `slot` of the context `src`, device to device (fedd_matrix_import); this context
+        carries the block's mesh"""
+        _chk(self._L.fedd_matrix_import(self._h, src._h, slot))
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _chk(self._L.fedd_csr_sizes(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        self.dofs = max(1, a.value // max(1, self.n_own))
+
+    def block_prec_attach(self, kind, velocity, schur, schur_scale=-1.0, slot_bt=2):
+        """Diagonal / Triangular block preconditioner of this context's merged system out of two child contexts, which
+        are not owned: detach (or close this context) before closing a child"""
+        _chk(self._L.fedd_block_prec_attach(self._h, kind, None if velocity is None else velocity._h,
+                                            None if schur is None else schur._h, float(schur_scale), slot_bt))
+        self._bp_children = (velocity, schur)       # keeps them alive while attached
+
+    def block_prec_detach(self):
+        _chk(self._L.fedd_block_prec_detach(self._h))
+        self._bp_children = None
+
+    def block_prec_info(self):
+        k, sl, n, sc = C.c_int(), C.c_int(), C.c_int64(), C.c_double()
+        _chk(self._L.fedd_block_prec_info(self._h, C.byref(k), C.byref(sc), C.byref(sl), C.byref(n)))
+        return {"kind": k.value, "schur_scale": sc.value, "slot_bt": sl.value, "applies": n.value}
 
     def newmark_begin(self):
         """u_n <- the current solution, v = w = 0; the next advance is the first step"""

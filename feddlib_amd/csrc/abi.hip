@@ -2,6 +2,7 @@
 #include "fedd_internal.hpp"
 #include <rccl/rccl.h>
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <unordered_map>
 
@@ -59,6 +60,8 @@ extern "C" int fedd_ctx_create(fedd_ctx** out, int device, const void* nccl_uniq
     FEDD_CHECK(out, "fedd_ctx_create: null output pointer");
     FEDD_CHECK(nranks >= 1 && rank >= 0 && rank < nranks, "fedd_ctx_create: bad rank %d of %d", rank, nranks);
     fedd_ctx* c = new fedd_ctx();
+    static std::atomic<uint64_t> next_uid{0};
+    c->uid = ++next_uid;
     c->device = device;
     c->rank = rank;
     c->nranks = nranks;
@@ -130,6 +133,8 @@ extern "C" int fedd_ctx_create(fedd_ctx** out, int device, const void* nccl_uniq
 
 extern "C" void fedd_ctx_destroy(fedd_ctx* c) {
     if (!c) return;
+    block_prec_child_gone(c);   // parents that apply this context as a block are detached (their streams finished first)
+    block_prec_unlink(c);       // ... and this context's own children forget it
     if (c->device >= 0) {
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
@@ -174,6 +179,7 @@ extern "C" void fedd_ctx_destroy(fedd_ctx* c) {
         if (c->h_pinned) (void)hipHostFree(c->h_pinned);
         if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
         if (c->ev_join) (void)hipEventDestroy(c->ev_join);
+        if (c->bp_ev) (void)hipEventDestroy(c->bp_ev);
         if (c->stream2) (void)hipStreamDestroy(c->stream2);
         (void)hipStreamDestroy(c->stream);
     }
@@ -183,6 +189,9 @@ extern "C" void fedd_ctx_destroy(fedd_ctx* c) {
 extern "C" int fedd_sync(fedd_ctx* c) {
     NEED_DEVICE(c);
     FEDD_HIP(hipStreamSynchronize(c->stream));
+    // an attached block preconditioner runs its children's applies in this stream; their own streams hold their setups
+    if (c->bp_kind && c->bp_vel && c->bp_vel->device >= 0) FEDD_HIP(hipStreamSynchronize(c->bp_vel->stream));
+    if (c->bp_kind && c->bp_schur && c->bp_schur->device >= 0) FEDD_HIP(hipStreamSynchronize(c->bp_schur->stream));
     return 0;
 }
 
@@ -763,6 +772,7 @@ extern "C" int fedd_schwarz_setup(fedd_ctx* c, int overlap, int combine, int two
     c->sw_combine = combine;
     c->sw_two_level = two_level ? 1 : 0;
     if (two_level) c->co_kind = coarse_kind;
+    ++c->sw_setup_gen;      // (a parent that applies this context as a block orders this stream in front of its own once more)
     return schwarz_setup(c);
 }
 
@@ -848,14 +858,15 @@ extern "C" int fedd_spmv_reuse_info(fedd_ctx* c, int* last_reused, int64_t* n_re
 
 extern "C" int fedd_schwarz_apply(fedd_ctx* c, const double* r_owned, double* z_owned) {
     NEED_DEVICE(c);
-    FEDD_CHECK(c->have_schwarz && r_owned && z_owned, "fedd_schwarz_apply: no preconditioner / null pointer");
-    FEDD_TRY(levels_check(c, "fedd_schwarz_apply"));
+    FEDD_CHECK((c->have_schwarz || c->bp_kind) && r_owned && z_owned, "fedd_schwarz_apply: no preconditioner / null pointer");
+    if (c->bp_kind) FEDD_TRY(block_prec_check(c, "fedd_schwarz_apply"));
+    else FEDD_TRY(levels_check(c, "fedd_schwarz_apply"));
     FEDD_HIP(hipSetDevice(c->device));
     FEDD_TRY(c->d_dtmp0.ensure((size_t)c->n_rows * 2));
     double* dr = c->d_dtmp0.p;
     double* dz = dr + c->n_rows;
     FEDD_HIP(hipMemcpyAsync(dr, r_owned, (size_t)c->n_rows * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    FEDD_TRY(schwarz_apply(c, dr, dz));
+    FEDD_TRY(prec_apply(c, dr, dz, false));
     FEDD_HIP(hipMemcpyAsync(z_owned, dz, (size_t)c->n_rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     FEDD_HIP(hipStreamSynchronize(c->stream));
     return 0;
@@ -863,14 +874,15 @@ extern "C" int fedd_schwarz_apply(fedd_ctx* c, const double* r_owned, double* z_
 
 extern "C" int fedd_schwarz_apply_device(fedd_ctx* c, int reps) {
     NEED_DEVICE(c);
-    FEDD_CHECK(c->have_schwarz, "fedd_schwarz_apply_device: no preconditioner");
-    FEDD_TRY(levels_check(c, "fedd_schwarz_apply_device"));
+    FEDD_CHECK(c->have_schwarz || c->bp_kind, "fedd_schwarz_apply_device: no preconditioner");
+    if (c->bp_kind) FEDD_TRY(block_prec_check(c, "fedd_schwarz_apply_device"));
+    else FEDD_TRY(levels_check(c, "fedd_schwarz_apply_device"));
     FEDD_HIP(hipSetDevice(c->device));
     FEDD_TRY(c->d_dtmp0.ensure((size_t)c->n_rows * 2));
     double* dr = c->d_dtmp0.p;
     double* dz = dr + c->n_rows;
     FEDD_HIP(hipMemcpyAsync(dr, c->d_rhs.p, (size_t)c->n_rows * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    for (int r = 0; r < reps; ++r) FEDD_TRY(schwarz_apply(c, dr, dz));
+    for (int r = 0; r < reps; ++r) FEDD_TRY(prec_apply(c, dr, dz, false));
     return 0;
 }
 
@@ -880,9 +892,10 @@ static int gmres_entry(fedd_ctx* c, const char* who, bool x0, const double* b_ow
                        int restart, int use_prec, int* its_out, double* relres_out) {
     NEED_DEVICE(c);
     FEDD_CHECK(c->have_pattern, "%s: no matrix", who);
-    FEDD_CHECK(!use_prec || c->have_schwarz, "%s: preconditioner requested but fedd_schwarz_setup was not called", who);
+    FEDD_CHECK(!use_prec || c->bp_kind || c->have_schwarz, "%s: preconditioner requested but fedd_schwarz_setup was not called", who);
     FEDD_CHECK(rtol > 0 && max_it >= 1 && restart >= 1 && restart <= 1000, "%s: bad rtol/max_it/restart", who);
-    if (use_prec) FEDD_TRY(levels_check(c, who));
+    if (use_prec && c->bp_kind) FEDD_TRY(block_prec_check(c, who));     // (and again at every apply)
+    else if (use_prec) FEDD_TRY(levels_check(c, who));
     FEDD_HIP(hipSetDevice(c->device));
     const size_t bytes = (size_t)c->n_rows * sizeof(double);
     if (b_owned) FEDD_HIP(hipMemcpyAsync(c->d_rhs.p, b_owned, bytes, hipMemcpyHostToDevice, c->stream));

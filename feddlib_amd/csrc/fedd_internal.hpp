@@ -352,7 +352,9 @@ struct fedd_ctx {
     fedd::DevBuf<int64_t> d_inv_ptr;           // [nsub+1] offsets into d_inv (elements)
     fedd::DevBuf<double> d_inv;                 // per subdomain [n_i][rp_i] column-major slab
     fedd::DevBuf<double> d_mult;                // [n_cols] multiplicity (averaging)
-    bool have_schwarz = false;
+    bool have_schwarz = false;                  // cleared by EVERY writer of the system matrix, its Dirichlet rows or the setup's buffers: a parent that
+                                                // applies this context as a block (blockprec.hip) trusts it, and orders this context's stream in front
+                                                // of its own whenever sw_setup_gen moved or this stream still has work
     int md2_gy = 0;                             // k_multidot2: column groups in flight per row block (0 = by vector length)
     int halo_overlap = 0;                       // several ranks: interior subdomains first, ghost import of r on a second stream meanwhile
     hipStream_t stream2 = nullptr;              // (created on first use)
@@ -416,6 +418,25 @@ struct fedd_ctx {
     int comb_slot_m = -1, comb_slot_a = -1;     // and the sys_value_gen it left
     double comb_cm = 0.0, comb_ca = 0.0;
     uint64_t comb_id_m = 0, comb_id_a = 0, comb_sys_gen = 0;
+
+    // ---- block preconditioner of a merged 2 x 2 system (blockprec.hip; one rank): the two Schwarz preconditioners live in child
+    //      contexts that this one does not own ----
+    int bp_kind = 0;                            // 0 = none attached, FEDD_BLOCKPREC_DIAGONAL / FEDD_BLOCKPREC_TRIANGULAR
+    fedd_ctx* bp_vel = nullptr;                 // V: preconditioner of block (0,0)
+    fedd_ctx* bp_schur = nullptr;               // S: preconditioner of the Schur complement's stand-in
+    double bp_scale = 1.0;                      // z_p = bp_scale * S(r_p)
+    int bp_slot_bt = -1;                        // B^T of the Triangular form
+    fedd::DevBuf<double> d_bp_ws;               // [n_rows] S(r_p) | t of the Triangular form
+    hipEvent_t bp_ev = nullptr;                 // orders a child's own stream before this one after the child was set up again
+    uint64_t bp_seen_vel = 0, bp_seen_schur = 0;   // the children's sw_setup_gen at the last such ordering
+    int64_t bp_applies = 0;                     // applies of the block operator since it was attached
+    uint64_t sw_setup_gen = 0;                  // counts the fedd_schwarz_setup calls of this context
+    // the system matrix is an import (fedd_matrix_import) of this block: the source context's uid, its mesh, the block's pattern id, and the
+    // pattern_gen the import left here -- while all four stand, the next import of that block moves values only
+    uint64_t uid = 0;                           // process-wide unique id of this context (fedd_ctx_create): an address can come back
+    uint64_t imp_src_uid = 0;                   // ... after a destroy, this number cannot
+    uint64_t imp_mesh_id = 0, imp_pattern_id = 0, imp_pattern_gen = 0;
+    std::vector<fedd_ctx*> bp_parents;          // contexts that hold this one as a child of their block preconditioner
 
     // ---- coarse level (two-level Schwarz) ----
     int sw_two_level = 0;
@@ -585,6 +606,17 @@ int assemble_tiles(fedd_ctx* c, int kform, const AsmArgs& a, int ntab);
 int matrix_store(fedd_ctx* c, int slot);
 int matrix_scale(fedd_ctx* c, int slot, double alpha);
 int block_merge(fedd_ctx* c, int slot_a, int slot_bt, int slot_b, int slot_c);
+
+// blockprec.hip: Diagonal / Triangular block preconditioner of a merged system out of two child contexts
+int block_prec_check(fedd_ctx* c, const char* who);    // everything an apply needs, with errors that name the child
+int block_prec_apply(fedd_ctx* c, const double* d_r_owned, double* d_z_owned);
+void block_prec_unlink(fedd_ctx* c);                   // c gives up its children (detach, re-attach, destroy of c)
+void block_prec_child_gone(fedd_ctx* child);           // a child is being destroyed: its parents are detached first
+// the preconditioner of the context: the attached block operator, else its own Schwarz preconditioner
+int schwarz_apply(fedd_ctx* c, const double* d_r_owned, double* d_z_owned, bool r_has_tail);
+inline int prec_apply(fedd_ctx* c, const double* d_r_owned, double* d_z_owned, bool r_has_tail) {
+    return c->bp_kind ? block_prec_apply(c, d_r_owned, d_z_owned) : schwarz_apply(c, d_r_owned, d_z_owned, r_has_tail);
+}
 
 // spmv.hip
 // x_has_tail: the buffer behind d_x_owned has room for all n_cols entries; the ghost values are then imported in

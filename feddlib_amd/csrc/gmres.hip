@@ -703,7 +703,7 @@ struct Frame {
             FEDD_TRY(schwarz_apply_multi(c, src, z, mk));
             return spmm_owned(c, z, out, mk, z);
         }
-        if (use_prec) FEDD_TRY(schwarz_apply(c, in, z, in_tail));
+        if (use_prec) FEDD_TRY(prec_apply(c, in, z, in_tail));   // (the attached block operator, else Schwarz)
         if (mk) {
             // z <- D M^-1 D in + (I - D) in   (M^-1 D in: the masked entries of `in` are excluded by a copy)
             if (use_prec) hipLaunchKernelGGL(k_mask_mix, gn, blk, 0, st, mk, (const double*)z, in, z, n);
@@ -754,7 +754,7 @@ struct Frame {
             FEDD_TRY(schwarz_apply_multi(c, r, z, mk));
             hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, x, 1.0, (const double*)z, dst, n);
         } else if (a->use_prec) {
-            FEDD_TRY(schwarz_apply(c, r, z, tail));
+            FEDD_TRY(prec_apply(c, r, z, tail));
             if (mk) hipLaunchKernelGGL(k_mask_mix, gn, blk, 0, st, mk, (const double*)z, (const double*)r, z, n);
             hipLaunchKernelGGL(k_axpby, gn, blk, 0, st, 1.0, x, 1.0, (const double*)z, dst, n);
         } else {

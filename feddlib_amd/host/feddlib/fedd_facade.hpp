@@ -560,6 +560,12 @@ public:
     const std::vector<int32_t>& connectivity() const { return conn_; }
     // facade internals
     DeviceContextPtr device() const { return dev_; }
+    // the same mesh into another context (one rank): the child contexts of the block preconditioners (LinearSolver)
+    void uploadMeshTo(fedd_ctx* ctx) const {
+        std::vector<int64_t> grep(mapRepeated_->gids().begin(), mapRepeated_->gids().end()), guni(mapUnique_->gids().begin(), mapUnique_->gids().end());
+        feddCheck(fedd_mesh_set(ctx, dim_, nen_, (int64_t)(conn_.size() / nen_), conn_.data(), (int64_t)grep.size(), xyz_.data(), grep.data(),
+                                (int64_t)guni.size(), guni.data(), flagUni_.data()), "fedd_mesh_set");
+    }
     int nodesPerElement() const { return nen_; }
     const std::vector<double>& xyzRepeated() const { return xyz_; }
     const std::vector<int32_t>& uniqueLocalOfRepeated() const { return uniOfRep_; }
@@ -939,6 +945,10 @@ public:
         std::fill(values.begin(), values.end(), 0.);
         feddCheck(fedd_dirichlet_rows(dev->ctx, (int64_t)rows.size(), rows.data(), values.data()), "fedd_dirichlet_rows");
     }
+    // the Dirichlet rows of one block in the merged numbering (block 0: the block's own numbering), values at time 0
+    void dirichletRowsOfBlock(const BlockMultiVectorPtr_Type& layout, int block, std::vector<int32_t>& rows, std::vector<double>& values) const {
+        mergedDirichletRows(layout, block, 0., rows, values);
+    }
     // BCBuilder::setRHS (:93-170), setVectorMinusBC and setBCMinusVector (the boundary rows of a nonlinear residual):
     // which = 0: v <- g, 1: v <- x - g, 2: v <- g - x on the Dirichlet rows
     void setRows(const BlockMultiVectorPtr_Type& v, const BlockMultiVectorPtr_Type& x, double t, int which) const {
@@ -1060,6 +1070,12 @@ public:
     typedef BlockMultiVector<SC, LO, GO, NO> BlockMultiVector_Type;
     typedef Teuchos::RCP<BlockMultiVector_Type> BlockMultiVectorPtr_Type;
     int solve(Problem_Type* problem, BlockMultiVectorPtr_Type rhs, std::string type = "Monolithic");
+    // the FROSch keys of one "ThyraPreconditioner" list -> fedd_schwarz_set_* + fedd_schwarz_setup on one context (the merged
+    // system, or a block of it)
+    static void setupSchwarz(fedd_ctx* ctx, Teuchos::ParameterList& thyraPrec, Teuchos::ParameterList& pl, bool blocks, bool verbose);
+    static int combineMode(Teuchos::ParameterList& frosch);
+    // "Diagonal" / "Triangular": children, import, pressure mass matrix, setups, attach (PrecBlock2x2)
+    static void setupBlockPreconditioner(Problem_Type* problem, fedd_ctx* ctx, const std::string& type);
     double lastRelativeResidual = 0.;
 private:
     typedef MultiVector<SC, LO, GO, NO> MV;
@@ -1273,6 +1289,16 @@ public:
     void addParemeterRhs(double para) { parasSourceFunc_.push_back(para); }
     double getLastRelativeResidual() const { return lastRelativeResidual_; }
     BCConstPtr_Type getBCFactory() const { return bcFactory_; }      // what TimeProblem reads (fedd_time.hpp)
+    // "Preconditioner Method" = "Diagonal" / "Triangular": the two child contexts (the reference's MinPrecProblems,
+    // Preconditioner_def.hpp:979-1062), made by the first solve that asks for them and kept for the problem's life.  The
+    // pressure mass matrix (Stokes_def.hpp:122-132, NavierStokes_def.hpp:177-183) is assembled in the Schur child, once.
+    struct BlockPrecChildren {
+        DeviceContextPtr velocity, schur;
+        bool schurReady = false;
+        fedd_ctx* parent = nullptr;
+        ~BlockPrecChildren() { if (parent) fedd_block_prec_detach(parent); }
+    };
+    Teuchos::RCP<BlockPrecChildren>& blockPrecChildren() const { return blockPrec_; }
     FEFacPtr_Type getFEFactory() const { return feFactory_; }
 
     int dim_;
@@ -1286,6 +1312,7 @@ protected:
     mutable DomainConstPtr_vec_Type domainPtr_vec_;
     std::vector<std::string> domain_FEType_vec_, variableName_vec_;
     mutable BCConstPtr_Type bcFactory_;
+    mutable Teuchos::RCP<BlockPrecChildren> blockPrec_;
     FEFacPtr_Type feFactory_;
     std::vector<int> dofsPerNode_vec_;
     mutable BlockMultiVectorPtr_Type sourceTerm_;
@@ -1297,8 +1324,11 @@ protected:
 
 template <class SC, class LO, class GO, class NO>
 int LinearSolver<SC, LO, GO, NO>::solve(Problem_Type* problem, BlockMultiVectorPtr_Type rhs, std::string type) {
-    TEUCHOS_TEST_FOR_EXCEPTION(type != "Monolithic" && type != "MonolithicConstPrec", std::logic_error,
-                               "Unknown solver type; only the monolithic path (LinearSolver_def.hpp:72-135) is built.");
+    const bool constPrec = type.size() > 9 && type.compare(type.size() - 9, 9, "ConstPrec") == 0;
+    const std::string method = constPrec ? type.substr(0, type.size() - 9) : type;
+    const bool blockMethod = method == "Diagonal" || method == "Triangular";
+    TEUCHOS_TEST_FOR_EXCEPTION(method != "Monolithic" && !blockMethod, std::logic_error,
+                               "\"Preconditioner Method\" = \"" + type + "\" is not built (Monolithic, Diagonal and Triangular are, each also as ...ConstPrec; Teko and FaCSI are not)");
     auto system = problem->getSystem();
     const bool blocks = system->size() > 1;
     TEUCHOS_TEST_FOR_EXCEPTION(blocks && system->mergedDevice().is_null(), std::logic_error,
@@ -1320,52 +1350,24 @@ int LinearSolver<SC, LO, GO, NO>::solve(Problem_Type* problem, BlockMultiVectorP
     const int numBlocks = gm.get("Num Blocks", 100);
     auto& frosch = pl->sublist("ThyraPreconditioner").sublist("Preconditioner Types").sublist("FROSch");
     const std::string precType = pl->sublist("ThyraPreconditioner").get("Preconditioner Type", "FROSch");
-    const int overlap = frosch.get("Overlap", 1);
-    auto& ovl = frosch.sublist("AlgebraicOverlappingOperator");
-    std::string combine = ovl.get("Combine Values in Overlap", "");
-    if (combine.empty()) combine = ovl.get("Overlapping Operator Combination", "Restricted");
-    const int cmb = combine == "Averaging" ? FEDD_COMBINE_AVERAGING : (combine == "Full" ? FEDD_COMBINE_FULL : FEDD_COMBINE_RESTRICTED);
-    const bool usePrec = precType != "None";
+    const int cmb = combineMode(frosch);
+    const bool usePrec = precType != "None" || blockMethod;
     // CG needs a symmetric preconditioner (the words of fedd_cg's own error)
     TEUCHOS_TEST_FOR_EXCEPTION(useCg && usePrec && problem->getUserPreconditioner().is_null() && cmb != FEDD_COMBINE_FULL, std::logic_error,
                                solverType + ": preconditioner not symmetric: use FEDD_COMBINE_FULL (\"Combine Values in Overlap\" = \"Full\")");
     TEUCHOS_TEST_FOR_EXCEPTION(useCg && !problem->getUserPreconditioner().is_null(), std::logic_error,
                                solverType + ": user preconditioner operators run with Block GMRES only");
     TEUCHOS_TEST_FOR_EXCEPTION(useCg && blocks, std::logic_error, solverType + ": a merged block system is not symmetric positive definite; use Block GMRES");
-    if (usePrec && type != "MonolithicConstPrec") {
-        // "TwoLevel" = true (parametersPrec.xml:17) switches the coarse level on.  The coarse space is
-        // this library's lattice space, not FROSch's GDSW: say so.
-        const bool twoLevel = frosch.get("TwoLevel", false);
-        // "CoarseOperator Type" (parametersPrec.xml:23): GDSWCoarseOperator / RGDSWCoarseOperator -> the library's GDSW /
-        // RGDSW level on the coarse lattice; "Q1" = lattice hat functions; anything else (IPOUHarmonicCoarseOperator, the
-        // third value the reference's XML files list) is not built: an error, not a silent substitute
-        const std::string coarseType = frosch.get("CoarseOperator Type", "GDSWCoarseOperator");
-        const int coarseKind = coarseType == "Q1" ? FEDD_COARSE_Q1 : (coarseType == "RGDSWCoarseOperator" ? FEDD_COARSE_RGDSW : FEDD_COARSE_GDSW);
-        TEUCHOS_TEST_FOR_EXCEPTION(twoLevel && coarseType != "GDSWCoarseOperator" && coarseType != "RGDSWCoarseOperator" && coarseType != "Q1",
-                                   std::logic_error, "CoarseOperator Type \"" + coarseType + "\" is not built (GDSWCoarseOperator, RGDSWCoarseOperator, Q1 are)");
-        const int target = frosch.get("Subdomain Nodes", 0);   // 0 = the library's default (27 / dofs per node)
-        feddCheck(fedd_schwarz_set_target(ctx, target, 1.0), "fedd_schwarz_set_target");
-        feddCheck(fedd_schwarz_set_coarse(ctx, frosch.get("Coarse Cells", 0.0)), "fedd_schwarz_set_coarse");
-        // merged block systems: monolithic one-level Schwarz on the large-subdomain path; the coarse level takes
-        // node-interleaved systems only (said once)
-        if (blocks && twoLevel && problem->getVerbose())
-            std::cout << "-- note: the coarse level is not built for merged block systems; running one level --" << std::endl;
-        const bool two = twoLevel && !blocks;
-        // rotations in the null space of the coarse space: "Rotations" of the coarse operator's block 1
-        // (steadyLinElas/parametersPrec.xml:100), which FROSch can only build from the node coordinates the reference hands over
-        // with "Use node lists" (Preconditioner_def.hpp:266, 353-381; default true).  The library ignores the switch for
-        // scalar problems (a rotation needs dofs = dim).
-        if (two && coarseKind != FEDD_COARSE_Q1) {
-            const bool nodeLists = pl->get("Use node lists", true);
-            const bool rotations = frosch.sublist(coarseType).sublist("Blocks").sublist("1").get("Rotations", false);
-            feddCheck(fedd_set_option(ctx, "gdsw_rotations", nodeLists && rotations ? 1.0 : 0.0), "fedd_set_option(gdsw_rotations)");
-        }
-        feddCheck(fedd_schwarz_setup(ctx, overlap, cmb, two ? 1 : 0, two ? coarseKind : 0), "fedd_schwarz_setup");
-        // "Level Combination" = "Multiplicative" (parametersPrec.xml:19): FROSch's TwoLevelPreconditioner combines the levels
-        // in every apply of the solve, z = (I - Pc A) M1^-1 r; the coarse pre-apply below supplies the Pc b term
-        const bool mult = two && std::string(frosch.get("Level Combination", "Additive")) == "Multiplicative";
-        feddCheck(fedd_schwarz_set_level_combination(ctx, mult ? FEDD_LEVELS_MULTIPLICATIVE : FEDD_LEVELS_ADDITIVE),
-                  "fedd_schwarz_set_level_combination");
+    if (blockMethod) {
+        TEUCHOS_TEST_FOR_EXCEPTION(!blocks || system->size() != 2, std::logic_error,
+                                   "\"Preconditioner Method\" = \"" + type + "\" needs a 2 x 2 block system (Stokes, NavierStokes)");
+        TEUCHOS_TEST_FOR_EXCEPTION(!problem->getUserPreconditioner().is_null(), std::logic_error, type + ": not with a user preconditioner operator");
+        if (!constPrec) setupBlockPreconditioner(problem, ctx, method);
+        TEUCHOS_TEST_FOR_EXCEPTION(problem->blockPrecChildren().is_null(), std::logic_error, type + ": no preconditioner has been built yet to keep");
+    } else {
+        // a block preconditioner of an earlier solve does not outlive a change of method
+        if (!problem->blockPrecChildren().is_null()) problem->blockPrecChildren() = Teuchos::null;
+        if (usePrec && !constPrec) setupSchwarz(ctx, pl->sublist("ThyraPreconditioner"), *pl, blocks, problem->getVerbose());
     }
     auto b = rhs.is_null() ? problem->getRhs() : rhs;
     auto x = problem->getSolution();
@@ -1377,7 +1379,7 @@ int LinearSolver<SC, LO, GO, NO>::solve(Problem_Type* problem, BlockMultiVectorP
     // preconditioner set up above)
     const bool zeroGuess = pl->get("Zero Initial Guess", true);
     if (zeroGuess) x->putScalar(0.);
-    const bool multiplicative = usePrec && std::string(frosch.get("Level Combination", "Additive")) == "Multiplicative";
+    const bool multiplicative = usePrec && !blockMethod && std::string(frosch.get("Level Combination", "Additive")) == "Multiplicative";
     TEUCHOS_TEST_FOR_EXCEPTION(multiplicative && (blocks || !frosch.get("TwoLevel", false)), std::logic_error,
                                "Level Combination = Multiplicative needs the coarse level (TwoLevel = true, single-block system)");
     if (!problem->getUserPreconditioner().is_null()) {
@@ -1419,6 +1421,107 @@ int LinearSolver<SC, LO, GO, NO>::solve(Problem_Type* problem, BlockMultiVectorP
     }
     lastRelativeResidual = rel;
     return its;
+}
+
+template <class SC, class LO, class GO, class NO>
+int LinearSolver<SC, LO, GO, NO>::combineMode(Teuchos::ParameterList& frosch) {
+    auto& ovl = frosch.sublist("AlgebraicOverlappingOperator");
+    std::string combine = ovl.get("Combine Values in Overlap", "");
+    if (combine.empty()) combine = ovl.get("Overlapping Operator Combination", "Restricted");
+    return combine == "Averaging" ? FEDD_COMBINE_AVERAGING : (combine == "Full" ? FEDD_COMBINE_FULL : FEDD_COMBINE_RESTRICTED);
+}
+
+template <class SC, class LO, class GO, class NO>
+void LinearSolver<SC, LO, GO, NO>::setupSchwarz(fedd_ctx* ctx, Teuchos::ParameterList& thyraPrec, Teuchos::ParameterList& pl, bool blocks, bool verbose) {
+    auto& frosch = thyraPrec.sublist("Preconditioner Types").sublist("FROSch");
+    const int overlap = frosch.get("Overlap", 1);
+    const int cmb = combineMode(frosch);
+    // "TwoLevel" = true (parametersPrec.xml:17) switches the coarse level on.  The coarse space is
+    // this library's lattice space, not FROSch's GDSW: say so.
+    const bool twoLevel = frosch.get("TwoLevel", false);
+    // "CoarseOperator Type" (parametersPrec.xml:23): GDSWCoarseOperator / RGDSWCoarseOperator -> the library's GDSW /
+    // RGDSW level on the coarse lattice; "Q1" = lattice hat functions; anything else (IPOUHarmonicCoarseOperator, the
+    // third value the reference's XML files list) is not built: an error, not a silent substitute
+    const std::string coarseType = frosch.get("CoarseOperator Type", "GDSWCoarseOperator");
+    const int coarseKind = coarseType == "Q1" ? FEDD_COARSE_Q1 : (coarseType == "RGDSWCoarseOperator" ? FEDD_COARSE_RGDSW : FEDD_COARSE_GDSW);
+    TEUCHOS_TEST_FOR_EXCEPTION(twoLevel && coarseType != "GDSWCoarseOperator" && coarseType != "RGDSWCoarseOperator" && coarseType != "Q1",
+                               std::logic_error, "CoarseOperator Type \"" + coarseType + "\" is not built (GDSWCoarseOperator, RGDSWCoarseOperator, Q1 are)");
+    const int target = frosch.get("Subdomain Nodes", 0);   // 0 = the library's default (27 / dofs per node)
+    feddCheck(fedd_schwarz_set_target(ctx, target, 1.0), "fedd_schwarz_set_target");
+    feddCheck(fedd_schwarz_set_coarse(ctx, frosch.get("Coarse Cells", 0.0)), "fedd_schwarz_set_coarse");
+    // merged block systems: monolithic one-level Schwarz on the large-subdomain path; the coarse level takes
+    // node-interleaved systems only (said once)
+    if (blocks && twoLevel && verbose)
+        std::cout << "-- note: the coarse level is not built for merged block systems; running one level --" << std::endl;
+    const bool two = twoLevel && !blocks;
+    // rotations in the null space of the coarse space: "Rotations" of the coarse operator's block 1
+    // (steadyLinElas/parametersPrec.xml:100), which FROSch can only build from the node coordinates the reference hands over
+    // with "Use node lists" (Preconditioner_def.hpp:266, 353-381; default true).  The library ignores the switch for
+    // scalar problems (a rotation needs dofs = dim).
+    if (two && coarseKind != FEDD_COARSE_Q1) {
+        const bool nodeLists = pl.get("Use node lists", true);
+        const bool rotations = frosch.sublist(coarseType).sublist("Blocks").sublist("1").get("Rotations", false);
+        feddCheck(fedd_set_option(ctx, "gdsw_rotations", nodeLists && rotations ? 1.0 : 0.0), "fedd_set_option(gdsw_rotations)");
+    }
+    feddCheck(fedd_schwarz_setup(ctx, overlap, cmb, two ? 1 : 0, two ? coarseKind : 0), "fedd_schwarz_setup");
+    // "Level Combination" = "Multiplicative" (parametersPrec.xml:19): FROSch's TwoLevelPreconditioner combines the levels
+    // in every apply of the solve, z = (I - Pc A) M1^-1 r; the coarse pre-apply below supplies the Pc b term
+    const bool mult = two && std::string(frosch.get("Level Combination", "Additive")) == "Multiplicative";
+    feddCheck(fedd_schwarz_set_level_combination(ctx, mult ? FEDD_LEVELS_MULTIPLICATIVE : FEDD_LEVELS_ADDITIVE),
+              "fedd_schwarz_set_level_combination");
+}
+
+// Preconditioner::buildPreconditionerBlock2x2 (Preconditioner_def.hpp:979-1062): one Schwarz preconditioner on the velocity block
+// getBlock(0,0) (slot 0 for Stokes, 4 for Navier-Stokes) with the velocity Dirichlet rows, one on (1 / nu) M_p -- the positive
+// definite matrix; the sign of the reference's -(1 / nu) M_p is the schur_scale -1 of the attach --, each from its own sublist
+// ("Velocity preconditioner", "Schur complement preconditioner": their "ThyraPreconditioner", with the "General" list merged
+// in as :1003-1008 does).  The children are made once per problem; every call imports the velocity block again (values only
+// when its pattern stands: the Newton loop) and sets the velocity child up again; the Schur child is built once and kept.
+template <class SC, class LO, class GO, class NO>
+void LinearSolver<SC, LO, GO, NO>::setupBlockPreconditioner(Problem_Type* problem, fedd_ctx* ctx, const std::string& method) {
+    auto pl = problem->getParameterList();
+    auto system = problem->getSystem();
+    auto& kids = problem->blockPrecChildren();
+    if (kids.is_null()) {
+        kids = Teuchos::rcp(new typename Problem_Type::BlockPrecChildren());
+        kids->velocity = Teuchos::rcp(new DeviceContext(problem->getDomain(0)->getComm()));
+        kids->schur = Teuchos::rcp(new DeviceContext(problem->getDomain(1)->getComm()));
+        problem->getDomain(0)->uploadMeshTo(kids->velocity->ctx);
+        problem->getDomain(1)->uploadMeshTo(kids->schur->ctx);
+    }
+    auto sublistOf = [&](const char* name) -> Teuchos::ParameterList& {
+        auto& sub = pl->sublist(name);
+        sub.sublist("General").setParameters(pl->sublist("General"));
+        return sub;
+    };
+    feddCheck(fedd_sync(ctx), "fedd_sync");
+    // velocity: F = getBlock(0,0), its Dirichlet rows, its setup
+    const int slotF = system->getBlock(0, 0)->slot();
+    TEUCHOS_TEST_FOR_EXCEPTION(slotF < 0, std::logic_error, method + ": block (0,0) is not a stored block of the device");
+    feddCheck(fedd_matrix_import(kids->velocity->ctx, ctx, slotF), "fedd_matrix_import");
+    TEUCHOS_TEST_FOR_EXCEPTION(problem->getBCFactory().is_null(), std::runtime_error, "No boundary conditions added.");
+    std::vector<int32_t> rows;
+    std::vector<double> values;
+    problem->getBCFactory()->dirichletRowsOfBlock(problem->getRhs(), 0, rows, values);
+    std::fill(values.begin(), values.end(), 0.);
+    feddCheck(fedd_dirichlet_rows(kids->velocity->ctx, (int64_t)rows.size(), rows.data(), values.data()), "fedd_dirichlet_rows");
+    auto& velList = sublistOf("Velocity preconditioner");
+    setupSchwarz(kids->velocity->ctx, velList.sublist("ThyraPreconditioner"), velList, false, problem->getVerbose());
+    // Schur complement: (1 / nu) M_p on the pressure mesh
+    if (!kids->schurReady) {
+        const double viscosity = pl->sublist("Parameter").get("Viscosity", 1.);
+        TEUCHOS_TEST_FOR_EXCEPTION(!(viscosity > 0.), std::logic_error, method + ": the pressure mass matrix is scaled by 1 / Viscosity, which must be positive");
+        feddCheck(fedd_pattern_build(kids->schur->ctx, 1, FEDD_BLOCK_SCALAR, nullptr), "fedd_pattern_build");
+        feddCheck(fedd_assemble(kids->schur->ctx, FEDD_FORM_MASS, nullptr), "fedd_assemble");
+        feddCheck(fedd_matrix_scale(kids->schur->ctx, -1, 1. / viscosity), "fedd_matrix_scale");
+        auto& schurList = sublistOf("Schur complement preconditioner");
+        setupSchwarz(kids->schur->ctx, schurList.sublist("ThyraPreconditioner"), schurList, false, problem->getVerbose());
+        kids->schurReady = true;
+    }
+    feddCheck(fedd_block_prec_attach(ctx, method == "Diagonal" ? FEDD_BLOCKPREC_DIAGONAL : FEDD_BLOCKPREC_TRIANGULAR, kids->velocity->ctx,
+                                     kids->schur->ctx, -1., 2), "fedd_block_prec_attach");
+    kids->parent = ctx;
+    if (problem->getVerbose()) std::cout << "-- block preconditioner " << method << ": velocity block from slot " << slotF << " --" << std::endl;
 }
 
 // Laplace (feddlib/problems/specific/Laplace_def.hpp:16-60)
@@ -1897,8 +2000,8 @@ public:
         TEUCHOS_TEST_FOR_EXCEPTION(type_ != "FixedPoint" && type_ != "Newton", std::logic_error,
                                    "\"Linearization\" = \"" + type_ + "\" is not built (FixedPoint and Newton are)");
         const std::string prec = pl->sublist("General").get("Preconditioner Method", "Monolithic");
-        TEUCHOS_TEST_FOR_EXCEPTION(prec != "Monolithic", std::logic_error,
-                                   "\"Preconditioner Method\" = \"" + prec + "\" is not built (Monolithic is; Teko is out of scope)");
+        TEUCHOS_TEST_FOR_EXCEPTION(prec != "Monolithic" && prec != "Diagonal" && prec != "Triangular", std::logic_error,
+                                   "\"Preconditioner Method\" = \"" + prec + "\" is not built (Monolithic, Diagonal and Triangular are; Teko and FaCSI are not)");
         TEUCHOS_TEST_FOR_EXCEPTION(pl->sublist("Parameter").get("Symmetric gradient", false), std::logic_error,
                                    "\"Symmetric gradient\" = true: assemblyStress is not built");
         const std::string levels = pl->sublist("ThyraPreconditioner").sublist("Preconditioner Types").sublist("FROSch").get("Level Combination", "Additive");

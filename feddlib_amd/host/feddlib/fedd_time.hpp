@@ -291,6 +291,10 @@ public:
         problem_->system_ = systemCombined_;
         LinearSolver<SC, LO, GO, NO> linSolver;
         int its = 0;
+        const std::string method = pl->sublist("General").get("Preconditioner Method", "Monolithic");
+        TEUCHOS_TEST_FOR_EXCEPTION(method != "Monolithic", std::logic_error,
+                                   "TimeProblem: \"Preconditioner Method\" = \"" + method + "\" is not built for time problems (Monolithic is; "
+                                   "Diagonal and Triangular are built for the steady Stokes and Navier-Stokes problems)");
         try {
             its = linSolver.solve(problem_, Teuchos::null, fresh_ ? "Monolithic" : "MonolithicConstPrec");
         } catch (...) {

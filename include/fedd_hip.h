@@ -88,7 +88,8 @@ enum fedd_timer {
     FEDD_T_NEWMARK  = 23, /* Newmark state update: k_newmark (timestep.hip)             */
     FEDD_T_BLOCK_APPLY = 24, /* y = alpha M x on a stored block: k_block_apply          */
     FEDD_T_MULTISTEP = 25, /* BDF history update: k_multistep (timestep.hip)              */
-    FEDD_T_COUNT    = 26
+    FEDD_T_BLOCKPREC_BT = 26, /* Triangular block preconditioner: t = r_u - B^T z_p, k_bt_sub (blockprec.hip) */
+    FEDD_T_COUNT    = 27
 };
 
 /* ------------------------------------------------------------------------------------------------
@@ -100,7 +101,8 @@ enum fedd_timer {
 int  fedd_ctx_create(fedd_ctx** out, int device, const void* nccl_unique_id, int rank, int nranks);
 void fedd_ctx_destroy(fedd_ctx* ctx);
 const char* fedd_last_error(void);
-int  fedd_sync(fedd_ctx* ctx);                       /* hipStreamSynchronize on the context's stream */
+int  fedd_sync(fedd_ctx* ctx);                       /* hipStreamSynchronize on the context's stream (and on the streams of
+                                                        the children of an attached block preconditioner) */
 int  fedd_nccl_unique_id(void* id128);               /* rank 0 calls this, then shares the 128 bytes */
 
 /* ------------------------------------------------------------------------------------------------
@@ -667,6 +669,80 @@ int fedd_cg_x0(fedd_ctx* ctx, const double* b_owned, double* x_owned, double rto
 #define FEDD_CG_BREAKDOWN_NONFINITE 3   /* a dot product was not finite */
 #define FEDD_CG_BREAKDOWN_NONSYMMETRIC 4 /* the matrix is not symmetric on its free rows (probed on the first direction) */
 int fedd_cg_info(fedd_ctx* ctx, int* replacements, int* breakdown);
+
+/* ------------------------------------------------------------------------------------------------
+ * Block preconditioners for merged 2 x 2 systems (Stokes, Navier-Stokes), one rank: the reference's "Preconditioner Method" =
+ * "Diagonal" / "Triangular", PrecBlock2x2::applyIt (feddlib/problems/Solver/PrecBlock2x2_def.hpp:114-164) as built by
+ * Preconditioner::buildPreconditionerBlock2x2 (Preconditioner_def.hpp:979-1062) with the pressure mass matrix of
+ * Stokes_def.hpp:122-132 / NavierStokes_def.hpp:177-183.  The reference keeps a small problem of its own per block
+ * (MinPrecProblem); here each block is a CHILD CONTEXT: a fedd_ctx with the block's mesh, whose system matrix is the block and
+ * whose fedd_schwarz_setup -- one-level or two-level, Q1 / GDSW / RGDSW, rotations, every option of the single-block path -- is the
+ * block's preconditioner.  A context holds one Schwarz preconditioner, so two of them need two contexts.
+ *
+ *   fedd_matrix_import    dst's system matrix <- the block stored in src's slot, pattern and values, device to device (no host
+ *                         round trip); both contexts on one device, one rank each.  dst must carry a mesh (fedd_mesh_set) without
+ *                         ghost nodes whose owned nodes x dofs per node (1 .. 3) equal the block's rows; the block must be square.
+ *                         Right-hand side and solution of dst are zeroed and its Dirichlet marks cleared, as by fedd_block_merge;
+ *                         the solver setups of dst are dropped.  The generations move as after a fedd_matrix_store in the other
+ *                         direction.  A second import of a block whose pattern id has not changed (the slot of
+ *                         fedd_assemble_advection in a Newton loop) moves values only and keeps dst's pattern generation, so the
+ *                         next fedd_schwarz_setup of dst keeps its structure stage (fedd_schwarz_reuse_info).  The copies run in
+ *                         dst's stream behind what src's stream has written, and src's stream waits for them: no host
+ *                         synchronisation.  Errors that name the cause: an empty slot, a non-square block, a size mismatch,
+ *                         contexts on different devices, more than one rank, a host-only context ("needs a GPU context").
+ *   fedd_block_prec_attach
+ *                         ctx holds a merged system (fedd_block_merge; block row 0 = n_A rows, block row 1 = n_p rows); velocity
+ *                         and schur are contexts on the same device whose systems have n_A and n_p rows.  The pointers are NOT
+ *                         owned: destroying ctx leaves the children alive.  fedd_ctx_destroy of a child that is still attached
+ *                         first waits for ctx's stream and detaches ctx (whose next preconditioned solve is then the error of a
+ *                         context without a preconditioner); detaching before destroying a child remains the orderly way.  While attached, fedd_gmres / fedd_gmres_x0 with use_prec = 1 and fedd_schwarz_apply /
+ *                         fedd_schwarz_apply_device on ctx apply the block operator below in the place of ctx's own Schwarz
+ *                         preconditioner (which need not exist); fedd_cg on a merged system stays an error.
+ *                         Checked at the attach: NULL children, the kind, more than one rank, child meshes that cannot belong to
+ *                         ctx (the velocity child's owned nodes differ from ctx's), an unmerged parent, other devices.  Checked at
+ *                         EVERY apply, because a child may be set up again between two solves, with errors that name the child: a
+ *                         child without a current fedd_schwarz_setup, wrong sizes, an unmerged parent, slot_bt empty or of another
+ *                         shape than n_A x n_p (Triangular), more than one rank, a child under FEDD_LEVELS_MULTIPLICATIVE (that
+ *                         operator is singular by construction).
+ *   fedd_block_prec_detach
+ *                         ctx's own preconditioner is in force again (an error in fedd_gmres if none was set up).
+ *   fedd_block_prec_info  kind (0: none attached), schur_scale, slot_bt (-1 for Diagonal), applies since the attach.  Needs no
+ *                         device; outputs may be NULL.
+ *
+ * The apply (NORMATIVE; PrecBlock2x2_def.hpp:135-160).  r = [r_u; r_p], z = [z_u; z_p], both contiguous in the merged layout;
+ * V and S are the children's Schwarz applies, called on pointers into ctx's device vectors (no staging copy of r or z):
+ *     FEDD_BLOCKPREC_DIAGONAL:     z_u = V(r_u)
+ *                                  z_p = schur_scale * S(r_p)
+ *     FEDD_BLOCKPREC_TRIANGULAR:   s   = S(r_p)
+ *                                  z_p = schur_scale * s                                         (rounded)
+ *                                  t_i = r_u,i - (sum_k B^T_ik z_p,col(k))     on the rows that are no Dirichlet rows of ctx's system
+ *                                  t_i = r_u,i                                  on Dirichlet rows (the reference's B^T has had
+ *                                                                               setLocalRowZero there, BCBuilder_def.hpp:653-707;
+ *                                                                               the stored slot has not)
+ *                                  z_u = V(t)
+ * z_p and t are written by ONE kernel, a single pass over the rectangular CSR of slot_bt that reads s, r_u and the Dirichlet
+ * marks.  Its row sums are those of fedd_matrix_apply: the same group of lanes per row (8 for rows of at most 32 entries, else
+ * 16), each lane adding its products in ascending column order, the same fixed tree; every product is rounded before it is
+ * added (no contraction) and the sum is rounded before the subtraction.  So B^T z_p is bit for bit what
+ * fedd_matrix_apply(ctx, slot_bt, 1.0, z_p) returns, and two applies agree bit for bit whenever the children's do
+ * (FEDD_COMBINE_RESTRICTED one-level children do).  Bytes: 12 nnz(B^T) + 4 (n_A + 1) + 4 n_A + 16 n_A + 16 n_p.
+ *
+ * schur_scale: one-level and additive two-level Schwarz are homogeneous of degree -1 in the matrix, S_{aM} = S_M / a.  The Schur
+ * child holds the POSITIVE definite (1/nu) M_p, the caller passes schur_scale = -1, and the result is what the reference gets
+ * from -(1/nu) M_p -- without the local and coarse factorisations ever seeing a negative definite matrix.
+ *
+ * Ordering: while attached, the children's apply kernels are enqueued in ctx's stream, so V, S and the kernel between them are
+ * ordered by the stream alone -- no event and no host synchronisation inside the Krylov loop -- and fedd_sync(ctx) covers them
+ * (it also waits for the children's own streams).  What a child did in its own stream before (import, Dirichlet rows, setup) is
+ * ordered in front by one event per fedd_schwarz_setup of the child.  The caller synchronises ctx (fedd_sync, or a solve that
+ * returned x) before it changes a child.
+ * ---------------------------------------------------------------------------------------------- */
+#define FEDD_BLOCKPREC_DIAGONAL 1
+#define FEDD_BLOCKPREC_TRIANGULAR 2
+int fedd_matrix_import(fedd_ctx* dst, fedd_ctx* src, int src_slot);
+int fedd_block_prec_attach(fedd_ctx* ctx, int kind, fedd_ctx* velocity, fedd_ctx* schur, double schur_scale, int slot_bt);
+int fedd_block_prec_detach(fedd_ctx* ctx);
+int fedd_block_prec_info(fedd_ctx* ctx, int* kind, double* schur_scale, int* slot_bt, int64_t* n_applies);
 /* The structures that depend on the mesh alone are built once per mesh, at the first call that needs them, and reused by every
  * later assembly: the node -> element adjacency (fedd_pattern_build) and the element-major tile structures of the assembly
  * kernel (fedd_assemble, P1 forms).  Their wall time (ms, device synchronised before and after) is not part of a steady-state
