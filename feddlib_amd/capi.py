@@ -18,7 +18,8 @@ COMBINE_RESTRICTED, COMBINE_AVERAGING, COMBINE_FULL = range(3)
  T_COARSE_APPLY, T_HALO, T_ALLREDUCE, T_SPMV_SETUP) = range(13)
 TIMER_NAMES = ["symbolic", "assemble", "rhs", "dirichlet", "spmv", "schwarz_setup", "schwarz_apply", "ortho",
                "coarse_setup", "coarse_apply", "halo", "allreduce", "spmv_setup", "gs_dot", "gs_update", "gs_fused",
-               "full_park_mfma", "full_park", "full_gather", "cg_pq", "cg_xr", "cg_rz", "cg_p", "newmark_state", "block_apply", "multistep_state", "blockprec_bt"]
+               "full_park_mfma", "full_park", "full_gather", "cg_pq", "cg_xr", "cg_rz", "cg_p", "newmark_state", "block_apply", "multistep_state", "blockprec_bt",
+               "newton_residual", "newton_update"]
 COARSE_Q1 = 1
 COARSE_GDSW = 2
 COARSE_RGDSW = 3
@@ -84,6 +85,14 @@ SIGNATURES = {
     "fedd_assemble_advection": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int],
     "fedd_assemble_hyperelastic": [C.c_void_p, C.c_int, _f64p, C.c_int, C.c_int],
     "fedd_hyperelastic_force_get": [C.c_void_p, _f64p],
+    "fedd_assemble_hyperelastic_time": [C.c_void_p, C.c_int, _f64p, C.c_int, C.c_int, C.c_int, C.c_double],
+    "fedd_newton_begin": [C.c_void_p],
+    "fedd_newton_source_set": [C.c_void_p, _f64p],
+    "fedd_newton_residual": [C.c_void_p, C.c_int, C.c_double, C.c_int, _i32p, _i32p, _f64p, _f64p],
+    "fedd_newton_update": [C.c_void_p, C.c_double, _f64p],
+    "fedd_newton_end": [C.c_void_p],
+    "fedd_newton_get": [C.c_void_p, _f64p],
+    "fedd_newton_info": [C.c_void_p, _ip, _i64p, _ip, _ip, _i64p, _i64p],
     "fedd_matrix_combine": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double],
     "fedd_matrix_combine_current": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, _ip],
     "fedd_matrix_apply": [C.c_void_p, C.c_int, C.c_double, _f64p, _f64p],
@@ -555,6 +564,58 @@ class Context:
         f = np.zeros(self.n_own * self._dim, dtype=np.float64)
         _chk(self._L.fedd_hyperelastic_force_get(self._h, _p(f, _f64p)))
         return f
+
+    def assemble_hyperelastic_time(self, model, params, slot_m, cm, what=HYPER_TANGENT | HYPER_FORCE):
+        """assemble_hyperelastic with (cm * M[slot_m]) + K(u) as tangent, in one pass (fedd_assemble_hyperelastic_time)"""
+        p = np.ascontiguousarray(params, dtype=np.float64).ravel()
+        _chk(self._L.fedd_assemble_hyperelastic_time(self._h, int(model), _p(p, _f64p), p.shape[0], int(what), int(slot_m), float(cm)))
+
+    def newton_begin(self):
+        """u_k <- the current solution, b <- the current right-hand side (held), nodal vector field <- u_k"""
+        _chk(self._L.fedd_newton_begin(self._h))
+
+    def newton_source_set(self, s=None):
+        """the step's source vector (None clears it)"""
+        if s is not None:
+            s = np.ascontiguousarray(s, dtype=np.float64)
+            if s.shape[0] != self.csr_sizes()[0]:
+                raise FeddError("newton_source_set: vector of %d entries, the system has %d rows" % (s.shape[0], self.csr_sizes()[0]))
+        _chk(self._L.fedd_newton_source_set(self._h, _p(s, _f64p)))
+
+    def newton_residual(self, slot_m, cm, flags=(), values=None, comp_mask=None):
+        """rhs <- ((b - f) + s) - cm M u_k, Dirichlet rows g - u_k; returns ||rhs||_2 (fedd_newton_residual)"""
+        fl = np.ascontiguousarray(flags, dtype=np.int32)
+        n = fl.shape[0]
+        v = np.zeros(max(1, n * self.dofs)) if values is None else np.ascontiguousarray(values, dtype=np.float64).ravel()
+        m = None if comp_mask is None else np.ascontiguousarray(comp_mask, dtype=np.int32).ravel()
+        nr = C.c_double()
+        _chk(self._L.fedd_newton_residual(self._h, int(slot_m), float(cm), n, _p(fl, _i32p), _p(m, _i32p), _p(v, _f64p), C.byref(nr)))
+        return nr.value
+
+    def newton_update(self, alpha=1.0):
+        """u_k <- u_k + alpha * (the device's solution vector), nodal vector field <- u_k; returns the update's 2-norm"""
+        nd = C.c_double()
+        _chk(self._L.fedd_newton_update(self._h, float(alpha), C.byref(nd)))
+        return nd.value
+
+    def newton_end(self):
+        """solution vector <- u_k, right-hand side <- the held one"""
+        _chk(self._L.fedd_newton_end(self._h))
+
+    def newton_info(self):
+        a, hs, ff = C.c_int(), C.c_int(), C.c_int()
+        n, nr, nu = C.c_int64(), C.c_int64(), C.c_int64()
+        _chk(self._L.fedd_newton_info(self._h, C.byref(a), C.byref(n), C.byref(hs), C.byref(ff), C.byref(nr), C.byref(nu)))
+        return {"active": bool(a.value), "n": n.value, "have_source": bool(hs.value), "force_fresh": bool(ff.value),
+                "residuals": nr.value, "updates": nu.value}
+
+    def newton_get(self):
+        info = self.newton_info()
+        if not info["active"]:      # the length of the host buffer comes from the state: none, no copy
+            raise FeddError("newton_get: no Newton state (fedd_newton_begin first; fedd_newton_end and fedd_mesh_set end it)")
+        out = np.zeros(info["n"])
+        _chk(self._L.fedd_newton_get(self._h, _p(out, _f64p)))
+        return out
 
     def matrix_combine(self, slot_m, cm, slot_a, ca):
         """system matrix <- (cm * M[slot_m]) + (ca * A[slot_a]) on the pattern of slot_a (TimeProblem::combineSystems)"""

@@ -219,6 +219,8 @@ static int mesh_set_impl(fedd_ctx* c, int dim, int nen, int64_t n_elem, const in
     c->adv_state = 0;    // ... and the pattern and lists of the advection matrices; the velocity belonged to the old nodes
     c->have_vel = false;
     c->hy_lists = c->have_hy_f = false;   // ... and the lists and the force vector of the hyperelastic path
+    c->nw_active = c->nw_have_src = c->nw_f_fresh = false;   // ... and the Newton state (newton.hip)
+    c->nw_n = -1;
     c->have_surf = false;   // ... and the surface elements
     c->n_surf = 0;
     for (auto& id : c->adv_pattern_id) id = 0;
@@ -511,6 +513,15 @@ extern "C" int fedd_assemble_hyperelastic(fedd_ctx* c, int model, const double* 
     FEDD_CHECK(c->n_node > 0, "fedd_assemble_hyperelastic: call fedd_mesh_set first");
     FEDD_HIP(hipSetDevice(c->device));
     return assemble_hyperelastic(c, model, params, n_params, what);
+}
+
+extern "C" int fedd_assemble_hyperelastic_time(fedd_ctx* c, int model, const double* params, int n_params, int what, int slot_m,
+                                               double cm) {
+    NEED_DEVICE(c);
+    CHECK_SLOT(slot_m);
+    FEDD_CHECK(c->n_node > 0, "fedd_assemble_hyperelastic_time: call fedd_mesh_set first");
+    FEDD_HIP(hipSetDevice(c->device));
+    return assemble_hyperelastic_time(c, model, params, n_params, what, slot_m, cm);
 }
 
 extern "C" int fedd_hyperelastic_force_get(fedd_ctx* c, double* f_owned) {

@@ -294,6 +294,14 @@ struct fedd_ctx {
     fedd::DevBuf<double> d_hy_f;                // [n_own * dim] the force vector of the last call that asked for it
     bool have_hy_f = false;
     fedd::DevBuf<int32_t> d_hy_flag;            // [1] smallest element with det F <= 0 at a quadrature point (INT32_MAX: none)
+    // ---- device-resident Newton state (newton.hip; one rank): buffers of their own, the state ends with fedd_mesh_set ----
+    fedd::DevBuf<double> d_nw_u, d_nw_b, d_nw_s;   // [nw_n] the iterate u_k, the held right-hand side b, the step's source vector
+    fedd::DevBuf<double> d_nw_part;             // per-workgroup partial sums of a norm | [1] the norm's square
+    int64_t nw_n = -1;                          // length of the system at fedd_newton_begin
+    bool nw_active = false;                     // between fedd_newton_begin and fedd_newton_end
+    bool nw_have_src = false;                   // fedd_newton_source_set gave a vector since the begin
+    bool nw_f_fresh = false;                    // d_hy_f was formed after the last fedd_newton_begin / fedd_newton_update
+    int64_t nw_residuals = 0, nw_updates = 0;   // calls since the last fedd_newton_begin
     bool merged = false;                        // system matrix = merged blocks (dof -> node map below)
     int64_t merged_nA = 0;                      // rows of block row 0
     int merged_dofsA = 1;                       // dofs per node of block row 0
@@ -632,6 +640,7 @@ int build_gather_lists(fedd_ctx* c, const int32_t* rowptr, const int32_t* colind
 
 // hyperelastic.hip
 int assemble_hyperelastic(fedd_ctx* c, int model, const double* params, int n_params, int what);
+int assemble_hyperelastic_time(fedd_ctx* c, int model, const double* params, int n_params, int what, int slot_m, double cm);
 
 // assemble_tiles.hip: the element-major tile path (P1 simplices; kform = Laplace or elasticity of assemble_common.hpp).
 // Returns -1, without error, when the mesh does not fit the tiles.

@@ -294,12 +294,28 @@ __global__ __launch_bounds__(256) void k_hyper_elem(HyArgs a, int64_t n_elem, do
     }
 }
 
-// rows of the system's FULL pattern from the element blocks, in the order of the gather lists
-template <int DIM, int NEN>
+// rows of the system's FULL pattern from the element blocks, in the order of the gather lists.  MASS != 0 (the time tangent of
+// fedd_assemble_hyperelastic_time): (cm * M) + K is stored, the product and the sum rounded on their own as k_combine_same
+// (MASS 1: M on the same FULL pattern) and k_combine_diag (MASS 2: M on the DIAG node-block pattern, one entry per slot in the
+// same slot order; an entry M does not have counts as 0.0 and is still multiplied and added) round them.  The mass entries of
+// a slot are loaded before its sources are walked.  From here to the end of the file no product is fused with a sum (the
+// kernels above this line keep the compiler's default; the ones below contain no other product followed by a sum).
+#pragma clang fp contract(off)
+
+struct HyMass {
+    int kind = 0;                   // 0 = none, 1 = same pattern, 2 = DIAG into FULL
+    const int32_t* rowptr = nullptr;
+    const double* val = nullptr;
+    double cm = 0.0;
+    int64_t nnz = 0;
+};
+
+template <int DIM, int NEN, int MASS>
 __global__ __launch_bounds__(256) void k_hyper_gather(const int32_t* __restrict__ n2e_ptr, const int32_t* __restrict__ n2e,
                                                       const int32_t* __restrict__ rowptr, int32_t nn,
                                                       const uint16_t* __restrict__ soff, const uint16_t* __restrict__ src,
-                                                      const double* __restrict__ ke, double* __restrict__ val) {
+                                                      const double* __restrict__ ke, const int32_t* __restrict__ m_rowptr,
+                                                      const double* __restrict__ m_val, double cm, double* __restrict__ val) {
     constexpr int DD = DIM * DIM;
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int64_t p = (int64_t)blockIdx.x * 4 + w; p < nn; p += (int64_t)gridDim.x * 4) {
@@ -308,8 +324,28 @@ __global__ __launch_bounds__(256) void k_hyper_gather(const int32_t* __restrict_
         const int32_t nslot = (rowptr[row + 1] - rs) / DIM, nb = rs / DD;
         const uint16_t* __restrict__ sp = src + (int64_t)ab * NEN;
         const int total = deg * NEN;
+        int32_t ms[DIM], mlen[DIM];
+        if (MASS == 2) {
+#pragma unroll
+            for (int r = 0; r < DIM; ++r) {
+                ms[r] = m_rowptr[row + r];
+                mlen[r] = m_rowptr[row + r + 1] - ms[r];
+            }
+        }
         for (int sl = lane; sl < nslot; sl += 64) {
             const int b = soff[nb + sl], e2 = sl + 1 < nslot ? (int)soff[nb + sl + 1] : total;
+            double mv[MASS == 1 ? DD : DIM];
+            if (MASS == 1) {
+#pragma unroll
+                for (int r = 0; r < DIM; ++r)
+#pragma unroll
+                    for (int cc = 0; cc < DIM; ++cc)
+                        mv[r * DIM + cc] = m_val[(int64_t)rs + (int64_t)r * nslot * DIM + (int64_t)sl * DIM + cc];
+            }
+            if (MASS == 2) {
+#pragma unroll
+                for (int r = 0; r < DIM; ++r) mv[r] = sl < mlen[r] ? m_val[ms[r] + sl] : 0.0;
+            }
             double acc[DD];
 #pragma unroll
             for (int m = 0; m < DD; ++m) acc[m] = 0.0;
@@ -323,7 +359,14 @@ __global__ __launch_bounds__(256) void k_hyper_gather(const int32_t* __restrict_
             for (int r = 0; r < DIM; ++r) {
                 const int64_t at = (int64_t)rs + (int64_t)r * nslot * DIM + (int64_t)sl * DIM;
 #pragma unroll
-                for (int cc = 0; cc < DIM; ++cc) val[at + cc] = acc[r * DIM + cc];
+                for (int cc = 0; cc < DIM; ++cc) {
+                    double v = acc[r * DIM + cc];
+                    if (MASS != 0) {
+                        const double pm = cm * (MASS == 1 ? mv[r * DIM + cc] : cc == r ? mv[r] : 0.0);
+                        v = pm + v;
+                    }
+                    val[at + cc] = v;
+                }
             }
         }
     }
@@ -348,22 +391,23 @@ __global__ void k_hyper_force(const int32_t* __restrict__ n2e_ptr, const int32_t
 }
 
 template <int DIM, int NEN>
-int launch_hyper(fedd_ctx* c, HyArgs a) {
+int launch_hyper(fedd_ctx* c, HyArgs a, const HyMass& mass, const char* who) {
     constexpr int DD = DIM * DIM;
     const int64_t nn = c->n_own;
     const int ntab = a.nq * (1 + NEN * DIM);
     const int per_wave = NEN * DIM + a.nq * (NEN * DIM + DD + DD * DD + NEN * DD * DIM);
     const size_t lds = ((size_t)ntab + 4 * (size_t)per_wave) * sizeof(double);
-    FEDD_CHECK(lds <= 64 * 1024, "fedd_assemble_hyperelastic: the element workspace (%zu bytes) does not fit the LDS", lds);
+    FEDD_CHECK(lds <= 64 * 1024, "%s: the element workspace (%zu bytes) does not fit the LDS", who, lds);
     int32_t h_flag = INT32_MAX;
     FEDD_HIP(hipMemsetD32Async((hipDeviceptr_t)a.flag, INT32_MAX, 1, c->stream));
     ScopedTimer t(c, FEDD_T_ASSEMBLE);
     // byte model: geometry, u and connectivity once per element; the element blocks and forces written and read once; the values
-    // and the force vector written
+    // and the force vector written; the time tangent reads the mass values once more (DIAG: with their row pointers)
     const bool kt = a.what & FEDD_HYPER_TANGENT, kf = a.what & FEDD_HYPER_FORCE;
+    const double mass_bytes = !kt || mass.kind == 0 ? 0.0 : (double)mass.nnz * 8.0 + (mass.kind == 2 ? 4.0 * (double)(nn * DIM + 1) : 0.0);
     // (stated before the first stop: a resumed timer counts time, not another launch's bytes)
     t.bytes((double)c->n_elem * (NEN * 4.0 + (kt ? 2.0 * NEN * NEN * DD * 8.0 : 0.0) + (kf ? 2.0 * NEN * DIM * 8.0 : 0.0)) +
-            (double)c->n_node * DIM * 16.0 + (kt ? (double)c->nnz * 8.0 : 0.0) + (kf ? (double)nn * DIM * 8.0 : 0.0));
+            (double)c->n_node * DIM * 16.0 + (kt ? (double)c->nnz * 8.0 : 0.0) + (kf ? (double)nn * DIM * 8.0 : 0.0) + mass_bytes);
     if (c->n_elem > 0) {
         const int64_t nwg = std::min<int64_t>((c->n_elem + 3) / 4, 256 * 8);
         hipLaunchKernelGGL((k_hyper_elem<DIM, NEN>), dim3((unsigned)nwg), dim3(256), lds, c->stream, a, c->n_elem, c->d_adv_ke.p,
@@ -376,31 +420,39 @@ int launch_hyper(fedd_ctx* c, HyArgs a) {
     FEDD_HIP(hipMemcpyAsync(&h_flag, a.flag, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     FEDD_HIP(hipStreamSynchronize(c->stream));
     FEDD_CHECK(h_flag == INT32_MAX,
-               "fedd_assemble_hyperelastic: element %d is inverted (det F <= 0 at a quadrature point, and the material takes ln det F); "
-               "the system matrix and the force vector were not written", h_flag);
+               "%s: element %d is inverted (det F <= 0 at a quadrature point, and the material takes ln det F); "
+               "the system matrix and the force vector were not written", who, h_flag);
     t.resume();
     if (a.what & FEDD_HYPER_TANGENT) {
         system_written(c, SYS_VALUES);
         const int nwg2 = (int)std::max<int64_t>(1, std::min<int64_t>((nn + 3) / 4, 256 * 32));
-        hipLaunchKernelGGL((k_hyper_gather<DIM, NEN>), dim3((unsigned)nwg2), dim3(256), 0, c->stream, (const int32_t*)c->d_n2e_ptr.p,
-                           (const int32_t*)c->d_n2e.p, (const int32_t*)c->d_rowptr.p, (int32_t)nn, (const uint16_t*)c->d_hy_soff.p,
-                           (const uint16_t*)c->d_hy_src.p, (const double*)c->d_adv_ke.p, c->d_val.p);
+        const dim3 grid2((unsigned)nwg2), blk(256);
+        const int32_t *n2e_ptr = c->d_n2e_ptr.p, *n2e = c->d_n2e.p, *rowptr = c->d_rowptr.p;
+        const uint16_t *soff = c->d_hy_soff.p, *src = c->d_hy_src.p;
+        const double* ke = c->d_adv_ke.p;
+        if (mass.kind == 0)
+            hipLaunchKernelGGL((k_hyper_gather<DIM, NEN, 0>), grid2, blk, 0, c->stream, n2e_ptr, n2e, rowptr, (int32_t)nn, soff, src, ke,
+                               (const int32_t*)nullptr, (const double*)nullptr, 0.0, c->d_val.p);
+        else if (mass.kind == 1)
+            hipLaunchKernelGGL((k_hyper_gather<DIM, NEN, 1>), grid2, blk, 0, c->stream, n2e_ptr, n2e, rowptr, (int32_t)nn, soff, src, ke,
+                               mass.rowptr, mass.val, mass.cm, c->d_val.p);
+        else
+            hipLaunchKernelGGL((k_hyper_gather<DIM, NEN, 2>), grid2, blk, 0, c->stream, n2e_ptr, n2e, rowptr, (int32_t)nn, soff, src, ke,
+                               mass.rowptr, mass.val, mass.cm, c->d_val.p);
     }
     if (a.what & FEDD_HYPER_FORCE) {
         hipLaunchKernelGGL(k_hyper_force<DIM>, dim3((unsigned)std::max<int64_t>(1, (nn + 255) / 256)), dim3(256), 0, c->stream,
                            (const int32_t*)c->d_n2e_ptr.p, (const int32_t*)c->d_n2e.p, (int32_t)nn, (const double*)c->d_hy_fe.p,
                            c->d_hy_f.p);
         c->have_hy_f = true;
+        c->nw_f_fresh = true;       // newer than the last fedd_newton_begin / fedd_newton_update (newton.hip)
     }
     t.stop();
     FEDD_HIP(hipGetLastError());
     return 0;
 }
 
-}  // namespace
-
-int assemble_hyperelastic(fedd_ctx* c, int model, const double* params, int n_params, int what) {
-    const char* who = "fedd_assemble_hyperelastic";
+int assemble_hyper(fedd_ctx* c, int model, const double* params, int n_params, int what, const HyMass& mass, const char* who) {
     FEDD_CHECK(c->nranks == 1, "%s: one rank only for now", who);
     FEDD_CHECK(model == FEDD_HYPER_NEOHOOKE || model == FEDD_HYPER_MOONEY_RIVLIN || model == FEDD_HYPER_STVK,
                "%s: unknown material model %d (built: Neo-Hooke, Mooney-Rivlin, Saint Venant-Kirchhoff)", who, model);
@@ -466,10 +518,43 @@ int assemble_hyperelastic(fedd_ctx* c, int model, const double* params, int n_pa
     a.conn = c->d_conn.p; a.xyz = c->d_xyz.p; a.u = c->d_vel.p; a.tab = c->d_hy_tab.p;
     a.nq = c->hy_nq;
     a.flag = c->d_hy_flag.p;
-    if (dim == 2 && nen == 3) return launch_hyper<2, 3>(c, a);
-    if (dim == 2 && nen == 6) return launch_hyper<2, 6>(c, a);
-    if (dim == 3 && nen == 4) return launch_hyper<3, 4>(c, a);
-    return launch_hyper<3, 10>(c, a);
+    if (dim == 2 && nen == 3) return launch_hyper<2, 3>(c, a, mass, who);
+    if (dim == 2 && nen == 6) return launch_hyper<2, 6>(c, a, mass, who);
+    if (dim == 3 && nen == 4) return launch_hyper<3, 4>(c, a, mass, who);
+    return launch_hyper<3, 10>(c, a, mass, who);
+}
+
+}  // namespace
+
+int assemble_hyperelastic(fedd_ctx* c, int model, const double* params, int n_params, int what) {
+    return assemble_hyper(c, model, params, n_params, what, HyMass(), "fedd_assemble_hyperelastic");
+}
+
+// the same with (cm * M[slot_m]) + K(u) as tangent: the pairings of fedd_matrix_combine (timestep.hip combine_pairing) with the
+// system matrix in the place of slot_a
+int assemble_hyperelastic_time(fedd_ctx* c, int model, const double* params, int n_params, int what, int slot_m, double cm) {
+    const char* who = "fedd_assemble_hyperelastic_time";
+    FEDD_CHECK(c->nranks == 1, "%s: one rank only (a context with %d ranks was given)", who, c->nranks);
+    const DevCsr& M = c->aux[slot_m];
+    FEDD_CHECK(M.valid, "%s: slot %d is empty", who, slot_m);
+    FEDD_CHECK(M.mesh_id == c->mesh_id, "%s: slot %d must hold a matrix of the current mesh (a fedd_mesh_set came between)", who, slot_m);
+    FEDD_CHECK(c->have_pattern && !c->merged && c->dofs == c->dim && c->block_mode == FEDD_BLOCK_FULL && c->n_rowg == 0,
+               "%s: needs the FULL pattern with dim dofs per node (fedd_pattern_build(dim, FEDD_BLOCK_FULL)) as system matrix", who);
+    FEDD_CHECK(M.block_mode >= 0 && M.dofs == c->dofs && M.n_rows == c->n_rows && M.n_cols == c->n_cols,
+               "%s: slot %d and the system matrix do not hold matrices of one space built by fedd_pattern_build", who, slot_m);
+    HyMass mass;
+    if (M.block_mode == FEDD_BLOCK_FULL && M.nnz == c->nnz) mass.kind = 1;
+    else {
+        FEDD_CHECK(M.block_mode == FEDD_BLOCK_DIAG && M.nnz * M.dofs == c->nnz,
+                   "%s: unsupported pattern pairing (block mode %d into the FULL system matrix): same pattern, or DIAG into FULL", who,
+                   M.block_mode);
+        mass.kind = 2;
+    }
+    mass.rowptr = M.rowptr.p;
+    mass.val = M.val.p;
+    mass.cm = cm;
+    mass.nnz = M.nnz;
+    return assemble_hyper(c, model, params, n_params, what, mass, who);
 }
 
 }  // namespace fedd

@@ -949,6 +949,43 @@ public:
     void dirichletRowsOfBlock(const BlockMultiVectorPtr_Type& layout, int block, std::vector<int32_t>& rows, std::vector<double>& values) const {
         mergedDirichletRows(layout, block, 0., rows, values);
     }
+    // the Dirichlet conditions of `block` as fedd_newton_residual takes them: per flag a component mask and one value per
+    // component.  A boundary function that varies over the nodes of a flag does not fit that table: an error that says so.
+    void dirichletFlagTable(int block, double t, std::vector<int32_t>& flags, std::vector<int32_t>& mask, std::vector<double>& values) const {
+        for (size_t k = 0; k < vecFlag_.size(); ++k) {
+            if (vecBlockID_[k] != block || vecBCType_[k].compare(0, 9, "Dirichlet") != 0) continue;
+            auto dom = vecDomain_[k];
+            const int dofs = vecDofs_[k], dim = (int)dom->getDimension();
+            vec_int_ptr_Type nodeFlags = dom->getBCFlagUnique();
+            vec2D_dbl_ptr_Type pts = dom->getPointsUnique();
+            const std::string& ty = vecBCType_[k];
+            vec_dbl_Type result(dofs, 0.), point(dim, 0.), first;
+            for (size_t i = 0; i < nodeFlags->size(); ++i) {
+                if ((*nodeFlags)[i] != vecFlag_[k]) continue;
+                for (int d = 0; d < dim; ++d) point[d] = (*pts)[i][d];
+                for (int d = 0; d < dofs; ++d) result[d] = d < dim ? (*pts)[i][d] : 0.;
+                vecBC_func_[k](point.data(), result.data(), t, vecBC_Parameters_[k].data());
+                if (first.empty()) first = result;
+                for (int d = 0; d < dofs; ++d) {
+                    const bool on = ty == "Dirichlet" || (ty == "Dirichlet_X" && d == 0) || (ty == "Dirichlet_Y" && d == 1) ||
+                                    (ty == "Dirichlet_Z" && d == 2) || (ty == "Dirichlet_X_Y" && d != 2) ||
+                                    (ty == "Dirichlet_X_Z" && d != 1) || (ty == "Dirichlet_Y_Z" && d != 0);
+                    TEUCHOS_TEST_FOR_EXCEPTION(on && result[d] != first[d], std::logic_error,
+                                               "Dirichlet values that vary over the nodes of flag " + std::to_string(vecFlag_[k]) +
+                                               " are not built for the device-resident Newton residual (one value per flag and component is)");
+                }
+            }
+            if (first.empty()) continue;
+            flags.push_back(vecFlag_[k]);
+            for (int d = 0; d < dofs; ++d) {
+                const bool on = ty == "Dirichlet" || (ty == "Dirichlet_X" && d == 0) || (ty == "Dirichlet_Y" && d == 1) ||
+                                (ty == "Dirichlet_Z" && d == 2) || (ty == "Dirichlet_X_Y" && d != 2) ||
+                                (ty == "Dirichlet_X_Z" && d != 1) || (ty == "Dirichlet_Y_Z" && d != 0);
+                mask.push_back(on ? 1 : 0);
+                values.push_back(first[d]);
+            }
+        }
+    }
     // BCBuilder::setRHS (:93-170), setVectorMinusBC and setBCMinusVector (the boundary rows of a nonlinear residual):
     // which = 0: v <- g, 1: v <- x - g, 2: v <- g - x on the Dirichlet rows
     void setRows(const BlockMultiVectorPtr_Type& v, const BlockMultiVectorPtr_Type& x, double t, int which) const {
@@ -1918,24 +1955,9 @@ public:
             auto dom = this->getDomain(0);
             auto dev = dom->device();
             const int dim = this->dim_;
-            const double nu = par.get("Poisson Ratio", 0.4), mu = par.get("Mu", 2.0e+6);
-            const bool stvk = model == "Saint Venant-Kirchhoff";
-            TEUCHOS_TEST_FOR_EXCEPTION(!stvk && model != "Neo-Hooke" && model != "Mooney-Rivlin", std::logic_error,
-                                       "Material model \"" + model + "\" is not built (Neo-Hooke, Mooney-Rivlin, Saint Venant-Kirchhoff are)");
-            TEUCHOS_TEST_FOR_EXCEPTION(dim == 2 && !stvk, std::logic_error, "Only Saint Venant-Kirchhoff in 2D.");
-            const double E = stvk ? mu * 2. * (1. + nu) : par.get("E", 3.0e+6);     // FE_def.hpp:883-891
-            for (int32_t flag : dom->elementFlags()) {
-                if (flag != 1 && flag != 2) continue;
-                const std::string base = stvk ? "Mu" : "E", key = base + (flag == 1 ? "1" : "2");
-                const double other = par.get(key, stvk ? 2.0e+6 : 3.0e+6);
-                TEUCHOS_TEST_FOR_EXCEPTION(other != (stvk ? mu : E), std::logic_error,
-                                           "NonLinElasticity: the mesh has elements with flag " + std::to_string(flag) + " and \"" + key +
-                                           "\" differs from \"" + base + "\": per-flag materials are not built (one material per assembly is)");
-            }
-            double p[3] = {E, nu, C_};
-            const int np = model == "Mooney-Rivlin" ? 3 : 2;
-            const int id = model == "Neo-Hooke" ? FEDD_HYPER_NEOHOOKE : (stvk ? FEDD_HYPER_STVK : FEDD_HYPER_MOONEY_RIVLIN);
-            if (stvk) { p[0] = (nu * E) / ((1 + nu) * (1 - 2 * nu)); p[1] = mu; }   // lambda, mue (:894)
+            double p[3];
+            int np = 0;
+            const int id = material(p, np);
             // u_rep_->importFromVector(u)
             auto mapRep = dom->getMapRepeated();
             auto mapUni = dom->getMapUnique();
@@ -1957,6 +1979,51 @@ public:
         }
         if (this->verbose_) std::cout << "done -- " << std::endl;
     }
+    // the material of the parameter list as fedd_assemble_hyperelastic* takes it: the model id, its parameters and their number
+    int material(double p[3], int& np) const {
+        auto& par = this->parameterList_->sublist("Parameter");
+        const std::string model = par.get("Material model", "Neo-Hooke");
+        auto dom = this->getDomain(0);
+        const int dim = this->dim_;
+        const double nu = par.get("Poisson Ratio", 0.4), mu = par.get("Mu", 2.0e+6);
+        const bool stvk = model == "Saint Venant-Kirchhoff";
+        TEUCHOS_TEST_FOR_EXCEPTION(!stvk && model != "Neo-Hooke" && model != "Mooney-Rivlin", std::logic_error,
+                                   "Material model \"" + model + "\" is not built (Neo-Hooke, Mooney-Rivlin, Saint Venant-Kirchhoff are)");
+        TEUCHOS_TEST_FOR_EXCEPTION(dim == 2 && !stvk, std::logic_error, "Only Saint Venant-Kirchhoff in 2D.");
+        const double E = stvk ? mu * 2. * (1. + nu) : par.get("E", 3.0e+6);     // FE_def.hpp:883-891
+        for (int32_t flag : dom->elementFlags()) {
+            if (flag != 1 && flag != 2) continue;
+            const std::string base = stvk ? "Mu" : "E", key = base + (flag == 1 ? "1" : "2");
+            const double other = par.get(key, stvk ? 2.0e+6 : 3.0e+6);
+            TEUCHOS_TEST_FOR_EXCEPTION(other != (stvk ? mu : E), std::logic_error,
+                                       "NonLinElasticity: the mesh has elements with flag " + std::to_string(flag) + " and \"" + key +
+                                       "\" differs from \"" + base + "\": per-flag materials are not built (one material per assembly is)");
+        }
+        p[0] = E; p[1] = nu; p[2] = C_;
+        np = model == "Mooney-Rivlin" ? 3 : 2;
+        if (stvk) { p[0] = (nu * E) / ((1 + nu) * (1 - 2 * nu)); p[1] = mu; }   // lambda, mue (:894)
+        return model == "Neo-Hooke" ? FEDD_HYPER_NEOHOOKE : (stvk ? FEDD_HYPER_STVK : FEDD_HYPER_MOONEY_RIVLIN);
+    }
+    // the system slot holds the FULL pattern again (after TimeProblem::assembleMassSystem used it for the mass matrix)
+    void restorePattern() const {
+        auto dom = this->getDomain(0);
+        auto dev = dom->device();
+        int64_t nnz = 0;
+        feddCheck(fedd_pattern_build(dev->ctx, this->dim_, FEDD_BLOCK_FULL, &nnz), "fedd_pattern_build");
+        rebind();
+    }
+    // the time tangent (cm M[slotMass]) + K(u) and the force for the displacement the DEVICE holds (fedd_newton_begin /
+    // fedd_newton_update wrote the nodal vector field): one pass, nothing read back (TimeProblem, fedd_time.hpp)
+    void reAssembleTime(int slotMass, double cm) const {
+        double p[3];
+        int np = 0;
+        const int id = material(p, np);
+        if (this->verbose_) std::cout << "-- Reassembly nonlinear elasticity, time tangent ... " << std::flush;
+        feddCheck(fedd_assemble_hyperelastic_time(this->getDomain(0)->device()->ctx, id, p, np, FEDD_HYPER_TANGENT | FEDD_HYPER_FORCE, slotMass, cm),
+                  "fedd_assemble_hyperelastic_time");
+        rebind();
+        if (this->verbose_) std::cout << "done -- " << std::endl;
+    }
     void reAssembleExtrapolation(std::vector<BlockMultiVectorPtr_Type> previousSolutions) {
         (void)previousSolutions;
         TEUCHOS_TEST_FOR_EXCEPTION(true, std::logic_error, "Only Newton implemented for nonlinear material models! (NOX and extrapolation are not built)");
@@ -1973,6 +2040,14 @@ public:
         this->bcFactory_->setBCMinusVector(this->residualVec_, this->solution_, time);
     }
 private:
+    void rebind() const {       // the system block follows the device's generation
+        auto dom = this->getDomain(0);
+        auto dev = dom->device();
+        dev->generation++;
+        MatrixPtr_Type W(new Matrix_Type(dom->getMapVecFieldUnique(), dom->getDimension() * dom->getApproxEntriesPerRow()));
+        W->bind(dev, this->dim_);
+        this->system_->addBlock(W, 0, 0);
+    }
     mutable std::vector<double> u_rep_;
     double C_;
 };
@@ -2264,7 +2339,10 @@ private:
 inline void addDeviceTimers(const DeviceContextPtr& dev, Teuchos::StackedTimer& st) {
     static const char* names[FEDD_T_COUNT] = {"symbolic", "assemble", "rhs", "dirichlet", "spmv", "schwarz setup", "schwarz apply",
                                              "orthogonalisation", "coarse setup", "coarse apply", "halo", "all-reduce", "spmv setup",
-                                             "orthogonalisation: dot sweep", "orthogonalisation: update sweep"};
+                                             "orthogonalisation: dot sweep", "orthogonalisation: update sweep", "orthogonalisation: fused sweep",
+                                             "full park (matrix cores)", "full park", "full gather", "cg pq", "cg xr", "cg rz", "cg p",
+                                             "newmark state", "block apply", "multistep state", "block preconditioner B^T",
+                                             "newton residual", "newton update"};
     for (int t = 0; t < FEDD_T_COUNT; ++t) {
         double ms = 0.;
         int64_t n = 0;

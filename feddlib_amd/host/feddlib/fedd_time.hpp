@@ -10,8 +10,11 @@
 //   DAESolverInTime     feddlib/problems/Solver/DAESolverInTime_def.hpp (advanceInTimeLinearNewmark :519-607,
 //                       advanceInTimeNonLinearMultistep :1209-1333)
 //   NonLinearSolver::solve(TimeProblem&, time)   NonLinearSolver_def.hpp:394-531
+//   nonlinear Newmark: "Newmark" on NonLinElasticity (1 x 1 definition, Newton) -- advanceInTimeNonLinearNewmark :613-722; the
+//                       Newton iterate, residual and update stay on the device (fedd_assemble_hyperelastic_time, fedd_newton_*),
+//                       the host vectors of the facade are refreshed once per step
 // Everything else these classes do in the reference (single-step / Butcher-table schemes, adaptive steps, "Extrapolation", NOX,
-// source terms in the nonlinear loop, FSI) is an error here that names what is built.
+// source terms in the multistep loop, FSI) is an error here that names what is built.
 #pragma once
 #include "fedd_facade.hpp"
 
@@ -97,6 +100,7 @@ public:
     typedef Teuchos::RCP<const Teuchos::Comm<int>> CommConstPtr_Type;
     typedef NonLinearProblem<SC, LO, GO, NO> NonLinearProblem_Type;
     typedef NavierStokes<SC, LO, GO, NO> NavierStokes_Type;
+    typedef NonLinElasticity<SC, LO, GO, NO> NonLinElasticity_Type;
     static constexpr int SLOT_MASS = 0, SLOT_SYSTEM = 1;
     // nonlinear path (Navier-Stokes occupies slots 0 .. 4): velocity mass, time-combined constant velocity block
     static constexpr int SLOT_NL_A = 0, SLOT_NL_MASS = 5, SLOT_NL_COMBINED = 6;
@@ -105,12 +109,18 @@ public:
         TEUCHOS_TEST_FOR_EXCEPTION(comm->getSize() != 1, std::logic_error, "TimeProblem: one rank only (the time-stepping device layer is one rank)");
         nl_ = dynamic_cast<NonLinearProblem_Type*>(problem_);
         ns_ = dynamic_cast<NavierStokes_Type*>(problem_);
-        TEUCHOS_TEST_FOR_EXCEPTION(nl_ != nullptr && ns_ == nullptr, std::logic_error,
-                                   "TimeProblem: NavierStokes is the nonlinear problem that is built");
+        nle_ = dynamic_cast<NonLinElasticity_Type*>(problem_);
+        TEUCHOS_TEST_FOR_EXCEPTION(nl_ != nullptr && ns_ == nullptr && nle_ == nullptr, std::logic_error,
+                                   "TimeProblem: NavierStokes (\"Multistep\") and NonLinElasticity (\"Newmark\") are the nonlinear problems that are built");
     }
     bool isNonLinear() const { return nl_ != nullptr; }
+    bool isNonLinElasticity() const { return nle_ != nullptr; }
     void setTimeDef(const SmallMatrix<int>& def) {
-        if (nl_) {
+        if (nle_) {
+            TEUCHOS_TEST_FOR_EXCEPTION(def.size() != 1 || def[0][0] != 1, std::logic_error,
+                                       "TimeProblem::setTimeDef: NonLinElasticity takes the 1 x 1 definition [[1]] (one block, \"Newmark\"); a " +
+                                           std::to_string(def.size()) + " x " + std::to_string(def.size()) + " definition is not built");
+        } else if (nl_) {
             TEUCHOS_TEST_FOR_EXCEPTION(def.size() != 2 || def[0][0] != 1 || def[0][1] != 1 || def[1][0] != 0 || def[1][1] != 0, std::logic_error,
                                        "TimeProblem::setTimeDef: a nonlinear problem takes the 2 x 2 definition [[1,1],[0,0]] (velocity, pressure)");
         } else {
@@ -121,6 +131,20 @@ public:
     // TimeProblem::assembleMassSystem (:599-663): FE::assemblyMass on the variable's space, scaled by "Density" (:605, 620).
     // The problem's own matrix, still in the device's system slot after Problem::assemble, moves to slot 1 first.
     void assembleMassSystem() {
+        if (nle_) {     // the mass as the linear Newmark path assembles it, with "Density", into slot 0; the FULL pattern goes back into the system slot
+            dev_ = problem_->getDomain(0)->device();
+            const int dim = (int)problem_->getDomain(0)->getDimension();
+            const double density = problem_->getParameterList()->sublist("Parameter").get("Density", 1.);
+            MatrixPtr_Type M = Teuchos::rcp(new Matrix_Type(problem_->getDomain(0)->getMapVecFieldUnique(), problem_->getDomain(0)->getApproxEntriesPerRow()));
+            problem_->getFEFactory()->assemblyMass(dim, problem_->getFEType(0), "Vector", M);
+            M->scale(density);
+            feddCheck(fedd_matrix_store(dev_->ctx, SLOT_MASS), "fedd_matrix_store");
+            M->bindSlot(dev_, SLOT_MASS);
+            systemMass_.reset(new BlockMatrix_Type(1));
+            systemMass_->addBlock(M, 0, 0);
+            nle_->restorePattern();
+            return;
+        }
         if (nl_) {      // the vector mass on the velocity space x "Density" into slot 5; the system slot is scratch until the next reAssemble
             dev_ = problem_->getDomain(0)->device();
             const int dim = (int)problem_->getDomain(0)->getDimension();
@@ -156,6 +180,14 @@ public:
         systemMass_->addBlock(M, 0, 0);
     }
     void setTimeParameters(const SmallMatrix<double>& massParameters, const SmallMatrix<double>& timeParameters) {
+        if (nle_) {
+            TEUCHOS_TEST_FOR_EXCEPTION(massParameters.size() != 1 || timeParameters.size() != 1, std::logic_error, "TimeProblem: 1 x 1 parameters only");
+            TEUCHOS_TEST_FOR_EXCEPTION(timeParameters[0][0] != 1., std::logic_error,
+                                       "TimeProblem::setTimeParameters: a problem coefficient other than 1.0 is not built for NonLinElasticity (Newmark gives 1.0)");
+            massParameters_ = massParameters;
+            timeParameters_ = timeParameters;
+            return;
+        }
         if (nl_) {
             TEUCHOS_TEST_FOR_EXCEPTION(massParameters.size() != 2 || timeParameters.size() != 2, std::logic_error, "TimeProblem: 2 x 2 parameters for a nonlinear problem");
             TEUCHOS_TEST_FOR_EXCEPTION(timeParameters[0][1] != 1. || timeParameters[1][0] != 1. || timeParameters[1][1] != 1., std::logic_error,
@@ -178,6 +210,10 @@ public:
     void combineSystems() {
         TEUCHOS_TEST_FOR_EXCEPTION(systemMass_.is_null(), std::logic_error, "TimeProblem::combineSystems: call assembleMassSystem first");
         const double cm = massParameters_[0][0], ca = timeParameters_[0][0];
+        if (nle_) {     // the tangent changes with u: (cm M) + K(u) is formed where K(u) is, in calculateNonLinResidualVec
+            ++combines_;
+            return;
+        }
         if (nl_) {
             if (nlCombined_ && cm == nlCm_ && ca == nlCa_) return;
             int cur = 0;
@@ -212,7 +248,7 @@ public:
     void updateNewmarkRhs(double dt, double beta, double gamma, vec_dbl_Type coeff) {
         TEUCHOS_TEST_FOR_EXCEPTION(!pend_ || dt != pendDt_ || beta != pendBeta_ || gamma != pendGamma_, std::logic_error,
                                    "TimeProblem::updateNewmarkRhs: call updateSolutionNewmarkPreviousStep with the same dt, beta, gamma first");
-        TEUCHOS_TEST_FOR_EXCEPTION(systemCombined_.is_null(), std::logic_error, "TimeProblem::updateNewmarkRhs: call combineSystems first");
+        TEUCHOS_TEST_FOR_EXCEPTION(systemCombined_.is_null() && !nle_, std::logic_error, "TimeProblem::updateNewmarkRhs: call combineSystems first");
         pend_ = false;
         if (!began_) {       // the start values of :913-926: u_n <- the problem's solution, v = w = 0
             feddCheck(fedd_solution_set(dev_->ctx, problem_->getSolution()->getBlock(0)->raw().data()), "fedd_solution_set");
@@ -255,16 +291,81 @@ public:
     // mass term the reference adds afterwards (:693-738, up to rounding); Dirichlet rows through setBCMinusVector / setVectorMinusBC
     void assemble(std::string type) const { needNl("assemble"); nl_->assemble(type); }
     void reAssemble(std::string type) const { needNl("reAssemble"); nl_->reAssemble(type); }
+    // NonLinElasticity: the first call of a step uploads the step's right-hand side and source and begins the device's Newton
+    // state; every call is one pass for the time tangent and the force, the Dirichlet rows of the tangent (fedd_dirichlet_nodes
+    // writes the right-hand side of its rows, so it comes before the residual: setBoundariesSystem then finds them set), and
+    // fedd_newton_residual, whose norm calculateResidualNorm returns.  No vector comes back to the host.
     void calculateNonLinResidualVec(std::string type = "standard", double time = 0.) {
         needNl("calculateNonLinResidualVec");
+        if (nle_) {
+            TEUCHOS_TEST_FOR_EXCEPTION(type != "reverse", std::logic_error,
+                                       "TimeProblem::calculateNonLinResidualVec: the \"reverse\" residual is built for NonLinElasticity (the Newton loop asks for it)");
+            fedd_ctx* ctx = dev_->ctx;
+            const double cm = massParameters_[0][0];
+            if (!stepOpen_) {
+                feddCheck(fedd_rhs_set(ctx, problem_->getRhs()->getBlock(0)->raw().data()), "fedd_rhs_set");
+                feddCheck(fedd_solution_set(ctx, problem_->getSolution()->getBlock(0)->raw().data()), "fedd_solution_set");
+                feddCheck(fedd_newton_begin(ctx), "fedd_newton_begin");
+                if (problem_->hasRhsFunction())      // NonLinElasticity::calculateNonLinResidualVec adds the source again (:254-263)
+                    feddCheck(fedd_newton_source_set(ctx, problem_->getSourceTerm()->getBlock(0)->raw().data()), "fedd_newton_source_set");
+                stepOpen_ = true;
+            }
+            nle_->reAssembleTime(SLOT_MASS, cm);
+            nl_->setBoundariesSystem();
+            std::vector<int32_t> flags, mask;
+            std::vector<double> values;
+            problem_->getBCFactory()->dirichletFlagTable(0, time, flags, mask, values);
+            feddCheck(fedd_newton_residual(ctx, SLOT_MASS, cm, (int)flags.size(), flags.data(), mask.data(), values.data(), &residualNorm_),
+                      "fedd_newton_residual");
+            return;
+        }
         combineSystems();
         nl_->calculateNonLinResidualVec(type, time);
     }
-    double calculateResidualNorm() const { needNl("calculateResidualNorm"); return nl_->calculateResidualNorm(); }
-    void setBoundariesSystem() const { needNl("setBoundariesSystem"); nl_->setBoundariesSystem(); }
+    double calculateResidualNorm() const { needNl("calculateResidualNorm"); return nle_ ? residualNorm_ : nl_->calculateResidualNorm(); }
+    void setBoundariesSystem() const {
+        needNl("setBoundariesSystem");
+        if (nle_) return;       // set with the tangent, before the residual took the right-hand side (see calculateNonLinResidualVec)
+        nl_->setBoundariesSystem();
+    }
     void setBoundariesRHS(double time = .0) const { needNl("setBoundariesRHS"); nl_->setBoundariesRHS(time); }
     int solveUpdate() { needNl("solveUpdate"); return nl_->solveUpdate(); }
-    int solveAndUpdate(const std::string& criterion, double& criterionValue) { needNl("solveAndUpdate"); return nl_->solveAndUpdate(criterion, criterionValue); }
+    int solveAndUpdate(const std::string& criterion, double& criterionValue) {
+        needNl("solveAndUpdate");
+        if (!nle_) return nl_->solveAndUpdate(criterion, criterionValue);
+        // Schwarz setup on the time tangent, GMRES on the device's vectors (zero initial guess: the unknown is the update), u_k += delta
+        auto pl = problem_->getParameterList();
+        const std::string method = pl->sublist("General").get("Preconditioner Method", "Monolithic");
+        TEUCHOS_TEST_FOR_EXCEPTION(method != "Monolithic", std::logic_error,
+                                   "TimeProblem: \"Preconditioner Method\" = \"" + method + "\" is not built for time problems (Monolithic is; "
+                                   "Diagonal and Triangular are built for the steady Stokes and Navier-Stokes problems)");
+        auto& belos = pl->sublist("ThyraSolver").sublist("Linear Solver Types").sublist("Belos");
+        const std::string solverType = belos.get("Solver Type", "Block GMRES");
+        TEUCHOS_TEST_FOR_EXCEPTION(solverType != "Block GMRES", std::logic_error,
+                                   "Solver Type \"" + solverType + "\" is not built for the nonlinear Newmark loop (Block GMRES is)");
+        auto& gm = belos.sublist("Solver Types").sublist(solverType);
+        const double tol = gm.get("Convergence Tolerance", 1e-8);
+        const int maxIt = gm.get("Maximum Iterations", 100), numBlocks = gm.get("Num Blocks", 100);
+        const bool usePrec = std::string(pl->sublist("ThyraPreconditioner").get("Preconditioner Type", "FROSch")) != "None";
+        fedd_ctx* ctx = dev_->ctx;
+        if (usePrec) LinearSolver<SC, LO, GO, NO>::setupSchwarz(ctx, pl->sublist("ThyraPreconditioner"), *pl, false, problem_->getVerbose());
+        int its = 0;
+        feddCheck(fedd_gmres(ctx, nullptr, nullptr, tol, maxIt, numBlocks, usePrec ? 1 : 0, &its, &lastRelativeResidual_), "fedd_gmres");
+        double normDelta = 0.;
+        feddCheck(fedd_newton_update(ctx, 1.0, &normDelta), "fedd_newton_update");
+        if (criterion == "Update") criterionValue = normDelta;
+        return its;
+    }
+    // the end of a step's nonlinear solve: u_{n+1} and the held right-hand side go back where fedd_newmark_advance looks for
+    // them, and the host copies the public getters and the exporter read are refreshed -- once per step
+    void endNonLinearStep() {
+        if (!nle_ || !stepOpen_) return;
+        fedd_ctx* ctx = dev_->ctx;
+        feddCheck(fedd_rhs_get(ctx, nl_->getResidualVector()->getBlockNonConst(0)->raw().data()), "fedd_rhs_get");
+        feddCheck(fedd_newton_end(ctx), "fedd_newton_end");
+        feddCheck(fedd_solution_get(ctx, problem_->getSolution()->getBlockNonConst(0)->raw().data()), "fedd_solution_get");
+        stepOpen_ = false;
+    }
     bool getVerbose() const { return problem_->getVerbose(); }
     BlockMultiVectorPtr_Type getRhs() const { return problem_->getRhs(); }
     ParameterListPtr_Type getParameterList() const { return problem_->getParameterList(); }
@@ -328,6 +429,9 @@ private:
     Problem_Type* problem_;
     NonLinearProblem_Type* nl_ = nullptr;
     NavierStokes_Type* ns_ = nullptr;
+    NonLinElasticity_Type* nle_ = nullptr;
+    bool stepOpen_ = false;
+    double residualNorm_ = 0.;
     bool nlCombined_ = false, msBegan_ = false, pendMs_ = false;
     double nlCm_ = 0., nlCa_ = 0.;
     int pendSteps_ = 0;
@@ -349,6 +453,9 @@ void NonLinearSolver<SC, LO, GO, NO>::solve(TimeProblem_Type& problem, double ti
                                "\"Linearization\" = \"" + type_ + "\" is not built for time problems (FixedPoint and Newton are; Extrapolation and NOX are not)");
     TEUCHOS_TEST_FOR_EXCEPTION(!problem.isNonLinear(), std::logic_error, "NonLinearSolver: the time problem wraps a linear problem");
     const bool newton = type_ == "Newton";
+    // NonLinElasticity::reAssembleExtrapolation (NonLinElasticity_def.hpp:129-134), which the fixed-point loop would reach
+    TEUCHOS_TEST_FOR_EXCEPTION(!newton && problem.isNonLinElasticity(), std::logic_error,
+                               "Only Newton implemented for nonlinear material models! (\"Linearization\" = \"" + type_ + "\" on NonLinElasticity; Newton is built)");
     const bool verbose = problem.getVerbose();
     problem.setBoundariesRHS(time);
     TEUCHOS_TEST_FOR_EXCEPTION(problem.getRhs()->getNumVectors() != 1, std::logic_error, "We need to change the code for numVectors>1.");
@@ -419,7 +526,8 @@ public:
     void advanceInTime() {
         TEUCHOS_TEST_FOR_EXCEPTION(timeSteppingTool_.is_null(), std::logic_error, "DAESolverInTime: call setupTimeStepping first");
         checkClass();
-        if (nonLinear_) advanceInTimeNonLinearMultistep();
+        if (nonLinear_ && problemTime_->isNonLinElasticity()) advanceInTimeNonLinearNewmark();
+        else if (nonLinear_) advanceInTimeNonLinearMultistep();
         else advanceInTimeLinearNewmark();
     }
     const std::vector<int>& nonLinearIterations() const { return nlItsPerStep_; }
@@ -429,12 +537,19 @@ private:
     void checkClass() const {
         // "Newmark" + linear and "Multistep" + nonlinear are built; the reference's default class is "Singlestep"
         const std::string cls = parameterList_->sublist("Timestepping Parameter").get("Class", nonLinear_ ? "Singlestep" : "Newmark");
-        const bool ok = nonLinear_ ? cls == "Multistep" : cls == "Newmark";
+        const bool nle = !problemTime_.is_null() && problemTime_->isNonLinElasticity();
+        const bool ok = nonLinear_ ? (nle ? cls == "Newmark" : cls == "Multistep") : cls == "Newmark";
         TEUCHOS_TEST_FOR_EXCEPTION(!ok, std::logic_error,
-                                   "Timestepping Parameter \"Class\" = \"" + cls + "\" on a " + (nonLinear_ ? "nonlinear" : "linear") +
-                                       " problem is not built (Singlestep and External are not); \"Newmark\" on a linear problem and \"Multistep\" (BDF 1, 2) on a nonlinear problem are");
+                                   "Timestepping Parameter \"Class\" = \"" + cls + "\" on " + (nle ? "NonLinElasticity" : nonLinear_ ? "a nonlinear problem" : "a linear problem") +
+                                       " is not built (Singlestep and External are not); \"Newmark\" on a linear problem and on NonLinElasticity "
+                                       "(1 x 1 time definition, Newton) and \"Multistep\" (BDF 1, 2) on NavierStokes are");
         if (nonLinear_) {
             const std::string lin = parameterList_->sublist("General").get("Linearization", "FixedPoint");
+            TEUCHOS_TEST_FOR_EXCEPTION(nle && lin == "FixedPoint", std::logic_error,
+                                       "Only Newton implemented for nonlinear material models! (\"Linearization\" = \"FixedPoint\" on NonLinElasticity; Newton is built)");
+            TEUCHOS_TEST_FOR_EXCEPTION(nle && timeStepDef_.size() != 1, std::logic_error,
+                                       "Newmark only implemented for systems of size 1x1: NonLinElasticity takes the 1 x 1 time definition [[1]] (\"Newmark\", Newton), a " +
+                                           std::to_string(timeStepDef_.size()) + " x " + std::to_string(timeStepDef_.size()) + " definition was given");
             TEUCHOS_TEST_FOR_EXCEPTION(lin != "FixedPoint" && lin != "Newton", std::logic_error,
                                        "\"Linearization\" = \"" + lin + "\" is not built for time problems (FixedPoint and Newton are; Extrapolation and NOX are not)");
         }
@@ -519,6 +634,44 @@ private:
         comm_->barrier();
         if (print && !exporter_.is_null()) exporter_->closeExporter();
     }
+    // DAESolverInTime::advanceInTimeNonLinearNewmark (:613-722), in the reference's order
+    void advanceInTimeNonLinearNewmark() {
+        const bool print = parameterList_->sublist("General").get("ParaViewExport", false);
+        if (print) exportTimestep();
+        TEUCHOS_TEST_FOR_EXCEPTION(timeStepDef_.size() > 1, std::runtime_error, "Newmark only implemented for systems of size 1x1.");
+        const double dt = timeSteppingTool_->get_dt(), beta = timeSteppingTool_->get_beta(), gamma = timeSteppingTool_->get_gamma();
+        SmallMatrix<double> massCoeff(1), problemCoeff(1);
+        massCoeff[0][0] = 1.0 / (dt * dt * beta);
+        problemCoeff[0][0] = 1.0;
+        const double coeffSourceTerm = 1.0;
+        vec_dbl_Type coeffTemp(1, 1.0);
+        problemTime_->setTimeParameters(massCoeff, problemCoeff);
+        const std::string linearization = parameterList_->sublist("General").get("Linearization", "FixedPoint");
+        while (timeSteppingTool_->continueTimeStepping()) {
+            problemTime_->combineSystems();
+            problemTime_->updateSolutionNewmarkPreviousStep(dt, beta, gamma);
+            const double time = timeSteppingTool_->currentTime() + dt;
+            problemTime_->updateTime(time);
+            problemTime_->updateNewmarkRhs(dt, beta, gamma, coeffTemp);
+            if (problemTime_->hasSourceTerm()) {
+                problemTime_->assembleSourceTerm(time);
+                addSourceTermToRHS(coeffSourceTerm);
+            }
+            NonLinearSolver<SC, LO, GO, NO> nlSolver(linearization);
+            try {
+                nlSolver.solve(*problemTime_, time);
+            } catch (...) {
+                problemTime_->endNonLinearStep();
+                throw;
+            }
+            problemTime_->endNonLinearStep();
+            nlItsPerStep_.push_back(nlSolver.lastNonLinIts);
+            timeSteppingTool_->advanceTime(true);
+            if (print) exportTimestep();
+        }
+        comm_->barrier();
+        if (print && !exporter_.is_null()) exporter_->closeExporter();
+    }
     void addSourceTermToRHS(double coeff) {                            // :1444-1450
         auto rhs = problemTime_->getUnderlyingProblem()->getRhs();
         rhs->update(coeff, *problemTime_->getSourceTerm(), 1.);
@@ -531,7 +684,7 @@ private:
             exportSolution_ = problem_->getSolution()->getBlock(0);
             const int dofs = problem_->getDofsPerNode(0);
             exporter_->addVariable(exportSolution_, problem_->getVariableName(0), dofs > 1 ? "Vector" : "Scalar", dofs, dom->getMapUnique());
-            if (nonLinear_) {                                           // velocity and pressure per step
+            if (nonLinear_ && problem_->getSolution()->size() > 1) {    // velocity and pressure per step
                 exporterP_.reset(new Exporter_Type());
                 auto domP = problem_->getDomain(1);
                 exporterP_->setup(problem_->getVariableName(1), domP->getMesh(), problem_->getFEType(1));

@@ -89,7 +89,9 @@ enum fedd_timer {
     FEDD_T_BLOCK_APPLY = 24, /* y = alpha M x on a stored block: k_block_apply          */
     FEDD_T_MULTISTEP = 25, /* BDF history update: k_multistep (timestep.hip)              */
     FEDD_T_BLOCKPREC_BT = 26, /* Triangular block preconditioner: t = r_u - B^T z_p, k_bt_sub (blockprec.hip) */
-    FEDD_T_COUNT    = 27
+    FEDD_T_NEWTON_RESIDUAL = 27, /* Newton residual of a Newmark step: k_newton_residual (newton.hip) */
+    FEDD_T_NEWTON_UPDATE = 28,   /* ... the iterate's update: k_newton_update                      */
+    FEDD_T_COUNT    = 29
 };
 
 /* ------------------------------------------------------------------------------------------------
@@ -521,6 +523,77 @@ enum fedd_hyper_model { FEDD_HYPER_NEOHOOKE = 0, FEDD_HYPER_MOONEY_RIVLIN = 1, F
 #define FEDD_HYPER_FORCE 2
 int fedd_assemble_hyperelastic(fedd_ctx* ctx, int model, const double* params, int n_params, int what);
 int fedd_hyperelastic_force_get(fedd_ctx* ctx, double* f_owned);
+
+/* ------------------------------------------------------------------------------------------------
+ * Nonlinear Newmark (unsteady nonlinear elasticity), one rank and one block like the Newmark and the hyperelastic entries it
+ * pairs: what DAESolverInTime::advanceInTimeNonLinearNewmark (feddlib/problems/Solver/DAESolverInTime_def.hpp:613-722) does in
+ * the Newton iterations of a time step -- TimeProblem::calculateNonLinResidualVec (feddlib/problems/abstract/
+ * TimeProblem_def.hpp:693-738), NonLinElasticity::calculateNonLinResidualVec (feddlib/problems/specific/
+ * NonLinElasticity_def.hpp:251-271), NonLinearSolver::solveNewton (feddlib/problems/Solver/NonLinearSolver_def.hpp:459-531) --
+ * with the iterate, the residual and the update resident on the device.  On a context with more than one rank every entry below
+ * is an error that says so; on a host-only context they fail with "needs a GPU context" (fedd_newton_info needs no device).  No
+ * multiplication is fused with an addition in any of them and there is no floating-point atomic.
+ *
+ *   fedd_assemble_hyperelastic_time
+ *                         fedd_assemble_hyperelastic with one difference in the tangent half: the system matrix receives
+ *                         (cm * M[slot_m]) + K(u), the time tangent of TimeProblem::combineSystems with the coefficients
+ *                         1 / (dt^2 beta) and 1.0, in the pass that sums the rows.  M has the system's FULL pattern or the DIAG
+ *                         node-block pattern, the pairings of fedd_matrix_combine.  NORMATIVE: the stored values are bit for bit
+ *                         those of fedd_assemble_hyperelastic(FEDD_HYPER_TANGENT), fedd_matrix_store(a free slot),
+ *                         fedd_matrix_combine(slot_m, cm, that slot, 1.0): the product cm * m is rounded, then added to the row
+ *                         sum; where M has no entry 0.0 is multiplied and added all the same (a row sum of -0.0 is stored as
+ *                         +0.0 for cm >= 0, as the sequence stores it).  The force half, the inverted-element behaviour (nothing
+ *                         written), the timers and the kept gather lists are those of fedd_assemble_hyperelastic; the Dirichlet
+ *                         marks are not reset (the sequence's combine resets them): fedd_dirichlet follows either.  Errors: an
+ *                         empty slot, a slot of an earlier mesh, a pairing fedd_matrix_combine would refuse.
+ *   fedd_newton_begin     u_k <- the device's current solution vector; b <- the device's current right-hand side, held in a
+ *                         buffer of its own; the nodal vector field (the buffer of fedd_velocity_set) <- u_k: on one rank without
+ *                         ghost nodes the repeated map is the owned map.  Clears the source vector and the counters.  The system
+ *                         must have dim dofs per node.
+ *   fedd_newton_source_set
+ *                         the step's source vector s, host pointer of the system's length, uploaded once; NULL clears it.
+ *   fedd_newton_residual  ONE kernel forms, per row i, m_i = cm * (sum_k M[slot_m]_ik u_k,col(k)) with the lanes per row (8 for rows
+ *                         of at most 32 entries, else 16), the ascending column order per lane and the fixed tree of
+ *                         fedd_matrix_apply, so that m carries the bits of fedd_matrix_apply(slot_m, cm, u_k), and then, each
+ *                         operation rounded on its own, in this order (NORMATIVE; the "reverse" residual):
+ *                             r = b - f
+ *                             r = r + s                    (only if a source is set)
+ *                             r = r - m
+ *                         f = the force vector of the last FEDD_HYPER_FORCE call.  Rows whose node flag is flags[k] and whose
+ *                         component has comp_mask[k * dofs + comp] != 0 (NULL: all), first match, get
+ *                             r = g - u_k                  g = values[k * dofs + comp]   (BCBuilder::setBCMinusVector)
+ *                         r is written into the context's right-hand side, so that fedd_gmres(ctx, NULL, NULL, ...) solves for the
+ *                         Newton update; fedd_dirichlet on the tangent comes BEFORE this call (it writes the right-hand side of
+ *                         its rows).  *norm2 = ||r||_2: every workgroup adds the squares of its rows by a fixed tree, one
+ *                         workgroup adds those partial sums in a fixed order, the host takes the root: two calls agree bit for
+ *                         bit.  Bytes: 12 nnz(M) + 4 (n + 1) + 32 n (+ 8 n with a source) + 4 n / dofs.
+ *                         Errors: no state, an empty slot, a slot of another size or mesh, no force vector, a force vector older
+ *                         than the last fedd_newton_begin / fedd_newton_update ("stale").
+ *   fedd_newton_update    u_k <- u_k + (alpha * delta), delta = the device's solution vector (what fedd_gmres left); the nodal
+ *                         vector field <- u_k; *norm_delta = ||delta||_2 (the reference's "Criterion" = "Update"), summed as
+ *                         above.  One streaming kernel, 32 bytes per row.
+ *   fedd_newton_end       solution vector <- u_k, right-hand side <- b: fedd_newmark_advance finds u_{n+1} where it looks for it.
+ *                         Ends the state.
+ *   fedd_newton_get       u_k to the host.
+ *   fedd_newton_info      active (0 / 1), the length, whether a source is set, whether the force vector is newer than the iterate,
+ *                         residual and update calls since the begin.  active, the length and the source flag describe the open
+ *                         state (0 after fedd_newton_end); the force flag and the two counters outlive fedd_newton_end and show the
+ *                         finished step until the next fedd_newton_begin.  Needs no device; outputs may be NULL.
+ *
+ * The source term is restated as the reference has it, not corrected: DAESolverInTime::addSourceTermToRHS adds it to the
+ * right-hand side b (here: fedd_rhs_axpy before fedd_newton_begin) and NonLinElasticity::calculateNonLinResidualVec adds it
+ * again (here: s), so a caller that follows the reference passes the same vector twice.  The steady class has the same doubling.
+ * ---------------------------------------------------------------------------------------------- */
+int fedd_assemble_hyperelastic_time(fedd_ctx* ctx, int model, const double* params, int n_params, int what, int slot_m, double cm);
+int fedd_newton_begin(fedd_ctx* ctx);
+int fedd_newton_source_set(fedd_ctx* ctx, const double* s_owned);
+int fedd_newton_residual(fedd_ctx* ctx, int slot_m, double cm, int n_bc, const int32_t* flags, const int32_t* comp_mask,
+                         const double* values, double* norm2);
+int fedd_newton_update(fedd_ctx* ctx, double alpha, double* norm_delta);
+int fedd_newton_end(fedd_ctx* ctx);
+int fedd_newton_get(fedd_ctx* ctx, double* u_k);
+int fedd_newton_info(fedd_ctx* ctx, int* active, int64_t* n, int* have_source, int* force_fresh, int64_t* n_residuals,
+                     int64_t* n_updates);
 
 /* read-back for Tpetra::CrsMatrix fill / parity (Matrix::getLocalRowView analog). col_gid maps
  * a local column index to its global dof id. */
