@@ -142,40 +142,7 @@ extern "C" void fedd_ctx_destroy(fedd_ctx* c) {
         for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
         c->ev_pool.clear();
         if (c->comm) ncclCommDestroy((ncclComm_t)c->comm);
-        fedd::DevBuf<int32_t>* ib[] = {&c->d_conn, &c->d_flag, &c->d_n2e_ptr, &c->d_n2e, &c->d_rowptr,
-                                       &c->d_colind, &c->d_isdir, &c->d_node_bin, &c->d_bin_ptr,
-                                       &c->d_bin_nodes, &c->d_sub_n, &c->d_sub_nown, &c->d_sub_dofs,
-                                       &c->d_itmp0, &c->d_itmp1, &c->d_itmp2, &c->d_flags, &c->d_spmv_rows,
-                                       &c->halo.d_send_lid, &c->halo.d_recv_lid};
-        for (auto* b : ib) b->release();
-        fedd::DevBuf<double>* db[] = {&c->d_xyz, &c->d_val, &c->d_rhs, &c->d_x, &c->d_xcol, &c->d_ycol,
-                                      &c->d_inv, &c->d_mult, &c->d_V, &c->d_Z, &c->d_w, &c->d_part,
-                                      &c->d_small, &c->d_dtmp0, &c->halo.d_send_buf, &c->halo.d_recv_buf};
-        for (auto* b : db) b->release();
-        c->d_inv_ptr.release();
-        c->d_dof_node.release();
-        c->d_pat_stash.release();
-        c->d_fbin_ptr.release();
-        c->d_fbin_nodes.release();
-        fedd::DevBuf<int32_t>* cib[] = {&c->d_co_key[0], &c->d_co_key[1], &c->d_co_val[0], &c->d_co_val[1],
-                                        &c->d_co_cell_ptr};
-        for (auto* b : cib) b->release();
-        fedd::DevBuf<double>* cdb[] = {&c->d_co_mask, &c->d_co_cellK, &c->d_co_K, &c->d_dense_ws,
-                                       &c->d_co_part, &c->d_co_r0, &c->d_co_z0};
-        for (auto* b : cdb) b->release();
-        c->d_vel.release();
-        c->d_adv_nptr.release();
-        c->d_adv_ncol.release();
-        c->d_adv_soff.release();
-        c->d_adv_src.release();
-        c->d_adv_tab.release();
-        c->d_adv_ke.release();
-        for (auto& m : c->aux) {
-            m.rowptr.release();
-            m.colind.release();
-            m.val.release();
-        }
-        for (auto& b : c->d_scan) b.release();
+        // (the device buffers are DevBuf members: `delete c` below frees them)
         if (c->h_pinned) (void)hipHostFree(c->h_pinned);
         if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
         if (c->ev_join) (void)hipEventDestroy(c->ev_join);
@@ -704,34 +671,33 @@ extern "C" int fedd_spmv_info(fedd_ctx* c, int64_t* nnz_pattern, int64_t* nnz_st
     NEED_DEVICE(c);
     FEDD_CHECK(c->have_pattern, "fedd_spmv_info: no matrix");
     if (nnz_pattern) *nnz_pattern = c->nnz;
-    if (nnz_streamed) *nnz_streamed = c->cs_valid ? c->cs_nnz : c->nnz;
+    if (nnz_streamed) *nnz_streamed = c->cs.valid ? c->cs.nnz : c->nnz;
     return 0;
 }
 
 extern "C" int fedd_spmv_patterns(fedd_ctx* c, int64_t* n_patterns, int64_t* n_rows_explicit) {
     NEED_DEVICE(c);
     FEDD_CHECK(c->have_pattern, "fedd_spmv_patterns: no matrix");
-    const bool on = c->cs_valid && c->cs_npat > 0 && c->spmv_pattern;
-    if (n_patterns) *n_patterns = on ? c->cs_npat : 0;
-    if (n_rows_explicit) *n_rows_explicit = on ? c->cs_nexpl : c->n_rows;
+    const bool on = c->cs.has_dictionary();
+    if (n_patterns) *n_patterns = on ? c->cs.npat : 0;
+    if (n_rows_explicit) *n_rows_explicit = on ? c->cs.nexpl : c->n_rows;
     return 0;
 }
 
 extern "C" int fedd_spmv_classes(fedd_ctx* c, int64_t* n_classes, int64_t* n_rows_in_classes, int64_t* nnz_streamed_rest) {
     NEED_DEVICE(c);
     FEDD_CHECK(c->have_pattern, "fedd_spmv_classes: no matrix");
-    const bool on = c->cs_valid && c->cs_npat > 0 && c->spmv_pattern && c->cs_ncls > 0 && c->spmv_classes;
-    if (n_classes) *n_classes = on ? c->cs_ncls : 0;
-    if (n_rows_in_classes) *n_rows_in_classes = on ? c->cs_cls_rows : 0;
-    if (nnz_streamed_rest) *nnz_streamed_rest = on ? c->cs_cls_rest : c->cs_nnz;
+    const bool on = c->cs.takes(fedd::SpmvStream::CLASSES);
+    if (n_classes) *n_classes = on ? c->cs.ncls : 0;
+    if (n_rows_in_classes) *n_rows_in_classes = on ? c->cs.cls_rows : 0;
+    if (nnz_streamed_rest) *nnz_streamed_rest = on ? c->cs.cls_rest : c->cs.nnz;
     return 0;
 }
 
 extern "C" int fedd_spmv_col_bytes(fedd_ctx* c, int* bytes_per_column_index, int64_t* entries_with_32bit_columns) {
     NEED_DEVICE(c);
     FEDD_CHECK(c->have_pattern && bytes_per_column_index, "fedd_spmv_col_bytes: no matrix / null output");
-    const bool pat = c->cs_valid && c->cs_npat > 0 && c->spmv_pattern;
-    const bool c16 = c->cs_valid && c->cs_col16 && !pat;
+    const bool pat = c->cs.has_dictionary(), c16 = c->cs.takes(fedd::SpmvStream::ENTRY16);
     *bytes_per_column_index = pat ? 0 : (c16 ? 2 : 4);
     if (entries_with_32bit_columns) {
         int32_t wide = 0;
@@ -739,7 +705,7 @@ extern "C" int fedd_spmv_col_bytes(fedd_ctx* c, int* bytes_per_column_index, int
             FEDD_HIP(hipMemcpyAsync(&wide, c->d_flags.p + 7, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
             FEDD_HIP(hipStreamSynchronize(c->stream));
         }
-        *entries_with_32bit_columns = pat ? 0 : (c16 ? (int64_t)wide : (c->cs_valid ? c->cs_nnz : c->nnz));
+        *entries_with_32bit_columns = pat ? 0 : (c16 ? (int64_t)wide : (c->cs.valid ? c->cs.nnz : c->nnz));
     }
     return 0;
 }
@@ -853,8 +819,8 @@ extern "C" int fedd_pattern_reuse_info(fedd_ctx* c, int* last_reused, int64_t* n
 
 extern "C" int fedd_spmv_reuse_info(fedd_ctx* c, int* last_reused, int64_t* n_reused) {
     FEDD_CHECK(c, "fedd_spmv_reuse_info: null context");
-    if (last_reused) *last_reused = c->cs_valid ? c->cs_last_reused : 0;
-    if (n_reused) *n_reused = c->cs_reuse_count;
+    if (last_reused) *last_reused = c->cs.valid ? c->cs.last_reused : 0;
+    if (n_reused) *n_reused = c->cs.reuse_count;
     return 0;
 }
 

@@ -352,9 +352,9 @@ static int build_tile_shapes(fedd_ctx* c) {
     uint32_t tsize = 1024;
     while (tsize < 2u * (uint32_t)nt) tsize <<= 1;
     // scratch: hashes [nt] | table keys [tsize] (64-bit), claimants [tsize] + counter (32-bit)
-    FEDD_TRY(c->d_cs_hash.ensure((size_t)nt + tsize));
+    FEDD_TRY(c->d_u64tmp.ensure((size_t)nt + tsize));
     FEDD_TRY(c->d_itmp0.ensure((size_t)tsize + 1));
-    unsigned long long* hash = (unsigned long long*)c->d_cs_hash.p;
+    unsigned long long* hash = (unsigned long long*)c->d_u64tmp.p;
     unsigned long long* tkey = hash + nt;
     int32_t* trep = c->d_itmp0.p;
     FEDD_HIP(hipMemsetAsync(tkey, 0, (size_t)tsize * sizeof(unsigned long long), c->stream));

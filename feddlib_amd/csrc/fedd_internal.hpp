@@ -133,6 +133,65 @@ struct TimerSlot {
     std::vector<Pair> pending;
 };
 
+// The solver's SpMV stream (spmv.hip): a solver-private compacted copy of the owned rows -- the numerically zero entries left
+// out (the structural zeros the reference's insertGlobalValues keeps in the pattern, the zeroed entries of Dirichlet rows) -- and
+// what is built from it.  fedd_csr_get keeps returning the reference pattern; the SpMV streams this one.  It stands from a build
+// to the next write to the system matrix (system_written); the options that decide it are members of fedd_ctx, and every one
+// of their setters drops it (OPT_DROPS_STREAM).
+struct SpmvStream {
+    bool valid = false;                         // false after any write to the system matrix (system_written)
+    // the kernel the stream takes, recorded at the end of a build and of a kept build: no entries | k_spmv_cls | k_spmv_pat |
+    // k_spmv_win with 32-bit | 16-bit columns
+    enum Path { EMPTY, CLASSES, PATTERNS, ENTRY32, ENTRY16 } path = EMPTY;
+    bool takes(Path p) const { return valid && path == p; }
+    bool has_dictionary() const { return valid && (path == CLASSES || path == PATTERNS); }
+    // ---- the compacted arrays ----
+    int64_t nnz = 0;
+    int32_t tot32 = 0;                          // nnz as the last row pointer (lives here: its copy to the device is asynchronous)
+    DevBuf<int32_t> d_rowptr, d_col;
+    DevBuf<double> d_val;
+    bool col16 = false;                         // 16-bit column offsets were built (k_cs_col16): d_col16, and
+    DevBuf<uint16_t> d_col16;
+    DevBuf<int32_t> d_wbase;                    // ... their bases per window (-1: the window keeps 32-bit columns)
+    int32_t max_len = 1;                        // longest row of the compacted stream
+    // ---- window -> first row lists ----
+    DevBuf<int32_t> d_rows_csr;                 // of the parity CSR (2048-entry windows), once per pattern
+    bool rows_csr_ready = false;                // ... cleared by a write to the pattern (system_written)
+    int win_nu = 8, pat_nu = 8;                 // windows of the compacted stream: 256 win_nu entries (k_spmv_win), 512 pat_nu values (k_spmv_pat)
+    DevBuf<int32_t> d_rows_win, d_rows_pat;     // ... first row of each of those windows
+    // ---- column-pattern dictionary and row classes ----
+    int32_t npat = 0, nexpl = 0;                // patterns in use (0: dictionary off), rows that keep explicit columns
+    int pat_len = SPMV_PAT_LMAX;                // longest pattern in the table
+    DevBuf<int32_t> d_pati;                     // slot of row [n] | table min row | pattern of slot | lengths | offset lists | counters (spmv.hip pat_layout)
+    DevBuf<uint16_t> d_pat;                     // pattern id per row (0xffff: explicit columns)
+    int32_t ncls = 0, cls_rows = 0, cls_rest = 0;   // classes in use (0: off), rows in a class, stream entries of the other rows
+    int cls_len = 8;                            // stride of the class table (8, 16 or 48 values)
+    DevBuf<uint32_t> d_cls;                     // per row: class << 8 | column pattern (0xffffffff: none)
+    DevBuf<uint16_t> d_clspat;                  // column pattern of a class
+    DevBuf<double> d_clsval;                    // [classes][cls_len] values of a class
+    DevBuf<int32_t> d_clsi;                     // slot of row [n] | table min row | class of slot | counters (spmv.hip cls_layout)
+    // ---- rows that read ghost columns (several ranks, overlapped import) ----
+    int32_t nbnd = -1;                          // their number (-1: not listed)
+    DevBuf<int32_t> d_bnd;                      // flags / positions [n + 2] | the rows
+    // ---- option "spmv_keep_dictionary": the builds the dictionary and the class table on the device come from; they are kept
+    //      while the next matrix' stream still matches them bit for bit ----
+    struct PatTab { int32_t n = -1, npat = 0, nexpl = 0, len = 0; } pat_tab;    // rows, patterns, explicit rows, longest pattern
+    struct ClsTab { int32_t n = -1, len = 0, ncls = 0, rows = 0; } cls_tab;     // rows, stride, classes, classed rows
+    // ---- option "spmv_reuse": the stream, its dictionary, classes and row lists are kept from matrix to matrix while this key
+    //      stands (spmv_reuse_try): written by a build, dropped by every option setter that invalidates the stream ----
+    struct Key {
+        bool valid = false;
+        uint64_t pattern_gen = 0;
+        int64_t n = 0, n_cols = 0, nnz = 0;
+        double drop_tol = 0.0;
+        bool cls_tried = false;                 // the build ran the class stage: its outcome follows the VALUES, so the keep must find them unchanged
+    } key;
+    int64_t last_reused = 0, reuse_count = 0;   // the stream in use was kept, not built; streams kept since the context was made
+    // ---- build scratch: written and read inside one build only ----
+    DevBuf<int32_t> d_wincnt;                   // kept entries per window of the parity CSR -> their offsets
+    DevBuf<uint64_t> d_clskey;                  // keys of the class hash table
+};
+
 }  // namespace fedd
 
 struct fedd_ctx {
@@ -208,61 +267,19 @@ struct fedd_ctx {
     fedd::DevBuf<uint32_t> tl_shape;            // [tl_ntile] first word of the shape part every tile reads (its own or an earlier tile's)
     int tl_nshared = 0;                         // tiles that read the shape of an earlier tile
     fedd::DevBuf<int32_t> d_pat_stash;          // pattern build: merged node lists of the count pass, [k][node]
-    fedd::DevBuf<int32_t> d_spmv_rows;          // CSR-stream: first row of every nnz window
-    bool spmv_rows_ready = false;
-    // solver-private compacted copy of the owned rows: the entries that are exactly 0.0 left out (the structural
-    // zeros the reference's insertGlobalValues keeps in the pattern, and the zeroed entries of Dirichlet rows).
-    // fedd_csr_get keeps returning the reference pattern; SpMV streams this one (same y bit for bit for finite x).
+    // ---- the solver's SpMV: options here, everything built from the matrix in `cs` (fedd::SpmvStream above) ----
     int spmv_compact = 1;                       // option "spmv_compact": 1 = on (default), 0 = stream the parity CSR
     double spmv_drop_tol = 2.220446049250313e-16;   // option "spmv_drop_tol": drop |a_ij| <= tol * max_k |a_ik|; 0 = exact zeros only
     int spmv_exact_public = 1;                  // option "spmv_exact_public": fedd_spmv multiplies with the parity CSR (every stored entry), not with the solver's compacted stream
-    bool cs_valid = false;                      // false after any write to the system matrix (system_written)
-    int64_t cs_nnz = 0;
-    int32_t cs_tot32 = 0;
-    fedd::DevBuf<int32_t> d_cs_rowptr, d_cs_col, d_cs_rows, d_cs_wincnt;
-    fedd::DevBuf<uint16_t> d_cs_col16;          // 16-bit column offsets of the compacted stream (k_cs_col16), d_cs_wbase their bases per window
-    fedd::DevBuf<int32_t> d_cs_wbase;
-    bool cs_col16 = false;
     int spmv_col16 = 1;                         // option "spmv_col16": 16-bit columns in the per-entry window SpMV where the windows allow it
-    fedd::DevBuf<double> d_cs_val;
     int spmv_pattern = 1;                       // option "spmv_pattern": rows that repeat their column offsets share a pattern (spmv.hip)
     int spmv_win_nu = 0;                        // option "spmv_win_nu": entries per lane of k_spmv_win on the compacted stream (4 ... 8; 0 = by row length)
-    int cs_win_nu = 8;
     int spmv_pat_nu = 0;                        // option "spmv_pat_nu": 16-byte loads per lane of k_spmv_pat (2 ... 8; 0 = by the usual row length)
-    int cs_pat_len = fedd::SPMV_PAT_LMAX;           // longest pattern in the table
-    int cs_pat_nu = 8;                          // pattern SpMV: window = 256 * cs_pat_nu values
-    fedd::DevBuf<int32_t> d_cs_prows;           // first row of each of those windows
-    int32_t cs_max_len = 1;                     // longest row of the compacted stream
-    int32_t cs_npat = 0, cs_nexpl = 0;          // patterns in use (0: dictionary off), rows that keep explicit columns
-    fedd::DevBuf<uint64_t> d_cs_hash;           // row hashes [n] | table keys
-    fedd::DevBuf<int32_t> d_cs_pati;            // slot of row [n] | table min row | pattern of slot | lengths | offset lists | counters
-    fedd::DevBuf<uint16_t> d_cs_pat;            // pattern id per row (0xffff: explicit columns)
     int spmv_classes = 1;                       // option "spmv_classes": rows that repeat their column pattern AND their values bit for bit share a class (spmv.hip k_spmv_cls)
-    int32_t cs_cls_tab_n = -1, cs_cls_tab_len = 0, cs_cls_tab_ncls = 0, cs_cls_tab_rows = 0;   // the class table and row words on the device: rows, stride, classes and classed rows of the build they come from (kept while the next matrix still matches them bit for bit)
-    int32_t cs_pat_tab_n = -1, cs_pat_tab_npat = 0, cs_pat_tab_nexpl = 0, cs_pat_tab_len = 0;   // the column-pattern dictionary on the device: rows, patterns, explicit rows, longest pattern of the build it comes from (kept while the next matrix still matches it)
     int spmv_cls_cover = 90;                    // option "spmv_classes_cover": the classes are used when they cover at least this percentage of the rows
     int spmv_keep_dict = 0;                     // option "spmv_keep_dictionary": 1 = the previous matrix' pattern dictionary and row classes are kept while the new stream matches them bit for bit (one verifying pass instead of the build: time loops that reassemble the same operator); 0 (default) = built per matrix
-    // the stream, its dictionary, classes and row lists are kept from matrix to matrix while this key stands (option "spmv_reuse";
-    // spmv.hip spmv_reuse_try): written by a build, dropped by every option setter that invalidates the stream
-    struct CsKey {
-        bool valid = false;
-        uint64_t pattern_gen = 0;
-        int64_t n = 0, n_cols = 0, nnz = 0;
-        double drop_tol = 0.0;
-        bool cls_tried = false;                 // the build ran the class stage: its outcome follows the VALUES, so the keep must find them unchanged
-    } cs_key;
     int spmv_reuse = 1;                         // option "spmv_reuse"
-    int cs_last_reused = 0;                     // the stream in use was kept, not built
-    int64_t cs_reuse_count = 0;
-    int32_t cs_nbnd = -1;                       // rows of the compacted stream that read ghost columns (-1: not listed)
-    fedd::DevBuf<int32_t> d_cs_bnd;             // flags / positions [n + 2] | the rows
-    int cs_cls_len = 8;                         // stride of the class table (8, 16 or 48 values)
-    int32_t cs_ncls = 0, cs_cls_rows = 0, cs_cls_rest = 0;   // classes in use (0: off), rows in a class, stream entries of the other rows
-    fedd::DevBuf<uint32_t> d_cs_cls;            // per row: class << 8 | column pattern (0xffffffff: none)
-    fedd::DevBuf<uint16_t> d_cs_clspat;         // column pattern of a class
-    fedd::DevBuf<double> d_cs_clsval;           // [classes][8] values of a class
-    fedd::DevBuf<int32_t> d_cs_clsi;            // slot of row [n] | table min row | class of slot | counters
-    fedd::DevBuf<uint64_t> d_cs_clskey;         // table keys
+    fedd::SpmvStream cs;
     fedd::DevCsr aux[fedd::MAX_AUX];            // stored blocks (A, B, B^T, C, F, M, A') of a mixed problem
     uint64_t pattern_counter = 0;               // source of DevCsr::pattern_id
     uint64_t mesh_id = 0;                       // counts the fedd_mesh_set calls: which mesh a stored pattern belongs to
@@ -495,6 +512,7 @@ struct fedd_ctx {
     fedd::DevBuf<int64_t> d_scan[3];            // block sums of the device scan, one per level
     fedd::DevBuf<int32_t> d_rs_hist;            // radix sort: digit histograms [256][tiles]
     fedd::DevBuf<double> d_dtmp0;
+    fedd::DevBuf<uint64_t> d_u64tmp;            // hashes and hash-table keys of a build in progress (SpMV dictionary, tile shapes)
     fedd::DevBuf<int32_t> d_flags;              // [16] device flags: 0 max scratch, 1 bad pivot, 2 DGKS gate, 3-5 coarse setup, 8-11 Schwarz setup counters, 12 s-step block length, 13 SpMV stream keep
 
     fedd::HaloPlan halo;
@@ -511,8 +529,8 @@ namespace fedd {
 // What a write to the system matrix invalidates (DESIGN.md has the table of writers).  Every writer of the system slot says
 // what it wrote, once, in the worker that launches the writing kernel, after its argument checks and before the first launch;
 // nothing else clears these fields or moves the two generations (assemble_div records a second time, after the build_pattern it
-// calls: see there).  A builder sets its own product (cs_valid, have_schwarz,
-// have_coarse, sym_ready, spmv_rows_ready, pat_repeatable, have_pattern) at the end of its build and may clear it at the start.
+// calls: see there).  A builder sets its own product (cs.valid, have_schwarz,
+// have_coarse, sym_ready, cs.rows_csr_ready, pat_repeatable, have_pattern) at the end of its build and may clear it at the start.
 enum : unsigned {
     SYS_VALUES = 1,      // d_val rewritten: assembly, scale of the system slot, merge, combine, import, tangent
     SYS_DIRICHLET = 2,   // unit rows / rhs / isdir written: not a new operator, sys_value_gen stays
@@ -520,14 +538,14 @@ enum : unsigned {
     SYS_GONE = 8,        // the slot holds no system matrix any more
 };
 inline void system_written(fedd_ctx* c, unsigned what) {
-    c->cs_valid = false;         // the solver's SpMV stream (cs_key stands: the next build may find the stream still fits)
+    c->cs.valid = false;         // the solver's SpMV stream (cs.key stands: the next build may find the stream still fits)
     c->have_schwarz = false;     // the numeric stage of the preconditioner: a parent that applies this context as a block sees it
     c->have_coarse = c->sym_ready = false;     // ... and what was built on it: the coarse level, the park + gather lists
     if (what & SYS_VALUES) ++c->sys_value_gen;
     if (what & SYS_PATTERN) {
         ++c->pattern_gen;
         c->pat_repeatable = false;
-        c->spmv_rows_ready = false;
+        c->cs.rows_csr_ready = false;
     }
     if (what & SYS_GONE) c->have_pattern = false;
 }
@@ -540,7 +558,7 @@ enum : unsigned {
     OPT_DROPS_REPEAT = 8,    // the next fedd_pattern_build builds
 };
 inline void option_drops(fedd_ctx* c, unsigned what) {
-    if (what & OPT_DROPS_STREAM) c->cs_valid = c->cs_key.valid = false;
+    if (what & OPT_DROPS_STREAM) c->cs.valid = c->cs.key.valid = false;
     if (what & OPT_DROPS_SCHWARZ) c->have_schwarz = false;
     if (what & OPT_DROPS_TILES) c->tl_state = 0;
     if (what & OPT_DROPS_REPEAT) c->pat_repeatable = false;

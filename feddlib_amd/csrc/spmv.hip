@@ -1080,54 +1080,291 @@ __global__ void k_spmv_rows(const int32_t* __restrict__ list, int32_t nl, const 
     y[r] = epi_apply(epi, s, r);
 }
 
-// window -> first row table of the parity CSR (one-off per pattern)
-static int spmv_window_rows(fedd_ctx* c) {
-    const int32_t nb = (int32_t)(c->nnz / SP_CHUNK + 1);
-    if (!c->spmv_rows_ready) {
-        FEDD_TRY(c->d_spmv_rows.ensure((size_t)nb + 1));
-        hipLaunchKernelGGL(k_spmv_block_rows, dim3((unsigned)((nb + 1 + 255) / 256)), dim3(256), 0, c->stream,
-                           (const int32_t*)c->d_rowptr.p, (int32_t)c->n_rows, nb, c->d_spmv_rows.p);
-        c->spmv_rows_ready = true;
-    }
+// ---- host side: layouts, launch tables, the build of the solver's stream, the dispatch ---------------------------------------
+namespace {
+// The two carved-up buffers of the build by name (n = rows).  Dictionary, cs.d_pati: slot of row | table min row | pattern of
+// slot | lengths | offset lists | counters; the SpMV reads the lengths and the offset lists, the rest is build scratch.
+struct PatLayout {
+    int32_t *slot_of, *tmin, *pat_of_slot, *plen, *pdelta;
+    int32_t* counters;   // claimed slots | patterns | explicit rows | longest row | longest pattern | rows that lost their pattern
+    static size_t size(int32_t n) { return (size_t)n + 2 * SPAT_TS + SPAT_P * (SPAT_L + 1) + 16; }
+};
+PatLayout pat_layout(const fedd_ctx* c, int32_t n) {
+    int32_t* p = c->cs.d_pati.p;
+    return {p, p + n, p + n + SPAT_TS, p + n + 2 * SPAT_TS, p + n + 2 * SPAT_TS + SPAT_P, p + n + 2 * SPAT_TS + SPAT_P * (SPAT_L + 1)};
+}
+// Row classes, cs.d_clsi: slot of row | table min row | class of slot | counters; all of it build scratch
+struct ClsLayout {
+    int32_t *slot_of, *tmin, *cls_of_slot;
+    int32_t* counters;   // claimed | classes | classed rows | stream entries of the other rows
+    static size_t size(int32_t n) { return (size_t)n + 2 * CLS_TS + 16; }
+};
+ClsLayout cls_layout(const fedd_ctx* c, int32_t n) {
+    int32_t* p = c->cs.d_clsi.p;
+    return {p, p + n, p + n + CLS_TS, p + n + 2 * CLS_TS};
+}
+
+// Launch tables: every instantiation of the SpMV kernels, indexed by its template arguments
+struct WinRow { decltype(&k_spmv_win<false, 8, false>) c32, c16; };     // C16 = false | true
+template <bool NT, int NU>
+constexpr WinRow WIN = {k_spmv_win<NT, NU, false>, k_spmv_win<NT, NU, true>};
+constexpr WinRow SPMV_WIN[2][5] = {{WIN<false, 4>, WIN<false, 5>, WIN<false, 6>, WIN<false, 7>, WIN<false, 8>},
+                                   {WIN<true, 4>, WIN<true, 5>, WIN<true, 6>, WIN<true, 7>, WIN<true, 8>}};     // [NT][NU - 4]
+struct PatRow { decltype(&k_spmv_pat<false, 8, 8>) lu8, lu16; };        // LU = 8: no pattern is longer | SPAT_LK
+template <bool NT, int NU>
+constexpr PatRow PAT = {k_spmv_pat<NT, NU, 8>, k_spmv_pat<NT, NU, SPAT_LK>};
+constexpr PatRow SPMV_PAT[2][7] = {{PAT<false, 2>, PAT<false, 3>, PAT<false, 4>, PAT<false, 5>, PAT<false, 6>, PAT<false, 7>, PAT<false, 8>},
+                                   {PAT<true, 2>, PAT<true, 3>, PAT<true, 4>, PAT<true, 5>, PAT<true, 6>, PAT<true, 7>, PAT<true, 8>}};   // [NT][NU - 2]
+struct ClsRow { int max_len, rpt; decltype(&k_spmv_cls<4, 8>) kernel; };   // takes class tables of at most this stride; rows per lane
+constexpr ClsRow SPMV_CLS[] = {{8, 4, k_spmv_cls<4, 8>}, {16, 4, k_spmv_cls<4, 16>}, {SPAT_L, 2, k_spmv_cls<2, SPAT_L>}};
+struct LprRow { double max_avg; int lpr; decltype(&k_spmv<4>) kernel; };    // takes matrices of at most this average row length
+constexpr LprRow SPMV_LPR[] = {{4.0, 4, k_spmv<4>}, {10.0, 8, k_spmv<8>}, {24.0, 16, k_spmv<16>}, {48.0, 32, k_spmv<32>}, {1e300, 64, k_spmv<64>}};
+constexpr decltype(&k_cs_reuse<false>) CS_REUSE[2] = {k_cs_reuse<false>, k_cs_reuse<true>};     // [REFRESH]
+
+// when the matrix takes the windowed kernels, and with them the solver's stream
+bool spmv_windowed(const fedd_ctx* c) { return c->spmv_kind == 0 && c->max_row_nnz <= 256 && c->nnz > 0; }
+// non-temporal matrix stream: by default for matrices that do not fit the 256 MB Infinity Cache anyway
+bool spmv_nontemporal(const fedd_ctx* c, int64_t nnz) { return c->spmv_nt < 0 ? 12.0 * (double)nnz > 256.0 * 1024.0 * 1024.0 : c->spmv_nt != 0; }
+int32_t spmv_overhang(const fedd_ctx* c) { return (int32_t)std::max<int64_t>(c->max_row_nnz, 1); }
+int32_t n_windows(int64_t nnz, int entries) { return (int32_t)(nnz / entries + 1); }
+unsigned rows_x8(int32_t n) { return (unsigned)(((int64_t)n * 8 + 255) / 256); }      // workgroups of the kernels with eight lanes per row
+
+}  // namespace
+
+// window -> first row list of a CSR for windows of `entries` entries
+static int launch_block_rows(fedd_ctx* c, const int32_t* rowptr, int64_t nnz, int entries, DevBuf<int32_t>& rows) {
+    const int32_t nb = n_windows(nnz, entries);
+    FEDD_TRY(rows.ensure((size_t)nb + 1));
+    hipLaunchKernelGGL(k_spmv_block_rows, dim3((unsigned)((nb + 1 + 255) / 256)), dim3(256), 0, c->stream, rowptr, (int32_t)c->n_rows, nb, rows.p, entries);
     return 0;
 }
 
-// The matrix changed, its graph and the options did not (cs_key): one pass over the assembled rows instead of the build, see
+// ... of the parity CSR (one-off per pattern)
+static int spmv_window_rows(fedd_ctx* c) {
+    if (!c->cs.rows_csr_ready) FEDD_TRY(launch_block_rows(c, c->d_rowptr.p, c->nnz, SP_CHUNK, c->cs.d_rows_csr));
+    c->cs.rows_csr_ready = true;
+    return 0;
+}
+
+// what spmv_owned runs on the stream; decided by the data and the options of the build (each of their setters drops the stream)
+static void cs_record_path(SpmvStream& s) {
+    s.path = s.nnz == 0 ? SpmvStream::EMPTY
+             : s.npat > 0 && s.ncls > 0 ? SpmvStream::CLASSES
+             : s.npat > 0 ? SpmvStream::PATTERNS
+             : s.col16 ? SpmvStream::ENTRY16 : SpmvStream::ENTRY32;
+    s.valid = true;
+}
+
+// The matrix changed, its graph and the options did not (cs.key): one pass over the assembled rows instead of the build, see
 // k_cs_reuse.  *kept = false: some row differs (or there is nothing to keep), the caller builds.
 static int spmv_reuse_try(fedd_ctx* c, bool* kept) {
     *kept = false;
-    const fedd_ctx::CsKey& k = c->cs_key;
+    SpmvStream& s = c->cs;
+    const SpmvStream::Key& k = s.key;
     if (!c->spmv_reuse || !k.valid) return 0;
     if (k.pattern_gen != c->pattern_gen || k.n != c->n_rows || k.n_cols != c->n_cols || k.nnz != c->nnz || k.drop_tol != c->spmv_drop_tol)
         return 0;
     const int32_t n = (int32_t)c->n_rows;
-    const bool dict = c->cs_npat > 0, classes = dict && c->cs_ncls > 0;
-    const int32_t* pdelta = dict ? c->d_cs_pati.p + n + 2 * SPAT_TS + SPAT_P : nullptr;
+    const bool dict = s.npat > 0, classes = dict && s.ncls > 0;
     ScopedTimer ts(c, FEDD_T_SPMV_SETUP);
     FEDD_TRY(c->d_flags.ensure(16));
     int32_t* flag = c->d_flags.p + 13;
     FEDD_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), c->stream));
-    const dim3 grid((unsigned)std::min<int64_t>(((int64_t)n * 8 + 255) / 256, 8192)), blk(256);
-#define CS_REUSE(REFRESH_)                                                                                                            \
-    hipLaunchKernelGGL(k_cs_reuse<REFRESH_>, grid, blk, 0, c->stream, (const int32_t*)c->d_rowptr.p, (const int32_t*)c->d_colind.p,    \
-                       (const double*)c->d_val.p, n, c->spmv_drop_tol, (const int32_t*)c->d_cs_rowptr.p, (const int32_t*)c->d_cs_col.p, \
-                       c->d_cs_val.p, dict ? (const uint16_t*)c->d_cs_pat.p : (const uint16_t*)nullptr, pdelta,                        \
-                       classes ? (const uint32_t*)c->d_cs_cls.p : (const uint32_t*)nullptr,                                            \
-                       classes ? (const double*)c->d_cs_clsval.p : (const double*)nullptr, c->cs_cls_len, flag)
     // (a build that ran the class stage decided by the values: they have to be the same; else they are written)
-    if (k.cls_tried) CS_REUSE(false);
-    else CS_REUSE(true);
-#undef CS_REUSE
+    hipLaunchKernelGGL(CS_REUSE[k.cls_tried ? 0 : 1], dim3(std::min(rows_x8(n), 8192u)), dim3(256), 0, c->stream, c->d_rowptr.p, c->d_colind.p,
+                       c->d_val.p, n, c->spmv_drop_tol, s.d_rowptr.p, s.d_col.p, s.d_val.p, dict ? s.d_pat.p : nullptr,
+                       dict ? pat_layout(c, n).pdelta : nullptr, classes ? s.d_cls.p : nullptr, classes ? s.d_clsval.p : nullptr, s.cls_len, flag);
     int32_t h_bad = 0;
     FEDD_HIP(hipMemcpyAsync(&h_bad, flag, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     FEDD_HIP(hipStreamSynchronize(c->stream));
     ts.stop();
     FEDD_HIP(hipGetLastError());
     if (h_bad) return 0;
-    c->cs_valid = true;
-    c->cs_last_reused = 1;
-    ++c->cs_reuse_count;
+    cs_record_path(s);
+    s.last_reused = 1;
+    ++s.reuse_count;
     *kept = true;
+    return 0;
+}
+
+// ---- the build, stage by stage (spmv_compact_build below is the driver) ----
+
+// stage 1: the compacted stream (cs.nnz = its entries) and the window rows of the per-entry kernel
+static int cs_compact(fedd_ctx* c) {
+    SpmvStream& s = c->cs;
+    const int32_t n = (int32_t)c->n_rows, nb = n_windows(c->nnz, SP_CHUNK);
+    FEDD_TRY(s.d_wincnt.ensure((size_t)nb + 1));
+    hipLaunchKernelGGL(k_cs_count, dim3((unsigned)nb), dim3(256), 0, c->stream, c->d_rowptr.p, c->d_val.p, s.d_rows_csr.p, nb, c->spmv_drop_tol,
+                       s.d_wincnt.p);
+    int64_t total = 0;
+    FEDD_TRY(exclusive_scan_i32(c, s.d_wincnt.p, s.d_wincnt.p, nb, &total));
+    s.nnz = total;
+    FEDD_TRY(s.d_rowptr.ensure((size_t)n + 1));
+    FEDD_TRY(s.d_col.ensure((size_t)total + 1));
+    FEDD_TRY(s.d_val.ensure((size_t)total + 4096 + 8));      // (k_spmv_pat reads whole 16-byte windows)
+    hipLaunchKernelGGL(k_cs_fill, dim3((unsigned)nb), dim3(256), 0, c->stream, c->d_rowptr.p, c->d_colind.p, c->d_val.p, s.d_rows_csr.p,
+                       s.d_wincnt.p, c->spmv_drop_tol, s.d_rowptr.p, s.d_col.p, s.d_val.p);
+    s.tot32 = (int32_t)total;   // (lives in the context: the copy below is asynchronous)
+    FEDD_HIP(hipMemcpyAsync(s.d_rowptr.p + n, &s.tot32, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    // (unlike k_spmv_pat the per-entry kernel gains nothing from one-trip windows: 214^3 cells, nu 8 / 7 / 6 / 5: 180 / 183 /
+    // 184 / 184 us; 107^3: 24.2 -> 22.5 us with 6, 100^3: no difference -- 8 stays, the option is kept for A/B)
+    s.win_nu = (c->spmv_win_nu >= 4 && c->spmv_win_nu <= 8) ? c->spmv_win_nu : 8;
+    return launch_block_rows(c, s.d_rowptr.p, total, 256 * s.win_nu, s.d_rows_win);
+}
+
+// stage 2: column patterns (see k_spmv_pat), the previous matrix' dictionary verified or a new one built.  cs.npat > 0: the
+// dictionary is worth it, and the pattern kernel's window rows exist
+static int cs_dictionary(fedd_ctx* c) {
+    SpmvStream& s = c->cs;
+    const int32_t n = (int32_t)c->n_rows;
+    const int64_t total = s.nnz;
+    FEDD_TRY(c->d_u64tmp.ensure((size_t)n + SPAT_TS));
+    FEDD_TRY(s.d_pati.ensure(PatLayout::size(n)));
+    FEDD_TRY(s.d_pat.ensure((size_t)n + 1));
+    unsigned long long* hash = (unsigned long long*)c->d_u64tmp.p;      // row hashes [n] | table keys [SPAT_TS]
+    unsigned long long* tkey = hash + n;
+    const PatLayout L = pat_layout(c, n);
+    const dim3 b256(256), gr((unsigned)((n + 255) / 256)), gr8(rows_x8(n));
+    int32_t h[6] = {0, 0, 0, 0, 0, 0};    // claimed slots | patterns | explicit rows | longest row | longest pattern | rows that lost their pattern
+    // the previous matrix' dictionary first: kept while every row that had a pattern still has it (one pass instead of four)
+    bool pat_kept = false;
+    if (c->spmv_keep_dict && s.pat_tab.n == n && s.pat_tab.npat > 0) {
+        FEDD_HIP(hipMemsetAsync(L.counters + 2, 0, 4 * sizeof(int32_t), c->stream));
+        hipLaunchKernelGGL(k_pat_rows, gr8, b256, 0, c->stream, s.d_rowptr.p, s.d_col.p, n, nullptr, nullptr, L.plen, L.pdelta, s.d_pat.p,
+                           L.counters + 2, s.d_pat.p, s.pat_tab.npat);
+        FEDD_HIP(hipMemcpyAsync(h + 2, L.counters + 2, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        FEDD_HIP(hipStreamSynchronize(c->stream));
+        if (h[5] == 0 && h[2] == s.pat_tab.nexpl) {
+            pat_kept = true;
+            h[1] = s.pat_tab.npat;
+            h[4] = s.pat_tab.len;
+        }
+    }
+    if (!pat_kept) {
+        s.pat_tab.n = -1;
+        FEDD_HIP(hipMemsetAsync(tkey, 0, SPAT_TS * sizeof(unsigned long long), c->stream));
+        FEDD_HIP(hipMemsetAsync(L.tmin, 0x7f, SPAT_TS * sizeof(int32_t), c->stream));
+        FEDD_HIP(hipMemsetAsync(L.counters, 0, 8 * sizeof(int32_t), c->stream));
+        hipLaunchKernelGGL(k_pat_hash, gr8, b256, 0, c->stream, s.d_rowptr.p, s.d_col.p, n, hash);
+        // (a table that fills up means "no repeated patterns": the rows that find no slot keep explicit columns)
+        hipLaunchKernelGGL(k_pat_insert, gr, b256, 0, c->stream, hash, n, tkey, L.tmin, L.slot_of, L.counters);
+        hipLaunchKernelGGL(k_pat_table, dim3(1), b256, 0, c->stream, tkey, L.tmin, s.d_rowptr.p, s.d_col.p, L.pat_of_slot, L.plen, L.pdelta,
+                           L.counters + 1);
+        hipLaunchKernelGGL(k_pat_rows, gr8, b256, 0, c->stream, s.d_rowptr.p, s.d_col.p, n, L.slot_of, L.pat_of_slot, L.plen, L.pdelta,
+                           s.d_pat.p, L.counters + 2, nullptr, 0);
+        FEDD_HIP(hipMemcpyAsync(h, L.counters, 5 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        FEDD_HIP(hipStreamSynchronize(c->stream));
+    }
+    // worth it when most rows found a pattern (an unstructured mesh fills the table and finds none)
+    s.max_len = std::max(1, h[3]);
+    s.npat = (h[1] >= 1 && (int64_t)h[2] * 4 <= (int64_t)n) ? std::min<int32_t>(h[1], SPAT_P) : 0;
+    s.nexpl = h[2];
+    s.pat_len = h[4];
+    if (!pat_kept && s.npat > 0) s.pat_tab = {n, s.npat, h[2], h[4]};      // (remembered for the next matrix)
+    if (s.npat > 0) {
+        s.pat_nu = (c->spmv_pat_nu >= 2 && c->spmv_pat_nu <= 8)
+                       ? c->spmv_pat_nu
+                       // about 256 rows per window, one per lane and one trip: 512 nu values ~ 256 x the usual row length
+                       // (214^3 cells, 6.8 entries per row: nu 3: 127 us, 4: 136, 5: 135, 6: 137)
+                       : (int)std::min<int64_t>(8, std::max<int64_t>(2, total / (2 * (int64_t)std::max<int32_t>(n, 1))));
+        FEDD_TRY(launch_block_rows(c, s.d_rowptr.p, total, 512 * s.pat_nu, s.d_rows_pat));
+    }
+    return 0;
+}
+
+// stage 3: row classes on top of the column patterns (see k_cls_insert): rows that repeat their values bit for bit; the previous
+// matrix' classes verified or new ones built.  *tried: the stage ran, so what the stream takes follows the values (cs.key)
+static int cs_classes(fedd_ctx* c, bool* tried) {
+    SpmvStream& s = c->cs;
+    const int32_t n = (int32_t)c->n_rows;
+    s.ncls = 0;
+    s.cls_rows = 0;
+    if (!(s.npat > 0 && c->spmv_classes)) return 0;
+    *tried = true;
+    FEDD_TRY(s.d_cls.ensure((size_t)n + 1));
+    const int cl = s.pat_len <= 8 ? 8 : (s.pat_len <= 16 ? 16 : SPAT_L);       // table stride
+    s.cls_len = cl;
+    FEDD_TRY(s.d_clsval.ensure((size_t)CLS_MAX * cl));
+    FEDD_TRY(s.d_clspat.ensure((size_t)CLS_MAX));
+    FEDD_TRY(s.d_clsi.ensure(ClsLayout::size(n)));
+    FEDD_TRY(s.d_clskey.ensure((size_t)CLS_TS));
+    unsigned long long* ckey = (unsigned long long*)s.d_clskey.p;
+    const ClsLayout L = cls_layout(c, n);
+    const dim3 b256(256), gr8(rows_x8(n)), gr8cap(std::min(gr8.x, 8192u));
+    // the previous matrix' classes first: if every row that had a class still matches it bit for bit, they are kept
+    bool kept = false;
+    if (c->spmv_keep_dict && s.cls_tab.n == n && s.cls_tab.len == cl && s.cls_tab.ncls > 0 && s.cls_tab.rows > 0) {
+        FEDD_HIP(hipMemsetAsync(L.counters, 0, 8 * sizeof(int32_t), c->stream));
+        hipLaunchKernelGGL(k_cls_verify, gr8cap, b256, 0, c->stream, s.d_rowptr.p, s.d_val.p, s.d_pat.p, n, s.d_cls.p, s.d_clsval.p,
+                           s.d_clspat.p, s.cls_tab.ncls, L.counters, cl);
+        int32_t hv[3] = {0, 0, 0};      // rows that match | previously classed rows that do not | stream entries of the rows without a class
+        FEDD_HIP(hipMemcpyAsync(hv, L.counters, sizeof(hv), hipMemcpyDeviceToHost, c->stream));
+        FEDD_HIP(hipStreamSynchronize(c->stream));
+        if (hv[1] == 0 && hv[0] == s.cls_tab.rows) {
+            kept = true;
+            s.ncls = s.cls_tab.ncls;
+            s.cls_rows = hv[0];
+            s.cls_rest = hv[2];
+        }
+    }
+    if (!kept) {
+        s.cls_tab.ncls = 0;
+        FEDD_HIP(hipMemsetAsync(ckey, 0, CLS_TS * sizeof(unsigned long long), c->stream));
+        FEDD_HIP(hipMemsetAsync(L.tmin, 0x7f, CLS_TS * sizeof(int32_t), c->stream));
+        FEDD_HIP(hipMemsetAsync(L.counters, 0, 8 * sizeof(int32_t), c->stream));
+        hipLaunchKernelGGL(k_cls_insert, gr8, b256, 0, c->stream, s.d_rowptr.p, s.d_val.p, s.d_pat.p, n, ckey, L.tmin, L.slot_of, L.counters);
+        hipLaunchKernelGGL(k_cls_table, dim3(1), dim3(1024), 0, c->stream, ckey, L.cls_of_slot, L.counters + 1);
+        hipLaunchKernelGGL(k_cls_fill, dim3(CLS_TS / 256), b256, 0, c->stream, L.cls_of_slot, L.tmin, s.d_rowptr.p, s.d_val.p, s.d_pat.p,
+                           s.d_clsval.p, s.d_clspat.p, cl);
+        hipLaunchKernelGGL(k_cls_rows, gr8cap, b256, 0, c->stream, s.d_rowptr.p, s.d_val.p, s.d_pat.p, n, L.slot_of, L.cls_of_slot, s.d_clsval.p,
+                           s.d_clspat.p, s.d_cls.p, L.counters + 2, cl);
+        int32_t hc[4] = {0, 0, 0, 0};   // claimed | classes | classed rows | stream entries of the other rows
+        FEDD_HIP(hipMemcpyAsync(hc, L.counters, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
+        FEDD_HIP(hipStreamSynchronize(c->stream));
+        // worth it when nearly every row is in a class (the other rows go through a per-row loop)
+        if (hc[1] >= 1 && (int64_t)hc[2] * 100 >= (int64_t)n * c->spmv_cls_cover) {
+            s.ncls = std::min<int32_t>(hc[1], CLS_MAX);
+            s.cls_rows = hc[2];
+            s.cls_rest = hc[3];
+            s.cls_tab = {n, cl, s.ncls, hc[2]};
+        }
+    }
+    return 0;
+}
+
+// stage 4: rows that read ghost columns (several ranks; for the overlapped import of the class SpMV, see k_bnd_flag)
+static int cs_ghost_rows(fedd_ctx* c) {
+    SpmvStream& s = c->cs;
+    const int32_t n = (int32_t)c->n_rows;
+    s.nbnd = -1;
+    if (!(s.ncls > 0 && c->n_cols > c->n_rows && s.nnz > 0)) return 0;
+    FEDD_TRY(s.d_bnd.ensure((size_t)2 * n + 4));
+    int32_t* bflag = s.d_bnd.p;             // [n + 1] flags -> positions
+    int32_t* blist = bflag + n + 2;         // [<= n] the rows
+    const dim3 gq((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(k_bnd_flag, gq, dim3(256), 0, c->stream, s.d_rowptr.p, s.d_col.p, n, bflag);
+    int64_t nb_rows = 0;
+    FEDD_TRY(exclusive_scan_i32(c, bflag, bflag, n, &nb_rows));
+    hipLaunchKernelGGL(k_bnd_list, gq, dim3(256), 0, c->stream, bflag, n, blist);
+    s.nbnd = (int32_t)nb_rows;
+    return 0;
+}
+
+// stage 5: 16-bit columns for the per-entry window kernel (option "spmv_col16"; decided by the data: every window's column span)
+// (not for a stream that goes through the column patterns: k_spmv_pat reads no column of a row that has one)
+static int cs_columns16(fedd_ctx* c) {
+    SpmvStream& s = c->cs;
+    s.col16 = false;
+    if (!(c->spmv_col16 && s.nnz > 0 && s.npat == 0)) return 0;
+    const int32_t nbc = n_windows(s.nnz, 256 * s.win_nu);
+    FEDD_TRY(s.d_col16.ensure((size_t)s.nnz + 4096 + 8));
+    FEDD_TRY(s.d_wbase.ensure((size_t)nbc + 1));
+    FEDD_TRY(c->d_flags.ensure(16));
+    int32_t* flag = c->d_flags.p + 7;
+    FEDD_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), c->stream));
+    hipLaunchKernelGGL(k_cs_col16, dim3((unsigned)nbc), dim3(256), 0, c->stream, s.d_col.p, (int32_t)s.nnz, 256 * s.win_nu, s.d_wbase.p,
+                       s.d_col16.p, flag);
+    s.col16 = true;     // (per window: nothing for the host to wait for; fedd_spmv_col_bytes reads the count when asked)
     return 0;
 }
 
@@ -1136,37 +1373,17 @@ static int spmv_compact_build(fedd_ctx* c) {
     bool kept = false;
     FEDD_TRY(spmv_reuse_try(c, &kept));
     if (kept) return 0;
-    c->cs_key.valid = false;
-    c->cs_last_reused = 0;
+    SpmvStream& s = c->cs;
+    s.key.valid = false;
+    s.last_reused = 0;
     bool cls_tried = false;
     const int32_t n = (int32_t)c->n_rows;
-    const int32_t nb = (int32_t)(c->nnz / SP_CHUNK + 1);
     FEDD_TRY(spmv_window_rows(c));
     ScopedTimer ts(c, FEDD_T_SPMV_SETUP);
-    FEDD_TRY(c->d_cs_wincnt.ensure((size_t)nb + 1));
-    hipLaunchKernelGGL(k_cs_count, dim3((unsigned)nb), dim3(256), 0, c->stream, (const int32_t*)c->d_rowptr.p,
-                       (const double*)c->d_val.p, (const int32_t*)c->d_spmv_rows.p, nb, c->spmv_drop_tol, c->d_cs_wincnt.p);
-    int64_t total = 0;
-    FEDD_TRY(exclusive_scan_i32(c, c->d_cs_wincnt.p, c->d_cs_wincnt.p, nb, &total));
-    c->cs_nnz = total;
-    FEDD_TRY(c->d_cs_rowptr.ensure((size_t)n + 1));
-    FEDD_TRY(c->d_cs_col.ensure((size_t)total + 1));
-    FEDD_TRY(c->d_cs_val.ensure((size_t)total + 4096 + 8));      // (k_spmv_pat reads whole 16-byte windows)
-    hipLaunchKernelGGL(k_cs_fill, dim3((unsigned)nb), dim3(256), 0, c->stream, (const int32_t*)c->d_rowptr.p,
-                       (const int32_t*)c->d_colind.p, (const double*)c->d_val.p, (const int32_t*)c->d_spmv_rows.p,
-                       (const int32_t*)c->d_cs_wincnt.p, c->spmv_drop_tol, c->d_cs_rowptr.p, c->d_cs_col.p, c->d_cs_val.p);
-    c->cs_tot32 = (int32_t)total;   // (lives in the context: the copy below is asynchronous)
-    FEDD_HIP(hipMemcpyAsync(c->d_cs_rowptr.p + n, &c->cs_tot32, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    // (unlike k_spmv_pat the per-entry kernel gains nothing from one-trip windows: 214^3 cells, nu 8 / 7 / 6 / 5: 180 / 183 /
-    // 184 / 184 us; 107^3: 24.2 -> 22.5 us with 6, 100^3: no difference -- 8 stays, the option is kept for A/B)
-    c->cs_win_nu = (c->spmv_win_nu >= 4 && c->spmv_win_nu <= 8) ? c->spmv_win_nu : 8;
-    const int32_t nbc = (int32_t)(total / (256 * c->cs_win_nu) + 1);
-    FEDD_TRY(c->d_cs_rows.ensure((size_t)nbc + 1));
-    hipLaunchKernelGGL(k_spmv_block_rows, dim3((unsigned)((nbc + 1 + 255) / 256)), dim3(256), 0, c->stream,
-                       (const int32_t*)c->d_cs_rowptr.p, n, nbc, c->d_cs_rows.p, 256 * c->cs_win_nu);
-    // column patterns (see k_spmv_pat)
-    c->cs_npat = 0;
-    c->cs_ncls = 0;
+    FEDD_TRY(cs_compact(c));
+    const int64_t total = s.nnz;
+    s.npat = 0;
+    s.ncls = 0;
     // (matrices that fit the Infinity Cache keep the per-entry kernel -- measured: 100^3 cells 20.5 us against 25 us --,
     // so the dictionary is not built for them; option value 2 forces it)
     const bool big = 12.0 * (double)total > 256.0 * 1024.0 * 1024.0 || c->spmv_pattern == 2;
@@ -1177,176 +1394,18 @@ static int spmv_compact_build(fedd_ctx* c) {
     // structured grid tried: 107^3 cells 23.2 -> 16.2 us --; without classes such a matrix goes back to the per-entry kernel)
     const bool try_classes = c->spmv_classes && !big && n >= 65536;
     if (c->spmv_pattern && total > 0 && (big || try_classes) && short_rows) {
-        FEDD_TRY(c->d_cs_hash.ensure((size_t)n + SPAT_TS));
-        FEDD_TRY(c->d_cs_pati.ensure((size_t)n + 2 * SPAT_TS + SPAT_P * (SPAT_L + 1) + 16));
-        FEDD_TRY(c->d_cs_pat.ensure((size_t)n + 1));
-        unsigned long long* hash = (unsigned long long*)c->d_cs_hash.p;
-        unsigned long long* tkey = hash + n;
-        int32_t* slot_of = c->d_cs_pati.p;
-        int32_t* tmin = slot_of + n;
-        int32_t* pat_of_slot = tmin + SPAT_TS;
-        int32_t* plen = pat_of_slot + SPAT_TS;
-        int32_t* pdelta = plen + SPAT_P;
-        int32_t* counters = pdelta + SPAT_P * SPAT_L;      // claimed slots | patterns | explicit rows
-        const dim3 b256(256), gr((unsigned)((n + 255) / 256)), gr8((unsigned)(((int64_t)n * 8 + 255) / 256));
-        int32_t h[6] = {0, 0, 0, 0, 0, 0};    // claimed slots | patterns | explicit rows | longest row | longest pattern | rows that lost their pattern
-        // the previous matrix' dictionary first: kept while every row that had a pattern still has it (one pass instead of four)
-        bool pat_kept = false;
-        if (c->spmv_keep_dict && c->cs_pat_tab_n == n && c->cs_pat_tab_npat > 0) {
-            FEDD_HIP(hipMemsetAsync(counters + 2, 0, 4 * sizeof(int32_t), c->stream));
-            hipLaunchKernelGGL(k_pat_rows, gr8, b256, 0, c->stream, (const int32_t*)c->d_cs_rowptr.p, (const int32_t*)c->d_cs_col.p, n,
-                               (const int32_t*)nullptr, (const int32_t*)nullptr, (const int32_t*)plen, (const int32_t*)pdelta,
-                               c->d_cs_pat.p, counters + 2, (const uint16_t*)c->d_cs_pat.p, c->cs_pat_tab_npat);
-            FEDD_HIP(hipMemcpyAsync(h + 2, counters + 2, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-            FEDD_HIP(hipStreamSynchronize(c->stream));
-            if (h[5] == 0 && h[2] == c->cs_pat_tab_nexpl) {
-                pat_kept = true;
-                h[1] = c->cs_pat_tab_npat;
-                h[4] = c->cs_pat_tab_len;
-            }
-        }
-        if (!pat_kept) {
-        c->cs_pat_tab_n = -1;
-        FEDD_HIP(hipMemsetAsync(tkey, 0, SPAT_TS * sizeof(unsigned long long), c->stream));
-        FEDD_HIP(hipMemsetAsync(tmin, 0x7f, SPAT_TS * sizeof(int32_t), c->stream));
-        FEDD_HIP(hipMemsetAsync(counters, 0, 8 * sizeof(int32_t), c->stream));
-        hipLaunchKernelGGL(k_pat_hash, gr8, b256, 0, c->stream, (const int32_t*)c->d_cs_rowptr.p, (const int32_t*)c->d_cs_col.p, n, hash);
-        // (a table that fills up means "no repeated patterns": the rows that find no slot keep explicit columns)
-        hipLaunchKernelGGL(k_pat_insert, gr, b256, 0, c->stream, (const unsigned long long*)hash, n, tkey, tmin, slot_of, counters);
-        hipLaunchKernelGGL(k_pat_table, dim3(1), b256, 0, c->stream, (const unsigned long long*)tkey, (const int32_t*)tmin,
-                           (const int32_t*)c->d_cs_rowptr.p, (const int32_t*)c->d_cs_col.p, pat_of_slot, plen, pdelta, counters + 1);
-        hipLaunchKernelGGL(k_pat_rows, gr8, b256, 0, c->stream, (const int32_t*)c->d_cs_rowptr.p, (const int32_t*)c->d_cs_col.p, n,
-                           (const int32_t*)slot_of, (const int32_t*)pat_of_slot, (const int32_t*)plen, (const int32_t*)pdelta,
-                           c->d_cs_pat.p, counters + 2, (const uint16_t*)nullptr, 0);
-        FEDD_HIP(hipMemcpyAsync(h, counters, 5 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        FEDD_HIP(hipStreamSynchronize(c->stream));
-        }
-        // worth it when most rows found a pattern (an unstructured mesh fills the table and finds none)
-        c->cs_max_len = std::max(1, h[3]);
-        c->cs_npat = (h[1] >= 1 && (int64_t)h[2] * 4 <= (int64_t)n) ? std::min<int32_t>(h[1], SPAT_P) : 0;
-        c->cs_nexpl = h[2];
-        c->cs_pat_len = h[4];
-        if (!pat_kept && c->cs_npat > 0) {      // (remembered for the next matrix)
-            c->cs_pat_tab_n = n;
-            c->cs_pat_tab_npat = c->cs_npat;
-            c->cs_pat_tab_nexpl = h[2];
-            c->cs_pat_tab_len = h[4];
-        }
-        if (c->cs_npat > 0) {
-            c->cs_pat_nu = (c->spmv_pat_nu >= 2 && c->spmv_pat_nu <= 8)
-                               ? c->spmv_pat_nu
-                               // about 256 rows per window, one per lane and one trip: 512 nu values ~ 256 x the usual row length
-                               // (214^3 cells, 6.8 entries per row: nu 3: 127 us, 4: 136, 5: 135, 6: 137)
-                               : (int)std::min<int64_t>(8, std::max<int64_t>(2, total / (2 * (int64_t)std::max<int32_t>(n, 1))));
-            const int32_t nbp = (int32_t)(total / (512 * c->cs_pat_nu) + 1);
-            FEDD_TRY(c->d_cs_prows.ensure((size_t)nbp + 1));
-            hipLaunchKernelGGL(k_spmv_block_rows, dim3((unsigned)((nbp + 1 + 255) / 256)), dim3(256), 0, c->stream,
-                               (const int32_t*)c->d_cs_rowptr.p, n, nbp, c->d_cs_prows.p, 512 * c->cs_pat_nu);
-        }
-        // row classes on top of the column patterns (see k_cls_insert): rows that repeat their values bit for bit
-        c->cs_ncls = 0;
-        c->cs_cls_rows = 0;
-        if (c->cs_npat > 0 && c->spmv_classes) {
-            cls_tried = true;
-            FEDD_TRY(c->d_cs_cls.ensure((size_t)n + 1));
-            const int cl = c->cs_pat_len <= 8 ? 8 : (c->cs_pat_len <= 16 ? 16 : SPAT_L);       // table stride
-            c->cs_cls_len = cl;
-            FEDD_TRY(c->d_cs_clsval.ensure((size_t)CLS_MAX * cl));
-            FEDD_TRY(c->d_cs_clspat.ensure((size_t)CLS_MAX));
-            FEDD_TRY(c->d_cs_clsi.ensure((size_t)n + 2 * CLS_TS + 16));
-            FEDD_TRY(c->d_cs_clskey.ensure((size_t)CLS_TS));
-            unsigned long long* ckey = (unsigned long long*)c->d_cs_clskey.p;
-            int32_t* cslot = c->d_cs_clsi.p;
-            int32_t* cmin = cslot + n;
-            int32_t* cof = cmin + CLS_TS;
-            int32_t* ccnt = cof + CLS_TS;       // claimed | classes | classed rows | stream entries of the other rows
-            // the previous matrix' classes first: if every row that had a class still matches it bit for bit, they are kept
-            bool kept = false;
-            if (c->spmv_keep_dict && c->cs_cls_tab_n == n && c->cs_cls_tab_len == cl && c->cs_cls_tab_ncls > 0 && c->cs_cls_tab_rows > 0) {
-                FEDD_HIP(hipMemsetAsync(ccnt, 0, 8 * sizeof(int32_t), c->stream));
-                hipLaunchKernelGGL(k_cls_verify, dim3(std::min<unsigned>(gr8.x, 8192u)), b256, 0, c->stream, (const int32_t*)c->d_cs_rowptr.p, (const double*)c->d_cs_val.p,
-                                   (const uint16_t*)c->d_cs_pat.p, n, (const uint32_t*)c->d_cs_cls.p, (const double*)c->d_cs_clsval.p,
-                                   (const uint16_t*)c->d_cs_clspat.p, c->cs_cls_tab_ncls, ccnt, cl);
-                int32_t hv[3] = {0, 0, 0};
-                FEDD_HIP(hipMemcpyAsync(hv, ccnt, sizeof(hv), hipMemcpyDeviceToHost, c->stream));
-                FEDD_HIP(hipStreamSynchronize(c->stream));
-                if (hv[1] == 0 && hv[0] == c->cs_cls_tab_rows) {
-                    kept = true;
-                    c->cs_ncls = c->cs_cls_tab_ncls;
-                    c->cs_cls_rows = hv[0];
-                    c->cs_cls_rest = hv[2];
-                }
-            }
-            if (!kept) {
-            c->cs_cls_tab_ncls = 0;
-            FEDD_HIP(hipMemsetAsync(ckey, 0, CLS_TS * sizeof(unsigned long long), c->stream));
-            FEDD_HIP(hipMemsetAsync(cmin, 0x7f, CLS_TS * sizeof(int32_t), c->stream));
-            FEDD_HIP(hipMemsetAsync(ccnt, 0, 8 * sizeof(int32_t), c->stream));
-            hipLaunchKernelGGL(k_cls_insert, gr8, b256, 0, c->stream, (const int32_t*)c->d_cs_rowptr.p, (const double*)c->d_cs_val.p,
-                               (const uint16_t*)c->d_cs_pat.p, n, ckey, cmin, cslot, ccnt);
-            hipLaunchKernelGGL(k_cls_table, dim3(1), dim3(1024), 0, c->stream, (const unsigned long long*)ckey, cof, ccnt + 1);
-            hipLaunchKernelGGL(k_cls_fill, dim3(CLS_TS / 256), b256, 0, c->stream, (const int32_t*)cof, (const int32_t*)cmin,
-                               (const int32_t*)c->d_cs_rowptr.p, (const double*)c->d_cs_val.p, (const uint16_t*)c->d_cs_pat.p,
-                               c->d_cs_clsval.p, c->d_cs_clspat.p, cl);
-            hipLaunchKernelGGL(k_cls_rows, dim3(std::min<unsigned>(gr8.x, 8192u)), b256, 0, c->stream, (const int32_t*)c->d_cs_rowptr.p, (const double*)c->d_cs_val.p,
-                               (const uint16_t*)c->d_cs_pat.p, n, (const int32_t*)cslot, (const int32_t*)cof,
-                               (const double*)c->d_cs_clsval.p, (const uint16_t*)c->d_cs_clspat.p, c->d_cs_cls.p, ccnt + 2, cl);
-            int32_t hc[4] = {0, 0, 0, 0};
-            FEDD_HIP(hipMemcpyAsync(hc, ccnt, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
-            FEDD_HIP(hipStreamSynchronize(c->stream));
-            if (getenv("FEDD_SPMV_DEBUG")) fprintf(stderr, "[spmv classes] n %d: slots claimed %d, classes %d, rows in classes %d, stream entries outside %d\n", n, hc[0], hc[1], hc[2], hc[3]);
-            // worth it when nearly every row is in a class (the other rows go through a per-row loop)
-            if (hc[1] >= 1 && (int64_t)hc[2] * 100 >= (int64_t)n * c->spmv_cls_cover) {
-                c->cs_ncls = std::min<int32_t>(hc[1], CLS_MAX);
-                c->cs_cls_rows = hc[2];
-                c->cs_cls_rest = hc[3];
-                c->cs_cls_tab_n = n;
-                c->cs_cls_tab_len = cl;
-                c->cs_cls_tab_ncls = c->cs_ncls;
-                c->cs_cls_tab_rows = hc[2];
-            }
-            }   // (!kept)
-        }
+        FEDD_TRY(cs_dictionary(c));
+        FEDD_TRY(cs_classes(c, &cls_tried));
         // (the dictionary was only tried for the classes' sake: a matrix in the Infinity Cache, or rows longer than k_spmv_pat unrolls)
-        if ((!big || c->cs_pat_len > SPAT_LK) && c->cs_ncls == 0) c->cs_npat = 0;
+        if ((!big || s.pat_len > SPAT_LK) && s.ncls == 0) s.npat = 0;
     }
-    // rows that read ghost columns (several ranks; for the overlapped import of the class SpMV, see k_bnd_flag)
-    c->cs_nbnd = -1;
-    if (c->cs_ncls > 0 && c->n_cols > c->n_rows && total > 0) {
-        FEDD_TRY(c->d_cs_bnd.ensure((size_t)2 * n + 4));
-        int32_t* bflag = c->d_cs_bnd.p;             // [n + 1] flags -> positions
-        int32_t* blist = bflag + n + 2;             // [<= n] the rows
-        const dim3 gq((unsigned)((n + 255) / 256));
-        hipLaunchKernelGGL(k_bnd_flag, gq, dim3(256), 0, c->stream, (const int32_t*)c->d_cs_rowptr.p, (const int32_t*)c->d_cs_col.p, n, bflag);
-        int64_t nb_rows = 0;
-        FEDD_TRY(exclusive_scan_i32(c, bflag, bflag, n, &nb_rows));
-        hipLaunchKernelGGL(k_bnd_list, gq, dim3(256), 0, c->stream, (const int32_t*)bflag, n, blist);
-        c->cs_nbnd = (int32_t)nb_rows;
-    }
-    // 16-bit columns for the per-entry window kernel (option "spmv_col16"; decided by the data: every window's column span)
-    // (not for a stream that goes through the column patterns: k_spmv_pat reads no column of a row that has one)
-    c->cs_col16 = false;
-    if (c->spmv_col16 && total > 0 && c->cs_npat == 0) {
-        FEDD_TRY(c->d_cs_col16.ensure((size_t)total + 4096 + 8));
-        FEDD_TRY(c->d_cs_wbase.ensure((size_t)nbc + 1));
-        FEDD_TRY(c->d_flags.ensure(16));
-        int32_t* flag = c->d_flags.p + 7;
-        FEDD_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), c->stream));
-        hipLaunchKernelGGL(k_cs_col16, dim3((unsigned)nbc), dim3(256), 0, c->stream, (const int32_t*)c->d_cs_col.p, (int32_t)total,
-                           256 * c->cs_win_nu, c->d_cs_wbase.p, c->d_cs_col16.p, flag);
-        c->cs_col16 = true;     // (per window: nothing for the host to wait for; fedd_spmv_col_bytes reads the count when asked)
-    }
+    FEDD_TRY(cs_ghost_rows(c));
+    FEDD_TRY(cs_columns16(c));
     ts.stop();
     FEDD_HIP(hipGetLastError());
-    c->cs_valid = true;
-    // what the next matrix has to share with this one for the stream to be kept (spmv_reuse_try)
-    c->cs_key.pattern_gen = c->pattern_gen;
-    c->cs_key.n = c->n_rows;
-    c->cs_key.n_cols = c->n_cols;
-    c->cs_key.nnz = c->nnz;
-    c->cs_key.drop_tol = c->spmv_drop_tol;
-    c->cs_key.cls_tried = cls_tried;
-    c->cs_key.valid = true;
+    cs_record_path(s);
+    // stage 6: what the next matrix has to share with this one for the stream to be kept (spmv_reuse_try)
+    s.key = {true, c->pattern_gen, c->n_rows, c->n_cols, c->nnz, c->spmv_drop_tol, cls_tried};
     return 0;
 }
 
@@ -1355,13 +1414,60 @@ __global__ void k_epi_only(double* __restrict__ y, SpmvEpi epi, int32_t n) {   /
     if (i < n) y[i] = epi_apply(epi, 0.0, i);
 }
 
+// ---- one launch function per kernel family: grid, LDS, one launch ----
+
+// the per-entry window kernel on a CSR and its window rows: the compacted stream (col16 != nullptr: with its 16-bit columns), or
+// the parity CSR (nu = 8)
+static void launch_win(fedd_ctx* c, int nu, const int32_t* rowptr, const int32_t* col, const double* val, const int32_t* rows, int64_t nnz,
+                       const uint16_t* col16, const int32_t* wbase, const double* x, double* y, const SpmvEpi& epi) {
+    const int32_t nb = n_windows(nnz, 256 * nu), ovh = spmv_overhang(c);
+    const WinRow& row = SPMV_WIN[spmv_nontemporal(c, nnz)][nu - 4];
+    hipLaunchKernelGGL(col16 ? row.c16 : row.c32, dim3((unsigned)nb), dim3(256), (size_t)(256 * nu + ovh) * sizeof(double), c->stream, rowptr, col,
+                       val, x, y, rows, nb, (int32_t)nnz, ovh, epi, col16, wbase);
+}
+
+// the pattern kernel: 16-byte loads, window = 512 nu values
+static void launch_pat(fedd_ctx* c, const double* x, double* y, const SpmvEpi& epi) {
+    const SpmvStream& s = c->cs;
+    const PatLayout L = pat_layout(c, (int32_t)c->n_rows);
+    const int32_t nb = n_windows(s.nnz, 512 * s.pat_nu), ovh = spmv_overhang(c);
+    const PatRow& row = SPMV_PAT[spmv_nontemporal(c, s.nnz)][s.pat_nu - 2];
+    hipLaunchKernelGGL(s.pat_len <= 8 ? row.lu8 : row.lu16, dim3((unsigned)nb), dim3(256), (size_t)(512 * s.pat_nu + ovh) * sizeof(double),
+                       c->stream, s.d_rowptr.p, s.d_col.p, s.d_val.p, s.d_pat.p, L.plen, L.pdelta, s.npat, x, y, s.d_rows_pat.p, nb,
+                       (int32_t)s.nnz, ovh, epi);
+}
+
+// the class kernel: a lane per row, the first row of the table that takes the class table's stride (8, 16 or SPAT_L: cs_classes)
+static void launch_cls(fedd_ctx* c, const double* x, double* y, const SpmvEpi& epi) {
+    const SpmvStream& s = c->cs;
+    const int32_t n = (int32_t)c->n_rows;
+    const PatLayout L = pat_layout(c, n);
+    const ClsRow* row = SPMV_CLS;
+    while (s.cls_len > row->max_len) ++row;
+    hipLaunchKernelGGL(row->kernel, dim3((unsigned)((n + 256 * row->rpt - 1) / (256 * row->rpt))), dim3(256), 0, c->stream, s.d_rowptr.p,
+                       s.d_col.p, s.d_val.p, s.d_pat.p, s.d_cls.p, s.d_clsval.p, L.plen, L.pdelta, s.npat, x, y, n, epi);
+}
+
+// row-per-lane-group on the parity CSR: the lane group by the average row length (the last row of the table takes every length)
+static void launch_lpr(fedd_ctx* c, double avg, const double* x, double* y, const SpmvEpi& epi) {
+    const int32_t n = (int32_t)c->n_rows;
+    const LprRow* row = SPMV_LPR;
+    while (avg > row->max_avg) ++row;
+    hipLaunchKernelGGL(row->kernel, dim3((unsigned)(((int64_t)n * row->lpr + 255) / 256)), dim3(256), 0, c->stream, c->d_rowptr.p, c->d_colind.p,
+                       c->d_val.p, x, y, n, epi);
+}
+
 int spmv_owned(fedd_ctx* c, const double* d_x_owned, double* d_y_owned, bool x_has_tail, const double* d_sub, double theta,
                int use_compact) {
     const double* x = d_x_owned;
     const SpmvEpi epi{d_sub, theta};
+    SpmvStream& s = c->cs;
     const bool compact = use_compact < 0 ? c->spmv_compact != 0 : use_compact != 0;
+    // spmv_kind: 0 = automatic (CSR-window, CSR-stream for rows longer than 256, row-per-lane-group for
+    // very long rows), 1 = row-per-lane-group, 2 = CSR-stream
+    const bool windowed = spmv_windowed(c);
     // (the solver's stream is built before the ghost import is issued: the overlapped import below needs its row list)
-    if (compact && c->spmv_kind == 0 && c->max_row_nnz <= 256 && c->nnz > 0 && !c->cs_valid) FEDD_TRY(spmv_compact_build(c));
+    if (compact && windowed && !s.valid) FEDD_TRY(spmv_compact_build(c));
     bool overlapped = false;
     if (c->n_cols != c->n_rows || !c->halo.peers.empty()) {   // also a rank that only sends takes part
         double* xb = const_cast<double*>(d_x_owned);
@@ -1372,9 +1478,8 @@ int spmv_owned(fedd_ctx* c, const double* d_x_owned, double* d_y_owned, bool x_h
         }
         // option "halo_overlap" with the class kernel (its build is current and lists the rows that read ghost columns): the
         // import goes to a second stream, the product over all rows runs meanwhile, the listed rows are redone afterwards
-        const bool cls_path = compact && c->spmv_kind == 0 && c->max_row_nnz <= 256 && c->nnz > 0 && c->cs_valid && c->cs_npat > 0 &&
-                              c->spmv_pattern && c->cs_ncls > 0 && c->spmv_classes && c->cs_nnz > 0;
-        if (c->halo_overlap && c->nranks > 1 && cls_path && c->cs_nbnd >= 0) {
+        const bool cls_path = compact && windowed && s.takes(SpmvStream::CLASSES);
+        if (c->halo_overlap && c->nranks > 1 && cls_path && s.nbnd >= 0) {
             if (!c->stream2) {
                 FEDD_HIP(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
                 FEDD_HIP(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
@@ -1395,133 +1500,43 @@ int spmv_owned(fedd_ctx* c, const double* d_x_owned, double* d_y_owned, bool x_h
     }
     const double avg = c->n_rows ? (double)c->nnz / (double)c->n_rows : 1.0;
     const int32_t n = (int32_t)c->n_rows;
-    // spmv_kind: 0 = automatic (CSR-window, CSR-stream for rows longer than 256, row-per-lane-group for
-    // very long rows), 1 = row-per-lane-group, 2 = CSR-stream
-    const bool windowed = c->spmv_kind == 0 && c->max_row_nnz <= 256 && c->nnz > 0;
     const bool streamed = !windowed && (c->spmv_kind == 0 || c->spmv_kind == 2) && avg <= 64.0 && c->max_row_nnz <= 2048;
+    if (windowed ? !compact : streamed) FEDD_TRY(spmv_window_rows(c));     // (the kernels on the parity CSR that take window rows)
+    ScopedTimer ts(c, FEDD_T_SPMV);
     if (windowed && compact) {
         // the compacted stream (numerically zero entries left out): same kernel, fewer bytes
-        if (!c->cs_valid) FEDD_TRY(spmv_compact_build(c));
-        const int wnu = c->cs_win_nu;
-        const int32_t nbc = (int32_t)(c->cs_nnz / (256 * wnu) + 1);
-        const int32_t ovh = (int32_t)std::max<int64_t>(c->max_row_nnz, 1);
-        const size_t lds = (size_t)(256 * wnu + ovh) * sizeof(double);
-        const bool nt = c->spmv_nt < 0 ? 12.0 * (double)c->cs_nnz > 256.0 * 1024.0 * 1024.0 : c->spmv_nt != 0;
-        ScopedTimer ts(c, FEDD_T_SPMV);
-        if (c->cs_nnz == 0) {
-            if (epi.sub) hipLaunchKernelGGL(k_epi_only, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_y_owned, epi, n);
-            else FEDD_HIP(hipMemsetAsync(d_y_owned, 0, (size_t)n * sizeof(double), c->stream));
-        } else if (c->cs_npat > 0 && c->spmv_pattern && c->cs_ncls > 0 && c->spmv_classes) {
-            const int32_t* plen = c->d_cs_pati.p + n + 2 * SPAT_TS;
-            const int32_t* pdelta = plen + SPAT_P;
-#define SPMV_CLS(RPT_, CL_)                                                                                                     \
-    hipLaunchKernelGGL((k_spmv_cls<RPT_, CL_>), dim3((unsigned)((n + 256 * RPT_ - 1) / (256 * RPT_))), dim3(256), 0, c->stream,     \
-                       (const int32_t*)c->d_cs_rowptr.p, (const int32_t*)c->d_cs_col.p, (const double*)c->d_cs_val.p,                 \
-                       (const uint16_t*)c->d_cs_pat.p, (const uint32_t*)c->d_cs_cls.p, (const double*)c->d_cs_clsval.p, plen, pdelta, \
-                       c->cs_npat, x, d_y_owned, n, epi)
-            if (c->cs_cls_len <= 8) SPMV_CLS(4, 8);
-            else if (c->cs_cls_len <= 16) SPMV_CLS(4, 16);
-            else SPMV_CLS(2, SPAT_L);
-#undef SPMV_CLS
-            if (overlapped) {   // the ghost values have arrived: the rows that read them, again
-                FEDD_HIP(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-                overlapped = false;
-                if (c->cs_nbnd > 0)
-                    hipLaunchKernelGGL(k_spmv_rows, dim3((unsigned)((c->cs_nbnd + 255) / 256)), dim3(256), 0, c->stream,
-                                       (const int32_t*)(c->d_cs_bnd.p + n + 2), c->cs_nbnd, (const int32_t*)c->d_cs_rowptr.p,
-                                       (const int32_t*)c->d_cs_col.p, (const double*)c->d_cs_val.p, x, d_y_owned, epi);
+        switch (s.path) {
+            case SpmvStream::EMPTY:
+                if (epi.sub) hipLaunchKernelGGL(k_epi_only, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_y_owned, epi, n);
+                else FEDD_HIP(hipMemsetAsync(d_y_owned, 0, (size_t)n * sizeof(double), c->stream));
+                break;
+            case SpmvStream::CLASSES:
+                launch_cls(c, x, d_y_owned, epi);
+                if (overlapped) {   // the ghost values have arrived: the rows that read them, again
+                    FEDD_HIP(hipStreamWaitEvent(c->stream, c->ev_join, 0));
+                    if (s.nbnd > 0)
+                        hipLaunchKernelGGL(k_spmv_rows, dim3((unsigned)((s.nbnd + 255) / 256)), dim3(256), 0, c->stream, s.d_bnd.p + n + 2,
+                                           s.nbnd, s.d_rowptr.p, s.d_col.p, s.d_val.p, x, d_y_owned, epi);
+                }
+                break;
+            case SpmvStream::PATTERNS: launch_pat(c, x, d_y_owned, epi); break;
+            case SpmvStream::ENTRY32:
+            case SpmvStream::ENTRY16: {
+                const bool c16 = s.path == SpmvStream::ENTRY16;
+                launch_win(c, s.win_nu, s.d_rowptr.p, s.d_col.p, s.d_val.p, s.d_rows_win.p, s.nnz, c16 ? s.d_col16.p : nullptr,
+                           c16 ? s.d_wbase.p : nullptr, x, d_y_owned, epi);
             }
-        } else if (c->cs_npat > 0 && c->spmv_pattern) {
-            const int32_t* plen = c->d_cs_pati.p + n + 2 * SPAT_TS;
-            const int32_t* pdelta = plen + SPAT_P;
-            const int nu = c->cs_pat_nu;                        // 16-byte loads per lane: window = 512 nu values
-            const int32_t nbp = (int32_t)(c->cs_nnz / (512 * nu) + 1);
-            const size_t ldp = (size_t)(512 * nu + ovh) * sizeof(double);
-#define SPMV_PAT1(NT_, NU_, LU_)                                                                                                    \
-    hipLaunchKernelGGL((k_spmv_pat<NT_, NU_, LU_>), dim3((unsigned)nbp), dim3(256), ldp, c->stream, (const int32_t*)c->d_cs_rowptr.p, \
-                       (const int32_t*)c->d_cs_col.p, (const double*)c->d_cs_val.p, (const uint16_t*)c->d_cs_pat.p, plen,           \
-                       pdelta, c->cs_npat, x, d_y_owned, (const int32_t*)c->d_cs_prows.p, nbp, (int32_t)c->cs_nnz, ovh, epi)
-#define SPMV_PAT(NT_, NU_)                                 \
-    if (c->cs_pat_len <= 8) SPMV_PAT1(NT_, NU_, 8);         \
-    else SPMV_PAT1(NT_, NU_, SPAT_LK)
-#define SPMV_PAT_NU(NT_)                 \
-    switch (nu) {                        \
-        case 2: SPMV_PAT(NT_, 2); break; \
-        case 3: SPMV_PAT(NT_, 3); break; \
-        case 4: SPMV_PAT(NT_, 4); break; \
-        case 5: SPMV_PAT(NT_, 5); break; \
-        case 6: SPMV_PAT(NT_, 6); break; \
-        case 7: SPMV_PAT(NT_, 7); break; \
-        default: SPMV_PAT(NT_, 8); break; \
-    }
-            if (nt) { SPMV_PAT_NU(true) } else { SPMV_PAT_NU(false) }
-#undef SPMV_PAT_NU
-#undef SPMV_PAT
-#undef SPMV_PAT1
-        } else {
-#define SPMV_WIN(NT_, NU_)                                                                                                       \
-    if (c->cs_col16)                                                                                                             \
-        hipLaunchKernelGGL((k_spmv_win<NT_, NU_, true>), dim3((unsigned)nbc), dim3(256), lds, c->stream,                         \
-                           (const int32_t*)c->d_cs_rowptr.p, (const int32_t*)c->d_cs_col.p, (const double*)c->d_cs_val.p, x,     \
-                           d_y_owned, (const int32_t*)c->d_cs_rows.p, nbc, (int32_t)c->cs_nnz, ovh, epi,                         \
-                           (const uint16_t*)c->d_cs_col16.p, (const int32_t*)c->d_cs_wbase.p);                                   \
-    else                                                                                                                         \
-        hipLaunchKernelGGL((k_spmv_win<NT_, NU_>), dim3((unsigned)nbc), dim3(256), lds, c->stream, (const int32_t*)c->d_cs_rowptr.p, \
-                           (const int32_t*)c->d_cs_col.p, (const double*)c->d_cs_val.p, x, d_y_owned,                            \
-                           (const int32_t*)c->d_cs_rows.p, nbc, (int32_t)c->cs_nnz, ovh, epi, (const uint16_t*)nullptr,           \
-                           (const int32_t*)nullptr)
-#define SPMV_WIN_NU(NT_)                 \
-    switch (wnu) {                       \
-        case 4: SPMV_WIN(NT_, 4); break; \
-        case 5: SPMV_WIN(NT_, 5); break; \
-        case 6: SPMV_WIN(NT_, 6); break; \
-        case 7: SPMV_WIN(NT_, 7); break; \
-        default: SPMV_WIN(NT_, 8); break; \
-    }
-            if (nt) { SPMV_WIN_NU(true) } else { SPMV_WIN_NU(false) }
-#undef SPMV_WIN_NU
-#undef SPMV_WIN
         }
-        ts.stop();
-        FEDD_HIP(hipGetLastError());
-        return 0;
+    } else if (windowed) {
+        launch_win(c, SP_CHUNK / 256, c->d_rowptr.p, c->d_colind.p, c->d_val.p, s.d_rows_csr.p, c->nnz, nullptr, nullptr, x, d_y_owned, epi);
+    } else if (streamed) {
+        const int32_t nb = n_windows(c->nnz, SP_CHUNK);
+        hipLaunchKernelGGL(k_spmv_stream, dim3((unsigned)nb), dim3(256), (size_t)(SP_CHUNK + spmv_overhang(c)) * sizeof(double), c->stream,
+                           c->d_rowptr.p, c->d_colind.p, c->d_val.p, x, d_y_owned, s.d_rows_csr.p, nb, epi);
+    } else {
+        launch_lpr(c, avg, x, d_y_owned, epi);
     }
-    if (windowed || streamed) {
-        const int32_t nb = (int32_t)(c->nnz / SP_CHUNK + 1);
-        FEDD_TRY(spmv_window_rows(c));
-        const int32_t ovh = (int32_t)std::max<int64_t>(c->max_row_nnz, 1);
-        const size_t lds = (size_t)(SP_CHUNK + ovh) * sizeof(double);
-        ScopedTimer ts(c, FEDD_T_SPMV);
-        // non-temporal matrix stream: by default for matrices that do not fit the 256 MB Infinity Cache anyway
-        const bool nt = c->spmv_nt < 0 ? 12.0 * (double)c->nnz > 256.0 * 1024.0 * 1024.0 : c->spmv_nt != 0;
-        if (windowed && nt)
-            hipLaunchKernelGGL(k_spmv_win<true>, dim3((unsigned)nb), dim3(256), lds, c->stream, (const int32_t*)c->d_rowptr.p,
-                               (const int32_t*)c->d_colind.p, (const double*)c->d_val.p, x, d_y_owned,
-                               (const int32_t*)c->d_spmv_rows.p, nb, (int32_t)c->nnz, ovh, epi);
-        else if (windowed)
-            hipLaunchKernelGGL(k_spmv_win<false>, dim3((unsigned)nb), dim3(256), lds, c->stream, (const int32_t*)c->d_rowptr.p,
-                               (const int32_t*)c->d_colind.p, (const double*)c->d_val.p, x, d_y_owned,
-                               (const int32_t*)c->d_spmv_rows.p, nb, (int32_t)c->nnz, ovh, epi);
-        else
-            hipLaunchKernelGGL(k_spmv_stream, dim3((unsigned)nb), dim3(256), lds, c->stream, (const int32_t*)c->d_rowptr.p,
-                               (const int32_t*)c->d_colind.p, (const double*)c->d_val.p, x, d_y_owned,
-                               (const int32_t*)c->d_spmv_rows.p, nb, epi);
-        ts.stop();
-        FEDD_HIP(hipGetLastError());
-        return 0;
-    }
-    ScopedTimer t(c, FEDD_T_SPMV);
-#define SPMV_LAUNCH(L)                                                                                        \
-    hipLaunchKernelGGL(k_spmv<L>, dim3((unsigned)(((int64_t)n * L + 255) / 256)), dim3(256), 0, c->stream,      \
-                       (const int32_t*)c->d_rowptr.p, (const int32_t*)c->d_colind.p, (const double*)c->d_val.p, \
-                       x, d_y_owned, n, epi)
-    if (avg <= 4.0) SPMV_LAUNCH(4);
-    else if (avg <= 10.0) SPMV_LAUNCH(8);
-    else if (avg <= 24.0) SPMV_LAUNCH(16);
-    else if (avg <= 48.0) SPMV_LAUNCH(32);
-    else SPMV_LAUNCH(64);
-#undef SPMV_LAUNCH
-    t.stop();
+    ts.stop();
     FEDD_HIP(hipGetLastError());
     return 0;
 }
