@@ -1,5 +1,5 @@
 // Stokes driver on the MI355X path, written against the FEDD:: operator surface the way the reference's driver is
-// (feddlib/problems/tests/stokes/main.cpp:96-360, "unstructured" branch): same XML parameter files, same call sequence
+// (feddlib/problems/tests/stokes/main.cpp:96-360, "structured" and "unstructured" branches): same XML parameter files, same call sequence
 //   Domain(comm, dim) x 2 -> MeshPartitioner::readAndPartition -> buildP2ofP1Domain -> BCBuilder::addBC ->
 //   Stokes(...) -> addBoundaries -> initializeProblem -> assemble -> setBoundaries -> solve -> ExporterParaView.
 // "Preconditioner Method" = "Monolithic" is the path built here (FROSch on the merged system, parametersPrec.xml);
@@ -73,7 +73,9 @@ int main(int argc, char* argv[]) {
         std::string meshType = parameterListProblem->sublist("Parameter").get("Mesh Type", "structured");
         int volumeID = parameterListProblem->sublist("Parameter").get("Volume ID", 0);
         std::string bcType = parameterListProblem->sublist("Parameter").get("BC Type", "parabolic");
-        TEUCHOS_TEST_FOR_EXCEPTION(meshType != "unstructured", std::logic_error, "this driver reads unstructured meshes");
+        TEUCHOS_TEST_FOR_EXCEPTION(meshType != "unstructured" && meshType != "structured", std::logic_error,
+                                   "\"Mesh Type\" = \"" << meshType << "\" is not built (structured and unstructured are)");
+        int m = parameterListProblem->sublist("Parameter").get("H/h", 5);
         TEUCHOS_TEST_FOR_EXCEPTION(discVelocity != "P2", std::logic_error, "this driver builds P2 / P1");
 
         ParameterListPtr_Type parameterListAll(new Teuchos::ParameterList(*parameterListProblem));
@@ -89,14 +91,31 @@ int main(int argc, char* argv[]) {
             Teuchos::TimeMonitor totalTimeMonitor(*totalTime);
             {
                 Teuchos::TimeMonitor buildMeshMonitor(*buildMesh);
-                domainPressure.reset(new Domain<SC, LO, GO, NO>(comm, dim));
-                domainVelocity.reset(new Domain<SC, LO, GO, NO>(comm, dim));
-                MeshPartitioner_Type::DomainPtrArray_Type domainP1Array(1);
-                domainP1Array[0] = domainPressure;
-                ParameterListPtr_Type pListPartitioner = Teuchos::sublist(parameterListAll, "Mesh Partitioner");
-                MeshPartitioner<SC, LO, GO, NO> partitionerP1(domainP1Array, pListPartitioner, "P1", dim);
-                partitionerP1.readAndPartition(volumeID);
-                domainVelocity->buildP2ofP1Domain(domainPressure);
+                if (meshType == "structured") {
+                    // the reference's "structured" branch (stokes/main.cpp:207-225): n = round(size^(1/dim)) blocks per direction,
+                    // m = H/h cells per block, both domains from Domain::buildMesh with flags option 1
+                    const int size = comm->getSize();
+                    const int n = (int)(std::pow((double)size, 1. / dim) + 100 * 2.220446049250313e-16);
+                    std::vector<double> x(dim, 0.0);
+                    if (dim == 2) {
+                        domainPressure.reset(new Domain<SC, LO, GO, NO>(x, 1., 1., comm));
+                        domainVelocity.reset(new Domain<SC, LO, GO, NO>(x, 1., 1., comm));
+                    } else {
+                        domainPressure.reset(new Domain<SC, LO, GO, NO>(x, 1., 1., 1., comm));
+                        domainVelocity.reset(new Domain<SC, LO, GO, NO>(x, 1., 1., 1., comm));
+                    }
+                    domainPressure->buildMesh(1, "Square", dim, discPressure, n, m, 0);
+                    domainVelocity->buildMesh(1, "Square", dim, discVelocity, n, m, 0);
+                } else {
+                    domainPressure.reset(new Domain<SC, LO, GO, NO>(comm, dim));
+                    domainVelocity.reset(new Domain<SC, LO, GO, NO>(comm, dim));
+                    MeshPartitioner_Type::DomainPtrArray_Type domainP1Array(1);
+                    domainP1Array[0] = domainPressure;
+                    ParameterListPtr_Type pListPartitioner = Teuchos::sublist(parameterListAll, "Mesh Partitioner");
+                    MeshPartitioner<SC, LO, GO, NO> partitionerP1(domainP1Array, pListPartitioner, "P1", dim);
+                    partitionerP1.readAndPartition(volumeID);
+                    domainVelocity->buildP2ofP1Domain(domainPressure);
+                }
             }
             std::vector<double> parameter_vec(1, parameterListProblem->sublist("Parameter").get("MaxVelocity", 1.));
             Teuchos::RCP<BCBuilder<SC, LO, GO, NO> > bcFactory(new BCBuilder<SC, LO, GO, NO>());
@@ -130,9 +149,14 @@ int main(int argc, char* argv[]) {
             Teuchos::RCP<const MultiVector<SC, LO, GO, NO> > exportSolutionP = stokes.getSolution()->getBlock(1);
             std::ofstream out(outFile);
             out << std::setprecision(17);
-            for (size_t i = 0; i < exportSolutionV->getLocalLength(); ++i) out << i << " " << exportSolutionV->getData(0)[i] << "\n";
+            // by global dof id (the maps' numbering: the identity for a mesh file, the reference's lattice ids for structured meshes)
+            auto mapV = domainVelocity->getMapUnique();
+            auto mapP = domainPressure->getMapUnique();
+            for (size_t i = 0; i < exportSolutionV->getLocalLength(); ++i)
+                out << (size_t)mapV->getGlobalElement((LO)(i / dim)) * dim + i % dim << " " << exportSolutionV->getData(0)[i] << "\n";
             const size_t off = exportSolutionV->getLocalLength();
-            for (size_t i = 0; i < exportSolutionP->getLocalLength(); ++i) out << off + i << " " << exportSolutionP->getData(0)[i] << "\n";
+            for (size_t i = 0; i < exportSolutionP->getLocalLength(); ++i)
+                out << off + (size_t)mapP->getGlobalElement((LO)i) << " " << exportSolutionP->getData(0)[i] << "\n";
             if (parameterListAll->sublist("General").get("ParaViewExport", false)) {
                 Teuchos::RCP<ExporterParaView<SC, LO, GO, NO> > exParaVelocity(new ExporterParaView<SC, LO, GO, NO>());
                 Teuchos::RCP<ExporterParaView<SC, LO, GO, NO> > exParaPressure(new ExporterParaView<SC, LO, GO, NO>());

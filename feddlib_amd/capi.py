@@ -47,6 +47,10 @@ SIGNATURES = {
                                    _i64p, _i32p, _i64p, _i32p],
     "fedd_mesh_structured_owner": [C.c_int, _ip, _ip, C.c_int64, _i64p, _i32p],
     "fedd_mesh_structured_row_ghosts": [C.c_int, _ip, _ip, C.c_int, C.c_int, _f64p, _f64p, C.c_int, _i64p, _i64p, _i32p],
+    "fedd_mesh_structured_p2_sizes": [C.c_int, _ip, _ip, C.c_int, _i64p, _i64p, _i64p],
+    "fedd_mesh_structured_p2_build": [C.c_int, _ip, _ip, C.c_int, C.c_int, _f64p, _i64p, _i64p, _i32p, _i32p, _i32p,
+                                      _i32p, _i32p],
+    "fedd_mesh_p2_vertices_first": [C.c_int, _ip, _ip, C.c_int, _i32p, _i64p],
     "fedd_mesh_read_sizes": [C.c_char_p, C.c_int, _i64p, _i64p, _i64p],
     "fedd_mesh_read": [C.c_char_p, C.c_int, _f64p, _i32p, _i32p, _i32p, _i32p, _i32p],
     "fedd_mesh_p2_sizes": [C.c_int, C.c_int64, _i32p, _i64p],
@@ -282,6 +286,58 @@ def structured_mesh(dim, N, M, rank=0, origin=None, size=None, flags_option=1, g
     return out
 
 
+def _inverse(perm):
+    inv = np.empty_like(perm)
+    inv[perm] = np.arange(perm.shape[0], dtype=perm.dtype)
+    return inv
+
+
+def vertices_first_perm(dim, N, M, rank=0):
+    """(perm, n_p1) of fedd_mesh_p2_vertices_first: perm[new] = reference local id, the P1 lattice nodes first"""
+    dec, cel = _decomp(dim, N), _decomp(dim, M)
+    nr, np1 = C.c_int64(), C.c_int64()
+    _chk(lib().fedd_mesh_structured_p2_sizes(dim, _ints(dec), _ints(cel), rank, C.byref(nr), None, None))
+    perm = np.zeros(nr.value, dtype=np.int32)
+    _chk(lib().fedd_mesh_p2_vertices_first(dim, _ints(dec), _ints(cel), rank, _p(perm, _i32p), C.byref(np1)))
+    return perm, int(np1.value)
+
+
+def structured_mesh_p2(dim, N, M, rank=0, flags_option=1, vertices_first=False):
+    """Structured P2 mesh of the unit square / cube, the rank-local mesh of the reference (no ghost layers): the keys of
+    structured_mesh plus owner_rep, elem_flag, perm and n_p1.  perm[new] = reference local id puts the P1 lattice nodes
+    first in the P1 generator's order; with vertices_first the node arrays and conn come renumbered by it (the order the
+    device layer wants for Stokes: pressure dof k = P1 node k), otherwise they are in the reference's numbering."""
+    L = lib()
+    dec, cel = _decomp(dim, N), _decomp(dim, M)
+    nr, nu, ne, np1 = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    _chk(L.fedd_mesh_structured_p2_sizes(dim, _ints(dec), _ints(cel), rank, C.byref(nr), C.byref(nu), C.byref(ne)))
+    nen = 10 if dim == 3 else 6
+    conn = np.zeros((ne.value, nen), dtype=np.int32)
+    xyz = np.zeros((nr.value, dim), dtype=np.float64)
+    gid_rep = np.zeros(nr.value, dtype=np.int64)
+    owner = np.zeros(nr.value, dtype=np.int32)
+    flag_rep = np.zeros(nr.value, dtype=np.int32)
+    gid_uni = np.zeros(nu.value, dtype=np.int64)
+    flag_uni = np.zeros(nu.value, dtype=np.int32)
+    eflag = np.zeros(ne.value, dtype=np.int32)
+    _chk(L.fedd_mesh_structured_p2_build(dim, _ints(dec), _ints(cel), rank, flags_option, _p(xyz, _f64p), _p(gid_rep, _i64p),
+                                         _p(gid_uni, _i64p), _p(owner, _i32p), _p(flag_rep, _i32p), _p(flag_uni, _i32p),
+                                         _p(conn, _i32p), _p(eflag, _i32p)))
+    perm, n_p1 = vertices_first_perm(dim, dec, cel, rank)
+    if vertices_first:
+        inv = _inverse(perm)
+        mine = owner == rank
+        uni_of_rep = np.cumsum(mine) - 1                      # unique index of an owned node in the reference order
+        conn = np.ascontiguousarray(inv[conn])
+        xyz, gid_rep, flag_rep, owner = (np.ascontiguousarray(a[perm]) for a in (xyz, gid_rep, flag_rep, owner))
+        keep = perm[mine[perm]]
+        gid_uni, flag_uni = gid_uni[uni_of_rep[keep]], flag_uni[uni_of_rep[keep]]
+    n_global = int(np.prod([2 * n * m + 1 for n, m in zip(dec, cel)]))
+    return dict(dim=dim, nen=nen, conn=conn, xyz=xyz, gid_rep=gid_rep, flag_rep=flag_rep, gid_uni=gid_uni, flag_uni=flag_uni,
+                n_global=n_global, decomp=dec, cells=cel, rank=rank, owner_rep=owner, elem_flag=eflag, perm=perm,
+                n_p1=n_p1, vertices_first=bool(vertices_first))
+
+
 def read_mesh(path, dim):
     """INRIA .mesh file -> one-rank P1 mesh dict (repeated = unique = identity numbering)."""
     L = lib()
@@ -379,9 +435,24 @@ def p2_surfaces(m, surf=None):
     return s2
 
 
-def structured_surfaces(dim, N, M, rank=0, flags_option=1, ghosts=False):
-    """(surf [n, dim] local repeated ids, flags [n]): the boundary faces of structured_mesh(dim, N, M, rank, ghosts=ghosts)"""
+def structured_surfaces(dim, N, M, rank=0, flags_option=1, ghosts=False, p2=False, vertices_first=False):
+    """(surf [n, dim] local repeated ids, flags [n]): the boundary faces of structured_mesh(dim, N, M, rank, ghosts=ghosts).
+    p2: the boundary edges [n, 3] / triangles [n, 6] of structured_mesh_p2(dim, N, M, rank, vertices_first=...) instead: the
+    same faces with the same flags, vertices then mid nodes in the slot order of fedd_mesh_p2_surfaces."""
     dec, cel = _decomp(dim, N), _decomp(dim, M)
+    if p2:
+        if ghosts:
+            raise FeddError("structured P2 meshes have no ghost layers")
+        s1, sflag = structured_surfaces(dim, dec, cel, rank, flags_option)
+        n1 = [c + 1 for c in cel] + [1] * (3 - dim)
+        p2m = [2 * c + 1 for c in cel] + [1] * (3 - dim)
+        r, s, t = s1 % n1[0], (s1 // n1[0]) % n1[1], s1 // (n1[0] * n1[1])
+        v = 2 * r + p2m[0] * (2 * s + p2m[1] * 2 * t)          # the P1 lattice node (r,s,t) is P2 lattice node (2r,2s,2t)
+        pairs = [(0, 1)] if dim == 2 else [(0, 1), (1, 2), (0, 2)]
+        surf = np.concatenate([v] + [((v[:, a] + v[:, b]) // 2)[:, None] for a, b in pairs], axis=1).astype(np.int32)
+        if vertices_first:
+            surf = _inverse(vertices_first_perm(dim, dec, cel, rank)[0])[surf]
+        return np.ascontiguousarray(surf), sflag
     n = C.c_int64()
     _chk(lib().fedd_mesh_structured_surfaces_sizes(dim, _ints(dec), _ints(cel), rank, int(ghosts), C.byref(n)))
     surf = np.zeros((n.value, dim), dtype=np.int32)

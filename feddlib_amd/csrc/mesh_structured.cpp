@@ -5,6 +5,9 @@
 //   MeshStructured::buildMesh3D P1 branch   feddlib/core/Mesh/MeshStructured_def.hpp:703-806
 //   setStructuredMeshFlags(1)               feddlib/core/Mesh/MeshStructured_def.hpp:2974-3203
 //   Map::buildUniqueMap                     feddlib/core/LinearAlgebra/Map_def.hpp:184-210
+// and, at the end of the file, the structured P2 lattice (no ghost layers):
+//   MeshStructured::buildMesh2D P2 branch   feddlib/core/Mesh/MeshStructured_def.hpp:468-619
+//   MeshStructured::buildMesh3D P2 branch   feddlib/core/Mesh/MeshStructured_def.hpp:808-994
 // Layout differences: flat SoA arrays instead of vector<vector<>>, per-direction block counts
 // (the reference only knows N x N x N), optional ghost-element layers, lowest-rank owner rule.
 // Ghost layers L: 0 = the reference's block; 1 = plus the layer of cells above the block that completes the
@@ -411,5 +414,193 @@ extern "C" int fedd_mesh_structured_surfaces(int dim, const int* decomp, const i
         if (sflag) sflag[n] = flag;
         ++n;
     });
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Structured P2 lattice: 6-node triangles / 10-node tetrahedra on the (2M+1)^dim points of a block.
+//   MeshStructured::buildMesh2D P2 branch   MeshStructured_def.hpp:468-619
+//   MeshStructured::buildMesh3D P2 branch   MeshStructured_def.hpp:808-994
+//   setStructuredMeshFlags(1) on P2 meshes  MeshStructured_def.hpp:2984-3011 (2D), :3137-3202 (3D)
+// A lattice point (r,s,t) of the block has local id r + s*P2M + t*P2M^2, P2M = 2M+1 (:491-492, :832-834).  The vertices of
+// an element are the P1 vertices at doubled indices and every mid node is the lattice point half-way between its two
+// vertices; the slots the reference writes out one by one (:572-596, :906-986) are (0,1),(1,2),(0,2) in 2D and
+// (0,1),(1,2),(0,2),(0,3),(1,3),(2,3) in 3D for every one of the 2 / 6 elements of a cell.
+namespace {
+
+struct BlockP2 {
+    Block b;          // the P1 block of the same decomp / cells, no ghosts
+    int p2m[3];       // lattice points per direction, 2M+1 (1 beyond dim)
+    int64_t P2[3];    // global lattice points per direction, 2NM+1
+};
+
+int make_block_p2(int dim, const int* decomp, const int* cells, int rank, BlockP2& q) {
+    if (make_block(dim, decomp, cells, rank, 0, q.b)) return 1;
+    for (int d = 0; d < 3; ++d) {
+        q.p2m[d] = d < dim ? 2 * (q.b.M[d] + 1) - 1 : 1;                                              // :563, :899
+        q.P2[d] = d < dim ? (int64_t)q.b.N[d] * q.p2m[d] - (q.b.N[d] - 1) : 1;                        // :325, :663
+    }
+    return 0;
+}
+
+inline int32_t p2_id(const BlockP2& q, int r, int s, int t) {
+    return (int32_t)(r + (int64_t)q.p2m[0] * (s + (int64_t)q.p2m[1] * t));
+}
+
+// (make_block sets lo_owned to 0 in the directions beyond dim, where the only index is 0)
+inline bool p2_owned(const BlockP2& q, int r, int s, int t) {
+    return r >= q.b.lo_owned[0] && s >= q.b.lo_owned[1] && t >= q.b.lo_owned[2];
+}
+
+const int P2_EDGE[6][2] = {{0, 1}, {1, 2}, {0, 2}, {0, 3}, {1, 3}, {2, 3}};
+
+// the generator's own flag: 1 on the sides of the square / cube (:506-509, :852-856)
+inline int32_t box_flag(int dim, const double* p, double snap) {
+    for (int d = 0; d < dim; ++d)
+        if (p[d] > 0.0 + 1.0 - snap || p[d] < 0.0 + snap) return 1;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int fedd_mesh_structured_p2_sizes(int dim, const int* decomp, const int* cells, int rank, int64_t* n_rep,
+                                             int64_t* n_uni, int64_t* n_elem) {
+    FEDD_CHECK(dim == 2 || dim == 3, "structured P2 mesh: dimension must be 2 or 3");
+    BlockP2 q;
+    FEDD_TRY(make_block_p2(dim, decomp, cells, rank, q));
+    int64_t nrep = 1, nuni = 1, ne = dim == 3 ? 6 : 2;
+    for (int d = 0; d < dim; ++d) {
+        nrep *= q.p2m[d];
+        nuni *= q.p2m[d] - q.b.lo_owned[d];
+        ne *= q.b.M[d];
+    }
+    if (n_rep) *n_rep = nrep;
+    if (n_uni) *n_uni = nuni;
+    if (n_elem) *n_elem = ne;
+    return 0;
+}
+
+extern "C" int fedd_mesh_structured_p2_build(int dim, const int* decomp, const int* cells, int rank, int flags_option,
+                                             double* xyz, int64_t* gid_rep, int64_t* gid_uni, int32_t* owner,
+                                             int32_t* bcflag_rep, int32_t* bcflag_uni, int32_t* conn, int32_t* eflag) {
+    FEDD_CHECK(dim == 2 || dim == 3, "structured P2 mesh: dimension must be 2 or 3");
+    FEDD_CHECK(flags_option == 0 || flags_option == 1, "structured P2 mesh: flags option %d not supported", flags_option);
+    FEDD_CHECK(xyz && gid_rep && gid_uni && bcflag_rep && bcflag_uni && conn, "fedd_mesh_structured_p2_build: null output");
+    BlockP2 q;
+    FEDD_TRY(make_block_p2(dim, decomp, cells, rank, q));
+    const Block& b = q.b;
+    const double o[3] = {0, 0, 0}, sz[3] = {1, 1, 1};   // coorRec and length / width / height of "Square"
+    double h[3] = {0, 0, 0}, H[3] = {0, 0, 0};
+    for (int d = 0; d < dim; ++d) {
+        h[d] = sz[d] / (b.M[d] * b.N[d]);  // :308, :648
+        H[d] = sz[d] / b.N[d];             // :309, :649
+    }
+    const double eps = std::numeric_limits<double>::epsilon();
+    const double snap = dim == 3 ? eps : 100 * eps;  // :843-847 vs :500-502
+    int64_t n_uni = 1;
+    for (int d = 0; d < dim; ++d) n_uni *= q.p2m[d] - b.lo_owned[d];
+    // repeated points, r fastest (:491-513, :832-862)
+    for (int t = 0; t < q.p2m[2]; ++t)
+        for (int s = 0; s < q.p2m[1]; ++s)
+            for (int r = 0; r < q.p2m[0]; ++r) {
+                const int32_t id = p2_id(q, r, s, t);
+                const int l[3] = {r, s, t};
+                double p[3] = {0, 0, 0};
+                int64_t g[3] = {0, 0, 0};
+                int ob[3] = {0, 0, 0};
+                for (int d = 0; d < dim; ++d) {
+                    double c = l[d] * h[d] / 2.0 + b.off[d] * H[d];  // :499, :842
+                    if (c < snap && c > -snap) c = 0.0;
+                    p[d] = c;
+                    xyz[(int64_t)id * dim + d] = c;
+                    g[d] = (int64_t)l[d] + (int64_t)b.off[d] * (q.p2m[d] - 1);  // :504, :849-850
+                    ob[d] = b.off[d] - (l[d] == 0 && b.off[d] > 0 ? 1 : 0);    // the lower neighbour owns the shared plane
+                }
+                gid_rep[id] = g[0] + q.P2[0] * (g[1] + q.P2[1] * g[2]);
+                if (owner) owner[id] = ob[0] + b.N[0] * (ob[1] + b.N[1] * ob[2]);
+                int32_t f = box_flag(dim, p, snap);
+                // 3D: the reference's loop over the repeated points stops at the number of unique points (:3170), so the
+                // repeated points beyond it keep the generator's flag
+                if (flags_option == 1 && (dim == 2 || id < n_uni)) f = flags_option1(dim, p, f, o, sz);
+                bcflag_rep[id] = f;
+            }
+    // unique list: repeated order filtered by ownership (Map_def.hpp:201-206)
+    int64_t nu = 0;
+    for (int t = 0; t < q.p2m[2]; ++t)
+        for (int s = 0; s < q.p2m[1]; ++s)
+            for (int r = 0; r < q.p2m[0]; ++r) {
+                if (!p2_owned(q, r, s, t)) continue;
+                const int32_t id = p2_id(q, r, s, t);
+                const int64_t gid = gid_rep[id];
+                gid_uni[nu] = gid;
+                double p[3] = {0, 0, 0};
+                if (dim == 2) {  // :541-543: the repeated point and its flag
+                    p[0] = xyz[(int64_t)id * 2];
+                    p[1] = xyz[(int64_t)id * 2 + 1];
+                } else {  // :872-879: the unique points are computed from the global id
+                    p[0] = (gid % q.P2[0]) * h[0] / 2;
+                    p[1] = ((int)((gid % (q.P2[0] * q.P2[1])) / q.P2[0]) + eps) * h[1] / 2;
+                    p[2] = ((int)(gid / (q.P2[0] * q.P2[1]) + eps)) * h[2] / 2;
+                    for (int d = 0; d < 3; ++d)
+                        if (p[d] < eps && p[d] > -eps) p[d] = 0.0;
+                }
+                int32_t f = box_flag(dim, p, snap);  // :543, :881-886
+                if (flags_option == 1) f = flags_option1(dim, p, f, o, sz);
+                bcflag_uni[nu] = f;
+                ++nu;
+            }
+    // elements: the cells r fastest, 2 / 6 elements per cell in the P1 order (:569-609, :902-992)
+    const int nv = dim + 1, nen = dim == 3 ? 10 : 6, nsub = dim == 3 ? 6 : 2;
+    int64_t e = 0;
+    for (int t = 0; t < (dim == 3 ? b.M[2] : 1); ++t)
+        for (int s = 0; s < b.M[1]; ++s)
+            for (int r = 0; r < b.M[0]; ++r)
+                for (int k = 0; k < nsub; ++k, ++e) {
+                    int v[4][3];
+                    for (int a = 0; a < nv; ++a)
+                        for (int d = 0; d < 3; ++d) {
+                            const int c = d == 0 ? r : (d == 1 ? s : t);
+                            v[a][d] = d < dim ? 2 * (c + (dim == 3 ? KUHN[k][a][d] : TRIS[k][a][d])) : 0;
+                        }
+                    int32_t* ce = conn + e * nen;
+                    for (int a = 0; a < nv; ++a) ce[a] = p2_id(q, v[a][0], v[a][1], v[a][2]);
+                    for (int m = 0; m < nen - nv; ++m) {
+                        const int* va = v[P2_EDGE[m][0]];
+                        const int* vb = v[P2_EDGE[m][1]];
+                        ce[nv + m] = p2_id(q, (va[0] + vb[0]) / 2, (va[1] + vb[1]) / 2, (va[2] + vb[2]) / 2);
+                    }
+                    if (eflag) {
+                        int32_t ef = 0;
+                        if (dim == 2) {  // :580-586: the reference marks a patch of the square by the vertex centroid
+                            const double x_ref = (xyz[2 * (int64_t)ce[0]] + xyz[2 * (int64_t)ce[1]] + xyz[2 * (int64_t)ce[2]]) / 3.;
+                            const double y_ref = (xyz[2 * (int64_t)ce[0] + 1] + xyz[2 * (int64_t)ce[1] + 1] + xyz[2 * (int64_t)ce[2] + 1]) / 3.;
+                            if (x_ref >= 0.3 && x_ref <= 0.7 && y_ref >= 0.6) ef = 1;
+                        }
+                        eflag[e] = ef;
+                    }
+                }
+    return 0;
+}
+
+/* Permutation of the local repeated nodes of the structured P2 mesh that puts the P1 lattice nodes (all indices even)
+ * first, in the order fedd_mesh_structured_build numbers the P1 mesh of the same decomp / cells; the other nodes follow in
+ * their reference order.  perm[new] = reference local id.  The device layer takes "pressure = the first n_p1 node ids". */
+extern "C" int fedd_mesh_p2_vertices_first(int dim, const int* decomp, const int* cells, int rank, int32_t* perm,
+                                           int64_t* n_p1) {
+    FEDD_CHECK(dim == 2 || dim == 3, "structured P2 mesh: dimension must be 2 or 3");
+    BlockP2 q;
+    FEDD_TRY(make_block_p2(dim, decomp, cells, rank, q));
+    int64_t n = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int t = 0; t < q.p2m[2]; ++t)
+            for (int s = 0; s < q.p2m[1]; ++s)
+                for (int r = 0; r < q.p2m[0]; ++r) {
+                    const bool p1 = r % 2 == 0 && s % 2 == 0 && t % 2 == 0;  // :494, :836
+                    if ((pass == 0) != p1) continue;
+                    if (perm) perm[n] = p2_id(q, r, s, t);
+                    ++n;
+                }
+        if (pass == 0 && n_p1) *n_p1 = n;
+    }
     return 0;
 }

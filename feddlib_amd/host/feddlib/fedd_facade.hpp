@@ -378,20 +378,26 @@ public:
     Domain(vec_dbl_Type coor, double l, double h, CommConstPtr_Type comm) : comm_(comm), coorRec(coor), length(l), height(h) {}
     Domain(vec_dbl_Type coor, double l, double w, double h, CommConstPtr_Type comm) : comm_(comm), coorRec(coor), length(l), width(w), height(h) {}
 
-    // Domain::buildMesh (Domain_def.hpp:201-265): structured square / cube, P1
+    // Domain::buildMesh (Domain_def.hpp:201-265): structured square / cube, P1 on any N^dim ranks, P2 on one rank
     void buildMesh(int flagsOption, std::string meshType, int dim, std::string FEType, int N, int M, int numProcsCoarseSolve = 0) {
         TEUCHOS_TEST_FOR_EXCEPTION(meshType != "Square", std::logic_error,
                                    "Select valid mesh. Structured types are 'structured' and 'structured_bfs'; only 'Square' (rectangle/box) is built here.");
         TEUCHOS_TEST_FOR_EXCEPTION(dim != 2 && dim != 3, std::logic_error, "Select valid mesh dimension. 2 or 3 dimensional meshes can be constructed.");
-        TEUCHOS_TEST_FOR_EXCEPTION(FEType != "P1", std::logic_error, "Wrong FE-Type: the structured generator of this build makes P1 meshes.");
+        TEUCHOS_TEST_FOR_EXCEPTION(FEType != "P1" && FEType != "P2", std::logic_error, "Wrong FE-Type, either P1 or P2.");
         TEUCHOS_TEST_FOR_EXCEPTION(!(M >= 1), std::logic_error, "H/h is to small.");
         TEUCHOS_TEST_FOR_EXCEPTION(numProcsCoarseSolve != 0, std::logic_error, "Mpi Ranks Coarse is not supported.");
         dim_ = dim; FEType_ = FEType; n_ = N; m_ = M; flagsOption_ = flagsOption;
         const int rank = comm_->getRank(), size = comm_->getSize();
+        TEUCHOS_TEST_FOR_EXCEPTION(FEType == "P2" && size > 1, std::logic_error,
+                                   "Domain::buildMesh: structured P2 domains are one rank in this build, the communicator has " << size);
         int nblocks = 1;
         for (int d = 0; d < dim; ++d) nblocks *= N;
         TEUCHOS_TEST_FOR_EXCEPTION(nblocks != size, std::logic_error, "Domain::buildMesh: " << N << "^" << dim << " subdomain blocks need as many ranks, the communicator has " << size);
         int dec[3] = {N, N, N}, cel[3] = {M, M, M};
+        if (FEType == "P2") {
+            buildStructuredP2(dec, cel, flagsOption);
+            return;
+        }
         // Several ranks: the rank's block (the reference's repeated map) plus four layers of ghost elements, which
         // complete the rows of the ghost nodes within three layers (row ghosts): the Schwarz boxes a rank boundary
         // crosses are then built whole on both sides and the preconditioner does not depend on the split
@@ -529,7 +535,8 @@ public:
     const std::vector<int32_t>& surfaceFlags() const { return surfFlag_; }
     // element flags of a mesh read from a file on one rank (FiniteElement::getFlag); empty: no element carries a flag
     const std::vector<int32_t>& elementFlags() const { return elemFlag_; }
-    int64_t numberOfP1Nodes() const { return nP1_; }      // P2-of-P1 domain: its first nodes are the P1 nodes
+    int64_t numberOfP1Nodes() const { return nP1_; }      // P2-of-P1 and structured P2 domains: their first local nodes are the P1 nodes
+    bool isStructuredP2() const { return structuredP2_; }
 
     LO getApproxEntriesPerRow() const {      // Domain_def.hpp:176-198 (allocation hint only)
         if (dim_ == 2) return FEType_ == "P1" ? 20 : 30;
@@ -575,6 +582,61 @@ public:
     const std::vector<int32_t>& rowGhostFlags() const { return rowGhostFlag_; }
 
 private:
+    // The reference's structured P2 lattice (MeshStructured_def.hpp:468-619, 808-994; fedd_mesh_structured_p2_build) on one rank.
+    // The maps carry the reference's global ids; the LOCAL order of nodes, vectors and matrices is vertices first
+    // (fedd_mesh_p2_vertices_first): local node k < numberOfP1Nodes() is node k of the structured P1 domain of the same N, M,
+    // which is what the device layer's "pressure = the first nodes" convention needs.  Local id -> reference id is
+    // getMapRepeated()->getGlobalElement(); the exporter writes at global positions, so its files are in reference numbering.
+    void buildStructuredP2(const int* dec, const int* cel, int flagsOption) {
+        const int dim = dim_;
+        bool unit = length == 1. && height == 1. && (dim == 2 || width == 1.);
+        for (size_t d = 0; d < coorRec.size() && d < (size_t)dim; ++d) unit = unit && coorRec[d] == 0.;
+        TEUCHOS_TEST_FOR_EXCEPTION(!unit, std::logic_error, "Domain::buildMesh: structured P2 meshes are built on the unit square / cube");
+        int64_t nr, nu, ne, np1;
+        feddCheck(fedd_mesh_structured_p2_sizes(dim, dec, cel, 0, &nr, &nu, &ne), "fedd_mesh_structured_p2_sizes");
+        const int nen = dim == 3 ? 10 : 6;
+        std::vector<double> xyz(nr * dim);
+        std::vector<int64_t> gref(nr), guniRef(nu);
+        std::vector<int32_t> frep(nr), funi(nu), conn(ne * nen), perm(nr), inv(nr);
+        feddCheck(fedd_mesh_structured_p2_build(dim, dec, cel, 0, flagsOption, xyz.data(), gref.data(), guniRef.data(), nullptr, frep.data(),
+                                                funi.data(), conn.data(), nullptr), "fedd_mesh_structured_p2_build");
+        feddCheck(fedd_mesh_p2_vertices_first(dim, dec, cel, 0, perm.data(), &np1), "fedd_mesh_p2_vertices_first");
+        for (int64_t i = 0; i < nr; ++i) inv[perm[i]] = (int32_t)i;
+        // one rank: unique = repeated, in the same order
+        conn_.resize(conn.size()); xyz_.resize(xyz.size()); flagRep_.resize(nr); flagUni_.resize(nr);
+        std::vector<int64_t> grep(nr);
+        for (size_t k = 0; k < conn.size(); ++k) conn_[k] = inv[conn[k]];
+        for (int64_t i = 0; i < nr; ++i) {
+            for (int d = 0; d < dim; ++d) xyz_[i * dim + d] = xyz[(int64_t)perm[i] * dim + d];
+            flagRep_[i] = frep[perm[i]];
+            flagUni_[i] = funi[perm[i]];
+            grep[i] = gref[perm[i]];
+        }
+        nP1_ = np1;
+        structuredP2_ = true;
+        finishMesh(grep, grep, nen, nr);
+        // boundary faces: those of the P1 mesh (whose ids are the first local ids here), then the mid nodes in the slot order of
+        // fedd_mesh_p2_surfaces: P1 node (r,s,t) is lattice node (2r,2s,2t), a mid node lies half-way in lattice indices
+        int64_t ns = 0;
+        feddCheck(fedd_mesh_structured_surfaces_sizes(dim, dec, cel, 0, 0, &ns), "fedd_mesh_structured_surfaces_sizes");
+        std::vector<int32_t> s1((size_t)ns * dim);
+        surfFlag_.assign((size_t)ns, 0);
+        feddCheck(fedd_mesh_structured_surfaces(dim, dec, cel, 0, flagsOption, 0, s1.data(), surfFlag_.data()), "fedd_mesh_structured_surfaces");
+        surfNsn_ = dim == 2 ? 3 : 6;
+        surf_.assign((size_t)ns * surfNsn_, 0);
+        const int64_t n1[3] = {cel[0] + 1, cel[1] + 1, dim == 3 ? cel[2] + 1 : 1}, p2m[2] = {2 * cel[0] + 1, 2 * cel[1] + 1};
+        const int pairs[3][2] = {{0, 1}, {1, 2}, {0, 2}};
+        for (int64_t k = 0; k < ns; ++k) {
+            int64_t ref[3];
+            for (int v = 0; v < dim; ++v) {
+                const int64_t id = s1[k * dim + v], r = id % n1[0], s = (id / n1[0]) % n1[1], t = id / (n1[0] * n1[1]);
+                ref[v] = 2 * r + p2m[0] * (2 * s + p2m[1] * 2 * t);
+                surf_[k * surfNsn_ + v] = inv[ref[v]];
+            }
+            for (int m = 0; m < surfNsn_ - dim; ++m) surf_[k * surfNsn_ + dim + m] = inv[(ref[pairs[m][0]] + ref[pairs[m][1]]) / 2];
+        }
+        uploadSurfaces();
+    }
     void finishMesh(const std::vector<int64_t>& grep, const std::vector<int64_t>& guni, int nen, int64_t nGlobal,
                     const std::vector<int64_t>* rowGhost = nullptr, const std::vector<int32_t>* rowGhostFlag = nullptr) {
         nen_ = nen;
@@ -630,6 +692,7 @@ private:
     std::vector<double> xyz_;
     int volumeID_ = 10;
     int64_t nP1_ = 0;
+    bool structuredP2_ = false;
     Teuchos::RCP<Map_Type> mapRepeated_, mapUnique_;
     DeviceContextPtr dev_;
 };
@@ -693,6 +756,20 @@ public:
         const UN loc1 = checkFE(dim, FEType1);
         auto dom = domainVec_.at(loc1);
         const int64_t n_p = (int64_t)map2->getNodeNumElements();
+        if (dom->isStructuredP2()) {
+            // two structured domains of the same N, M: pressure node k must sit on velocity node k (vertices first), bit for bit, and
+            // the element lists must walk in step (the vertices of velocity element T are the nodes of pressure element T)
+            auto domP = domainVec_.at(checkFE(dim, FEType2));
+            const std::vector<double>& xv = dom->xyzRepeated();
+            const std::vector<double>& xp = domP->xyzRepeated();
+            bool same = n_p == dom->numberOfP1Nodes() && (int64_t)xp.size() == n_p * dim && domP->getNumElements() == dom->getNumElements() &&
+                        std::memcmp(xv.data(), xp.data(), xp.size() * sizeof(double)) == 0;
+            const int nenV = dom->nodesPerElement(), nenP = domP->nodesPerElement();
+            for (LO T = 0; same && T < dom->getNumElements(); ++T)
+                for (int v = 0; v <= dim; ++v) same = same && dom->connectivity()[(size_t)T * nenV + v] == domP->connectivity()[(size_t)T * nenP + v];
+            TEUCHOS_TEST_FOR_EXCEPTION(!same, std::logic_error, "assemblyDivAndDivT: the structured P2 velocity domain and the P1 pressure domain "
+                                       "do not match (same N and M are needed: pressure node k must be velocity node k, coordinates bit for bit)");
+        }
         feddCheck(fedd_set_option(dom->device()->ctx, "asm_zero_eps", setZeros_ ? myeps_ : 0.), "fedd_set_option");   // (FE_def.hpp:2002-2004, 2032-2034)
         feddCheck(fedd_assemble_div(dom->device()->ctx, n_p, 1, 2), "fedd_assemble_div");
         dom->device()->generation++;

@@ -140,6 +140,35 @@ int fedd_mesh_structured_row_ghosts(int dim, const int* decomp, const int* cells
                                     int64_t* n_row_ghosts, int64_t* gid /*nullable*/, int32_t* flag /*nullable*/);
 
 /* ------------------------------------------------------------------------------------------------
+ * structured P2 mesh generator, host side: the rank-local mesh of the reference, no ghost layers
+ * replaces MeshStructured::buildMesh2D/3D P2 branch (MeshStructured_def.hpp:468-619, 808-994: 6-node triangles,
+ * 10-node tetrahedra, six per cell) + setStructuredMeshFlags as it acts on P2 meshes (:2984-3011, :3137-3202)
+ * + Map::buildUniqueMap (Map_def.hpp:184-210, lowest-rank owner as in the P1 generator), on the unit square / cube.
+ *   local ids      r + s*(2M+1) + t*(2M+1)^2 on the block's lattice; element order and node slots are the reference's:
+ *                  vertices, then the mid nodes of (0,1),(1,2),(0,2)[,(0,3),(1,3),(2,3)]
+ *   global ids     r + s*n1 + t*n1^2, n1 = 2*N*M + 1, plus the rank offsets of :504 / :849-850
+ *   coordinates    r*h/2 + offset*H, snapped to 0.0 below 100 eps (2D) / eps (3D), in the reference's operation order
+ *   flags          the generator's 1 on the sides, then flags_option 1 (0 leaves them).  3D: the unique flags are
+ *                  decided on the coordinates the reference recomputes from the global id (:872-886), and its loop over
+ *                  the repeated points stops at n_uni (:3170), so later repeated points keep the generator's flag
+ *   owner          owning rank of every repeated node, nullable
+ *   eflag          element flag, nullable: 2D the reference's patch 0.3 <= x <= 0.7, y >= 0.6 (:580-586), 3D zero
+ * fedd_mesh_p2_vertices_first: perm[n_rep] (nullable) with perm[new] = local id, the P1 lattice nodes (all indices even)
+ * first in the order fedd_mesh_structured_build numbers the P1 mesh of the same decomp / cells, then the others in
+ * their reference order; n_p1 = their count.  A mesh renumbered by it obeys the device layer's convention "pressure
+ * dofs = the first n_pressure_nodes node ids", and pressure dof k is the pressure domain's node k.
+ * ---------------------------------------------------------------------------------------------- */
+int fedd_mesh_structured_p2_sizes(int dim, const int* decomp, const int* cells, int rank,
+                                  int64_t* n_rep, int64_t* n_uni, int64_t* n_elem);
+int fedd_mesh_structured_p2_build(int dim, const int* decomp, const int* cells, int rank, int flags_option,
+                                  double* xyz /*[n_rep*dim]*/, int64_t* gid_rep /*[n_rep]*/, int64_t* gid_uni /*[n_uni]*/,
+                                  int32_t* owner /*[n_rep], nullable*/, int32_t* bcflag_rep /*[n_rep]*/,
+                                  int32_t* bcflag_uni /*[n_uni]*/, int32_t* conn /*[n_elem*(6|10)]*/,
+                                  int32_t* eflag /*[n_elem], nullable*/);
+int fedd_mesh_p2_vertices_first(int dim, const int* decomp, const int* cells, int rank, int32_t* perm /*nullable*/,
+                                int64_t* n_p1);
+
+/* ------------------------------------------------------------------------------------------------
  * unstructured input, host side, one rank: INRIA/medit ".mesh" reader (MeshFileReader.cpp:16-106,
  * MeshFileReader.hpp:35-127, 1-based ids converted as MeshUnstructured_def.hpp:1181-1190) and the
  * P2-from-P1 construction (MeshUnstructured::buildP2ofP1MeshEdge, MeshUnstructured_def.hpp:129-410;
