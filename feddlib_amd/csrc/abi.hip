@@ -1069,6 +1069,7 @@ const Option OPTIONS[] = {
     {"gmres_spec", INT(gmres_spec), range(Legal::CLOSED, 0, 16), 0},
     {"gmres_tol_blocks", INT(gmres_tol_blocks), any, 0},
     {"gmres_dot_gy", INT(gmres_dot_gy), range(Legal::CLOSED, 0, 8), 0},
+    {"gmres_dot_own", INT(gmres_dot_own), zero_one, 0},
     {"gmres_newton", INT(gmres_newton), any, 0},
     {"gmres_chol_tol", REAL(gmres_chol_tol), range(Legal::OPEN, 0.0, 1.0), 0},
     {"ghost_overlap", INT(ghost_overlap), any, 0},

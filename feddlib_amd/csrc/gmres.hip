@@ -1039,11 +1039,36 @@ __device__ __forceinline__ double2 ldp(const double* __restrict__ p, const RowPa
 
 constexpr int SS_LDS_GROUPS = 32;   // column groups whose wave totals are parked in LDS between two workgroup barriers
 
+// the products of one group of the block's own columns, W_i . W_j for i = g * SS_CG + cc and j >= i, from the W tile in
+// registers (G = W^T W is symmetric: the flush stores each total to (i, j) and (j, i)).  The per-lane expression is the one
+// the streamed columns go through, with a register copy of W_i in the place of the loaded column: same bits.
+// Called from fully unrolled loops only -- g, and with it every index into w, is a compile-time constant there.
+template <int S, int NCH, int SS_CG>
+__device__ __forceinline__ void own_products(const double2 (&w)[S][NCH], int g, double (&acc)[SS_CG * S]) {
+#pragma unroll
+    for (int cc = 0; cc < SS_CG; ++cc)
+#pragma unroll
+        for (int j = 0; j < S; ++j) {
+            const int i = g * SS_CG + cc;
+            double s = 0.0;
+            if (j >= i) {
+#pragma unroll
+                for (int ch = 0; ch < NCH; ++ch) s += w[i][ch].x * w[j][ch].x + w[i][ch].y * w[j][ch].y;
+            }
+            acc[cc * S + j] = s;
+        }
+}
+
 // partial[(col * S + j) * nblk + blk] = sum over the workgroup's rows of V_col . W_j, col < k + sa
 // (W_j = V_{k+j}); the W tile stays in registers across the column groups, every basis column is read once.
 // The wave totals of a column group are parked in LDS and added (fixed order) once per SS_LDS_GROUPS groups:
 // no barrier between the loads of consecutive groups.
-template <int S, int NCH, int SS_CG>
+// OWN (option "gmres_dot_own"): only the k final basis columns are streamed; the rows k .. k + sa - 1 of the result, W^T W,
+// come from the W tile the lanes already hold (own_products) -- 8 n sa bytes less per sweep, the same bits.  The groups
+// are then numbered: first those of the block's own columns, then those of the basis (a group never holds both kinds);
+// the workgroups of a row block share them round robin as before.  The first basis group is loaded before the own
+// groups are worked on, so its latency passes behind them.  !OWN streams all k + sa columns (the A/B reference).
+template <int S, int NCH, int SS_CG, bool OWN>
 __global__ __launch_bounds__(256) void k_blockdot(const double* __restrict__ V, int64_t ldv, int64_t n, int k, int sa_req,
                                                   const int32_t* __restrict__ d_sa, double* __restrict__ partial, int nblk) {
     constexpr int NV = SS_CG * S;
@@ -1070,37 +1095,70 @@ __global__ __launch_bounds__(256) void k_blockdot(const double* __restrict__ V, 
             w[j][ch].x = jj < sa ? t.x : 0.0;
             w[j][ch].y = jj < sa ? t.y : 0.0;
         }
-    const int ncol = k + sa;
-    const int ncg = (ncol + SS_CG - 1) / SS_CG;
+    constexpr int NWG = S / SS_CG;                          // OWN: groups the block's own columns fill at most ...
+    static_assert(NWG <= SS_LDS_GROUPS, "own groups are parked without a flush");
+    const int nwg = OWN ? (sa + SS_CG - 1) / SS_CG : 0;     // ... and those with a column below sa: group numbers 0 .. nwg - 1
+    const int ncol = OWN ? k : k + sa;                      // streamed columns: group numbers nwg .. ncg - 1
+    const int ncg = nwg + (ncol + SS_CG - 1) / SS_CG;
     int parked = 0, first_cg = blockIdx.y;
     constexpr int GRP = 64 / NV;
     auto flush = [&](int count) {
         __syncthreads();
         for (int e = tid; e < count * NV; e += 256) {
             const int g = e / NV, idx = e % NV;
-            const int col = (first_cg + g * (int)gridDim.y) * SS_CG + idx / S;
-            if (col < ncol) partial[((int64_t)col * S + (idx % S)) * nblk + blockIdx.x] = ((sh[g][0][idx] + sh[g][1][idx]) + sh[g][2][idx]) + sh[g][3][idx];
+            const int grp = first_cg + g * (int)gridDim.y;
+            const double tot = ((sh[g][0][idx] + sh[g][1][idx]) + sh[g][2][idx]) + sh[g][3][idx];
+            if (OWN && grp < nwg) {
+                // W_i . W_j, formed for j >= i: row k + i takes it at j and, if W_j is part of the block, row k + j at i
+                // (columns j >= sa of a row stay zero: w[j] is)
+                const int i = grp * SS_CG + idx / S, j = idx % S;
+                if (i < sa && j >= i) {
+                    partial[((int64_t)(k + i) * S + j) * nblk + blockIdx.x] = tot;
+                    if (j > i && j < sa) partial[((int64_t)(k + j) * S + i) * nblk + blockIdx.x] = tot;
+                }
+            } else {
+                const int col = (grp - nwg) * SS_CG + idx / S;
+                if (col < ncol) partial[((int64_t)col * S + (idx % S)) * nblk + blockIdx.x] = tot;
+            }
         }
         __syncthreads();
     };
     double2 v[SS_CG][NCH];
-    auto load_group = [&](int cg) {
+    auto load_group = [&](int cg) {   // cg: number of a group of streamed columns
 #pragma unroll
         for (int cc = 0; cc < SS_CG; ++cc) {
-            const int col = cg * SS_CG + cc;
+            const int col = (cg - nwg) * SS_CG + cc;
             const double* __restrict__ a = V + (int64_t)(col < ncol ? col : 0) * ldv;
 #pragma unroll
             for (int ch = 0; ch < NCH; ++ch) {
-                // final basis columns are streamed (non-temporal); the block's own columns are re-read soon.
+                // final basis columns are streamed (non-temporal); the block's own columns (!OWN) are re-read soon.
                 // Raw loads, no selects behind them (a select would make the wave wait for the load right here instead of
                 // at the products after the reduction of the previous group): rows past n meet w = 0 there (the padding
                 // rows of the basis are zeroed when it is allocated), columns past ncol are dropped when the sums are stored
-                v[cc][ch] = col < k ? ldraw<true>(a, rp[ch]) : ldraw<false>(a, rp[ch]);
+                v[cc][ch] = OWN || col < k ? ldraw<true>(a, rp[ch]) : ldraw<false>(a, rp[ch]);
             }
         }
     };
-    if ((int)blockIdx.y < ncg) load_group(blockIdx.y);
-    for (int cg = blockIdx.y; cg < ncg; cg += gridDim.y) {
+    int cg = blockIdx.y;
+    if constexpr (OWN) {
+        // this workgroup's first group of streamed columns, in flight while its own groups are formed
+        const int gy = gridDim.y;
+        const int cq = cg >= nwg ? cg : cg + (nwg - cg + gy - 1) / gy * gy;
+        if (cq < ncg) load_group(cq);
+#pragma unroll
+        for (int g = 0; g < NWG; ++g)
+            if (g == cg && g < nwg) {
+                double acc[NV];
+                own_products<S, NCH, SS_CG>(w, g, acc);
+                const double tot = wave_reduce_transpose<NV>(acc, lane);
+                if ((lane & (GRP - 1)) == 0) sh[parked][wave][lane / GRP] = tot;
+                ++parked;
+                cg += gy;
+            }
+    } else {
+        if (cg < ncg) load_group(cg);
+    }
+    for (; cg < ncg; cg += gridDim.y) {
         double acc[NV];
 #pragma unroll
         for (int cc = 0; cc < SS_CG; ++cc)
@@ -1217,7 +1275,9 @@ __global__ __launch_bounds__(256) void k_blockaxpy(double* __restrict__ V, int64
 // basis columns are read a second time -- from the Infinity Cache, where the first read of the workgroup's rows left them
 // (tools/microbench/reread.hip: two passes over the same rows of 64 columns 1.43 ms against 2 x 0.84 for two sweeps).
 // partial[(col * S + j) * nblk + blk] as k_blockdot writes it, nblk = gridDim.x (512 rows per workgroup).
-template <int S>
+// OWN (option "gmres_dot_own"): as in k_blockdot, the second walk streams the k basis columns only and W'^T W' comes from the
+// W' the lane has just stored (its groups numbered first); !OWN reads those columns back (the A/B reference).
+template <int S, bool OWN>
 __global__ __launch_bounds__(256) void k_blockfuse(double* __restrict__ V, int64_t ldv, int64_t n, int k, int sa_req,
                                                    const int32_t* __restrict__ d_sa, const double* __restrict__ cf,
                                                    const double* __restrict__ rinv, double* __restrict__ partial, int nblk) {
@@ -1282,31 +1342,64 @@ __global__ __launch_bounds__(256) void k_blockfuse(double* __restrict__ V, int64
         }
     }
     // ---- second pass' dot products over the same rows ----
-    const int ncol = k + sa;
-    const int ncg = (ncol + SS_CG - 1) / SS_CG;
+    constexpr int NWG = S / SS_CG;
+    static_assert(NWG <= SS_LDS_GROUPS, "own groups are parked without a flush");
+    const int nwg = OWN ? (sa + SS_CG - 1) / SS_CG : 0;     // groups 0 .. nwg - 1: the block's own columns (OWN)
+    const int ncol = OWN ? k : k + sa;                      // groups nwg .. ncg - 1: the streamed columns
+    const int ncg = nwg + (ncol + SS_CG - 1) / SS_CG;
     int parked = 0, first_cg = 0;
     constexpr int GRP = 64 / NV;
     auto flush = [&](int count) {
         __syncthreads();
         for (int e = tid; e < count * NV; e += 256) {
             const int g = e / NV, idx = e % NV;
-            const int col = (first_cg + g) * SS_CG + idx / S;
-            if (col < ncol) partial[((int64_t)col * S + (idx % S)) * nblk + blockIdx.x] = ((sh[g][0][idx] + sh[g][1][idx]) + sh[g][2][idx]) + sh[g][3][idx];
+            const int grp = first_cg + g;
+            const double tot = ((sh[g][0][idx] + sh[g][1][idx]) + sh[g][2][idx]) + sh[g][3][idx];
+            if (OWN && grp < nwg) {   // (k_blockdot: formed for j >= i, stored to both halves)
+                const int i = grp * SS_CG + idx / S, j = idx % S;
+                if (i < sa && j >= i) {
+                    partial[((int64_t)(k + i) * S + j) * nblk + blockIdx.x] = tot;
+                    if (j > i && j < sa) partial[((int64_t)(k + j) * S + i) * nblk + blockIdx.x] = tot;
+                }
+            } else {
+                const int col = (grp - nwg) * SS_CG + idx / S;
+                if (col < ncol) partial[((int64_t)col * S + (idx % S)) * nblk + blockIdx.x] = tot;
+            }
         }
         __syncthreads();
     };
     double2 v[SS_CG];
-    auto load_group = [&](int cg) {
+    auto load_group = [&](int cg) {   // cg: number of a group of streamed columns
 #pragma unroll
         for (int cc = 0; cc < SS_CG; ++cc) {
-            const int col = cg * SS_CG + cc;
+            const int col = (cg - nwg) * SS_CG + cc;
             const double* __restrict__ a = V + (int64_t)(col < ncol ? col : 0) * ldv;
-            // basis columns: second and last read of this sweep (non-temporal); the block's own columns were stored above by this lane
-            v[cc] = col < k ? ldraw<true>(a, rp) : ldp<false>(a, rp);
+            // basis columns: second and last read of this sweep (non-temporal); the block's own columns (!OWN) were stored above by this lane
+            v[cc] = OWN || col < k ? ldraw<true>(a, rp) : ldp<false>(a, rp);
         }
     };
-    load_group(0);
-    for (int cg = 0; cg < ncg; ++cg) {
+    int cg = 0;
+    if (nwg < ncg) load_group(nwg);   // (OWN: in flight while the own groups are formed)
+    if constexpr (OWN) {
+#pragma unroll
+        for (int g = 0; g < NWG; ++g)
+            if (g < nwg) {
+                double acc[NV];
+                // (the expression of the loop below with w[i] in the place of the loaded column; g, i, j: compile-time constants)
+#pragma unroll
+                for (int cc = 0; cc < SS_CG; ++cc)
+#pragma unroll
+                    for (int j = 0; j < S; ++j) {
+                        const int i = g * SS_CG + cc;
+                        acc[cc * S + j] = j >= i ? w[i].x * w[j].x + w[i].y * w[j].y : 0.0;
+                    }
+                const double tot = wave_reduce_transpose<NV>(acc, lane);
+                if ((lane & (GRP - 1)) == 0) sh[parked][wave][lane / GRP] = tot;
+                ++parked;
+                ++cg;
+            }
+    }
+    for (; cg < ncg; ++cg) {
         double acc[NV];
 #pragma unroll
         for (int cc = 0; cc < SS_CG; ++cc)
@@ -1751,6 +1844,7 @@ static int gmres_solve_sstep(fedd_ctx* c, const GmresCall& call, int s, int* its
     // 15.54 / 15.64 / 15.77 / 15.97, 275 k rows 9.24 / 9.32 / 9.29 / 9.09; the old rule, 2048 workgroups in flight, took 2, 3 and 8)
     const int gy_dot = c->gmres_dot_gy > 0 ? c->gmres_dot_gy
                                            : (int)std::max<int64_t>(1, std::min<int64_t>(4, (1024 + nblkd / 2) / std::max(nblkd, 1)));
+    const bool dot_own = c->gmres_dot_own != 0;                       // W^T W from the W tile in registers (k_blockdot, k_blockfuse)
     double* hout = c->h_pinned + 16;                                  // host mirror of the block result
     double* hout_dev = c->h_pinned_dev ? c->h_pinned_dev + 16 : nullptr;
 
@@ -1829,9 +1923,14 @@ static int gmres_solve_sstep(fedd_ctx* c, const GmresCall& call, int s, int* its
                 const int ncg = (k + sa + dot_cg - 1) / dot_cg;
                 const dim3 gd(nblkd, std::min(gy_dot, ncg));
                 auto launch_dot = [&](const int32_t* dsa) {
-                    hipLaunchKernelGGL((k_blockdot<S, 2, dot_cg>), gd, blk, 0, st, (const double*)V, ldv, n, k, sa, dsa, c->d_part.p, nblkd);
+                    if (dot_own)
+                        hipLaunchKernelGGL((k_blockdot<S, 2, dot_cg, true>), gd, blk, 0, st, (const double*)V, ldv, n, k, sa, dsa, c->d_part.p, nblkd);
+                    else
+                        hipLaunchKernelGGL((k_blockdot<S, 2, dot_cg, false>), gd, blk, 0, st, (const double*)V, ldv, n, k, sa, dsa, c->d_part.p, nblkd);
                 };
-                const double dot_bytes = 8.0 * (double)n * (k + 2 * sa), upd_bytes = 8.0 * (double)n * (k + 2 * sa);
+                // algorithmic bytes of a dot sweep: the basis and the block read once -- the block's own columns a second time
+                // where they are streamed past the W tile (gmres_dot_own 0)
+                const double dot_bytes = 8.0 * (double)n * (k + (dot_own ? sa : 2 * sa)), upd_bytes = 8.0 * (double)n * (k + 2 * sa);
                 {
                     ScopedTimer td(c, FEDD_T_GS_DOT);
                     td.bytes(dot_bytes);
@@ -1852,8 +1951,12 @@ static int gmres_solve_sstep(fedd_ctx* c, const GmresCall& call, int s, int* its
                     if constexpr (S == 16) {
                         ScopedTimer tu(c, FEDD_T_GS_FUSED);
                         tu.bytes(upd_bytes);
-                        hipLaunchKernelGGL(k_blockfuse<S>, dim3(nblk2), blk, 0, st, V, ldv, n, k, sa, (const int32_t*)d_sa,
-                                           (const double*)(Sx + o3.cf1), (const double*)(Sx + o3.ri1), c->d_part.p, nblk2);
+                        if (dot_own)
+                            hipLaunchKernelGGL((k_blockfuse<S, true>), dim3(nblk2), blk, 0, st, V, ldv, n, k, sa, (const int32_t*)d_sa,
+                                               (const double*)(Sx + o3.cf1), (const double*)(Sx + o3.ri1), c->d_part.p, nblk2);
+                        else
+                            hipLaunchKernelGGL((k_blockfuse<S, false>), dim3(nblk2), blk, 0, st, V, ldv, n, k, sa, (const int32_t*)d_sa,
+                                               (const double*)(Sx + o3.cf1), (const double*)(Sx + o3.ri1), c->d_part.p, nblk2);
                     }
                 } else {
                     {

@@ -907,7 +907,10 @@ int fedd_gmres_fused_blocks(fedd_ctx* ctx, int* blocks);
  * instead of a tolerance); "gmres_fuse" 1 = blocks of 16: the first pass' update and the second pass' dot products run as one
  * sweep (k_blockfuse: three sweeps per block; the second read of a workgroup's rows comes from the Infinity Cache), 0 = four
  * sweeps, -1 (default) = one sweep from 4 million rows per rank on; unless 0 the last update of a block that fills a restart cycle
- * also forms the solution update sum_c y_c V_c (one read of the basis less per cycle); "gmres_spec" n > 0: n operator applications of the next block are put into the
+ * also forms the solution update sum_c y_c V_c (one read of the basis less per cycle); "gmres_dot_own" 1 (default) = the dot
+ * sweeps of a block (k_blockdot, and the second walk of k_blockfuse) stream the final basis columns only and take W^T W from the
+ * rows of the block they hold in registers, 0 = they stream the block's own columns too (8 n s bytes more per sweep; the same
+ * bits either way: an A/B switch); "gmres_spec" n > 0: n operator applications of the next block are put into the
  * stream before the host reads a block's outcome, so that the GPU works through that round trip -- default 0: on one GPU the
  * round trip is not what the step waits for (tools/share_n8.py), an A/B switch for multi-GPU runs), see fedd_gmres_info;
  * "box_kind" 0 = Schwarz boxes from one lattice over the nodes of all ranks, 1 = a lattice per rank;
