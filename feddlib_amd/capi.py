@@ -138,6 +138,7 @@ SIGNATURES = {
     "fedd_schwarz_conforming": [C.c_void_p, _i64p],
     "fedd_spmv_patterns": [C.c_void_p, _i64p, _i64p],
     "fedd_spmv_classes": [C.c_void_p, _i64p, _i64p, _i64p],
+    "fedd_spmv_cls_blocks": [C.c_void_p, _i64p, _i64p],
     "fedd_spmv_col_bytes": [C.c_void_p, C.POINTER(C.c_int), _i64p],
     "fedd_gmres": [C.c_void_p, _f64p, _f64p, C.c_double, C.c_int, C.c_int, C.c_int, _ip, _f64p],
     "fedd_set_option": [C.c_void_p, C.c_char_p, C.c_double],
@@ -853,9 +854,12 @@ class Context:
         _chk(self._L.fedd_spmv_col_bytes(self._h, C.byref(cb), C.byref(wide)))
         nc, rc, rest = C.c_int64(), C.c_int64(), C.c_int64()
         _chk(self._L.fedd_spmv_classes(self._h, C.byref(nc), C.byref(rc), C.byref(rest)))
+        bl, bf = C.c_int64(), C.c_int64()
+        _chk(self._L.fedd_spmv_cls_blocks(self._h, C.byref(bl), C.byref(bf)))
         return dict(nnz_pattern=a.value, nnz_streamed=b.value, column_patterns=p.value, rows_with_explicit_columns=e.value,
                     column_index_bytes=cb.value, entries_with_32bit_columns=wide.value, row_classes=nc.value,
-                    rows_in_classes=rc.value, nnz_streamed_outside_classes=rest.value)
+                    rows_in_classes=rc.value, nnz_streamed_outside_classes=rest.value, class_blocks_lds=bl.value,
+                    class_blocks_fallback=bf.value)
 
     def spmv_device(self, reps):
         _chk(self._L.fedd_spmv_device(self._h, reps))

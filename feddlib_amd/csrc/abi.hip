@@ -694,6 +694,15 @@ extern "C" int fedd_spmv_classes(fedd_ctx* c, int64_t* n_classes, int64_t* n_row
     return 0;
 }
 
+extern "C" int fedd_spmv_cls_blocks(fedd_ctx* c, int64_t* n_blocks_lds, int64_t* n_blocks_fallback) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(c->have_pattern, "fedd_spmv_cls_blocks: no matrix");
+    const bool on = c->cs.takes(fedd::SpmvStream::CLASSES);
+    if (n_blocks_lds) *n_blocks_lds = on ? c->cs.blk_lds : 0;
+    if (n_blocks_fallback) *n_blocks_fallback = on ? c->cs.blk_fallback : 0;
+    return 0;
+}
+
 extern "C" int fedd_spmv_col_bytes(fedd_ctx* c, int* bytes_per_column_index, int64_t* entries_with_32bit_columns) {
     NEED_DEVICE(c);
     FEDD_CHECK(c->have_pattern && bytes_per_column_index, "fedd_spmv_col_bytes: no matrix / null output");
@@ -1033,6 +1042,8 @@ const Option OPTIONS[] = {
     {"spmv_classes", INT(spmv_classes), any, OPT_DROPS_STREAM},
     {"spmv_keep_dictionary", INT(spmv_keep_dict), any, 0},
     {"spmv_classes_cover", INT(spmv_cls_cover), any, OPT_DROPS_STREAM},
+    {"spmv_cls_lds", INT(spmv_cls_lds), any, OPT_DROPS_STREAM},
+    {"spmv_cls_lds_cap", INT(spmv_cls_lds_cap), any, OPT_DROPS_STREAM},     // (development: 0 = what the kernel's LDS holds)
     {"asm_tiles_host", INT(asm_tiles_host), zero_one, OPT_DROPS_TILES},
     {"asm_p2_elem", INT(asm_p2_elem), upto_two, 0},
     {"asm_zero_eps", REAL(asm_zero_eps), range(Legal::AT_LEAST, 0.0, 0.0), 0},

@@ -170,6 +170,14 @@ struct SpmvStream {
     DevBuf<uint16_t> d_clspat;                  // column pattern of a class
     DevBuf<double> d_clsval;                    // [classes][cls_len] values of a class
     DevBuf<int32_t> d_clsi;                     // slot of row [n] | table min row | class of slot | counters (spmv.hip cls_layout)
+    // ---- block-local class lists (option "spmv_cls_lds", spmv.hip k_cls_blocks): per workgroup of k_spmv_cls_lds the distinct
+    //      classes of its rows, whose values the workgroup brings to LDS ----
+    bool cls_lds = false;                       // the lists stand for d_cls and the class kernel takes them
+    int32_t blk_lds = 0, blk_fallback = 0;      // workgroups with a list | flagged (more classes than the cap, or a row without a class)
+    DevBuf<uint16_t> d_cls16;                   // per row: slot in its block's list << 6 | column pattern
+    DevBuf<int32_t> d_blkn;                     // per block: classes in its list, -1: flagged
+    DevBuf<uint16_t> d_blklist;                 // [blocks][cap of the stride] class ids, ascending
+    struct BlkTab { int32_t n = -1, len = 0, cap = 0, lds = 0; } blk_tab;   // rows, stride and cap the lists were built for (n = -1: d_cls was rewritten since), blocks with a list
     // ---- rows that read ghost columns (several ranks, overlapped import) ----
     int32_t nbnd = -1;                          // their number (-1: not listed)
     DevBuf<int32_t> d_bnd;                      // flags / positions [n + 2] | the rows
@@ -276,6 +284,8 @@ struct fedd_ctx {
     int spmv_win_nu = 0;                        // option "spmv_win_nu": entries per lane of k_spmv_win on the compacted stream (4 ... 8; 0 = by row length)
     int spmv_pat_nu = 0;                        // option "spmv_pat_nu": 16-byte loads per lane of k_spmv_pat (2 ... 8; 0 = by the usual row length)
     int spmv_classes = 1;                       // option "spmv_classes": rows that repeat their column pattern AND their values bit for bit share a class (spmv.hip k_spmv_cls)
+    int spmv_cls_lds = 1;                       // option "spmv_cls_lds": the class kernel takes its block's class values from LDS and unit-stride x from the neighbouring lanes (spmv.hip k_spmv_cls_lds); 0: k_spmv_cls
+    int spmv_cls_lds_cap = 0;                   // option "spmv_cls_lds_cap" (development): classes a block's list may hold, 0 = what the kernel's LDS holds; fewer: more blocks are flagged
     int spmv_cls_cover = 90;                    // option "spmv_classes_cover": the classes are used when they cover at least this percentage of the rows
     int spmv_keep_dict = 0;                     // option "spmv_keep_dictionary": 1 = the previous matrix' pattern dictionary and row classes are kept while the new stream matches them bit for bit (one verifying pass instead of the build: time loops that reassemble the same operator); 0 (default) = built per matrix
     int spmv_reuse = 1;                         // option "spmv_reuse"

@@ -1048,6 +1048,251 @@ __global__ __launch_bounds__(256) void k_spmv_cls(const int32_t* __restrict__ ro
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Block-local class lists (round 9, option "spmv_cls_lds").  k_spmv_cls is bound by the address path of its vector-memory
+// reads (texture-address units busy 83-93 % of the launch), and of the twelve reads of an interior row four are the 16-byte
+// loads of the class entry: "cache resident", but fetched once per row through that path.  A workgroup's 256 RPT consecutive
+// rows use a few dozen classes.  So: per block the DISTINCT classes of its rows, listed once with the classes (k_cls_blocks,
+// ascending class ids), and a 16-bit word per row -- slot in the block's list << 6 | column pattern -- in place of the 4-byte
+// word.  The workgroup copies the listed entries to LDS (coalesced 16-byte loads, under the barrier the offset lists need
+// anyway) and its rows read their values from there.  A block with more classes than its list holds, or with a row in no
+// class, is flagged (count -1) and runs the table path in the same launch.  The second saving is in x: a pattern whose entries
+// C - 1, C, C + 1 sit at offsets d - 1, d, d + 1 (C the middle entry: the 7- and 5-entry rows of a structured grid) reads
+// x[r + d] only; the two neighbours are what the adjacent lanes read (a lane per row, consecutive rows), and only the first /
+// last lane of the wave loads its outer one.  Entry order, products and sums are those of k_spmv_cls: the same bits.
+// ------------------------------------------------------------------------------------------------
+constexpr uint16_t CLS16_NONE = 0xffff;
+// classes a block's list holds at a table stride: values + offset lists (stride CL here) + lengths fill what k_spmv_cls takes
+// for its offset lists alone at strides 8 and 16 (12.25 KB: 160 x 64 B + 2 KB, 64 x 128 B + 4 KB); 23.9 KB at SPAT_L (six
+// workgroups per CU instead of eight: a block of 512 elasticity rows holds 22 classes at the least, fewer would list none)
+constexpr int cls_lds_cap(int cl) { return cl <= 8 ? 160 : (cl <= 16 ? 64 : 31); }
+static_assert(SPAT_P <= 64 && cls_lds_cap(8) <= 1023, "the 16-bit row word: 6 bits of pattern, 10 of slot, 0xffff unused");
+
+// one workgroup per block of rows_per_blk rows: a bitmap of the class ids in LDS, a scan of its popcounts gives every class its
+// slot (ascending ids: the list does not depend on the order the rows arrive in); counters: [0] blocks with a list, [1] flagged
+__global__ __launch_bounds__(256) void k_cls_blocks(const uint32_t* __restrict__ cls, int32_t n, int32_t rows_per_blk, int32_t cap,
+                                                    int32_t list_stride, uint16_t* __restrict__ cls16, int32_t* __restrict__ blk_n,
+                                                    uint16_t* __restrict__ blk_list, int32_t* __restrict__ counters) {
+    constexpr int NW = CLS_MAX / 32, PER = NW / 256;
+    __shared__ uint32_t bits[NW];
+    __shared__ int32_t part[256];
+    __shared__ int32_t s_none;
+    const int tid = threadIdx.x;
+    const int64_t r0 = (int64_t)blockIdx.x * rows_per_blk;
+    for (int i = tid; i < NW; i += 256) bits[i] = 0u;
+    if (tid == 0) s_none = 0;
+    __syncthreads();
+    for (int i = tid; i < rows_per_blk; i += 256) {
+        const int64_t r = r0 + i;
+        if (r < n) {
+            const uint32_t w = cls[r];
+            if (w == CLS_NONE || (w >> 8) >= (uint32_t)CLS_MAX) s_none = 1;
+            else atomicOr(&bits[w >> 13], 1u << ((w >> 8) & 31u));
+        }
+    }
+    __syncthreads();
+    int cnt = 0;
+    for (int k = 0; k < PER; ++k) cnt += __popc(bits[tid * PER + k]);
+    part[tid] = cnt;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const int t = tid >= off ? part[tid - off] : 0;
+        __syncthreads();
+        part[tid] += t;
+        __syncthreads();
+    }
+    const int total = part[255], first = part[tid] - cnt;
+    const bool ok = total <= cap && s_none == 0;     // (uniform)
+    __syncthreads();
+    part[tid] = first;
+    __syncthreads();
+    if (tid == 0) {
+        blk_n[blockIdx.x] = ok ? total : -1;
+        atomicAdd(counters + (ok ? 0 : 1), 1);
+    }
+    if (ok) {
+        int slot = first;
+        for (int k = 0; k < PER; ++k) {
+            uint32_t b = bits[tid * PER + k];
+            while (b) {
+                const int bit = __ffs((int)b) - 1;
+                b &= b - 1u;
+                blk_list[(size_t)blockIdx.x * list_stride + slot++] = (uint16_t)((tid * PER + k) * 32 + bit);
+            }
+        }
+    }
+    for (int i = tid; i < rows_per_blk; i += 256) {
+        const int64_t r = r0 + i;
+        if (r >= n) continue;
+        uint16_t o = CLS16_NONE;
+        if (ok) {
+            const uint32_t w = cls[r];
+            const int id = (int)(w >> 8), word = id >> 5;
+            int slot = part[word / PER];
+            for (int k = (word / PER) * PER; k < word; ++k) slot += __popc(bits[k]);
+            slot += __popc(bits[word] & ((1u << (id & 31)) - 1u));
+            o = (uint16_t)((slot << 6) | (int)(w & 63u));
+        }
+        cls16[r] = o;
+    }
+}
+
+// a row of LEN entries without a predicate (every lane of the wave has LEN); LANES and the whole wave on one pattern whose
+// middle three offsets are consecutive: x at the outer two from the neighbouring lanes
+template <int LEN, bool LANES>
+__device__ __forceinline__ double cls_row_fixed(const double (&av)[8], const int32_t* __restrict__ dl, int32_t r, const double* __restrict__ x,
+                                                bool same_pat) {
+    constexpr int C = LEN / 2;
+    double xv[LEN];
+    double s = 0.0;
+    {
+#pragma clang fp contract(off)
+        // (inactive lanes -- rows past the end -- leave their bits zero: a partial wave loads everything)
+        const bool lanes = LANES && __ballot(same_pat && dl[C - 1] + 1 == dl[C] && dl[C] + 1 == dl[C + 1]) == ~0ull;
+        if (lanes) {    // (wave-uniform)
+            const int lane = threadIdx.x & 63;
+#pragma unroll
+            for (int j = 0; j < LEN; ++j)
+                if (j != C - 1 && j != C + 1) xv[j] = x[r + dl[j]];
+            double xe = 0.0;
+            if (lane == 0 || lane == 63) xe = x[r + (lane == 0 ? dl[C - 1] : dl[C + 1])];
+            const double lo = __shfl_up(xv[C], 1), hi = __shfl_down(xv[C], 1);
+            xv[C - 1] = lane == 0 ? xe : lo;
+            xv[C + 1] = lane == 63 ? xe : hi;
+        } else {
+#pragma unroll
+            for (int j = 0; j < LEN; ++j) xv[j] = x[r + dl[j]];
+        }
+#pragma unroll
+        for (int j = 0; j < LEN; ++j) {
+            const double pr = av[j] * xv[j];
+            s = s + pr;
+        }
+    }
+    return s;
+}
+
+// a classed row: its CL values at cv (the table, or the block's copy in LDS), its offsets at dl (LDS); the two forms of k_spmv_cls
+template <int CL, bool LANES>
+__device__ __forceinline__ double cls_row(const vd2* __restrict__ cv, const int32_t* __restrict__ dl, int len, int32_t r,
+                                          const double* __restrict__ x, bool same_pat) {
+    double s = 0.0;
+    const int len_u = __builtin_amdgcn_readfirstlane(len);
+    const bool uniform = CL == 8 && (len_u == 7 || len_u == 5) && __ballot(len == len_u) == __ballot(1);
+    if (uniform) {      // (wave-uniform)
+        double av[8];
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) {
+            const vd2 a2 = cv[j >> 1];
+            av[j] = a2.x;
+            av[j + 1] = a2.y;
+        }
+        s = len_u == 7 ? cls_row_fixed<7, LANES>(av, dl, r, x, same_pat) : cls_row_fixed<5, LANES>(av, dl, r, x, same_pat);
+    } else {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int j0 = 0; j0 < CL; j0 += 8) {
+            if (j0 < len) {
+                double xv[8], av[8];
+#pragma unroll
+                for (int j = 0; j < 8; j += 2) {
+                    const vd2 a2 = j0 + j < len ? cv[(j0 + j) >> 1] : vd2{0.0, 0.0};
+                    av[j] = a2.x;
+                    av[j + 1] = a2.y;
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) xv[j] = j0 + j < len ? x[r + dl[j0 + j]] : 0.0;
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (j0 + j < len) {
+                        const double pr = av[j] * xv[j];
+                        s = s + pr;
+                    }
+            }
+        }
+    }
+    return s;
+}
+
+// k_spmv_cls with the block's class values in LDS: same rows per workgroup (the lists of k_cls_blocks are per workgroup), the
+// offset lists at stride CL (no pattern of a class table of stride CL is longer)
+template <int RPT, int CL>
+__global__ __launch_bounds__(256) void k_spmv_cls_lds(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                      const double* __restrict__ val, const uint16_t* __restrict__ pat,
+                                                      const uint32_t* __restrict__ cls, const uint16_t* __restrict__ cls16,
+                                                      const int32_t* __restrict__ blk_n, const uint16_t* __restrict__ blk_list,
+                                                      const double* __restrict__ cls_val, const int32_t* __restrict__ plen,
+                                                      const int32_t* __restrict__ pdelta, int32_t n_pat, const double* __restrict__ x,
+                                                      double* __restrict__ y, int32_t n, SpmvEpi epi) {
+    constexpr int CAP = cls_lds_cap(CL), CV = CL / 2;       // CV: 16-byte words of a class entry
+    __shared__ vd2 sval[CAP * CV];
+    __shared__ int32_t sdelta[SPAT_P * CL];
+    __shared__ int32_t slen[SPAT_P];
+    const int tid = threadIdx.x;
+    const int32_t nwg = gridDim.x, q = nwg >> 3, rem = nwg & 7, xcd = blockIdx.x & 7, within = blockIdx.x >> 3;
+    const int32_t lb = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + within;
+    const int32_t r0 = lb * (256 * RPT);
+    const int32_t cnt = blk_n[lb];                          // classes in the block's list (at most CAP), -1: flagged
+    const vd2* __restrict__ tv = reinterpret_cast<const vd2*>(cls_val);
+    for (int i = tid; i < n_pat * CL; i += 256) sdelta[i] = pdelta[(i / CL) * SPAT_L + (i % CL)];
+    for (int i = tid; i < n_pat; i += 256) slen[i] = plen[i];
+    if (cnt >= 0) {     // (uniform over the workgroup)
+        uint32_t w[RPT];
+#pragma unroll
+        for (int u = 0; u < RPT; ++u) {
+            const int32_t r = r0 + tid + 256 * u;
+            w[u] = r < n ? (uint32_t)cls16[r] : 0u;
+        }
+        const uint16_t* __restrict__ list = blk_list + (size_t)lb * CAP;
+        for (int i = tid; i < cnt * CV; i += 256) sval[i] = tv[(size_t)list[i / CV] * CV + (i % CV)];
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < RPT; ++u) {
+            const int32_t r = r0 + tid + 256 * u;
+            if (r >= n) continue;
+            const int pid = (int)(w[u] & 63u);
+            const bool same_pat = pid == __builtin_amdgcn_readfirstlane(pid);
+            const double s = cls_row<CL, true>(sval + (int)(w[u] >> 6) * CV, sdelta + pid * CL, slen[pid], r, x, same_pat);
+            y[r] = epi_apply(epi, s, r);
+        }
+    } else {
+        uint32_t id[RPT];
+#pragma unroll
+        for (int u = 0; u < RPT; ++u) {
+            const int32_t r = r0 + tid + 256 * u;
+            id[u] = r < n ? cls[r] : CLS_NONE;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < RPT; ++u) {
+            const int32_t r = r0 + tid + 256 * u;
+            if (r >= n) continue;
+            double s = 0.0;
+            if (id[u] != CLS_NONE) {
+                const int pid = (int)(id[u] & 255u);
+                s = cls_row<CL, false>(tv + (size_t)(id[u] >> 8) * CV, sdelta + pid * CL, slen[pid], r, x, false);
+            } else {
+#pragma clang fp contract(off)
+                const int32_t b = rowptr[r], e = rowptr[r + 1];
+                const uint16_t pid = pat[r];
+                if (pid != SPAT_EXPL) {
+                    const int32_t* __restrict__ dl = sdelta + (int)pid * CL;
+                    for (int32_t p = b; p < e; ++p) {
+                        const double pr = val[p] * x[r + dl[p - b]];
+                        s = s + pr;
+                    }
+                } else {
+                    for (int32_t p = b; p < e; ++p) {
+                        const double pr = val[p] * x[colind[p]];
+                        s = s + pr;
+                    }
+                }
+            }
+            y[r] = epi_apply(epi, s, r);
+        }
+    }
+}
+
 // Several ranks, option "halo_overlap": the rows that read ghost columns (a few node planes along the rank boundary) are
 // listed at setup (k_bnd_flag -> scan -> k_bnd_list); the SpMV on row classes then runs over ALL rows while the ghost import
 // travels on a second stream, and k_spmv_rows recomputes the listed rows when it has arrived -- the same entries in the same
@@ -1118,6 +1363,8 @@ constexpr PatRow SPMV_PAT[2][7] = {{PAT<false, 2>, PAT<false, 3>, PAT<false, 4>,
 struct ClsRow { int max_len, rpt; decltype(&k_spmv_cls<4, 8>) kernel; };   // takes class tables of at most this stride; rows per lane
 constexpr ClsRow SPMV_CLS[] = {{8, 4, k_spmv_cls<4, 8>}, {16, 4, k_spmv_cls<4, 16>}, {SPAT_L, 2, k_spmv_cls<2, SPAT_L>}};
 struct LprRow { double max_avg; int lpr; decltype(&k_spmv<4>) kernel; };    // takes matrices of at most this average row length
+struct ClsLdsRow { int max_len, rpt; decltype(&k_spmv_cls_lds<4, 8>) kernel; };     // the same rows per workgroup, row by row, as SPMV_CLS
+constexpr ClsLdsRow SPMV_CLS_LDS[] = {{8, 4, k_spmv_cls_lds<4, 8>}, {16, 4, k_spmv_cls_lds<4, 16>}, {SPAT_L, 2, k_spmv_cls_lds<2, SPAT_L>}};
 constexpr LprRow SPMV_LPR[] = {{4.0, 4, k_spmv<4>}, {10.0, 8, k_spmv<8>}, {24.0, 16, k_spmv<16>}, {48.0, 32, k_spmv<32>}, {1e300, 64, k_spmv<64>}};
 constexpr decltype(&k_cs_reuse<false>) CS_REUSE[2] = {k_cs_reuse<false>, k_cs_reuse<true>};     // [REFRESH]
 
@@ -1272,6 +1519,39 @@ static int cs_dictionary(fedd_ctx* c) {
     return 0;
 }
 
+// stage 3b: the block-local class lists of k_spmv_cls_lds (see k_cls_blocks), for the row words cs.d_cls holds; lists that were
+// built for these words, this stride and this cap stand (the words of kept classes are not rewritten)
+static int cs_class_blocks(fedd_ctx* c) {
+    SpmvStream& s = c->cs;
+    const int32_t n = (int32_t)c->n_rows;
+    if (!c->spmv_cls_lds) return 0;
+    const ClsLdsRow* row = SPMV_CLS_LDS;
+    while (s.cls_len > row->max_len) ++row;
+    const int rows = 256 * row->rpt, cap_max = cls_lds_cap(row->max_len);
+    const int cap = c->spmv_cls_lds_cap > 0 ? std::min(c->spmv_cls_lds_cap, cap_max) : cap_max;
+    const int32_t nblk = (n + rows - 1) / rows;
+    int32_t hb[2] = {0, 0};     // blocks with a list | flagged
+    if (s.blk_tab.n == n && s.blk_tab.len == s.cls_len && s.blk_tab.cap == cap) {
+        hb[0] = s.blk_tab.lds;
+        hb[1] = nblk - s.blk_tab.lds;
+    } else {
+        FEDD_TRY(s.d_cls16.ensure((size_t)n + 1));
+        FEDD_TRY(s.d_blkn.ensure((size_t)nblk));
+        FEDD_TRY(s.d_blklist.ensure((size_t)nblk * cap_max));
+        int32_t* counters = cls_layout(c, n).counters + 8;
+        FEDD_HIP(hipMemsetAsync(counters, 0, 2 * sizeof(int32_t), c->stream));
+        hipLaunchKernelGGL(k_cls_blocks, dim3((unsigned)nblk), dim3(256), 0, c->stream, s.d_cls.p, n, rows, cap, cap_max, s.d_cls16.p, s.d_blkn.p,
+                           s.d_blklist.p, counters);
+        FEDD_HIP(hipMemcpyAsync(hb, counters, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
+        FEDD_HIP(hipStreamSynchronize(c->stream));
+        s.blk_tab = {n, s.cls_len, cap, hb[0]};
+    }
+    s.blk_lds = hb[0];
+    s.blk_fallback = hb[1];
+    s.cls_lds = hb[0] > 0;      // (every block flagged: k_spmv_cls as it is)
+    return 0;
+}
+
 // stage 3: row classes on top of the column patterns (see k_cls_insert): rows that repeat their values bit for bit; the previous
 // matrix' classes verified or new ones built.  *tried: the stage ran, so what the stream takes follows the values (cs.key)
 static int cs_classes(fedd_ctx* c, bool* tried) {
@@ -1279,6 +1559,8 @@ static int cs_classes(fedd_ctx* c, bool* tried) {
     const int32_t n = (int32_t)c->n_rows;
     s.ncls = 0;
     s.cls_rows = 0;
+    s.cls_lds = false;
+    s.blk_lds = s.blk_fallback = 0;
     if (!(s.npat > 0 && c->spmv_classes)) return 0;
     *tried = true;
     FEDD_TRY(s.d_cls.ensure((size_t)n + 1));
@@ -1309,6 +1591,7 @@ static int cs_classes(fedd_ctx* c, bool* tried) {
     }
     if (!kept) {
         s.cls_tab.ncls = 0;
+        s.blk_tab.n = -1;       // (the row words are rewritten)
         FEDD_HIP(hipMemsetAsync(ckey, 0, CLS_TS * sizeof(unsigned long long), c->stream));
         FEDD_HIP(hipMemsetAsync(L.tmin, 0x7f, CLS_TS * sizeof(int32_t), c->stream));
         FEDD_HIP(hipMemsetAsync(L.counters, 0, 8 * sizeof(int32_t), c->stream));
@@ -1329,6 +1612,7 @@ static int cs_classes(fedd_ctx* c, bool* tried) {
             s.cls_tab = {n, cl, s.ncls, hc[2]};
         }
     }
+    if (s.ncls > 0) FEDD_TRY(cs_class_blocks(c));
     return 0;
 }
 
@@ -1442,6 +1726,14 @@ static void launch_cls(fedd_ctx* c, const double* x, double* y, const SpmvEpi& e
     const SpmvStream& s = c->cs;
     const int32_t n = (int32_t)c->n_rows;
     const PatLayout L = pat_layout(c, n);
+    if (s.cls_lds) {    // (the block lists stand: cs_class_blocks)
+        const ClsLdsRow* row = SPMV_CLS_LDS;
+        while (s.cls_len > row->max_len) ++row;
+        hipLaunchKernelGGL(row->kernel, dim3((unsigned)((n + 256 * row->rpt - 1) / (256 * row->rpt))), dim3(256), 0, c->stream, s.d_rowptr.p,
+                           s.d_col.p, s.d_val.p, s.d_pat.p, s.d_cls.p, s.d_cls16.p, s.d_blkn.p, s.d_blklist.p, s.d_clsval.p, L.plen, L.pdelta,
+                           s.npat, x, y, n, epi);
+        return;
+    }
     const ClsRow* row = SPMV_CLS;
     while (s.cls_len > row->max_len) ++row;
     hipLaunchKernelGGL(row->kernel, dim3((unsigned)((n + 256 * row->rpt - 1) / (256 * row->rpt))), dim3(256), 0, c->stream, s.d_rowptr.p,

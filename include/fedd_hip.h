@@ -987,6 +987,13 @@ int fedd_spmv_patterns(fedd_ctx* ctx, int64_t* n_patterns, int64_t* n_rows_expli
  * verifying pass instead of the build -- for drivers that reassemble the same operator); default 0: built for every matrix.
  * Option "spmv_classes_cover" (default 90): the percentage of the rows the classes must cover to be used. */
 int fedd_spmv_classes(fedd_ctx* ctx, int64_t* n_classes, int64_t* n_rows_in_classes, int64_t* nnz_streamed_rest);
+/* Block-local class lists (option "spmv_cls_lds", default 1): every workgroup of the class kernel copies the values of the
+ * classes its rows use to LDS -- a list per block of 1024 (512 at the widest table stride) rows, built once with the classes --
+ * and its rows read them from there; rows whose pattern holds offsets d - 1, d, d + 1 take x at d -/+ 1 from the neighbouring
+ * lanes.  Same products, same order: y identical bit for bit.  A block with more classes than its list holds (160 / 64 / 31 at
+ * table stride 8 / 16 / 48; development option "spmv_cls_lds_cap": fewer), or with a row in no class, is flagged and runs the
+ * table path.  n_blocks_lds / n_blocks_fallback: blocks with a list / flagged; both 0: not in use.  Outputs may be NULL. */
+int fedd_spmv_cls_blocks(fedd_ctx* ctx, int64_t* n_blocks_lds, int64_t* n_blocks_fallback);
 /* The solver's stream is kept from one matrix to the next while the pattern, the sizes and the SpMV options stand (option
  * "spmv_reuse", default 1): the first SpMV after the matrix changed walks the ASSEMBLED rows once, applies the drop rule and
  * checks every kept entry against what the stream already holds -- count and columns always; with row classes in use also
