@@ -10,6 +10,14 @@
     SPMV_PAT[NT=1][NU 2 ... 8] lu8 | lu16       test_pattern_rows below
     SPMV_CLS (4, 8) | (4, 16) | (2, 48)         test_gpu_edge_cases.test_spmv_row_classes_give_the_same_bits: scalar Laplace (7 / 5
                                                 entries per row) | 2D two-dof elasticity (14) | 3D elasticity (45)
+    SPMV_CLS_LDS (4, 8) | (4, 16) | (2, 48)     test_gpu_spmv_cls_lds: per stride, listed and flagged blocks in one launch.  Within
+                                                (4, 8), cls_row takes a wave of 64 rows by its kind (test_gpu_spmv_cls_waves,
+                                                bit for bit against a host product; the lattices are named there):
+      (a) one pattern, 7 entries, x from lanes    lattice A (every block listed), B (cap forced low: flagged blocks), E (default gates)
+      (b) one pattern, 5 entries, x from lanes    lattice C; lattices A and B without Dirichlet rows (an edge along x)
+      (c) one pattern, middle offsets no run      lattice D (7 entries); lattices A and B without Dirichlet rows (5: the other x-edges)
+      (d) one length of 7 / 5, several patterns   lattice D (7 entries)
+      (e) one pattern, 6 or 4 entries             lattices A, B without Dirichlet rows and E (6: a face); C without Dirichlet rows (4)
     SPMV_LPR 4 | 8 | 16 | 32 | 64               test_lane_group_rows below, one system per bracket of the average row length
                                                 (test_gpu_edge_cases.test_spmv_kernels_agree reaches 8 and 16 without saying so)
     CS_REUSE[REFRESH=0 | 1]                     test_gpu_spmv_reuse (streams built with | without the class stage)
