@@ -11,7 +11,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libfedd_hip.so")
 
-FORM_LAPLACE, FORM_LAPLACE_VEC, FORM_MASS, FORM_MASS_VEC, FORM_LINELAS, FORM_BDSTAB = range(6)
+FORM_LAPLACE, FORM_LAPLACE_VEC, FORM_MASS, FORM_MASS_VEC, FORM_LINELAS, FORM_BDSTAB, FORM_STRESS = range(7)
 BLOCK_SCALAR, BLOCK_DIAG, BLOCK_FULL = range(3)
 COMBINE_RESTRICTED, COMBINE_AVERAGING, COMBINE_FULL = range(3)
 (T_SYMBOLIC, T_ASSEMBLE, T_RHS, T_DIRICHLET, T_SPMV, T_SCHWARZ_SETUP, T_SCHWARZ_APPLY, T_ORTHO, T_COARSE_SETUP,
@@ -75,6 +75,7 @@ SIGNATURES = {
                            _i64p, _i32p, C.c_int64, _i64p, _i32p],
     "fedd_pattern_build": [C.c_void_p, C.c_int, C.c_int, _i64p],
     "fedd_assemble": [C.c_void_p, C.c_int, _f64p],
+    "fedd_assemble_stress": [C.c_void_p, _f64p, C.c_int64],
     "fedd_assemble_rhs": [C.c_void_p, C.c_int, _f64p, C.c_int],
     "fedd_dirichlet": [C.c_void_p, C.c_int, _i32p, _i32p, _f64p],
     "fedd_dirichlet_nodes": [C.c_void_p, C.c_int64, _i32p, _i32p, _f64p],
@@ -552,6 +553,12 @@ class Context:
     def assemble(self, form, params=None):
         p = None if params is None else np.ascontiguousarray(params, dtype=np.float64)
         _chk(self._L.fedd_assemble(self._h, form, _p(p, _f64p)))
+
+    def assemble_stress(self, coeff=None):
+        """the velocity block in stress form, c grad v : (grad u + grad u^T), into the FULL system pattern (fedd_assemble_stress);
+        coeff[n_elem, nq] = c at the quadrature points of every element, None: c = 1"""
+        q = None if coeff is None else np.ascontiguousarray(coeff, dtype=np.float64).reshape(-1)
+        _chk(self._L.fedd_assemble_stress(self._h, _p(q, _f64p), 0 if q is None else q.shape[0]))
 
     def assemble_rhs(self, f_const, extra_degree=0):
         f = np.ascontiguousarray(np.atleast_1d(f_const), dtype=np.float64)

@@ -344,6 +344,15 @@ extern "C" int fedd_assemble(fedd_ctx* c, int form, const double* params) {
     return assemble_matrix(c, form, params);
 }
 
+extern "C" int fedd_assemble_stress(fedd_ctx* c, const double* coeff_q, int64_t n_coeff) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(c->have_pattern, "fedd_assemble_stress: no pattern; call fedd_pattern_build(dim, FEDD_BLOCK_FULL) first");
+    FEDD_CHECK(c->have_adj, "fedd_assemble_stress: %s", NO_ADJACENCY);
+    FEDD_CHECK(!coeff_q || n_coeff >= 0, "fedd_assemble_stress: negative n_coeff %lld", (long long)n_coeff);
+    FEDD_HIP(hipSetDevice(c->device));
+    return assemble_matrix(c, FEDD_FORM_STRESS, nullptr, coeff_q, n_coeff);
+}
+
 extern "C" int fedd_assemble_rhs(fedd_ctx* c, int dofs_per_node, const double* f_const, int extra_degree) {
     NEED_DEVICE(c);
     FEDD_CHECK(c->have_pattern, "fedd_assemble_rhs: call fedd_pattern_build first");

@@ -873,9 +873,177 @@ int launch_p2_gather(fedd_ctx* c) {
     return 0;
 }
 
-// The dispatch: tiles, then P2 element matrices + gather lists, then launch_matrix.
+// ---------------------------------------------------------------------------------------------
+// Stress form of the velocity block, FE::assemblyStress (FE_def.hpp:2407-2733; 2D element loop :2457-2562, 3D :2587-2727):
+//   K[(i,a),(j,b)] = |det B| sum_k c_k w_k ( delta_ab grad phi_i . grad phi_j + d_b phi_i d_a phi_j )
+// with the transformed gradients (dPhiTrans) and c_k the coefficient at x_k = B xi_k + p_1 (a.coeff, nullptr: 1).
+// A node pair (i, j) holds dim^2 distinct sums O[b][a] = sum_k c_k w_k d_b phi_i d_a phi_j; the scalar part is their trace, and
+// the block of (j, i) is the transpose of the block of (i, j).  So the element pass, ONE ELEMENT PER WAVEFRONT with the
+// reference gradients and weights staged in LDS, evaluates the NEN (NEN + 1) / 2 pairs i <= j only -- 55 lanes of one wave for
+// a P2 tetrahedron, dim^2 sums each, in place of the 900 entries of the 30 x 30 element matrix -- and writes
+// S_ij[a][b] = |det B| (O[b][a] + delta_ab tr O) as one contiguous stream [pair][a][b]: 8 * n_elem * NEN (NEN + 1) / 2 * dim^2
+// bytes of scratch (d_adv_ke; 3960 bytes per P2 tetrahedron, 55 % of a full element matrix).
+// The rows are then summed through the gather lists of the system's FULL pattern (full_lists_ensure, shared with the
+// hyperelastic tangent): a wave per node, a lane per node-level nonzero, the element blocks added in adjacency order, read
+// transposed where the row's local index is the larger one.  No atomics, bitwise reproducible.
+// Operation order per pair: k ascending; (c_k w_k) d_b phi_i, times d_a phi_j, accumulated; the trace added; times |det B|.
+// ---------------------------------------------------------------------------------------------
+template <int DIM, int NEN>
+__global__ __launch_bounds__(256) void k_stress_elem(AsmArgs a, int64_t n_elem, double* __restrict__ ke) {
+    constexpr int DD = DIM * DIM, NP = NEN * (NEN + 1) / 2;
+    extern __shared__ double sm[];
+    const int nq = a.nq;
+    const int ntab = nq * (1 + NEN * DIM);      // w[nq] | dphi[nq * NEN * DIM]
+    const double* s_w = sm;
+    const double* s_dphi = sm + nq;
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int per_wave = nq * NEN * DIM + nq;
+    double* Gs = sm + ntab + (size_t)w * per_wave;      // this wave's transformed gradients [k][i][d]
+    double* cw = Gs + nq * NEN * DIM;                   // c_k w_k
+    for (int i = tid; i < ntab; i += 256) sm[i] = a.tab[i];
+    __syncthreads();
+    const int64_t nwave = (int64_t)gridDim.x * 4;
+    const int64_t trips = (n_elem + nwave - 1) / nwave;
+    for (int64_t k = 0; k < trips; ++k) {
+        const int64_t e = k * nwave + (int64_t)blockIdx.x * 4 + w;
+        const bool on = e < n_elem;
+        double xv = 0.0;
+        if (on && lane < (DIM + 1) * DIM) xv = a.xyz[(int64_t)a.conn[e * NEN + lane / DIM] * DIM + (lane % DIM)];
+        double X[DIM + 1][DIM];
+#pragma unroll
+        for (int v = 0; v <= DIM; ++v)
+#pragma unroll
+            for (int d = 0; d < DIM; ++d) X[v][d] = __shfl(xv, v * DIM + d, 64);
+        double Binv[DIM][DIM];
+        const double absdet = on ? fabs(affine<DIM>(X, Binv)) : 0.0;
+        if (on) {
+            for (int t = lane; t < nq * NEN; t += 64) {
+                double g[DIM];
+                grad_t<DIM, NEN>(s_dphi, t / NEN, t % NEN, Binv, g);
+#pragma unroll
+                for (int d = 0; d < DIM; ++d) Gs[t * DIM + d] = g[d];
+            }
+            for (int q = lane; q < nq; q += 64) cw[q] = (a.coeff ? a.coeff[e * nq + q] : 1.0) * s_w[q];
+        }
+        __syncthreads();
+        if (on) {
+            double* __restrict__ out = ke + e * (NP * DD);
+            for (int t = lane; t < NP; t += 64) {
+                int i = 0, rem = t;
+                while (rem >= NEN - i) {
+                    rem -= NEN - i;
+                    ++i;
+                }
+                const int j = i + rem;
+                double O[DIM][DIM];
+#pragma unroll
+                for (int b = 0; b < DIM; ++b)
+#pragma unroll
+                    for (int d = 0; d < DIM; ++d) O[b][d] = 0.0;
+                for (int q = 0; q < nq; ++q) {
+                    const double* gi = Gs + (q * NEN + i) * DIM;
+                    const double* gj = Gs + (q * NEN + j) * DIM;
+#pragma unroll
+                    for (int b = 0; b < DIM; ++b) {
+                        const double s = cw[q] * gi[b];
+#pragma unroll
+                        for (int d = 0; d < DIM; ++d) O[b][d] += s * gj[d];
+                    }
+                }
+                double tr = 0.0;
+#pragma unroll
+                for (int d = 0; d < DIM; ++d) tr += O[d][d];
+#pragma unroll
+                for (int r = 0; r < DIM; ++r)
+#pragma unroll
+                    for (int cc = 0; cc < DIM; ++cc) out[t * DD + r * DIM + cc] = absdet * (O[cc][r] + (r == cc ? tr : 0.0));
+            }
+        }
+        // Gs and cw are rewritten by the next trip.  Both barriers of the loop order one wave's LDS writes against its own lanes'
+        // reads only (the buffers are private to the wave), so a wave-level barrier would do; the workgroup barrier is what the
+        // other one-element-per-wave kernels of this file use (k_elem_matrix, k_adv_elem), it is legal because `trips` is uniform
+        // over the workgroup, and its cost -- four waves in step, each with the same work per trip -- has not been measured apart.
+        __syncthreads();
+    }
+}
+
+// rows of the system's FULL pattern from the packed pair blocks of k_stress_elem
+template <int DIM, int NEN>
+__global__ __launch_bounds__(256) void k_stress_gather(const int32_t* __restrict__ n2e_ptr, const int32_t* __restrict__ n2e,
+                                                       const int32_t* __restrict__ rowptr, int32_t nn,
+                                                       const uint16_t* __restrict__ soff, const uint16_t* __restrict__ src,
+                                                       const double* __restrict__ ke, double* __restrict__ val) {
+    constexpr int DD = DIM * DIM, NP = NEN * (NEN + 1) / 2;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int64_t p = (int64_t)blockIdx.x * 4 + w; p < nn; p += (int64_t)gridDim.x * 4) {
+        const int32_t ab = n2e_ptr[p], deg = n2e_ptr[p + 1] - ab;
+        const int32_t row = (int32_t)p * DIM, rs = rowptr[row];
+        const int32_t nslot = (rowptr[row + 1] - rs) / DIM, nb = rs / DD;
+        const uint16_t* __restrict__ sp = src + (int64_t)ab * NEN;
+        const int total = deg * NEN;
+        for (int sl = lane; sl < nslot; sl += 64) {
+            const int b = soff[nb + sl], e2 = sl + 1 < nslot ? (int)soff[nb + sl + 1] : total;
+            double acc[DD];
+#pragma unroll
+            for (int m = 0; m < DD; ++m) acc[m] = 0.0;
+            for (int k = b; k < e2; ++k) {
+                const uint32_t sr = sp[k];
+                const int32_t at = n2e[ab + (sr >> 4)];         // element * NEN + local index of node p in it
+                const int32_t el = at / NEN;
+                const int i = at - el * NEN, j = (int)(sr & 15u);
+                const int lo = i < j ? i : j, hi = i < j ? j : i;
+                const double* __restrict__ kb = ke + ((int64_t)el * NP + (lo * NEN - lo * (lo - 1) / 2 + (hi - lo))) * DD;
+                if (i <= j) {
+#pragma unroll
+                    for (int m = 0; m < DD; ++m) acc[m] += kb[m];
+                } else {
+#pragma unroll
+                    for (int r = 0; r < DIM; ++r)
+#pragma unroll
+                        for (int cc = 0; cc < DIM; ++cc) acc[r * DIM + cc] += kb[cc * DIM + r];
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < DIM; ++r) {
+                const int64_t to = (int64_t)rs + (int64_t)r * nslot * DIM + (int64_t)sl * DIM;
+#pragma unroll
+                for (int cc = 0; cc < DIM; ++cc) val[to + cc] = acc[r * DIM + cc];
+            }
+        }
+    }
+}
+
+// a.tab / a.nq: the tables of full_lists_ensure (w | dphi); the lists are c->d_hy_soff / d_hy_src
+template <int DIM, int NEN>
+int launch_stress(fedd_ctx* c, const AsmArgs& a) {
+    constexpr int DD = DIM * DIM, NP = NEN * (NEN + 1) / 2;
+    const int64_t nn = c->n_own;
+    FEDD_TRY(c->d_adv_ke.ensure((size_t)c->n_elem * NP * DD));
+    const int ntab = a.nq * (1 + NEN * DIM);
+    const int per_wave = a.nq * NEN * DIM + a.nq;
+    const size_t lds = ((size_t)ntab + 4 * (size_t)per_wave) * sizeof(double);
+    FEDD_CHECK(lds <= 64 * 1024, "fedd_assemble_stress: the quadrature tables of %d points do not fit the LDS", a.nq);
+    ScopedTimer t(c, FEDD_T_ASSEMBLE);
+    // byte model: connectivity, geometry and c once; the pair blocks written and read once; the values written; the lists read
+    t.bytes((double)c->n_elem * (NEN * 4.0 + 2.0 * NP * DD * 8.0 + (a.coeff ? a.nq * 8.0 : 0.0)) + (double)c->n_node * DIM * 8.0 +
+            (double)c->nnz * 8.0 + (double)(c->nnz / DD) * 2.0 * 2.0);
+    if (c->n_elem > 0) {
+        const int64_t nwg = std::min<int64_t>((c->n_elem + 3) / 4, 256 * 8);
+        hipLaunchKernelGGL((k_stress_elem<DIM, NEN>), dim3((unsigned)nwg), dim3(256), lds, c->stream, a, c->n_elem, c->d_adv_ke.p);
+    }
+    const int nwg2 = (int)std::max<int64_t>(1, std::min<int64_t>((nn + 3) / 4, 256 * 32));
+    hipLaunchKernelGGL((k_stress_gather<DIM, NEN>), dim3((unsigned)nwg2), dim3(256), 0, c->stream, (const int32_t*)c->d_n2e_ptr.p,
+                       (const int32_t*)c->d_n2e.p, (const int32_t*)c->d_rowptr.p, (int32_t)nn, (const uint16_t*)c->d_hy_soff.p,
+                       (const uint16_t*)c->d_hy_src.p, (const double*)c->d_adv_ke.p, c->d_val.p);
+    t.stop();
+    FEDD_HIP(hipGetLastError());
+    return 0;
+}
+
+// The dispatch: the stress form, tiles, then P2 element matrices + gather lists, then launch_matrix.
 template <int DIM, int NEN>
 int launch_assemble(fedd_ctx* c, int kform, AsmArgs a, int ntab) {
+    if (kform == F_STRESS) return launch_stress<DIM, NEN>(c, a);
     if constexpr (NEN == DIM + 1) {
         // element-major tiles for the P1 forms they cover (option "asm_tiles" 0: the pair kernels)
         if (c->asm_kind == 0 && c->asm_tiles && a.nq == 1 && (kform == F_LAPLACE || kform == F_LINELAS)) {
@@ -1341,6 +1509,37 @@ int build_gather_lists(fedd_ctx* c, const int32_t* rowptr, const int32_t* colind
     return 0;
 }
 
+// The gather lists of the system's FULL pattern and the tables w | dphi of the rule determineDegree(dim, FEType, FEType, Grad,
+// Grad) (P1 0 + 0 -> 1, FE_def.hpp:5508-5509; P2 1 + 1), built once per (mesh, pattern) and kept: one copy for the hyperelastic
+// tangent and the stress form, which sum their element blocks into the same rows from the same rule.
+int full_lists_ensure(fedd_ctx* c, const char* who) {
+    if (c->hy_lists && c->hy_mesh_id == c->mesh_id && c->hy_pattern_gen == c->pattern_gen) return 0;
+    const int dim = c->dim, nen = c->nen;
+    c->hy_lists = false;
+    ScopedTimer t(c, FEDD_T_SYMBOLIC);
+    int32_t n2e_total = 0;
+    FEDD_HIP(hipMemcpyAsync(&n2e_total, c->d_n2e_ptr.p + c->n_own, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    FEDD_HIP(hipStreamSynchronize(c->stream));
+    FEDD_TRY(c->d_hy_soff.ensure((size_t)(c->nnz / (dim * dim)) + 2));
+    FEDD_TRY(c->d_hy_src.ensure((size_t)n2e_total * nen + 2));
+    FEDD_TRY(build_gather_lists(c, c->d_rowptr.p, c->d_colind.p, dim, 1, c->d_hy_soff.p, c->d_hy_src.p, who));
+    t.stop();
+    int degree = 2 * fe_degree(nen, dim, true);
+    if (degree == 0) degree = 1;
+    FeTables tb;
+    FEDD_TRY(fe_tables(dim, nen, degree, tb));
+    std::vector<double> host(tb.w);
+    host.insert(host.end(), tb.dphi.begin(), tb.dphi.end());
+    FEDD_TRY(c->d_hy_tab.ensure(host.size()));
+    FEDD_HIP(hipMemcpyAsync(c->d_hy_tab.p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    FEDD_HIP(hipStreamSynchronize(c->stream));  // `host` is a local
+    c->hy_nq = tb.nq;
+    c->hy_mesh_id = c->mesh_id;
+    c->hy_pattern_gen = c->pattern_gen;
+    c->hy_lists = true;
+    return 0;
+}
+
 // what NavierStokes::u_rep_ holds (NavierStokes_def.hpp:282-321), brought to the column-local numbering of the mesh
 int velocity_set(fedd_ctx* c, const double* u_rep) {
     FEDD_CHECK(c->nranks == 1, "fedd_velocity_set: one rank only for now");
@@ -1406,7 +1605,7 @@ int assemble_advection(fedd_ctx* c, int kind, double scale, int slot_add, int sl
     return 0;
 }
 
-int assemble_matrix(fedd_ctx* c, int form, const double* params) {
+int assemble_matrix(fedd_ctx* c, int form, const double* params, const double* coeff_q, int64_t n_coeff) {
     const int dim = c->dim, nen = c->nen;
     int kform, degree;
     const int dg = fe_degree(nen, dim, true), ds = fe_degree(nen, dim, false);
@@ -1431,13 +1630,32 @@ int assemble_matrix(fedd_ctx* c, int form, const double* params) {
             FEDD_CHECK(c->dofs == dim && c->block_mode == FEDD_BLOCK_FULL, "assemblyLinElasXDim needs a FULL pattern with dim dofs per node");
             FEDD_CHECK(params, "assemblyLinElasXDim needs params = {lambda, mu}");
             kform = F_LINELAS; degree = dg + dg; break;
+        case FEDD_FORM_STRESS:
+            FEDD_CHECK(c->nranks == 1, "fedd_assemble_stress: one rank only (a context with %d ranks was given)", c->nranks);
+            FEDD_CHECK(!c->merged && c->dofs == dim && c->block_mode == FEDD_BLOCK_FULL && c->n_rowg == 0,
+                       "fedd_assemble_stress: assemblyStress needs a FULL pattern with dim dofs per node "
+                       "(fedd_pattern_build(dim, FEDD_BLOCK_FULL)) as system matrix");
+            kform = F_STRESS; degree = dg + dg; break;
         default:
             FEDD_CHECK(false, "fedd_assemble: unknown form %d", form);
     }
     if (degree == 0) degree = 1;  // FE::determineDegree, FE_def.hpp:5508-5509
-    system_written(c, SYS_VALUES);
     int nq = 0, ntab = 0;
-    FEDD_TRY(upload_tables(c, degree, nq, ntab));
+    if (kform == F_STRESS) {
+        // the lists of the FULL pattern and the tables of this rule are kept per (mesh, pattern); c(x_k) goes up beside them
+        FEDD_TRY(full_lists_ensure(c, "fedd_assemble_stress"));
+        nq = c->hy_nq;
+        FEDD_CHECK(!coeff_q || n_coeff == c->n_elem * nq,
+                   "fedd_assemble_stress: n_coeff = %lld, but the mesh has %lld elements x %d quadrature points = %lld", (long long)n_coeff,
+                   (long long)c->n_elem, nq, (long long)(c->n_elem * nq));
+        if (coeff_q && n_coeff > 0) {
+            FEDD_TRY(c->d_dtmp0.ensure(std::max<size_t>((size_t)n_coeff, c->d_dtmp0.cap)));
+            FEDD_HIP(hipMemcpyAsync(c->d_dtmp0.p, coeff_q, (size_t)n_coeff * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            FEDD_HIP(hipStreamSynchronize(c->stream));  // the array is the caller's
+        }
+    }
+    system_written(c, SYS_VALUES);
+    if (kform != F_STRESS) FEDD_TRY(upload_tables(c, degree, nq, ntab));
     AsmArgs a;
     a.conn = c->d_conn.p; a.n2e_ptr = c->d_n2e_ptr.p; a.n2e = c->d_n2e.p; a.rowptr = c->d_rowptr.p;
     a.colind = c->d_colind.p; a.xyz = c->d_xyz.p; a.val = c->d_val.p; a.tab = c->d_dtmp0.p;
@@ -1447,6 +1665,10 @@ int assemble_matrix(fedd_ctx* c, int form, const double* params) {
     a.ke = nullptr;
     // doSetZeros: of the matrix forms built here only the vector Laplacian thresholds (FE_def.hpp:719-721; assemblyLaplace does not)
     a.zero_eps = form == FEDD_FORM_LAPLACE_VEC ? c->asm_zero_eps : 0.0;
+    if (kform == F_STRESS) {
+        a.tab = c->d_hy_tab.p;
+        a.coeff = coeff_q && n_coeff > 0 ? c->d_dtmp0.p : nullptr;
+    }
     if (kform == F_MASS) {   // the constant the Bochev-Dohrmann block takes off every mass entry: |ref. element| x scale (FE_def.hpp:2183-2192)
         a.p0 = form == FEDD_FORM_BDSTAB ? (dim == 2 ? 0.5 : 1.0 / 6.0) : 0.0;
         a.p1 = form == FEDD_FORM_BDSTAB ? (dim == 2 ? 1.0 / 9.0 : 1.0 / 16.0) : 0.0;

@@ -7,7 +7,8 @@ namespace fedd {
 // F_DIV / F_DIVT: FE::assemblyDivAndDivT (feddlib/core/FE/FE_def.hpp:1932-2057), pressure = P1 on
 // the element's vertices.  F_DIV rows = pressure nodes, columns = DIM*velocity node + d;
 // F_DIVT rows = velocity dofs, columns = pressure nodes.
-enum { F_LAPLACE = 0, F_MASS = 1, F_LINELAS = 2, F_DIV = 3, F_DIVT = 4 };
+// F_STRESS: FE::assemblyStress (FE_def.hpp:2407-2733), the velocity block in stress form; assemble.hip k_stress_elem.
+enum { F_LAPLACE = 0, F_MASS = 1, F_LINELAS = 2, F_DIV = 3, F_DIVT = 4, F_STRESS = 5 };
 
 struct AsmArgs {
     const int32_t* conn;
@@ -25,6 +26,7 @@ struct AsmArgs {
     const double* ke;   // != nullptr: element matrices [E][NEN][NEN] computed beforehand by k_elem_matrix (P2 scalar forms)
     double zero_eps; // > 0: element contributions of magnitude below it are set to zero before they are added (the reference's
                      // optional setZeros_ / myeps_, FE_def.hpp:74-79, 719-721, 2002-2004, 2032-2034: vector Laplacian, B, B^T)
+    const double* coeff = nullptr;  // F_STRESS: c(x_k) per element and quadrature point [E][nq]; nullptr: c = 1
 };
 
 namespace {

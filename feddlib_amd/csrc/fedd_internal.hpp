@@ -311,7 +311,8 @@ struct fedd_ctx {
     fedd::DevBuf<double> d_adv_ke;              // [n_elem][nen][nen][1 | dim * dim] element blocks of the assembly in progress
     uint64_t adv_pattern_id[fedd::MAX_AUX] = {};   // pattern id of the slots that hold the FULL pattern written here
     // ---- hyperelastic tangent and forces (hyperelastic.hip assemble_hyperelastic; one rank): u is d_vel, the element blocks
-    //      pass through d_adv_ke, the tangent goes into the system matrix ----
+    //      pass through d_adv_ke, the tangent goes into the system matrix.  The lists and tables (full_lists_ensure) also serve
+    //      the stress form (assemble.hip k_stress_elem, k_stress_gather), whose packed pair blocks pass through d_adv_ke too ----
     bool hy_lists = false;                      // the gather lists and tables below belong to hy_mesh_id / hy_pattern_gen
     uint64_t hy_mesh_id = 0, hy_pattern_gen = 0;
     fedd::DevBuf<uint16_t> d_hy_soff, d_hy_src; // gather lists of the node-level nonzeros of the system's FULL pattern (k_p2_lists)
@@ -648,7 +649,11 @@ int build_node_pattern(fedd_ctx* c, DevBuf<int32_t>& nptr, DevBuf<int32_t>& ncol
 int expand_node_pattern(fedd_ctx* c, const int32_t* nptr, const int32_t* ncol, int dofs, int full, int32_t* rowptr, int32_t* colind);
 
 // assemble.hip
-int assemble_matrix(fedd_ctx* c, int form, const double* params);
+// (coeff_q / n_coeff: the coefficient array of FEDD_FORM_STRESS, nullptr = 1; the other forms ignore them)
+int assemble_matrix(fedd_ctx* c, int form, const double* params, const double* coeff_q = nullptr, int64_t n_coeff = 0);
+// gather lists of the system's FULL pattern + the tables w | dphi of the (Grad, Grad) rule, kept per (mesh, pattern) in
+// d_hy_soff / d_hy_src / d_hy_tab / hy_nq: shared by the hyperelastic tangent and the stress form
+int full_lists_ensure(fedd_ctx* c, const char* who);
 int assemble_rhs(fedd_ctx* c, int dofs, const double* f_const, int extra_degree);
 int surface_set(fedd_ctx* c, int nsn, int64_t n_surf, const int32_t* surf, const int32_t* sflag);
 // g_surf != nullptr: one load per surface element; else n_flags == 0: g[dofs] on every element, n_flags > 0: g[n_flags * dofs] by flag

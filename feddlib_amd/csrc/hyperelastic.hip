@@ -486,31 +486,7 @@ int assemble_hyper(fedd_ctx* c, int model, const double* params, int n_params, i
         ScopedTimer t(c, FEDD_T_SYMBOLIC);
         FEDD_TRY(build_adjacency(c));
     }
-    if (!(c->hy_lists && c->hy_mesh_id == c->mesh_id && c->hy_pattern_gen == c->pattern_gen)) {
-        c->hy_lists = false;
-        ScopedTimer t(c, FEDD_T_SYMBOLIC);
-        int32_t n2e_total = 0;
-        FEDD_HIP(hipMemcpyAsync(&n2e_total, c->d_n2e_ptr.p + c->n_own, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        FEDD_HIP(hipStreamSynchronize(c->stream));
-        FEDD_TRY(c->d_hy_soff.ensure((size_t)(c->nnz / (dim * dim)) + 2));
-        FEDD_TRY(c->d_hy_src.ensure((size_t)n2e_total * nen + 2));
-        FEDD_TRY(build_gather_lists(c, c->d_rowptr.p, c->d_colind.p, dim, 1, c->d_hy_soff.p, c->d_hy_src.p, who));
-        t.stop();
-        // determineDegree(dim, FEType, FEType, Grad, Grad) (FE_def.hpp:856): P1 0 + 0 -> 1 (:5508-5509), P2 1 + 1
-        int degree = 2 * fe_degree(nen, dim, true);
-        if (degree == 0) degree = 1;
-        FeTables tb;
-        FEDD_TRY(fe_tables(dim, nen, degree, tb));
-        std::vector<double> host(tb.w);
-        host.insert(host.end(), tb.dphi.begin(), tb.dphi.end());
-        FEDD_TRY(c->d_hy_tab.ensure(host.size()));
-        FEDD_HIP(hipMemcpyAsync(c->d_hy_tab.p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        FEDD_HIP(hipStreamSynchronize(c->stream));  // `host` is a local
-        c->hy_nq = tb.nq;
-        c->hy_mesh_id = c->mesh_id;
-        c->hy_pattern_gen = c->pattern_gen;
-        c->hy_lists = true;
-    }
+    FEDD_TRY(full_lists_ensure(c, who));    // determineDegree(dim, FEType, FEType, Grad, Grad) (FE_def.hpp:856)
     if (what & FEDD_HYPER_TANGENT) FEDD_TRY(c->d_adv_ke.ensure((size_t)c->n_elem * nen * nen * dim * dim));
     FEDD_TRY(c->d_hy_fe.ensure((size_t)c->n_elem * nen * dim));
     FEDD_TRY(c->d_hy_f.ensure((size_t)c->n_own * dim));

@@ -51,6 +51,9 @@ typedef Teuchos::RCP<Teuchos::ParameterList> ParameterListPtr_Type;
 // feddlib/core/FEDDCore.hpp:115-118 (boost::function there)
 typedef std::function<void(double* x, double* res, double* parameters)> RhsFunc_Type;
 typedef std::function<void(double* x, double* res, double t, const double* parameters)> BC_func_Type;
+typedef std::function<double(double* x, int* parameters)> CoeffFunc_Type;                      // FEDDCore.hpp:115
+// the coefficient Stokes and NavierStokes hand to FE::assemblyStress (Stokes_def.hpp:21-24, NavierStokes_def.hpp:33-36)
+inline double OneFunction(double* x, int* parameter) { (void)x; (void)parameter; return 1.0; }
 
 inline void feddCheck(int rc, const char* what) {
     TEUCHOS_TEST_FOR_EXCEPTION(rc != 0, std::runtime_error, what << ": " << fedd_last_error());
@@ -745,6 +748,51 @@ public:
         TEUCHOS_TEST_FOR_EXCEPTION(FEType == "P0", std::logic_error, "Not implemented for P0");
         const double p[2] = {lambda, mu};
         assembleInto(checkFE(dim, FEType), dim, FEDD_BLOCK_FULL, FEDD_FORM_LINELAS, p, A, callFillComplete);
+    }
+    // FE::assemblyStress (FE_def.hpp:2407-2733): int func(x) grad v : (grad u + grad u^T), the velocity block in stress form, on
+    // the FULL pattern.  func is evaluated on the host at x_k = B xi_k + p_1 of every element and quadrature point of the rule
+    // determineDegree(dim, FEType, FEType, Grad, Grad) (:2427, 2487-2493, 2616-2625) and handed to the device as an array; the
+    // facade's OneFunction needs no array.
+    void assemblyStress(int dim, std::string FEType, MatrixPtr_Type& A, CoeffFunc_Type func, int* parameters, bool callFillComplete = true) {
+        TEUCHOS_TEST_FOR_EXCEPTION(FEType == "P0", std::logic_error, "Not implemented for P0");
+        TEUCHOS_TEST_FOR_EXCEPTION(A.is_null(), std::runtime_error, "Matrix is null.");
+        auto dom = domainVec_.at(checkFE(dim, FEType));
+        TEUCHOS_TEST_FOR_EXCEPTION((size_t)A->getMap()->getNodeNumElements() != (size_t)dom->getMapUnique()->getNodeNumElements() * dim,
+                                   std::logic_error, "Matrix row map does not match the unique map of the domain.");
+        typedef double (*plain_fn)(double*, int*);
+        const plain_fn* target = func.template target<plain_fn>();
+        const bool one = target && *target == static_cast<plain_fn>(&OneFunction);
+        std::vector<double> cq;
+        if (!one) {
+            const int nen = dom->nodesPerElement(), deg = nen == dim + 1 ? 1 : 2;
+            int nq = 0;
+            feddCheck(fedd_fe_quadrature(dim, deg, &nq, nullptr, nullptr), "fedd_fe_quadrature");
+            std::vector<double> xi((size_t)nq * dim), w((size_t)nq);
+            feddCheck(fedd_fe_quadrature(dim, deg, &nq, xi.data(), w.data()), "fedd_fe_quadrature");
+            const auto& conn = dom->connectivity();
+            const auto& xyz = dom->xyzRepeated();
+            const size_t nel = conn.size() / nen;
+            cq.resize(nel * nq);
+            std::vector<double> x(dim);
+            for (size_t T = 0; T < nel; ++T) {
+                const double* p1 = &xyz[(size_t)conn[T * nen] * dim];
+                for (int k = 0; k < nq; ++k) {
+                    for (int d = 0; d < dim; ++d) {
+                        x[d] = 0.;
+                        for (int r = 0; r < dim; ++r) x[d] += (xyz[(size_t)conn[T * nen + r + 1] * dim + d] - p1[d]) * xi[(size_t)k * dim + r];
+                        x[d] += p1[d];
+                    }
+                    cq[T * nq + k] = func(x.data(), parameters);
+                }
+            }
+        }
+        fedd_ctx* ctx = dom->device()->ctx;
+        int64_t nnz;
+        feddCheck(fedd_pattern_build(ctx, dim, FEDD_BLOCK_FULL, &nnz), "fedd_pattern_build");
+        feddCheck(fedd_assemble_stress(ctx, one ? nullptr : cq.data(), (int64_t)cq.size()), "fedd_assemble_stress");
+        dom->device()->generation++;
+        A->bind(dom->device(), dim);
+        if (!callFillComplete) A->resumeFill();
     }
     // FE::assemblyDivAndDivT (FE_def.hpp:1932-2057): velocity = FEType1 on the first domain, pressure = P1 on the vertices,
     // which are the first nodes of a P2-of-P1 velocity domain.  B and B^T land in slots 1 and 2 of the velocity domain's
@@ -1731,8 +1779,6 @@ public:
         (void)type;
         if (this->verbose_) std::cout << "-- Assembly ... " << std::flush;
         const double viscosity = this->parameterList_->sublist("Parameter").get("Viscosity", 1.);
-        TEUCHOS_TEST_FOR_EXCEPTION(this->parameterList_->sublist("Parameter").get("Symmetric gradient", false), std::logic_error,
-                                   "assemblyStress (symmetric gradient) is not built");
         TEUCHOS_TEST_FOR_EXCEPTION(this->getFEType(1) != "P1", std::logic_error, "Stokes: P1 pressure in this build");
         auto domV = this->getDomain(0);
         auto dev = domV->device();
@@ -1741,7 +1787,11 @@ public:
         auto pressureMap = this->getDomain(1)->getMapUnique();
         MatrixPtr_Type B(new Matrix_Type(pressureMap, domV->getDimension() * domV->getApproxEntriesPerRow()));
         if (this->verbose_) std::cout << " A ... " << std::flush;
-        this->feFactory_->assemblyLaplaceVecField(this->dim_, this->domain_FEType_vec_.at(0), 2, A, true);
+        if (this->parameterList_->sublist("Parameter").get("Symmetric gradient", false)) {   // Stokes_def.hpp:69-70: block (0,0) is FULL
+            int dummy[1] = {0};
+            this->feFactory_->assemblyStress(this->dim_, this->domain_FEType_vec_.at(0), A, OneFunction, dummy, true);
+        } else
+            this->feFactory_->assemblyLaplaceVecField(this->dim_, this->domain_FEType_vec_.at(0), 2, A, true);
         A->resumeFill();
         feddCheck(fedd_matrix_scale(dev->ctx, -1, viscosity), "fedd_matrix_scale");        // A->scale(viscosity), Stokes_def.hpp:83
         feddCheck(fedd_matrix_store(dev->ctx, 0), "fedd_matrix_store");
@@ -1878,7 +1928,7 @@ public:
         auto& par = this->parameterList_->sublist("Parameter");
         const double viscosity = par.get("Viscosity", 1.), density = par.get("Density", 1.);
         TEUCHOS_TEST_FOR_EXCEPTION(par.get("Symmetric gradient", false), std::logic_error,
-                                   "\"Symmetric gradient\" = true: assemblyStress is not built");
+                                   "\"Symmetric gradient\" = true is refused by NavierStokes in this build: its velocity block is the vector Laplacian (set the key to false); of the flow problems Stokes assembles the stress form");
         TEUCHOS_TEST_FOR_EXCEPTION(this->getFEType(1) != "P1", std::logic_error, "NavierStokes: P1 pressure in this build");
         TEUCHOS_TEST_FOR_EXCEPTION(this->comm_->getSize() > 1, std::logic_error, "NavierStokes: one rank in this build");
         auto domV = this->getDomain(0);
@@ -2155,7 +2205,7 @@ public:
         TEUCHOS_TEST_FOR_EXCEPTION(prec != "Monolithic" && prec != "Diagonal" && prec != "Triangular", std::logic_error,
                                    "\"Preconditioner Method\" = \"" + prec + "\" is not built (Monolithic, Diagonal and Triangular are; Teko and FaCSI are not)");
         TEUCHOS_TEST_FOR_EXCEPTION(pl->sublist("Parameter").get("Symmetric gradient", false), std::logic_error,
-                                   "\"Symmetric gradient\" = true: assemblyStress is not built");
+                                   "\"Symmetric gradient\" = true is refused by the nonlinear problems of this build: their velocity block is the vector Laplacian (set the key to false); of the flow problems Stokes assembles the stress form");
         const std::string levels = pl->sublist("ThyraPreconditioner").sublist("Preconditioner Types").sublist("FROSch").get("Level Combination", "Additive");
         TEUCHOS_TEST_FOR_EXCEPTION(levels == "Multiplicative", std::logic_error,
                                    "\"Level Combination\" = \"Multiplicative\" is not supported for nonlinear problems (NonLinearProblem_def.hpp:578)");

@@ -112,6 +112,11 @@ public:
         nle_ = dynamic_cast<NonLinElasticity_Type*>(problem_);
         TEUCHOS_TEST_FOR_EXCEPTION(nl_ != nullptr && ns_ == nullptr && nle_ == nullptr, std::logic_error,
                                    "TimeProblem: NavierStokes (\"Multistep\") and NonLinElasticity (\"Newmark\") are the nonlinear problems that are built");
+        // the BDF layer combines the DIAG velocity mass (slot 5) and A (slot 0) as two DIAG matrices; with the stress form A is FULL
+        TEUCHOS_TEST_FOR_EXCEPTION(ns_ != nullptr && problem_->getParameterList()->sublist("Parameter").get("Symmetric gradient", false),
+                                   std::logic_error,
+                                   "TimeProblem: \"Symmetric gradient\" = true is refused in the time loop: steady Stokes is the problem that assembles the "
+                                   "stress form; Navier-Stokes and its time loop take the vector Laplacian (set the key to false)");
     }
     bool isNonLinear() const { return nl_ != nullptr; }
     bool isNonLinElasticity() const { return nle_ != nullptr; }

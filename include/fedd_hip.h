@@ -33,9 +33,11 @@ enum fedd_form {
     FEDD_FORM_MASS_VEC    = 3, /* FE::assemblyMass "Vector"    FE_def.hpp:454-524   (dofs dim, diag)  */
     FEDD_FORM_LINELAS     = 4, /* FE::assemblyLinElasXDim      FE_def.hpp:2739-3040 (dofs dim, full);
                                   params = {lambda, mu}                                              */
-    FEDD_FORM_BDSTAB      = 5  /* FE::assemblyBDStabilization  FE_def.hpp:2151-2220 (dofs 1, P1 only): the Bochev-Dohrmann
+    FEDD_FORM_BDSTAB      = 5, /* FE::assemblyBDStabilization  FE_def.hpp:2151-2220 (dofs 1, P1 only): the Bochev-Dohrmann
                                   pressure block of P1/P1 Stokes, C_ij = |det B| (sum_q w_q phi_i phi_j - |ref| scale),
                                   scaled by -1/viscosity by the caller (Stokes_def.hpp:98-105)        */
+    FEDD_FORM_STRESS      = 6  /* FE::assemblyStress           FE_def.hpp:2407-2733 (dofs dim, full): the velocity block in
+                                  stress form with c = 1; fedd_assemble_stress takes a coefficient     */
 };
 
 /* ---- what fedd_assemble_advection builds from the velocity of fedd_velocity_set ---- */
@@ -292,6 +294,37 @@ int fedd_pattern_reuse_info(fedd_ctx* ctx, int* last_reused, int64_t* n_reused);
 
 /* numeric assembly into the pattern; FE::assemblyXxx + fillComplete (file:line per form above). */
 int fedd_assemble(fedd_ctx* ctx, int form, const double* params);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stress form of the velocity block ("Symmetric gradient" of Stokes and Navier-Stokes, Stokes_def.hpp:69-70,
+ * NavierStokes_def.hpp:142-143): FE::assemblyStress (feddlib/core/FE/FE_def.hpp:2407-2733; element loops :2457-2562 in 2D,
+ * :2587-2727 in 3D), int c(x) grad v : (grad u + grad u^T) in place of the vector Laplacian.  One rank.
+ *   For element T, local nodes i, j, row component a, column component b, with the transformed gradients (dPhiTrans):
+ *       K[(i,a),(j,b)] = |det B| sum_k c_k w_k ( delta_ab grad phi_i . grad phi_j + d_b phi_i d_a phi_j )
+ *   at row dim * gid(i) + a, column dim * gid(j) + b: e_a^i.innerProduct(e_b^j) with e_b^j = E + E^T (:2495-2559, 2629-2724;
+ *   SmallMatrix::innerProduct is the Frobenius product, SmallMatrix.hpp:164-196).
+ *   Quadrature: determineDegree(dim, FEType, FEType, Grad, Grad) (:2427) -- P1 one point, P2 degree 2 (nq = 3 in 2D, 5 in 3D);
+ *   the points and weights are those of fedd_fe_quadrature.
+ *   coeff_q  NULL: c = 1 (the reference's OneFunction, the only coefficient its two problem classes pass).  Otherwise
+ *            coeff_q[e * nq + k] = c(x_k) of element e (in the order of fedd_mesh_set) at x_k = B xi_k + p_1, p_1 the element's
+ *            first vertex (:2487-2493, 2616-2625), and n_coeff must equal n_elem * nq.
+ *   The system matrix must have the pattern of fedd_pattern_build(dim, FEDD_BLOCK_FULL); every (a, b) pair of every node pair is
+ *   written, structural zeros kept.  fedd_assemble(ctx, FEDD_FORM_STRESS, NULL) is this call with c = 1.
+ *   Operation order: per element and node pair i <= j the dim x dim sums O[b][a] = sum_k (c_k w_k d_b phi_i) d_a phi_j, k
+ *   ascending; then tr O is added on a == b and the block is multiplied by |det B|; the block of (j, i) is the transpose of that
+ *   of (i, j), taken from the same numbers.  The element blocks are added to their rows in the order of the node -> element
+ *   adjacency.  No floating-point atomics: two calls on one input agree bit for bit.  Parity with the reference's loop is at
+ *   1e-10 of a row's largest magnitude, not bit for bit.
+ *   Like every assemble the call overwrites the values of the system matrix: Dirichlet rows are to be set again, Schwarz, SpMV
+ *   and CG setups are dropped.  The gather lists of the row sums are those of fedd_assemble_hyperelastic (one copy per mesh and
+ *   pattern, built at the first call of either: FEDD_T_SYMBOLIC); later calls move values only (FEDD_T_ASSEMBLE).
+ *   Memory: the pair blocks pass through the scratch of fedd_assemble_advection, here 8 * n_elem * nen (nen + 1) / 2 * dim^2
+ *   bytes -- 3960 bytes per P2 tetrahedron, 0.78 GB on the P2 mesh of a 32^3-cell cube -- held between calls and released by the
+ *   next fedd_mesh_set*.
+ *   Errors: a host-only context ("needs a GPU context"); no pattern, or one that is not dim dofs per node / FULL;
+ *   n_coeff != n_elem * nq; more than one rank.
+ * ---------------------------------------------------------------------------------------------- */
+int fedd_assemble_stress(fedd_ctx* ctx, const double* coeff_q, int64_t n_coeff);
 
 /* FE::assemblyRHS + MultiVector::exportFromVector(...,"Add") (FE_def.hpp:4694-4766,
  * feddlib/problems/abstract/Problem_def.hpp:184-216): constant f per dof, quadrature degree
