@@ -19,7 +19,7 @@ COMBINE_RESTRICTED, COMBINE_AVERAGING, COMBINE_FULL = range(3)
 TIMER_NAMES = ["symbolic", "assemble", "rhs", "dirichlet", "spmv", "schwarz_setup", "schwarz_apply", "ortho",
                "coarse_setup", "coarse_apply", "halo", "allreduce", "spmv_setup", "gs_dot", "gs_update", "gs_fused",
                "full_park_mfma", "full_park", "full_gather", "cg_pq", "cg_xr", "cg_rz", "cg_p", "newmark_state", "block_apply", "multistep_state", "blockprec_bt",
-               "newton_residual", "newton_update"]
+               "newton_residual", "newton_update", "mesh_move", "move_check"]
 COARSE_Q1 = 1
 COARSE_GDSW = 2
 COARSE_RGDSW = 3
@@ -73,6 +73,9 @@ SIGNATURES = {
                       _i64p, _i32p],
     "fedd_mesh_set_rows": [C.c_void_p, C.c_int, C.c_int, C.c_int64, _i32p, C.c_int64, _f64p, _i64p, C.c_int64,
                            _i64p, _i32p, C.c_int64, _i64p, _i32p],
+    "fedd_mesh_move": [C.c_void_p, _f64p],
+    "fedd_mesh_move_info": [C.c_void_p, _i64p, _i64p, _f64p],
+    "fedd_mesh_coords_get": [C.c_void_p, _f64p],
     "fedd_pattern_build": [C.c_void_p, C.c_int, C.c_int, _i64p],
     "fedd_assemble": [C.c_void_p, C.c_int, _f64p],
     "fedd_assemble_stress": [C.c_void_p, _f64p, C.c_int64],
@@ -539,10 +542,34 @@ class Context:
                                        _p(flag_uni, _i32p)))
         self.n_own = gid_uni.shape[0]
         self._dim = dim
+        self._n_rep = xyz.shape[0]
 
     def mesh_set_dict(self, m):
         self.mesh_set(m["dim"], m["conn"], m["xyz"], m["gid_rep"], m["gid_uni"], m["flag_uni"],
                       m.get("row_ghost_gid"), m.get("row_ghost_flag"))
+
+    def mesh_move(self, disp=None):
+        """x = x_ref + disp on the repeated map of mesh_set ([n_rep, dim] or flat), relative to the uploaded coordinates and not
+        cumulative; None restores them.  Raises, and moves nothing, if an element would be inverted (fedd_mesh_move)"""
+        d = None
+        if disp is not None:
+            d = np.ascontiguousarray(disp, dtype=np.float64).ravel()
+            n = getattr(self, "_n_rep", None)
+            if n is not None and d.shape[0] != n * self._dim:
+                raise FeddError("mesh_move: displacement of %d entries, the repeated map has %d nodes in %dD" % (d.shape[0], n, self._dim))
+        _chk(self._L.fedd_mesh_move(self._h, _p(d, _f64p)))
+
+    def mesh_move_info(self):
+        a, g, r = C.c_int64(), C.c_int64(), C.c_double()
+        _chk(self._L.fedd_mesh_move_info(self._h, C.byref(a), C.byref(g), C.byref(r)))
+        return {"n_moves": a.value, "geometry_id": g.value, "min_det_ratio": r.value}
+
+    def mesh_coords(self):
+        """the coordinates in force, [n_rep, dim] on the repeated map of mesh_set"""
+        n = getattr(self, "_n_rep", 0)
+        out = np.zeros((max(n, 1), getattr(self, "_dim", 1)))
+        _chk(self._L.fedd_mesh_coords_get(self._h, _p(out, _f64p)))
+        return out[:n]
 
     def pattern_build(self, dofs=1, block_mode=BLOCK_SCALAR) -> int:
         nnz = C.c_int64()

@@ -200,6 +200,9 @@ static int mesh_set_impl(fedd_ctx* c, int dim, int nen, int64_t n_elem, const in
     c->d_ms_u[1].release();
     c->d_ms_t.release();
     ++c->mesh_gen;          // the Schwarz structure (schwarz.hip) belongs to the old nodes
+    c->have_xref = false;   // the coordinates uploaded below are the new reference of fedd_mesh_move
+    c->n_moves = 0;
+    c->min_det_ratio = 1.0;
     c->halo.reset();
 
     // column-local numbering: owned nodes in unique-map order, then ghosts sorted by global id
@@ -315,6 +318,29 @@ extern "C" int fedd_mesh_set_rows(fedd_ctx* c, int dim, int nen, int64_t n_elem,
                          row_ghost_gid, row_ghost_bcflag);
 }
 
+extern "C" int fedd_mesh_move(fedd_ctx* c, const double* disp_rep) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(c->n_node > 0, "fedd_mesh_move: call fedd_mesh_set first");
+    FEDD_HIP(hipSetDevice(c->device));
+    return mesh_move(c, disp_rep);
+}
+
+extern "C" int fedd_mesh_move_info(fedd_ctx* c, int64_t* n_moves, int64_t* geometry_id, double* min_det_ratio) {
+    FEDD_CHECK(c, "fedd_mesh_move_info: null context");
+    if (n_moves) *n_moves = c->n_moves;
+    if (geometry_id) *geometry_id = (int64_t)c->geometry_id;
+    if (min_det_ratio) *min_det_ratio = c->min_det_ratio;
+    return 0;
+}
+
+extern "C" int fedd_mesh_coords_get(fedd_ctx* c, double* xyz_rep) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(c->n_node > 0, "fedd_mesh_coords_get: call fedd_mesh_set first");
+    FEDD_CHECK(xyz_rep, "fedd_mesh_coords_get: null pointer");
+    FEDD_HIP(hipSetDevice(c->device));
+    return mesh_coords_get(c, xyz_rep);
+}
+
 extern "C" int fedd_pattern_build(fedd_ctx* c, int dofs_per_node, int block_mode, int64_t* nnz_out) {
     NEED_DEVICE(c);
     FEDD_CHECK(c->n_node > 0, "fedd_pattern_build: call fedd_mesh_set first");
@@ -324,7 +350,9 @@ extern "C" int fedd_pattern_build(fedd_ctx* c, int dofs_per_node, int block_mode
                "fedd_pattern_build: block mode SCALAR <=> one dof per node");
     FEDD_HIP(hipSetDevice(c->device));
     {
-        ScopedTimer t(c, FEDD_T_SYMBOLIC);
+        // (a build that repeats runs nothing of the symbolic class, and is not counted as a launch of it: a time loop on a moving
+        // mesh shows by this counter that a move costs no symbolic work)
+        ScopedTimer t(c, c->have_adj && pattern_repeats(c, dofs_per_node, block_mode) ? -1 : FEDD_T_SYMBOLIC);
         if (!c->have_adj) FEDD_TRY(build_adjacency(c));
         FEDD_TRY(build_pattern(c, dofs_per_node, block_mode));
     }

@@ -1132,7 +1132,33 @@ int launch_tiles(fedd_ctx* c, const AsmArgs& a, int ntab) {
     return 0;
 }
 
+// a workgroup per tile: the coordinates of its NE <= 255 extended nodes, the leading 2 DIM NE words of its blob, from xyz
+template <int DIM>
+__global__ __launch_bounds__(256) void k_tile_coords(const TileHdr* __restrict__ hdr, uint32_t* __restrict__ blob,
+                                                     const double* __restrict__ xyz) {
+    const TileHdr h = hdr[blockIdx.x];
+    uint32_t* b = blob + h.off;
+    double* cw = reinterpret_cast<double*>(b);
+    const uint32_t* ext = b + 2 * DIM * (int)h.NE;
+    for (int t = threadIdx.x; t < (int)h.NE * DIM; t += 256) cw[t] = xyz[(size_t)ext[t / DIM] * DIM + (t % DIM)];
+}
+
 }  // namespace
+
+// The tile blobs lead with copies of their nodes' coordinates (phase 0 of k_assemble_tiles reads them as one stream): the only
+// part of the tile structures that follows d_xyz.  After a fedd_mesh_move they are written again; node lists, element records,
+// gather lists and shapes stand.  (The tiles keep the clusters of the coordinates they were built on: a matter of locality.)
+int tiles_refresh_coords(fedd_ctx* c) {
+    if (c->tl_state != 1 || c->tl_ntile <= 0) return 0;
+    if (c->dim == 3)
+        hipLaunchKernelGGL(k_tile_coords<3>, dim3((unsigned)c->tl_ntile), dim3(256), 0, c->stream, (const TileHdr*)c->tl_hdr.p,
+                           c->tl_blob.p, (const double*)c->d_xyz.p);
+    else
+        hipLaunchKernelGGL(k_tile_coords<2>, dim3((unsigned)c->tl_ntile), dim3(256), 0, c->stream, (const TileHdr*)c->tl_hdr.p,
+                           c->tl_blob.p, (const double*)c->d_xyz.p);
+    FEDD_HIP(hipGetLastError());
+    return 0;
+}
 
 // the tile path for the forms it covers (P1 simplices; F_LAPLACE, F_LINELAS); -1 (without error) when the mesh does not fit
 int assemble_tiles(fedd_ctx* c, int kform, const AsmArgs& a, int ntab) {

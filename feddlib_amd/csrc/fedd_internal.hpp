@@ -223,6 +223,15 @@ struct fedd_ctx {
     fedd::DevBuf<int32_t> d_conn;               // [n_elem*nen]
     fedd::DevBuf<double> d_xyz;                 // [n_node*dim]
     fedd::DevBuf<int32_t> d_flag;               // [n_own] bc flags of owned nodes
+    // ---- moving mesh (mesh_move.hip fedd_mesh_move; one rank): d_xyz = x_ref + d of the last move ----
+    bool have_xref = false;                     // d_xyz_ref holds what the last fedd_mesh_set* uploaded (copied at the first move: until then d_xyz is it)
+    fedd::DevBuf<double> d_xyz_ref, d_xyz_cand; // [n_node*dim] the reference; the candidate of a move (changes places with d_xyz when the check passes)
+    fedd::DevBuf<double> d_mv_disp, d_mv_part;  // the displacement in column-local numbering; partial minima of k_move_check | its three results
+    fedd::DevBuf<int32_t> d_mv_flag;            // [2] elements with det * det_ref <= 0, the smallest of them
+    std::vector<double> h_mv_disp;              // host staging of the permuted displacement (kept: its copy to the device is asynchronous)
+    int64_t n_moves = 0;                        // moves committed since the last fedd_mesh_set*
+    uint64_t geometry_id = 0;                   // moves committed since the context was made: which coordinates a result belongs to
+    double min_det_ratio = 1.0;                 // smallest |det B| / |det B_ref| of the last committed move
 
     // ---- node -> (element, local index) adjacency of owned nodes ----
     fedd::DevBuf<int32_t> d_n2e_ptr, d_n2e;     // [n_own+1], [sum]
@@ -362,7 +371,8 @@ struct fedd_ctx {
     // structure stage of the setup (lattice, bins, dof lists: the five buffers above, d_fbin_* and the sizes sw_nsub, sw_max_size,
     // sw_max_own, sw_max_size_all): a function of the node coordinates, the matrix graph and the parameters of SwStructKey, kept
     // from setup to setup while those stand (option "schwarz_reuse", default 1; 0 = built by every setup)
-    uint64_t mesh_gen = 0;                      // bumped by whatever can change coordinates, node counts, ghost layout, owners or halo
+    uint64_t mesh_gen = 0;                      // bumped by whatever can change node counts, ghost layout, owners or halo (fedd_mesh_set*, which
+                                                // also brings new coordinates; a fedd_mesh_move moves geometry_id instead and leaves this one)
     uint64_t pattern_gen = 0;                   // bumped by whatever writes d_rowptr / d_colind (system_written), except a fedd_pattern_build that repeats
                                                 // the one the pattern came from (same mesh_gen, dofs per node, block mode)
     bool pat_repeatable = false;                // the system pattern is the output of build_pattern on pat_mesh_gen (and nothing wrote it since)
@@ -371,12 +381,12 @@ struct fedd_ctx {
     int pat_last_reused = 0;                    // the last build_pattern kept them
     int64_t pat_reuse_count = 0;                // builds that kept them since the context was made
     struct SwStructKey {
-        uint64_t mesh_gen = 0, pattern_gen = 0;
+        uint64_t mesh_gen = 0, pattern_gen = 0, geometry_id = 0;
         int64_t n_own = 0, n_rows = 0, n_rows_ext = 0, merged_nA = 0;
         double scale = 0.0;
         int target = 0, overlap = 0, box_kind = 0, whole_boxes = 0, ghost_overlap = 0, merged = 0, dofs = 0, dim = 0, nranks = 0;
         bool operator==(const SwStructKey& o) const {
-            return mesh_gen == o.mesh_gen && pattern_gen == o.pattern_gen && n_own == o.n_own && n_rows == o.n_rows &&
+            return mesh_gen == o.mesh_gen && pattern_gen == o.pattern_gen && geometry_id == o.geometry_id && n_own == o.n_own && n_rows == o.n_rows &&
                    n_rows_ext == o.n_rows_ext && merged_nA == o.merged_nA && scale == o.scale && target == o.target &&
                    overlap == o.overlap && box_kind == o.box_kind && whole_boxes == o.whole_boxes &&
                    ghost_overlap == o.ghost_overlap && merged == o.merged && dofs == o.dofs && dim == o.dim && nranks == o.nranks;
@@ -548,9 +558,16 @@ enum : unsigned {
     SYS_DIRICHLET = 2,   // unit rows / rhs / isdir written: not a new operator, sys_value_gen stays
     SYS_PATTERN = 4,     // d_rowptr / d_colind rewritten, or declared rewritten (the values-only merge)
     SYS_GONE = 8,        // the slot holds no system matrix any more
+    SYS_GEOMETRY = 16,   // the node coordinates moved (fedd_mesh_move), on its own: the matrix and its SpMV stream stand, what was laid
+                         // over the old coordinates goes -- the preconditioner here, the Schwarz box structure through
+                         // SwStructKey::geometry_id, the last combine's record (its matrices belong to the old coordinates)
 };
 inline void system_written(fedd_ctx* c, unsigned what) {
-    c->cs.valid = false;         // the solver's SpMV stream (cs.key stands: the next build may find the stream still fits)
+    if (what & SYS_GEOMETRY) {
+        ++c->geometry_id;
+        c->comb_sys_gen = ~(uint64_t)0;        // fedd_matrix_combine_current answers 0
+    }
+    if (what & ~SYS_GEOMETRY) c->cs.valid = false;   // the solver's SpMV stream (cs.key stands: the next build may find the stream still fits)
     c->have_schwarz = false;     // the numeric stage of the preconditioner: a parent that applies this context as a block sees it
     c->have_coarse = c->sym_ready = false;     // ... and what was built on it: the coarse level, the park + gather lists
     if (what & SYS_VALUES) ++c->sys_value_gen;
@@ -644,6 +661,7 @@ int build_adjacency(fedd_ctx* c);
 int build_node_lists(fedd_ctx* c, const int32_t* d_conn, int64_t n_ent, int32_t n_nodes, DevBuf<int32_t>& ptr, DevBuf<int32_t>& lst,
                      int32_t* max_deg);
 int build_pattern(fedd_ctx* c, int dofs, int block_mode);
+bool pattern_repeats(const fedd_ctx* c, int dofs, int block_mode);   // build_pattern would keep d_rowptr / d_colind: no symbolic work
 // the node-level pattern alone into buffers of the caller's (the system slot is not touched), and its closed-form expansion to dofs
 int build_node_pattern(fedd_ctx* c, DevBuf<int32_t>& nptr, DevBuf<int32_t>& ncol, int32_t* max_nn, int64_t* node_nnz);
 int expand_node_pattern(fedd_ctx* c, const int32_t* nptr, const int32_t* ncol, int dofs, int full, int32_t* rowptr, int32_t* colind);
@@ -672,6 +690,10 @@ int assemble_advection(fedd_ctx* c, int kind, double scale, int slot_add, int sl
 int build_gather_lists(fedd_ctx* c, const int32_t* rowptr, const int32_t* colind, int dofs, int full, uint16_t* soff, uint16_t* src,
                        const char* who);
 
+// mesh_move.hip
+int mesh_move(fedd_ctx* c, const double* disp_rep);     // nullptr: back to the reference coordinates
+int mesh_coords_get(fedd_ctx* c, double* xyz_rep);
+
 // hyperelastic.hip
 int assemble_hyperelastic(fedd_ctx* c, int model, const double* params, int n_params, int what);
 int assemble_hyperelastic_time(fedd_ctx* c, int model, const double* params, int n_params, int what, int slot_m, double cm);
@@ -680,6 +702,7 @@ int assemble_hyperelastic_time(fedd_ctx* c, int model, const double* params, int
 // Returns -1, without error, when the mesh does not fit the tiles.
 struct AsmArgs;
 int assemble_tiles(fedd_ctx* c, int kform, const AsmArgs& a, int ntab);
+int tiles_refresh_coords(fedd_ctx* c);   // the coordinate copies at the head of the tile blobs, from d_xyz (after a move; no-op without tiles)
 
 // blocks.hip
 int matrix_store(fedd_ctx* c, int slot);

@@ -1591,6 +1591,7 @@ fedd_ctx::SwStructKey schwarz_struct_key(const fedd_ctx* c) {
     fedd_ctx::SwStructKey k;
     k.mesh_gen = c->mesh_gen;
     k.pattern_gen = c->pattern_gen;
+    k.geometry_id = c->geometry_id;     // d_xyz is also written by fedd_mesh_move, which leaves mesh_gen alone
     k.n_own = c->n_own;
     k.n_rows = c->n_rows;
     k.n_rows_ext = c->n_rows_ext;

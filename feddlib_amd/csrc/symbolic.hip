@@ -339,13 +339,20 @@ int expand_node_pattern(fedd_ctx* c, const int32_t* nptr, const int32_t* ncol, i
     return 0;
 }
 
+// the build would write the pattern the system slot holds (whether it then keeps the arrays is option "pattern_reuse")
+static bool same_pattern_again(const fedd_ctx* c, int dofs, int block_mode) {
+    return c->pat_repeatable && c->have_pattern && !c->merged && c->pat_mesh_gen == c->mesh_gen && c->dofs == dofs &&
+           c->block_mode == block_mode;
+}
+
+bool pattern_repeats(const fedd_ctx* c, int dofs, int block_mode) { return c->pat_reuse && same_pattern_again(c, dofs, block_mode); }
+
 int build_pattern(fedd_ctx* c, int dofs, int block_mode) {
     // The same build on the same mesh writes the same pattern (every writer of d_rowptr / d_colind clears pat_repeatable): the
     // pattern generation stands (schwarz.hip keeps the box structure of a pattern it has seen, spmv.hip its stream), and with
     // option "pattern_reuse" the arrays stand too -- every kernel, reduction, scan and copy below would rewrite them with the
     // integers they hold.  What is left of the call is what it promises beside the pattern: zeroed values and vectors.
-    const bool repeat = c->pat_repeatable && c->have_pattern && !c->merged && c->pat_mesh_gen == c->mesh_gen && c->dofs == dofs &&
-                        c->block_mode == block_mode;
+    const bool repeat = same_pattern_again(c, dofs, block_mode);
     c->pat_last_reused = 0;
     if (repeat && c->pat_reuse) {
         system_written(c, SYS_VALUES);

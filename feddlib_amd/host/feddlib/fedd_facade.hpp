@@ -570,12 +570,39 @@ public:
     const std::vector<int32_t>& connectivity() const { return conn_; }
     // facade internals
     DeviceContextPtr device() const { return dev_; }
-    // the same mesh into another context (one rank): the child contexts of the block preconditioners (LinearSolver)
-    void uploadMeshTo(fedd_ctx* ctx) const {
+    // the same mesh into another context (one rank): the child contexts of the block preconditioners (LinearSolver).  The
+    // context gets the REFERENCE coordinates and then the displacement in force, so that a later moveMesh means the same
+    // there as on the domain's own context; the domain remembers it (weakly) for that
+    void uploadMeshTo(const DeviceContextPtr& dev) const {
         std::vector<int64_t> grep(mapRepeated_->gids().begin(), mapRepeated_->gids().end()), guni(mapUnique_->gids().begin(), mapUnique_->gids().end());
-        feddCheck(fedd_mesh_set(ctx, dim_, nen_, (int64_t)(conn_.size() / nen_), conn_.data(), (int64_t)grep.size(), xyz_.data(), grep.data(),
+        const std::vector<double>& ref = xyzRef_.empty() ? xyz_ : xyzRef_;
+        feddCheck(fedd_mesh_set(dev->ctx, dim_, nen_, (int64_t)(conn_.size() / nen_), conn_.data(), (int64_t)grep.size(), ref.data(), grep.data(),
                                 (int64_t)guni.size(), guni.data(), flagUni_.data()), "fedd_mesh_set");
+        if (!disp_.empty()) feddCheck(fedd_mesh_move(dev->ctx, disp_.data()), "fedd_mesh_move");
+        uploads_.push_back(dev.shared());
     }
+    // Domain::moveMesh (Domain_def.hpp:673-676 -> Mesh::moveMesh, Mesh_def.hpp:297-330): points = reference points + displacement,
+    // one addition per entry, relative to the points the mesh was built with (pointsRepRef_ / pointsUniRef_) and not cumulative.
+    // The unique points of this facade are a view of the repeated ones (getPointsUnique), so the repeated displacement moves
+    // both; the unique one is checked like the reference checks it.  The device goes first: fedd_mesh_move refuses a
+    // displacement that inverts an element and then nothing, here or there, has moved.  One rank (the device call says so).
+    void moveMesh(Teuchos::RCP<MultiVector<SC, LO, GO, NO> > displacementUnique, Teuchos::RCP<MultiVector<SC, LO, GO, NO> > displacementRepeated) {
+        TEUCHOS_TEST_FOR_EXCEPTION(displacementRepeated.is_null(), std::runtime_error, " displacementRepeated in moveMesh is null.");
+        TEUCHOS_TEST_FOR_EXCEPTION(displacementUnique.is_null(), std::runtime_error, " displacementRepeated in moveMesh is null.");
+        const std::vector<SC>& d = displacementRepeated->raw(0);
+        TEUCHOS_TEST_FOR_EXCEPTION(d.size() != xyz_.size(), std::runtime_error,
+                                   "Domain::moveMesh: displacementRepeated has " << d.size() << " entries, the repeated points have " << xyz_.size());
+        TEUCHOS_TEST_FOR_EXCEPTION(displacementUnique->raw(0).size() != (size_t)mapUnique_->getNodeNumElements() * dim_, std::runtime_error,
+                                   "Domain::moveMesh: displacementUnique does not live on the unique vector-field map");
+        if (xyzRef_.empty()) xyzRef_ = xyz_;       // pointsRepRef_ (and, through uniOfRep_, pointsUniRef_)
+        feddCheck(fedd_mesh_move(dev_->ctx, d.data()), "fedd_mesh_move");
+        for (auto& w : uploads_)
+            if (auto child = w.lock()) feddCheck(fedd_mesh_move(child->ctx, d.data()), "fedd_mesh_move (child context)");
+        disp_.assign(d.begin(), d.end());
+        for (size_t k = 0; k < xyz_.size(); ++k) xyz_[k] = xyzRef_[k] + disp_[k];
+    }
+    vec2D_dbl_ptr_Type getPointsRepeatedRef() const { return points(xyzRef_.empty() ? xyz_ : xyzRef_, (size_t)mapRepeated_->getNodeNumElements(), nullptr); }
+    vec2D_dbl_ptr_Type getPointsUniqueRef() const { return points(xyzRef_.empty() ? xyz_ : xyzRef_, (size_t)mapUnique_->getNodeNumElements(), &uniOfRep_); }
     int nodesPerElement() const { return nen_; }
     const std::vector<double>& xyzRepeated() const { return xyz_; }
     const std::vector<int32_t>& uniqueLocalOfRepeated() const { return uniOfRep_; }
@@ -693,6 +720,8 @@ private:
     std::string FEType_;
     std::vector<int32_t> conn_, flagRep_, flagUni_, uniOfRep_, surf_, surfFlag_, rowGhostRep_, rowGhostFlag_, elemFlag_;
     std::vector<double> xyz_;
+    std::vector<double> xyzRef_, disp_;         // moveMesh: the points the mesh was built with, the displacement in force (empty: never moved)
+    mutable std::vector<std::weak_ptr<DeviceContext> > uploads_;     // contexts of uploadMeshTo
     int volumeID_ = 10;
     int64_t nP1_ = 0;
     bool structuredP2_ = false;
@@ -1648,8 +1677,8 @@ void LinearSolver<SC, LO, GO, NO>::setupBlockPreconditioner(Problem_Type* proble
         kids = Teuchos::rcp(new typename Problem_Type::BlockPrecChildren());
         kids->velocity = Teuchos::rcp(new DeviceContext(problem->getDomain(0)->getComm()));
         kids->schur = Teuchos::rcp(new DeviceContext(problem->getDomain(1)->getComm()));
-        problem->getDomain(0)->uploadMeshTo(kids->velocity->ctx);
-        problem->getDomain(1)->uploadMeshTo(kids->schur->ctx);
+        problem->getDomain(0)->uploadMeshTo(kids->velocity);
+        problem->getDomain(1)->uploadMeshTo(kids->schur);
     }
     auto sublistOf = [&](const char* name) -> Teuchos::ParameterList& {
         auto& sub = pl->sublist(name);
@@ -1749,6 +1778,45 @@ public:
         MatrixPtr_Type K = Teuchos::rcp(new Matrix_Type(this->getDomain(0)->getMapVecFieldUnique(), this->getDomain(0)->getApproxEntriesPerRow()));
         this->feFactory_->assemblyLinElasXDim(this->dim_, this->getDomain(0)->getFEType(), K, lambda, mu);
         this->system_->addBlock(K, 0, 0);
+        this->assembleSourceTerm(0.);
+        this->addToRhs(this->sourceTerm_);
+        if (this->verbose_) std::cout << "done -- " << std::endl;
+    }
+};
+
+// Geometry (feddlib/problems/specific/Geometry_def.hpp:37-101): the extension of a boundary displacement into the fluid mesh,
+// one variable d_f.  "Model" = "Elasticity": assemblyLinElasXDim with the reference's lambda from "Poisson Ratio" (default 0.3)
+// and "Mu".  "Model" = "Laplace" (the reference's default when the key is absent) scales the Laplacian by the distance of an
+// element to the FSI interface, which this code has no notion of: an error that names "Elasticity".
+template <class SC = default_sc, class LO = default_lo, class GO = default_go, class NO = default_no>
+class Geometry : public Problem<SC, LO, GO, NO> {
+public:
+    typedef Problem<SC, LO, GO, NO> Problem_Type;
+    typedef typename Problem_Type::DomainConstPtr_Type DomainConstPtr_Type;
+    typedef typename Problem_Type::Matrix_Type Matrix_Type;
+    typedef typename Problem_Type::MatrixPtr_Type MatrixPtr_Type;
+    Geometry(const DomainConstPtr_Type& domain, std::string FEType, ParameterListPtr_Type parameterList)
+        : Problem_Type(parameterList, domain->getComm()) {
+        this->addVariable(domain, FEType, "d_f", (int)domain->getDimension());
+        this->dim_ = (int)this->getDomain(0)->getDimension();
+    }
+    void info() override { this->infoProblem(); }
+    void assemble(std::string type = "") const override {
+        (void)type;
+        const std::string model = this->parameterList_->sublist("Parameter").get("Model", "Laplace");
+        TEUCHOS_TEST_FOR_EXCEPTION(model == "Laplace", std::logic_error,
+                                   "Geometry: \"Model\" = \"Laplace\" (also the default when the key is absent) scales the Laplacian by the distance to an FSI "
+                                   "interface, which is not built here; set \"Model\" to \"Elasticity\".");
+        TEUCHOS_TEST_FOR_EXCEPTION(model != "Elasticity", std::logic_error, "Unknown model for geometry.");
+        if (this->verbose_) std::cout << "-- Assembly Geometry (linear elasticity)... " << std::flush;
+        const double poissonRatio = this->parameterList_->sublist("Parameter").get("Poisson Ratio", 0.3);
+        const double mu = this->parameterList_->sublist("Parameter").get("Mu", 2.0e+6);
+        const double youngModulus = mu * 2. * (1 + poissonRatio);
+        const double lambda = (poissonRatio * youngModulus) / ((1 + poissonRatio) * (1 - 2 * poissonRatio));
+        MatrixPtr_Type H = Teuchos::rcp(new Matrix_Type(this->getDomain(0)->getMapVecFieldUnique(),
+                                                        this->getDomain(0)->getDimension() * this->getDomain(0)->getApproxEntriesPerRow()));
+        this->feFactory_->assemblyLinElasXDim(this->dim_, this->getDomain(0)->getFEType(), H, lambda, mu);
+        this->system_->addBlock(H, 0, 0);
         this->assembleSourceTerm(0.);
         this->addToRhs(this->sourceTerm_);
         if (this->verbose_) std::cout << "done -- " << std::endl;
@@ -2469,7 +2537,7 @@ inline void addDeviceTimers(const DeviceContextPtr& dev, Teuchos::StackedTimer& 
                                              "orthogonalisation: dot sweep", "orthogonalisation: update sweep", "orthogonalisation: fused sweep",
                                              "full park (matrix cores)", "full park", "full gather", "cg pq", "cg xr", "cg rz", "cg p",
                                              "newmark state", "block apply", "multistep state", "block preconditioner B^T",
-                                             "newton residual", "newton update"};
+                                             "newton residual", "newton update", "mesh move", "mesh move check"};
     for (int t = 0; t < FEDD_T_COUNT; ++t) {
         double ms = 0.;
         int64_t n = 0;

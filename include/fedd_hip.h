@@ -93,7 +93,9 @@ enum fedd_timer {
     FEDD_T_BLOCKPREC_BT = 26, /* Triangular block preconditioner: t = r_u - B^T z_p, k_bt_sub (blockprec.hip) */
     FEDD_T_NEWTON_RESIDUAL = 27, /* Newton residual of a Newmark step: k_newton_residual (newton.hip) */
     FEDD_T_NEWTON_UPDATE = 28,   /* ... the iterate's update: k_newton_update                      */
-    FEDD_T_COUNT    = 29
+    FEDD_T_MESH_MOVE = 29,  /* fedd_mesh_move: k_mesh_move, candidate = x_ref + d (mesh_move.hip)  */
+    FEDD_T_MOVE_CHECK = 30, /* ... k_move_check + k_move_min, det B of every element against the reference */
+    FEDD_T_COUNT    = 31
 };
 
 /* ------------------------------------------------------------------------------------------------
@@ -280,6 +282,60 @@ int fedd_mesh_set_rows(fedd_ctx* ctx, int dim, int nen, int64_t n_elem, const in
                        int64_t n_rep, const double* xyz, const int64_t* gid_rep,
                        int64_t n_uni, const int64_t* gid_uni, const int32_t* bcflag_uni,
                        int64_t n_row_ghosts, const int64_t* row_ghost_gid, const int32_t* row_ghost_bcflag);
+
+/* ------------------------------------------------------------------------------------------------
+ * Moving mesh: new coordinates for the mesh that is on the device (one rank).
+ * Replaces Mesh::moveMesh (feddlib/core/Mesh/Mesh_def.hpp:297-330) as Domain::moveMesh calls it in the ALE / FSI loops and in
+ * problems/tests/geometry/main.cpp:683.
+ *
+ * fedd_mesh_move sets x[i][j] = x_ref[i][j] + disp_rep[dim*i + j] on the repeated map of fedd_mesh_set, ghost nodes included:
+ * one addition in double per entry (Mesh_def.hpp:312).  x_ref is what the last fedd_mesh_set* uploaded (kept in a second
+ * device buffer from the first move on).  Moves are relative to x_ref and NOT cumulative; disp_rep = NULL restores x_ref.
+ *
+ * Commit only on success.  The candidate coordinates are written to a buffer of their own and every element is checked: det B
+ * of the candidate and of the reference element from the first dim + 1 nodes (FE::buildTransformation, FE_def.hpp:5342-5357).
+ * If det * det_ref <= 0 for an element, the call fails with a message that names the smallest such element and its ratio
+ * det / det_ref, and NOTHING is committed: coordinates, geometry_id and every cache stay as they were.  Otherwise the
+ * coordinates are in force, n_moves and geometry_id go up by one and min_det_ratio = min over the elements of |det| / |det_ref|
+ * is recorded (1.0 after a restore, which is not checked).  The check is a host-visible error, never a device fault.
+ * An element that is degenerate in the REFERENCE mesh (det_ref == 0) fails the check under every displacement, the zero
+ * displacement included: such a mesh cannot be moved (only restored, which is a copy).
+ *
+ * A move KEEPS (none of these reads a coordinate; after fedd_mesh_set* all of them are built again):
+ *   - the node -> element adjacency;
+ *   - the assembly's tile structures and tile shapes (the coordinate copies that lead the tile blobs are written again by the
+ *     move; node lists, element records, gather lists and shapes stand -- the tiles keep the clusters they were built on);
+ *   - the node and dof patterns: the system pattern (the next fedd_pattern_build repeats, fedd_pattern_reuse_info), the patterns
+ *     of the stored slots, the node-level pattern of the advection matrices;
+ *   - the gather lists (P2 row sums, advection, the FULL-pattern lists of the hyperelastic tangent and the stress form);
+ *   - the advection / stress / hyperelastic scratch and reference tables, the velocity of fedd_velocity_set;
+ *   - the surface set of fedd_surface_set;
+ *   - the Dirichlet flag tables (boundary flags of the nodes);
+ *   - the halo plan;
+ *   - the time-stepping histories (Newmark state, multistep history) and the Newton state;
+ *   - the system matrix, right-hand side and solution, the solver's SpMV stream, and the stored slots with their VALUES: they
+ *     belong to the coordinates they were assembled on, and geometry_id lets the caller tell (record it beside a store).
+ * A move DROPS, to be built at next use (everything derived from coordinates, as opposed to matrix values):
+ *   - the Schwarz box lattice and box structure (the next fedd_schwarz_setup builds its structure stage: the lattice is laid
+ *     over the bounding box of the owned nodes, a node belongs to box floor((x - lo) / w) per direction, see fedd_schwarz_setup);
+ *   - the preconditioner with its coarse level: coarse lattice, classification of the nodes, prolongation (a solve wants
+ *     fedd_schwarz_setup again, as after an assembly);
+ *   - the park + gather lists of the symmetric apply (they follow the box structure);
+ *   - kept per-element geometry: the coordinate copies in the tile blobs (written again at once, above); there is no other;
+ *   - the record of the last fedd_matrix_combine: fedd_matrix_combine_current answers 0.
+ * What is derived from VALUES is left to the next assembly, which drops it already: the SpMV stream, dictionary and classes,
+ * the Schwarz inverses and fingerprints, the CG setup.
+ *
+ * Errors: a host-only context ("needs a GPU context"), no mesh, more than one rank.
+ * Left out: mesh velocity and ALE convection, interface distances (the scaled-Laplace extension), more than one rank.
+ *
+ * fedd_mesh_move_info: moves committed since the last fedd_mesh_set*, moves committed since the context was made, the ratio
+ * above (0, 0, 1.0 on a fresh context).  Needs no device; outputs may be NULL.
+ * fedd_mesh_coords_get: the coordinates in force, xyz_rep[n_rep * dim] on the repeated map.
+ * ---------------------------------------------------------------------------------------------- */
+int fedd_mesh_move(fedd_ctx* ctx, const double* disp_rep);
+int fedd_mesh_move_info(fedd_ctx* ctx, int64_t* n_moves, int64_t* geometry_id, double* min_det_ratio);
+int fedd_mesh_coords_get(fedd_ctx* ctx, double* xyz_rep);
 
 /* symbolic CSR on the owned (unique-map) rows: what Tpetra's dynamic insert + fillComplete
  * discover (feddlib/core/LinearAlgebra/Matrix_def.hpp:88-92,192-199). */
