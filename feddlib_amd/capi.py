@@ -26,6 +26,7 @@ COARSE_RGDSW = 3
 LEVELS_ADDITIVE = 0         # FROSch "Level Combination" (fedd_schwarz_set_level_combination)
 LEVELS_MULTIPLICATIVE = 1
 ADV_N, ADV_W, ADV_NEWTON = range(3)     # fedd_assemble_advection
+ALE_P, ALE_FIXEDPOINT, ALE_NEWTON = range(3)     # fedd_assemble_advection_ale
 HYPER_NEOHOOKE, HYPER_MOONEY_RIVLIN, HYPER_STVK = range(3)   # fedd_assemble_hyperelastic: model
 HYPER_TANGENT, HYPER_FORCE = 1, 2                            # ... what (or-ed)
 BLOCKPREC_DIAGONAL, BLOCKPREC_TRIANGULAR = 1, 2              # fedd_block_prec_attach: kind
@@ -91,6 +92,10 @@ SIGNATURES = {
     "fedd_matrix_get": [C.c_void_p, C.c_int, _i64p, _i32p, _f64p],
     "fedd_velocity_set": [C.c_void_p, _f64p],
     "fedd_assemble_advection": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int],
+    "fedd_mesh_velocity_set": [C.c_void_p, _f64p],
+    "fedd_mesh_velocity_diff": [C.c_void_p, _f64p, _f64p, C.c_double],
+    "fedd_mesh_velocity_get": [C.c_void_p, _f64p],
+    "fedd_assemble_advection_ale": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int],
     "fedd_assemble_hyperelastic": [C.c_void_p, C.c_int, _f64p, C.c_int, C.c_int],
     "fedd_hyperelastic_force_get": [C.c_void_p, _f64p],
     "fedd_assemble_hyperelastic_time": [C.c_void_p, C.c_int, _f64p, C.c_int, C.c_int, C.c_int, C.c_double],
@@ -659,6 +664,29 @@ class Context:
     def assemble_advection(self, kind, scale=1.0, slot_add=-1, slot_out=4):
         """slot_out <- scale * (N | W | N + W)(u) + M[slot_add], FULL velocity pattern (fedd_assemble_advection)"""
         _chk(self._L.fedd_assemble_advection(self._h, kind, float(scale), slot_add, slot_out))
+
+    def mesh_velocity_set(self, w_rep):
+        """w_rep: [n_rep, dim] or flat dim * node + d, on the repeated map of mesh_set; None clears (fedd_mesh_velocity_set)"""
+        w = None if w_rep is None else np.ascontiguousarray(w_rep, dtype=np.float64).ravel()
+        _chk(self._L.fedd_mesh_velocity_set(self._h, _p(w, _f64p)))
+
+    def mesh_velocity_diff(self, d_new_rep, d_old_rep, dt):
+        """w <- (d_new - d_old) * (1.0 / dt) on the device (fedd_mesh_velocity_diff)"""
+        a = np.ascontiguousarray(d_new_rep, dtype=np.float64).ravel()
+        b = np.ascontiguousarray(d_old_rep, dtype=np.float64).ravel()
+        _chk(self._L.fedd_mesh_velocity_diff(self._h, _p(a, _f64p), _p(b, _f64p), float(dt)))
+
+    def mesh_velocity(self):
+        """the mesh velocity in force, [n_rep, dim] on the repeated map of mesh_set (fedd_mesh_velocity_get)"""
+        n = getattr(self, "_n_rep", 0)
+        out = np.zeros((max(n, 1), getattr(self, "_dim", 1)))
+        _chk(self._L.fedd_mesh_velocity_get(self._h, _p(out, _f64p)))
+        return out[:n]
+
+    def assemble_advection_ale(self, kind, scale=1.0, slot_add=-1, slot_out=4):
+        """slot_out <- scale * (P(w) | N(u - w) - P(w) | N(u - w) + W(u) - P(w)) + M[slot_add], FULL velocity pattern
+        (fedd_assemble_advection_ale)"""
+        _chk(self._L.fedd_assemble_advection_ale(self._h, kind, float(scale), slot_add, slot_out))
 
     def assemble_hyperelastic(self, model, params, what=HYPER_TANGENT | HYPER_FORCE):
         """tangent -> system matrix (FULL pattern, dim dofs per node) and / or force vector of the material at the displacement

@@ -3,6 +3,7 @@
 #include <rccl/rccl.h>
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstring>
 #include <unordered_map>
 
@@ -185,6 +186,8 @@ static int mesh_set_impl(fedd_ctx* c, int dim, int nen, int64_t n_elem, const in
     c->p2_state = 0;     // ... and so do the gather lists of the P2 row sums
     c->adv_state = 0;    // ... and the pattern and lists of the advection matrices; the velocity belonged to the old nodes
     c->have_vel = false;
+    c->have_mvel = false;   // ... and so did the mesh velocity, whose buffer goes with them
+    c->d_mvel.release();
     c->hy_lists = c->have_hy_f = false;   // ... and the lists and the force vector of the hyperelastic path
     c->nw_active = c->nw_have_src = c->nw_f_fresh = false;   // ... and the Newton state (newton.hip)
     c->nw_n = -1;
@@ -510,6 +513,41 @@ extern "C" int fedd_assemble_advection(fedd_ctx* c, int kind, double scale, int 
     FEDD_CHECK(c->n_node > 0, "fedd_assemble_advection: call fedd_mesh_set first");
     FEDD_HIP(hipSetDevice(c->device));
     return assemble_advection(c, kind, scale, slot_add, slot_out);
+}
+
+extern "C" int fedd_mesh_velocity_set(fedd_ctx* c, const double* w_rep) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(c->n_node > 0, "fedd_mesh_velocity_set: call fedd_mesh_set first");
+    FEDD_HIP(hipSetDevice(c->device));
+    return mesh_velocity_set(c, w_rep);
+}
+
+extern "C" int fedd_mesh_velocity_diff(fedd_ctx* c, const double* d_new_rep, const double* d_old_rep, double dt) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(c->n_node > 0, "fedd_mesh_velocity_diff: call fedd_mesh_set first");
+    FEDD_CHECK(d_new_rep && d_old_rep, "fedd_mesh_velocity_diff: null array");
+    FEDD_CHECK(std::isfinite(dt) && dt > 0.0, "fedd_mesh_velocity_diff: the time step must be positive and finite (dt = %g was given)", dt);
+    FEDD_HIP(hipSetDevice(c->device));
+    return mesh_velocity_diff(c, d_new_rep, d_old_rep, dt);
+}
+
+extern "C" int fedd_mesh_velocity_get(fedd_ctx* c, double* w_rep) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(w_rep, "fedd_mesh_velocity_get: null pointer");
+    FEDD_HIP(hipSetDevice(c->device));
+    return mesh_velocity_get(c, w_rep);
+}
+
+extern "C" int fedd_assemble_advection_ale(fedd_ctx* c, int kind, double scale, int slot_add, int slot_out) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(kind == FEDD_ALE_P || kind == FEDD_ALE_FIXEDPOINT || kind == FEDD_ALE_NEWTON,
+               "fedd_assemble_advection_ale: unknown kind %d", kind);
+    CHECK_SLOT(slot_out);
+    FEDD_CHECK(slot_add < fedd::MAX_AUX, "matrix slot %d out of range", slot_add);
+    FEDD_CHECK(slot_add != slot_out, "fedd_assemble_advection_ale: slot_add and slot_out must differ");
+    FEDD_CHECK(c->n_node > 0, "fedd_assemble_advection_ale: call fedd_mesh_set first");
+    FEDD_HIP(hipSetDevice(c->device));
+    return assemble_advection_ale(c, kind, scale, slot_add, slot_out);
 }
 
 extern "C" int fedd_assemble_hyperelastic(fedd_ctx* c, int model, const double* params, int n_params, int what) {

@@ -1226,18 +1226,40 @@ namespace {
 // The rows are then summed by gather lists (k_p2_lists on the node-level pattern, built once per mesh): a wave per node, a lane
 // per node-level nonzero, the element blocks added in adjacency order -- no atomics, bitwise reproducible -- and written as
 // scale * block + M[slot_add] into the FULL pattern, whose positions follow from the node-level pattern in closed form.
+//
+// ALE convection on a moved mesh (fedd_assemble_advection_ale; template parameter ALE, 0 = the fixed-mesh kinds above, whose
+// code it leaves untouched) for a mesh velocity w given at the nodes (d_mvel):
+//   P(w)  FE::assemblyAdditionalConvection  FE_def.hpp:3044-3255   p_ij = |det B| sum_q w_q (div w_h)(x_q) phi_i phi_j on the dim
+//                                                                   diagonal component pairs, rule of W (below)
+// ALE_FUSED: the wave stages u, w and c = u - w (one subtraction per nodal value); beta is formed from c, grad u_h from u, and
+// its lanes add pw_q = w_q (div w_h)(x_q) per quadrature point next to beta:  for d: g_r = sum_i w[i][d] dphi_i,r (i ascending),
+// div += g_r Binv[r][d] (r ascending); pw_q = w_q * div.  Pair (i, j): p = |det B| * sum_q (phi_i phi_j) pw_q (q ascending), taken
+// from n_ij AFTER the setZeros threshold of n_ij (and of the W block): FIXEDPOINT writes n_ij - p_ij, NEWTON adds n_ij - p_ij to the
+// diagonal of the thresholded W block.  ALE_P_ONLY writes p_ij alone and reads no u.  With w = 0 every p is a zero and c = u, so
+// the fused kinds return the bits of the fixed-mesh kinds.
 // ---------------------------------------------------------------------------------------------
+enum { ALE_NONE = 0, ALE_FUSED = 1, ALE_P_ONLY = 2 };
+
 struct AdvArgs {
     const int32_t* conn;
     const double* xyz;
     const double* u;
+    const double* w;        // mesh velocity at the nodes (ALE kinds only)
     const double* tab;      // w | phi | dphi of the rule of N; the same of the rule of W at off_w (0: one rule for both)
     int nq_n, nq_w, off_w;
     double zero_eps;        // setZeros_ / myeps_ (FE_def.hpp:1816, 1908): element values of N and of W below it are set to zero
 };
 
-template <int DIM, int NEN, int KIND>
+// LDS doubles of one wave: u, beta, grad u_h; the ALE kinds add w, u - w and pw
+template <int DIM, int NEN, int ALE>
+__host__ __device__ constexpr int adv_per_wave(int nqn, int nqw) {
+    return NEN * DIM + nqn * DIM + nqw * DIM * DIM + (ALE != ALE_NONE ? 2 * NEN * DIM + nqw : 0);
+}
+
+template <int DIM, int NEN, int KIND, int ALE = ALE_NONE>
 __global__ __launch_bounds__(256) void k_adv_elem(AdvArgs a, int64_t n_elem, double* __restrict__ ke) {
+    static_assert(ALE != ALE_P_ONLY || KIND == FEDD_ADV_N, "P alone leaves as one value per node pair");
+    static_assert(ALE == ALE_NONE || KIND != FEDD_ADV_W, "no ALE form of W alone");
     constexpr int BLK = KIND == FEDD_ADV_N ? 1 : DIM * DIM;
     extern __shared__ double sm[];
     const int nqn = a.nq_n, nqw = a.nq_w;
@@ -1249,10 +1271,14 @@ __global__ __launch_bounds__(256) void k_adv_elem(AdvArgs a, int64_t n_elem, dou
     const double* phiw = ww + nqw;
     const double* dphiw = phiw + nqw * NEN;
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int per_wave = NEN * DIM + nqn * DIM + nqw * DIM * DIM;
+    const int per_wave = adv_per_wave<DIM, NEN, ALE>(nqn, nqw);
     double* Us = sm + ntab + (size_t)w * per_wave;      // this wave's velocity values [i][d]
     double* beta = Us + NEN * DIM;                      // w_q B^-1 u_h(x_q) [q][r]
     double* wG = beta + nqn * DIM;                      // w_q (d u_d1 / d x_d2)(x_q) [q][d1][d2]
+    double* Ws = wG + nqw * DIM * DIM;                  // ALE: mesh velocity values [i][d]
+    double* Cs = Ws + NEN * DIM;                        // ALE: u - w [i][d], what convects
+    double* pw = Cs + NEN * DIM;                        // ALE: w_q (div w_h)(x_q) [q]
+    const double* Ub = ALE == ALE_FUSED ? Cs : Us;      // the field behind beta
     for (int i = tid; i < ntab; i += 256) sm[i] = a.tab[i];
     const int64_t nwave = (int64_t)gridDim.x * 4;
     const int64_t trips = (n_elem + nwave - 1) / nwave;
@@ -1261,7 +1287,20 @@ __global__ __launch_bounds__(256) void k_adv_elem(AdvArgs a, int64_t n_elem, dou
         const bool on = e < n_elem;
         double xv = 0.0;
         if (on && lane < (DIM + 1) * DIM) xv = a.xyz[(int64_t)a.conn[e * NEN + lane / DIM] * DIM + (lane % DIM)];
-        if (on && lane < NEN * DIM) Us[lane] = a.u[(int64_t)a.conn[e * NEN + lane / DIM] * DIM + (lane % DIM)];
+        if constexpr (ALE == ALE_NONE) {
+            if (on && lane < NEN * DIM) Us[lane] = a.u[(int64_t)a.conn[e * NEN + lane / DIM] * DIM + (lane % DIM)];
+        } else {
+            if (on && lane < NEN * DIM) {
+                const int64_t at = (int64_t)a.conn[e * NEN + lane / DIM] * DIM + (lane % DIM);
+                const double wv = a.w[at];
+                Ws[lane] = wv;
+                if constexpr (ALE == ALE_FUSED) {
+                    const double uv = a.u[at];
+                    Us[lane] = uv;
+                    Cs[lane] = uv - wv;
+                }
+            }
+        }
         double X[DIM + 1][DIM];
 #pragma unroll
         for (int v = 0; v <= DIM; ++v)
@@ -1271,14 +1310,14 @@ __global__ __launch_bounds__(256) void k_adv_elem(AdvArgs a, int64_t n_elem, dou
         const double absdet = on ? fabs(affine<DIM>(X, Binv)) : 0.0;
         __syncthreads();        // tables (first trip) and Us
         if (on) {
-            if constexpr (KIND != FEDD_ADV_W) {
+            if constexpr (KIND != FEDD_ADV_W && ALE != ALE_P_ONLY) {
                 for (int q = lane; q < nqn; q += 64) {
                     double uq[DIM];
 #pragma unroll
                     for (int d = 0; d < DIM; ++d) uq[d] = 0.0;
                     for (int i = 0; i < NEN; ++i)
 #pragma unroll
-                        for (int d = 0; d < DIM; ++d) uq[d] += Us[i * DIM + d] * phin[q * NEN + i];
+                        for (int d = 0; d < DIM; ++d) uq[d] += Ub[i * DIM + d] * phin[q * NEN + i];
 #pragma unroll
                     for (int r = 0; r < DIM; ++r) {
                         double s = 0.0;
@@ -1306,6 +1345,23 @@ __global__ __launch_bounds__(256) void k_adv_elem(AdvArgs a, int64_t n_elem, dou
                     }
                 }
             }
+            if constexpr (ALE != ALE_NONE) {
+                for (int q = lane; q < nqw; q += 64) {
+                    double dv = 0.0;
+#pragma unroll
+                    for (int d = 0; d < DIM; ++d) {
+                        double gr[DIM];
+#pragma unroll
+                        for (int r = 0; r < DIM; ++r) gr[r] = 0.0;
+                        for (int i = 0; i < NEN; ++i)
+#pragma unroll
+                            for (int r = 0; r < DIM; ++r) gr[r] += Ws[i * DIM + d] * dphiw[(q * NEN + i) * DIM + r];
+#pragma unroll
+                        for (int r = 0; r < DIM; ++r) dv += gr[r] * Binv[r][d];
+                    }
+                    pw[q] = ww[q] * dv;
+                }
+            }
         }
         __syncthreads();
         if (on) {
@@ -1313,7 +1369,7 @@ __global__ __launch_bounds__(256) void k_adv_elem(AdvArgs a, int64_t n_elem, dou
             for (int t = lane; t < NEN * NEN; t += 64) {
                 const int i = t / NEN, j = t - i * NEN;
                 double n = 0.0;
-                if constexpr (KIND != FEDD_ADV_W) {
+                if constexpr (KIND != FEDD_ADV_W && ALE != ALE_P_ONLY) {
                     for (int q = 0; q < nqn; ++q) {
                         const double* dp = dphin + (q * NEN + j) * DIM;
                         double cq = 0.0;
@@ -1323,6 +1379,12 @@ __global__ __launch_bounds__(256) void k_adv_elem(AdvArgs a, int64_t n_elem, dou
                     }
                     n *= absdet;
                     n = (a.zero_eps > 0.0 && fabs(n) < a.zero_eps) ? 0.0 : n;
+                }
+                if constexpr (ALE != ALE_NONE) {        // after the threshold of n
+                    double p = 0.0;
+                    for (int q = 0; q < nqw; ++q) p += (phiw[q * NEN + i] * phiw[q * NEN + j]) * pw[q];
+                    p *= absdet;
+                    n = ALE == ALE_P_ONLY ? p : n - p;
                 }
                 if constexpr (KIND == FEDD_ADV_N) {
                     out[t] = n;
@@ -1345,7 +1407,7 @@ __global__ __launch_bounds__(256) void k_adv_elem(AdvArgs a, int64_t n_elem, dou
                 }
             }
         }
-        __syncthreads();        // Us, beta, wG are rewritten by the next trip
+        __syncthreads();        // Us, beta, wG (and Ws, Cs, pw of the ALE kinds) are rewritten by the next trip
     }
 }
 
@@ -1444,23 +1506,23 @@ int adv_setup(fedd_ctx* c) {
     return 0;
 }
 
-template <int DIM, int NEN, int KIND>
+template <int DIM, int NEN, int KIND, int ALE = ALE_NONE>
 int launch_advection(fedd_ctx* c, double scale, const DevCsr* add, DevCsr& out) {
     constexpr int BLK = KIND == FEDD_ADV_N ? 1 : DIM * DIM;
     FEDD_TRY(c->d_adv_ke.ensure((size_t)c->n_elem * NEN * NEN * BLK));
     AdvArgs a;
-    a.conn = c->d_conn.p; a.xyz = c->d_xyz.p; a.u = c->d_vel.p; a.tab = c->d_adv_tab.p;
+    a.conn = c->d_conn.p; a.xyz = c->d_xyz.p; a.u = c->d_vel.p; a.w = c->d_mvel.p; a.tab = c->d_adv_tab.p;
     a.nq_n = c->adv_nq[0]; a.nq_w = c->adv_nq[1]; a.off_w = c->adv_tab_off_w;
     a.zero_eps = c->asm_zero_eps;
     const int ntab = a.off_w + a.nq_w * (1 + NEN + NEN * DIM);
-    const int per_wave = NEN * DIM + a.nq_n * DIM + a.nq_w * DIM * DIM;
+    const int per_wave = adv_per_wave<DIM, NEN, ALE>(a.nq_n, a.nq_w);
     const size_t lds = ((size_t)ntab + 4 * (size_t)per_wave) * sizeof(double);
     FEDD_CHECK(lds <= 64 * 1024, "advection: the quadrature tables do not fit the LDS");
     const int64_t nn = c->n_own;
     ScopedTimer t(c, FEDD_T_ASSEMBLE);
     if (c->n_elem > 0) {
         const int64_t nwg = std::min<int64_t>((c->n_elem + 3) / 4, 256 * 8);
-        hipLaunchKernelGGL((k_adv_elem<DIM, NEN, KIND>), dim3((unsigned)nwg), dim3(256), lds, c->stream, a, c->n_elem, c->d_adv_ke.p);
+        hipLaunchKernelGGL((k_adv_elem<DIM, NEN, KIND, ALE>), dim3((unsigned)nwg), dim3(256), lds, c->stream, a, c->n_elem, c->d_adv_ke.p);
     }
     const int nwg2 = (int)std::min<int64_t>((nn + 3) / 4, 256 * 32);
     const int add_full = add && add->block_mode == FEDD_BLOCK_FULL ? 1 : 0;
@@ -1468,8 +1530,9 @@ int launch_advection(fedd_ctx* c, double scale, const DevCsr* add, DevCsr& out) 
                        (const int32_t*)c->d_n2e.p, (const int32_t*)c->d_adv_nptr.p, (int32_t)nn, (const uint16_t*)c->d_adv_soff.p,
                        (const uint16_t*)c->d_adv_src.p, (const double*)c->d_adv_ke.p, scale, add ? (const double*)add->val.p : nullptr,
                        add_full, out.val.p);
-    // byte model: geometry, u and connectivity once per element, the element blocks written and read once, the FULL values written
-    t.bytes(((double)c->n_elem * (NEN * 4.0 + 2.0 * NEN * NEN * BLK * 8.0) + (double)c->n_node * DIM * 16.0 +
+    // byte model: geometry, u and connectivity once per element, the element blocks written and read once, the FULL values written;
+    // the fused ALE kinds read one more nodal field, w (P alone reads w in the place of u)
+    t.bytes(((double)c->n_elem * (NEN * 4.0 + 2.0 * NEN * NEN * BLK * 8.0) + (double)c->n_node * DIM * (ALE == ALE_FUSED ? 24.0 : 16.0) +
              (double)c->adv_node_nnz * (DIM * DIM * 8.0 + (add ? (add_full ? DIM * DIM : DIM) * 8.0 : 0.0))));
     t.stop();
     FEDD_HIP(hipGetLastError());
@@ -1481,6 +1544,20 @@ int advection_kind(fedd_ctx* c, int kind, double scale, const DevCsr* add, DevCs
     if (kind == FEDD_ADV_N) return launch_advection<DIM, NEN, FEDD_ADV_N>(c, scale, add, out);
     if (kind == FEDD_ADV_W) return launch_advection<DIM, NEN, FEDD_ADV_W>(c, scale, add, out);
     return launch_advection<DIM, NEN, FEDD_ADV_NEWTON>(c, scale, add, out);
+}
+
+template <int DIM, int NEN>
+int advection_ale_kind(fedd_ctx* c, int kind, double scale, const DevCsr* add, DevCsr& out) {
+    if (kind == FEDD_ALE_P) return launch_advection<DIM, NEN, FEDD_ADV_N, ALE_P_ONLY>(c, scale, add, out);
+    if (kind == FEDD_ALE_FIXEDPOINT) return launch_advection<DIM, NEN, FEDD_ADV_N, ALE_FUSED>(c, scale, add, out);
+    return launch_advection<DIM, NEN, FEDD_ADV_NEWTON, ALE_FUSED>(c, scale, add, out);
+}
+
+// w_i = (a_i - b_i) * rdt: one subtraction, one multiplication by the reciprocal the host formed (FSI_def.hpp:460-462)
+__global__ __launch_bounds__(256) void k_mesh_velocity_diff(const double* __restrict__ d_new, const double* __restrict__ d_old,
+                                                            int64_t n, double rdt, double* __restrict__ w) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        w[i] = (d_new[i] - d_old[i]) * rdt;
 }
 
 }  // namespace
@@ -1540,14 +1617,20 @@ int full_lists_ensure(fedd_ctx* c, const char* who) {
     return 0;
 }
 
+// a nodal vector field on the repeated map, brought to the column-local numbering of the mesh
+static void field_to_columns(const fedd_ctx* c, const double* rep, std::vector<double>& col) {
+    const int dim = c->dim;
+    const size_t n_rep = c->h_col_of_rep.size();
+    col.assign((size_t)c->n_node * dim, 0.0);
+    for (size_t i = 0; i < n_rep; ++i)
+        for (int d = 0; d < dim; ++d) col[(size_t)c->h_col_of_rep[i] * dim + d] = rep[i * dim + d];
+}
+
 // what NavierStokes::u_rep_ holds (NavierStokes_def.hpp:282-321), brought to the column-local numbering of the mesh
 int velocity_set(fedd_ctx* c, const double* u_rep) {
     FEDD_CHECK(c->nranks == 1, "fedd_velocity_set: one rank only for now");
-    const int dim = c->dim;
-    const size_t n_rep = c->h_col_of_rep.size();
-    std::vector<double> u((size_t)c->n_node * dim, 0.0);
-    for (size_t i = 0; i < n_rep; ++i)
-        for (int d = 0; d < dim; ++d) u[(size_t)c->h_col_of_rep[i] * dim + d] = u_rep[i * dim + d];
+    std::vector<double> u;
+    field_to_columns(c, u_rep, u);
     FEDD_TRY(c->d_vel.ensure(u.size()));
     FEDD_HIP(hipMemcpyAsync(c->d_vel.p, u.data(), u.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     FEDD_HIP(hipStreamSynchronize(c->stream));  // `u` is a local
@@ -1555,10 +1638,64 @@ int velocity_set(fedd_ctx* c, const double* u_rep) {
     return 0;
 }
 
-// aux[slot_out] <- scale * (N | W | N + W)(u) + aux[slot_add]: NavierStokes::reAssemble (NavierStokes_def.hpp:282-321) in one pass
-int assemble_advection(fedd_ctx* c, int kind, double scale, int slot_add, int slot_out) {
-    FEDD_CHECK(c->nranks == 1, "fedd_assemble_advection: one rank only for now");
-    FEDD_CHECK(c->have_vel, "fedd_assemble_advection: call fedd_velocity_set first");
+// what FSI::w_rep_ holds (FSI_def.hpp:445-464), in a buffer of its own beside d_vel; NULL clears
+int mesh_velocity_set(fedd_ctx* c, const double* w_rep) {
+    FEDD_CHECK(c->nranks == 1, "fedd_mesh_velocity_set: one rank only (a context with %d ranks was given)", c->nranks);
+    if (!w_rep) {
+        c->have_mvel = false;
+        return 0;
+    }
+    std::vector<double> w;
+    field_to_columns(c, w_rep, w);
+    FEDD_TRY(c->d_mvel.ensure(w.size()));
+    FEDD_HIP(hipMemcpyAsync(c->d_mvel.p, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    FEDD_HIP(hipStreamSynchronize(c->stream));  // `w` is a local
+    c->have_mvel = true;
+    return 0;
+}
+
+// w = (d_new - d_old) * (1.0 / dt): w_rep_->update(-1, old, 1); w_rep_->scale(1.0 / dt) (FSI_def.hpp:460-462), the arithmetic on
+// the device.  Around it the host permutes both arrays to the column-local numbering and copies them up (pageable, one
+// synchronise), like fedd_velocity_set: a call made once per time step, whose cost is that host side, not the kernel.
+int mesh_velocity_diff(fedd_ctx* c, const double* d_new_rep, const double* d_old_rep, double dt) {
+    FEDD_CHECK(c->nranks == 1, "fedd_mesh_velocity_diff: one rank only (a context with %d ranks was given)", c->nranks);
+    const double rdt = 1.0 / dt;
+    std::vector<double> both, old;
+    field_to_columns(c, d_new_rep, both);
+    field_to_columns(c, d_old_rep, old);
+    const size_t n = both.size();
+    both.insert(both.end(), old.begin(), old.end());
+    FEDD_TRY(c->d_mvel.ensure(n));
+    FEDD_TRY(c->d_dtmp0.ensure(2 * n));
+    FEDD_HIP(hipMemcpyAsync(c->d_dtmp0.p, both.data(), 2 * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (n > 0) {
+        const int nwg = (int)std::min<int64_t>(((int64_t)n + 255) / 256, 256 * 8);
+        hipLaunchKernelGGL(k_mesh_velocity_diff, dim3((unsigned)nwg), dim3(256), 0, c->stream, (const double*)c->d_dtmp0.p,
+                           (const double*)(c->d_dtmp0.p + n), (int64_t)n, rdt, c->d_mvel.p);
+    }
+    FEDD_HIP(hipStreamSynchronize(c->stream));  // `both` is a local
+    FEDD_HIP(hipGetLastError());
+    c->have_mvel = true;
+    return 0;
+}
+
+int mesh_velocity_get(fedd_ctx* c, double* w_rep) {
+    FEDD_CHECK(c->nranks == 1, "fedd_mesh_velocity_get: one rank only (a context with %d ranks was given)", c->nranks);
+    FEDD_CHECK(c->have_mvel, "fedd_mesh_velocity_get: no mesh velocity (fedd_mesh_velocity_set or fedd_mesh_velocity_diff first)");
+    const int dim = c->dim;
+    std::vector<double> w((size_t)c->n_node * dim);
+    FEDD_HIP(hipStreamSynchronize(c->stream));
+    FEDD_HIP(hipMemcpy(w.data(), c->d_mvel.p, w.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const size_t n_rep = c->h_col_of_rep.size();
+    for (size_t i = 0; i < n_rep; ++i)
+        for (int d = 0; d < dim; ++d) w_rep[i * dim + d] = w[(size_t)c->h_col_of_rep[i] * dim + d];
+    return 0;
+}
+
+// aux[slot_out] <- scale * E + aux[slot_add] on the FULL velocity pattern; ale = false: E = (N | W | N + W)(u), kind a
+// fedd_advection; ale = true: E = (P(w) | N(u - w) - P(w) | N(u - w) + W(u) - P(w)), kind a fedd_advection_ale.  The one writer
+// of these slots: structures, slot rules and the record of the write (value_id) are the same for both entries.
+static int advection_into_slot(fedd_ctx* c, const char* who, bool ale, int kind, double scale, int slot_add, int slot_out) {
     const int dim = c->dim, nen = c->nen;
     if (!c->have_adj) {
         ScopedTimer t(c, FEDD_T_SYMBOLIC);
@@ -1573,13 +1710,13 @@ int assemble_advection(fedd_ctx* c, int kind, double scale, int slot_add, int sl
     const int64_t n_rows = c->n_own * dim, nnz = c->adv_node_nnz * dim * dim;
     const DevCsr* add = slot_add >= 0 ? &c->aux[slot_add] : nullptr;
     if (add) {
-        FEDD_CHECK(add->valid, "fedd_assemble_advection: slot %d is empty", slot_add);
+        FEDD_CHECK(add->valid, "%s: slot %d is empty", who, slot_add);
         // stored from a fedd_pattern_build pattern of THIS mesh (or written here): its entries then sit where the closed form says
         const bool tagged = add->mesh_id == c->mesh_id && add->dofs == dim &&
                             (add->block_mode == FEDD_BLOCK_DIAG || add->block_mode == FEDD_BLOCK_FULL);
         const int64_t want = add->block_mode == FEDD_BLOCK_FULL ? nnz : c->adv_node_nnz * dim;
         FEDD_CHECK(tagged && add->n_rows == n_rows && add->n_cols == c->n_node * dim && add->nnz == want,
-                   "fedd_assemble_advection: slot %d does not hold a DIAG or FULL velocity matrix of this mesh", slot_add);
+                   "%s: slot %d does not hold a DIAG or FULL velocity matrix of this mesh", who, slot_add);
     }
     DevCsr& out = c->aux[slot_out];
     if (!(out.valid && out.pattern_id != 0 && out.pattern_id == c->adv_pattern_id[slot_out])) {
@@ -1596,13 +1733,36 @@ int assemble_advection(fedd_ctx* c, int kind, double scale, int slot_add, int sl
     out.dofs = dim;
     out.block_mode = FEDD_BLOCK_FULL;
     out.mesh_id = c->mesh_id;
-    if (dim == 2 && nen == 3) FEDD_TRY((advection_kind<2, 3>(c, kind, scale, add, out)));
-    else if (dim == 2 && nen == 6) FEDD_TRY((advection_kind<2, 6>(c, kind, scale, add, out)));
-    else if (dim == 3 && nen == 4) FEDD_TRY((advection_kind<3, 4>(c, kind, scale, add, out)));
-    else FEDD_TRY((advection_kind<3, 10>(c, kind, scale, add, out)));
+    if (ale) {
+        if (dim == 2 && nen == 3) FEDD_TRY((advection_ale_kind<2, 3>(c, kind, scale, add, out)));
+        else if (dim == 2 && nen == 6) FEDD_TRY((advection_ale_kind<2, 6>(c, kind, scale, add, out)));
+        else if (dim == 3 && nen == 4) FEDD_TRY((advection_ale_kind<3, 4>(c, kind, scale, add, out)));
+        else FEDD_TRY((advection_ale_kind<3, 10>(c, kind, scale, add, out)));
+    } else {
+        if (dim == 2 && nen == 3) FEDD_TRY((advection_kind<2, 3>(c, kind, scale, add, out)));
+        else if (dim == 2 && nen == 6) FEDD_TRY((advection_kind<2, 6>(c, kind, scale, add, out)));
+        else if (dim == 3 && nen == 4) FEDD_TRY((advection_kind<3, 4>(c, kind, scale, add, out)));
+        else FEDD_TRY((advection_kind<3, 10>(c, kind, scale, add, out)));
+    }
     out.valid = true;
     out.value_id = ++c->value_counter;
     return 0;
+}
+
+// aux[slot_out] <- scale * (N | W | N + W)(u) + aux[slot_add]: NavierStokes::reAssemble (NavierStokes_def.hpp:282-321) in one pass
+int assemble_advection(fedd_ctx* c, int kind, double scale, int slot_add, int slot_out) {
+    FEDD_CHECK(c->nranks == 1, "fedd_assemble_advection: one rank only for now");
+    FEDD_CHECK(c->have_vel, "fedd_assemble_advection: call fedd_velocity_set first");
+    return advection_into_slot(c, "fedd_assemble_advection", false, kind, scale, slot_add, slot_out);
+}
+
+// ... and on a moving mesh: NavierStokes::reAssembleFSI (NavierStokes_def.hpp:245-278) with the P of FSI_def.hpp:497-503
+int assemble_advection_ale(fedd_ctx* c, int kind, double scale, int slot_add, int slot_out) {
+    FEDD_CHECK(c->nranks == 1, "fedd_assemble_advection_ale: one rank only (a context with %d ranks was given)", c->nranks);
+    FEDD_CHECK(kind == FEDD_ALE_P || c->have_vel, "fedd_assemble_advection_ale: no velocity: call fedd_velocity_set first");
+    FEDD_CHECK(c->have_mvel,
+               "fedd_assemble_advection_ale: no mesh velocity: call fedd_mesh_velocity_set or fedd_mesh_velocity_diff first");
+    return advection_into_slot(c, "fedd_assemble_advection_ale", true, kind, scale, slot_add, slot_out);
 }
 
 int assemble_matrix(fedd_ctx* c, int form, const double* params, const double* coeff_q, int64_t n_coeff) {

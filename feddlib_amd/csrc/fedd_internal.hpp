@@ -310,6 +310,8 @@ struct fedd_ctx {
     std::vector<int32_t> h_col_of_rep;          // [n_rep] column-local node id of every repeated node (fedd_mesh_set)
     fedd::DevBuf<double> d_vel;                 // [n_node * dim] velocity at the nodes, column-local numbering (fedd_velocity_set)
     bool have_vel = false;
+    fedd::DevBuf<double> d_mvel;                // [n_node * dim] mesh velocity w at the nodes, same numbering (fedd_mesh_velocity_set / _diff)
+    bool have_mvel = false;
     int adv_state = 0;                          // per-mesh structures below: 0 = not built, 1 = ready
     int64_t adv_node_nnz = 0;                   // nonzeros of the node-level pattern
     int adv_max_nn = 0;                         // its longest row
@@ -684,6 +686,10 @@ int apply_dirichlet_nodes(fedd_ctx* c, int64_t n, const int32_t* nodes, const in
 int apply_dirichlet_rows(fedd_ctx* c, int64_t n, const int32_t* rows, const double* values);
 int assemble_div(fedd_ctx* c, int64_t n_pressure_nodes, int slot_b, int slot_bt);
 int velocity_set(fedd_ctx* c, const double* u_rep);
+int mesh_velocity_set(fedd_ctx* c, const double* w_rep);
+int mesh_velocity_diff(fedd_ctx* c, const double* d_new_rep, const double* d_old_rep, double dt);
+int mesh_velocity_get(fedd_ctx* c, double* w_rep);
+int assemble_advection_ale(fedd_ctx* c, int kind, double scale, int slot_add, int slot_out);
 int assemble_advection(fedd_ctx* c, int kind, double scale, int slot_add, int slot_out);
 // k_p2_lists on a pattern of the caller's (rows of the first dof of every owned node; full: FULL blocks, else scalar / DIAG):
 // soff [node-level nnz + 2], src [adjacency entries * nen + 2]; `who` names the caller in the error text

@@ -63,6 +63,7 @@ inline void feddCheck(int rc, const char* what) {
 struct DeviceContext {
     fedd_ctx* ctx = nullptr;
     long generation = 0;      // bumped by every assembly into the context
+    long aleSerial = 0;       // number of the last P(w) that FE::assemblyAdditionalConvection built here (0: none)
     Teuchos::RCP<const Teuchos::Comm<int> > comm;
     explicit DeviceContext(int device) { feddCheck(fedd_ctx_create(&ctx, device, nullptr, 0, 1), "fedd_ctx_create"); }
     // One context per rank of the communicator (the reference: one MPI rank per subdomain block).  Ranks = processes:
@@ -249,7 +250,12 @@ public:
         TEUCHOS_TEST_FOR_EXCEPTION(dev_.is_null(), std::runtime_error, "Matrix::scale: no assembled data");
         feddCheck(fedd_matrix_scale(dev_->ctx, slot_, alpha), "fedd_matrix_scale");
         hostValid_ = false;
+        aleScale_ *= alpha;
     }
+    // provenance of a P(w) from FE::assemblyAdditionalConvection: which one of its context it is and what it was scaled by since
+    void markAdditionalConvection(long serial) { aleSerial_ = serial; aleScale_ = 1.; }
+    long additionalConvectionSerial() const { return aleSerial_; }
+    SC additionalConvectionScale() const { return aleScale_; }
     void fillComplete(MapConstPtr_Type, MapConstPtr_Type) { filled_ = true; }
     bool isResident() const { return !dev_.is_null() && (slot_ >= 0 || gen_ == dev_->generation); }
     DeviceContextPtr device() const { return dev_; }
@@ -295,7 +301,8 @@ private:
     }
     MapConstPtr_Type map_;
     DeviceContextPtr dev_;
-    long gen_ = -1;
+    long gen_ = -1, aleSerial_ = 0;
+    SC aleScale_ = 1.;
     int dofs_ = 1, slot_ = -1;
     bool filled_ = false, hostValid_ = false;
     std::vector<int64_t> rowptr_, colGid_;
@@ -821,6 +828,25 @@ public:
         feddCheck(fedd_assemble_stress(ctx, one ? nullptr : cq.data(), (int64_t)cq.size()), "fedd_assemble_stress");
         dom->device()->generation++;
         A->bind(dom->device(), dim);
+        if (!callFillComplete) A->resumeFill();
+    }
+    // FE::assemblyAdditionalConvection (FE_def.hpp:3044-3255): P(w) for the mesh velocity w on the repeated vector-field map.  w is
+    // uploaded (fedd_mesh_velocity_set), FEDD_ALE_P runs into slot 3 -- the slot of the stabilisation block C, which a P2 / P1
+    // problem leaves free; P1 velocities are refused for that reason -- and the matrix returned is bound to it, with the positive
+    // sign of the reference.  The matrix remembers that it is the last P of its context (NavierStokes::reAssembleFSI checks).
+    void assemblyAdditionalConvection(int dim, std::string FEType, MatrixPtr_Type& A, MultiVectorPtr_Type w, bool callFillComplete = true) {
+        TEUCHOS_TEST_FOR_EXCEPTION(FEType == "P0", std::logic_error, "Not implemented for P0");
+        TEUCHOS_TEST_FOR_EXCEPTION(FEType != "P2", std::logic_error,
+                                   "assemblyAdditionalConvection: built for P2 velocities (P lives in slot 3, which holds C for P1 / P1)");
+        TEUCHOS_TEST_FOR_EXCEPTION(A.is_null() || w.is_null(), std::runtime_error, "Matrix or mesh velocity is null.");
+        auto dom = domainVec_.at(checkFE(dim, FEType));
+        TEUCHOS_TEST_FOR_EXCEPTION(w->raw(0).size() != (size_t)dom->getMapRepeated()->getNodeNumElements() * dim, std::logic_error,
+                                   "assemblyAdditionalConvection: w does not live on the repeated vector-field map of the domain");
+        auto dev = dom->device();
+        feddCheck(fedd_mesh_velocity_set(dev->ctx, w->raw(0).data()), "fedd_mesh_velocity_set");
+        feddCheck(fedd_assemble_advection_ale(dev->ctx, FEDD_ALE_P, 1., -1, 3), "fedd_assemble_advection_ale");
+        A->bindSlot(dev, 3);
+        A->markAdditionalConvection(++dev->aleSerial);
         if (!callFillComplete) A->resumeFill();
     }
     // FE::assemblyDivAndDivT (FE_def.hpp:1932-2057): velocity = FEType1 on the first domain, pressure = P1 on the vertices,
@@ -2044,19 +2070,24 @@ public:
         const double density = this->parameterList_->sublist("Parameter").get("Density", 1.);
         auto domV = this->getDomain(0);
         auto dev = domV->device();
+        // after a residual with mesh velocity (calculateNonLinResidualVecWithMeshVelo) the Newton matrix is that of the ALE block,
+        // FSI_def.hpp:533-541; a "FixedPoint" call is the fixed-mesh one and needs clearMeshVelocity() first
+        TEUCHOS_TEST_FOR_EXCEPTION(aleActive_ && type == "FixedPoint", std::logic_error,
+                                   "reAssemble(\"FixedPoint\") with a mesh velocity in force: what is built is reAssembleFSI(\"FixedPoint\", u_minus_w, P) "
+                                   "for the ALE block, or clearMeshVelocity() and then the fixed-mesh block");
         if (type == "FixedPoint") {     // u_rep_->importFromVector(u): the "Newton" call that follows keeps this velocity
-            auto mapRep = domV->getMapRepeated();
-            auto mapUni = domV->getMapUnique();
-            const auto& u = this->solution_->getBlock(0)->raw();
-            const int dim = this->dim_;
-            u_rep_.assign((size_t)mapRep->getNodeNumElements() * dim, 0.);
-            for (LO i = 0; i < mapRep->getNodeNumElements(); ++i) {
-                const LO k = mapUni->getLocalElement(mapRep->getGlobalElement(i));
-                for (int d = 0; d < dim; ++d) u_rep_[(size_t)i * dim + d] = u[(size_t)k * dim + d];
-            }
+            importVelocity();
             feddCheck(fedd_velocity_set(dev->ctx, u_rep_.data()), "fedd_velocity_set");
         }
-        feddCheck(fedd_assemble_advection(dev->ctx, type == "Newton" ? FEDD_ADV_NEWTON : FEDD_ADV_N, density, baseSlot_, 4), "fedd_assemble_advection");
+        if (aleActive_) feddCheck(fedd_assemble_advection_ale(dev->ctx, FEDD_ALE_NEWTON, density, baseSlot_, 4), "fedd_assemble_advection_ale");
+        else feddCheck(fedd_assemble_advection(dev->ctx, type == "Newton" ? FEDD_ADV_NEWTON : FEDD_ADV_N, density, baseSlot_, 4), "fedd_assemble_advection");
+        finishVelocityBlock();
+        if (this->verbose_) std::cout << "done -- " << std::endl;
+    }
+    // block (0,0) <- slot 4, merged with the constant blocks (values only after the first time)
+    void finishVelocityBlock() const {
+        auto domV = this->getDomain(0);
+        auto dev = domV->device();
         MatrixPtr_Type ANW(new Matrix_Type(domV->getMapVecFieldUnique(), domV->getDimension() * domV->getApproxEntriesPerRow()));
         ANW->bindSlot(dev, 4);
         ANW->fillComplete(domV->getMapVecFieldUnique(), domV->getMapVecFieldUnique());
@@ -2064,12 +2095,70 @@ public:
         feddCheck(fedd_block_merge(dev->ctx, 4, 2, 1, slotC_), "fedd_block_merge");
         dev->generation++;
         this->system_->setMerged(dev);
+    }
+    // u_rep_->importFromVector(u) (NavierStokes_def.hpp:251, 290)
+    void importVelocity() const {
+        auto domV = this->getDomain(0);
+        auto mapRep = domV->getMapRepeated();
+        auto mapUni = domV->getMapUnique();
+        const auto& u = this->solution_->getBlock(0)->raw();
+        const int dim = this->dim_;
+        u_rep_.assign((size_t)mapRep->getNodeNumElements() * dim, 0.);
+        for (LO i = 0; i < mapRep->getNodeNumElements(); ++i) {
+            const LO k = mapUni->getLocalElement(mapRep->getGlobalElement(i));
+            for (int d = 0; d < dim; ++d) u_rep_[(size_t)i * dim + d] = u[(size_t)k * dim + d];
+        }
+    }
+    // NavierStokes::reAssembleFSI (NavierStokes_def.hpp:245-278): block (0,0) = A + density N(u - w) + P, P = -density P(w) given
+    // by the caller (FSI_def.hpp:497-503).  The device forms u - w and -density P(w) itself from u_rep_ and the mesh velocity in
+    // force (FEDD_ALE_FIXEDPOINT, scale = density, one pass), so the two arguments are CHECKED, not used: P must be the matrix
+    // FE::assemblyAdditionalConvection returned last on this context, scaled by exactly -density, and u_minus_w must equal
+    // u_rep_ - w entry by entry.
+    void reAssembleFSI(std::string type, Teuchos::RCP<MultiVector<SC, LO, GO, NO> > u_minus_w, MatrixPtr_Type P) const {
+        if (this->verbose_) std::cout << "-- Reassembly Navier-Stokes (FSI) ... " << std::flush;
+        TEUCHOS_TEST_FOR_EXCEPTION(type != "FixedPoint", std::logic_error, "Newton method not implemented in reAssembleFSI.");
+        const double density = this->parameterList_->sublist("Parameter").get("Density", 1.);
+        auto domV = this->getDomain(0);
+        auto dev = domV->device();
+        TEUCHOS_TEST_FOR_EXCEPTION(P.is_null() || u_minus_w.is_null(), std::runtime_error, "reAssembleFSI: P or u_minus_w is null.");
+        TEUCHOS_TEST_FOR_EXCEPTION(P->device().is_null() || P->device()->ctx != dev->ctx || P->additionalConvectionSerial() == 0 || P->additionalConvectionSerial() != dev->aleSerial,
+                                   std::logic_error, "reAssembleFSI: P is not the matrix FE::assemblyAdditionalConvection returned last on this domain; what is built is "
+                                   "A + density N(u - w) - density P(w) for the mesh velocity in force, formed on the device");
+        TEUCHOS_TEST_FOR_EXCEPTION(P->additionalConvectionScale() != -density, std::logic_error,
+                                   "reAssembleFSI: P is scaled by " << P->additionalConvectionScale() << " and must be scaled by exactly -density = " << -density
+                                   << " (P->scale(density); P->scale(-1.0), FSI_def.hpp:501-503); what is built is A + density N(u - w) - density P(w)");
+        importVelocity();
+        std::vector<double> w(u_rep_.size());
+        feddCheck(fedd_mesh_velocity_get(dev->ctx, w.data()), "fedd_mesh_velocity_get");
+        const auto& c = u_minus_w->raw(0);
+        TEUCHOS_TEST_FOR_EXCEPTION(c.size() != u_rep_.size(), std::logic_error, "reAssembleFSI: u_minus_w does not live on the repeated vector-field map");
+        for (size_t i = 0; i < c.size(); ++i)
+            TEUCHOS_TEST_FOR_EXCEPTION(c[i] != u_rep_[i] - w[i], std::logic_error,
+                                       "reAssembleFSI: u_minus_w is not u - w (entry " << i << ": " << c[i] << " against " << u_rep_[i] - w[i]
+                                       << "); what is built convects by the solution's velocity minus the mesh velocity in force");
+        feddCheck(fedd_velocity_set(dev->ctx, u_rep_.data()), "fedd_velocity_set");
+        feddCheck(fedd_assemble_advection_ale(dev->ctx, FEDD_ALE_FIXEDPOINT, density, baseSlot_, 4), "fedd_assemble_advection_ale");
+        aleActive_ = true;
+        finishVelocityBlock();
         if (this->verbose_) std::cout << "done -- " << std::endl;
+    }
+    // NavierStokes_def.hpp:754-760, then the residual of calculateNonLinResidualVec
+    void calculateNonLinResidualVecWithMeshVelo(std::string type, double time, Teuchos::RCP<MultiVector<SC, LO, GO, NO> > u_minus_w, MatrixPtr_Type P) const {
+        reAssembleFSI("FixedPoint", u_minus_w, P);
+        residualOfTheSystem(type, time);
+    }
+    // facade only: back to the fixed-mesh path
+    void clearMeshVelocity() const {
+        feddCheck(fedd_mesh_velocity_set(this->getDomain(0)->device()->ctx, nullptr), "fedd_mesh_velocity_set");
+        aleActive_ = false;
     }
     // NavierStokes_def.hpp:723-751: residual = system(u) x - rhs ("standard") or rhs - system(u) x ("reverse"), the Dirichlet
     // rows x - g / g - x
     void calculateNonLinResidualVec(std::string type = "standard", double time = 0.) const override {
         reAssemble("FixedPoint");
+        residualOfTheSystem(type, time);
+    }
+    void residualOfTheSystem(std::string type, double time) const {
         auto dev = this->getDomain(0)->device();
         std::vector<double> x, y;
         for (UN b = 0; b < this->solution_->size(); ++b)
@@ -2096,6 +2185,7 @@ private:
     mutable MatrixPtr_Type A_;
     mutable std::vector<double> u_rep_;
     mutable int slotC_ = -1, baseSlot_ = 0;
+    mutable bool aleActive_ = false;   // the last residual was one with mesh velocity: reAssemble("Newton") builds the ALE Newton block
 };
 
 // NonLinElasticity (feddlib/problems/specific/NonLinElasticity_def.hpp:16-120, 251-271): one vector block; every

@@ -49,6 +49,14 @@ enum fedd_advection {
     FEDD_ADV_NEWTON = 2        /* N + W, both from one pass over the elements -- the Newton linearisation                   */
 };
 
+/* ---- what fedd_assemble_advection_ale builds from that velocity u and the mesh velocity w of fedd_mesh_velocity_* ---- */
+enum fedd_advection_ale {
+    FEDD_ALE_P          = 0,   /* FE::assemblyAdditionalConvection  FE_def.hpp:3044-3255: p_ij = |det B| sum_q w_q (div w_h) phi_i phi_j
+                                  on the dim pairs (dim*i+d, dim*j+d), sign as the reference returns it; needs no u          */
+    FEDD_ALE_FIXEDPOINT = 1,   /* N(u - w) - P(w): the velocity block of NavierStokes::reAssembleFSI                         */
+    FEDD_ALE_NEWTON     = 2    /* N(u - w) + W(u) - P(w): W sees u, not u - w                                                */
+};
+
 /* ---- how the dofs of a node couple in the CSR pattern ---- */
 enum fedd_block_mode {
     FEDD_BLOCK_SCALAR = 0,     /* dofs_per_node == 1                                                  */
@@ -308,7 +316,9 @@ int fedd_mesh_set_rows(fedd_ctx* ctx, int dim, int nen, int64_t n_elem, const in
  *   - the node and dof patterns: the system pattern (the next fedd_pattern_build repeats, fedd_pattern_reuse_info), the patterns
  *     of the stored slots, the node-level pattern of the advection matrices;
  *   - the gather lists (P2 row sums, advection, the FULL-pattern lists of the hyperelastic tangent and the stress form);
- *   - the advection / stress / hyperelastic scratch and reference tables, the velocity of fedd_velocity_set;
+ *   - the advection / stress / hyperelastic scratch and reference tables, the velocity of fedd_velocity_set and the mesh
+ *     velocity of fedd_mesh_velocity_set / fedd_mesh_velocity_diff (section "ALE convection"; nodal values, they read no
+ *     coordinate);
  *   - the surface set of fedd_surface_set;
  *   - the Dirichlet flag tables (boundary flags of the nodes);
  *   - the halo plan;
@@ -327,7 +337,7 @@ int fedd_mesh_set_rows(fedd_ctx* ctx, int dim, int nen, int64_t n_elem, const in
  * the Schwarz inverses and fingerprints, the CG setup.
  *
  * Errors: a host-only context ("needs a GPU context"), no mesh, more than one rank.
- * Left out: mesh velocity and ALE convection, interface distances (the scaled-Laplace extension), more than one rank.
+ * Left out: interface distances (the scaled-Laplace extension), more than one rank.
  *
  * fedd_mesh_move_info: moves committed since the last fedd_mesh_set*, moves committed since the context was made, the ratio
  * above (0, 0, 1.0 on a fresh context).  Needs no device; outputs may be NULL.
@@ -596,6 +606,61 @@ int fedd_multistep_info(fedd_ctx* ctx, int* order, int* count);
  * ---------------------------------------------------------------------------------------------- */
 int fedd_velocity_set(fedd_ctx* ctx, const double* u_rep);
 int fedd_assemble_advection(fedd_ctx* ctx, int kind, double scale, int slot_add, int slot_out);
+
+/* ------------------------------------------------------------------------------------------------
+ * ALE convection (one rank, like the advection path it extends): the velocity block of the fluid on a moving mesh,
+ * A + rho N(u - w) - rho P(w) and in a Newton step + rho W(u) (feddlib/problems/specific/FSI_def.hpp:445-464, 497-503, 533-541;
+ * NavierStokes::reAssembleFSI, NavierStokes_def.hpp:245-278, 754-760), on the coordinates fedd_mesh_move put in force.
+ *   fedd_mesh_velocity_set   w_rep[n_rep * dim], node-wise interleaved (dim * node + d) on the repeated map of fedd_mesh_set:
+ *                            what FSI::meshVelocity / w_rep_ holds.  It lives in a device buffer of its own beside the one of
+ *                            fedd_velocity_set, with the same lifetime: kept by fedd_mesh_move, released by fedd_mesh_set*.
+ *                            w_rep = NULL clears it (the next fedd_assemble_advection_ale is an error).
+ *   fedd_mesh_velocity_diff  w = (d_new - d_old) * (1.0 / dt), the arithmetic in one device kernel after the host has permuted both
+ *                            arrays to the mesh's numbering and copied them up (the cost of the call, made once per time
+ *                            step, is that host side, as for fedd_velocity_set), NORMATIVE in this order: one subtraction
+ *                            per entry, one multiplication by the reciprocal formed in double on the host -- what
+ *                            w_rep_->update(-1, old, 1); w_rep_->scale(1.0 / dt) does (FSI_def.hpp:460-462).  d_new_rep,
+ *                            d_old_rep: displacements on the repeated map, like fedd_mesh_move's.  Errors: dt <= 0, a dt that
+ *                            is not finite, a null array.
+ *   fedd_mesh_velocity_get   w_rep[n_rep * dim] back.  Errors: no mesh velocity, more than one rank.
+ *   fedd_assemble_advection_ale
+ *                            slot_out <- scale * E + M[slot_add] on the FULL velocity pattern, u from fedd_velocity_set, w from
+ *                            the calls above:
+ *                              FEDD_ALE_P           E = P(w), FE::assemblyAdditionalConvection (FE_def.hpp:3044-3255): entry
+ *                                                   (dim*i+d, dim*j+d) = |det B| sum_q w_q (div w_h)(x_q) phi_i(x_q) phi_j(x_q),
+ *                                                   div w_h(x_q) = sum_i sum_d w[i][d] (grad phi_i B^-1)_d; positive sign, as
+ *                                                   the reference returns it; off-diagonal component pairs are structural
+ *                                                   zeros of the FULL pattern
+ *                              FEDD_ALE_FIXEDPOINT  E = N(u - w) - P(w)
+ *                              FEDD_ALE_NEWTON      E = N(u - w) + W(u) - P(w); W takes u, not u - w (FSI_def.hpp:540 ->
+ *                                                   NavierStokes::reAssemble("Newton") on u_rep_)
+ *                            With scale = density the fused kinds are the reference's A + (-rho) P + rho N [+ rho W]
+ *                            (FSI_def.hpp:497-503, NavierStokes_def.hpp:262-272).  The pattern, gather lists, slot rules (slot_add
+ *                            < 0, DIAG or FULL, never slot_out) and error texts are those of fedd_assemble_advection, and so are
+ *                            the structures: a first call on a mesh may build them (FEDD_T_SYMBOLIC), later calls -- also after
+ *                            fedd_mesh_move -- move values only (FEDD_T_ASSEMBLE).  The write of slot_out is recorded like
+ *                            every other slot write: fedd_matrix_combine_current answers 0 for a combine that read the slot.
+ *                            Quadrature: N as in fedd_assemble_advection; P by determineDegree(dim, FE, FE, Std, Std,
+ *                            determineDegree(dim, FE, Grad)) (FE_def.hpp:3064-3065).  The inner call returns 1 for P1 as well as
+ *                            for P2 (a degree 0 is raised to 1, :5540-5541), so the rule is degree 3 for P1 and 5 for P2: the
+ *                            rule of W, not the one of N (they coincide for P2 only).  No third table is staged.
+ *                            Operation order, NORMATIVE: per element c = u - w at its nodes (one subtraction); beta from c and
+ *                            grad u_h from u as in fedd_assemble_advection; per point q of the rule of W,
+ *                            div = sum_d sum_r (sum_i w[i][d] dphi_i,r) Binv[r][d] (i, r, d ascending), pw_q = w_q * div; per node
+ *                            pair p_ij = |det B| * sum_q (phi_i phi_j) pw_q (q ascending).  N and W keep their setZeros threshold
+ *                            ("asm_zero_eps") per element value; P has none in the reference and gets none; the threshold is
+ *                            applied to n_ij (and the W block) BEFORE p_ij is subtracted.  With w = 0 the fused kinds return
+ *                            the bits of FEDD_ADV_N / FEDD_ADV_NEWTON and FEDD_ALE_P is zero.  No atomics: two calls agree bit
+ *                            for bit.  Memory: the scratch of fedd_assemble_advection.
+ *                            Errors: a host-only context ("needs a GPU context"), more than one rank, no velocity (except
+ *                            FEDD_ALE_P, which needs none), no mesh velocity, unknown kind, every slot error of
+ *                            fedd_assemble_advection.
+ * Left out: the FSI problem class, geometry-implicit coupling, shape derivatives, more than one rank.
+ * ---------------------------------------------------------------------------------------------- */
+int fedd_mesh_velocity_set(fedd_ctx* ctx, const double* w_rep);               /* NULL clears */
+int fedd_mesh_velocity_diff(fedd_ctx* ctx, const double* d_new_rep, const double* d_old_rep, double dt);
+int fedd_mesh_velocity_get(fedd_ctx* ctx, double* w_rep);
+int fedd_assemble_advection_ale(fedd_ctx* ctx, int kind, double scale, int slot_add, int slot_out);
 
 /* ------------------------------------------------------------------------------------------------
  * nonlinear elasticity (one rank, like the advection path): tangent and internal forces of a hyperelastic material for the
