@@ -2,6 +2,8 @@
 // (feddlib/problems/tests/geometry/main.cpp:436-700) on ONE domain, written against the FEDD:: operator surface with the
 // reference's three XML parameter files:
 //   Domain::buildMesh -> BCBuilder::addBC (zero Dirichlet on the outer flags 1 and 2, a prescribed displacement on "Moving Flag")
+//   -> with --interface-flag=N (may repeat): Domain::identifyInterfaceParallelAndDistance(domain, {N, ...}) on the driver's own
+//      domain, which gives it the distances the default model "Laplace" of Geometry needs (without the option nothing changes)
 //   -> Geometry(...) -> initializeProblem -> assemble -> setBoundaries -> solve          (the extension d_f of the displacement)
 //   -> the repeated displacement from the unique solution -> Domain::moveMesh(d_unique, d_repeated)      (main.cpp:683)
 //   -> Laplace(...) on the MOVED domain: assemble -> setBoundaries -> solve.
@@ -11,6 +13,7 @@
 // Output: <out>.d.txt (the extension, by global dof id), <out>.u.txt (the Laplace solution on the moved mesh, by global node
 // id), <out>.xyz.txt (the moved repeated points, read back from the device), and on stdout the iteration counts, n_moves,
 // min_det_ratio and the launches of the symbolic timer before the move and after the move and the assembly that follows it.
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iomanip>
@@ -59,6 +62,7 @@ int main(int argc, char* argv[]) {
     Teuchos::GlobalMPISession mpiSession(&argc, &argv);
     std::string xmlProblemFile = "parametersProblem.xml", xmlPrecFile = "parametersPrec.xml", xmlSolverFile = "parametersSolver.xml";
     std::string outFile = "geometry";
+    std::vector<int> interfaceFlags;        // --interface-flag=N, may repeat
     for (int i = 1; i < argc; ++i) {
         std::string a(argv[i]);
         auto val = [&](const char* key, std::string& dst) {
@@ -67,6 +71,17 @@ int main(int argc, char* argv[]) {
             return false;
         };
         if (val("problemfile", xmlProblemFile) || val("precfile", xmlPrecFile) || val("solverfile", xmlSolverFile) || val("out", outFile)) continue;
+        std::string flagText;
+        if (val("interface-flag", flagText)) {
+            char* end = nullptr;
+            const long f = std::strtol(flagText.c_str(), &end, 10);
+            if (flagText.empty() || *end != '\0') {
+                std::cerr << "--interface-flag wants an integer, got \"" << flagText << "\"" << std::endl;
+                return 2;
+            }
+            interfaceFlags.push_back((int)f);
+            continue;
+        }
         std::cerr << "unknown option " << a << std::endl;
         return 2;
     }
@@ -110,6 +125,15 @@ int main(int argc, char* argv[]) {
         for (int flag = 1; flag <= 3; ++flag) {
             if (flag == movingFlag) bcGeometry->addBC(dim == 2 ? movedBC2D : movedBC3D, flag, 0, domain, "Dirichlet", dim);
             else bcGeometry->addBC(dim == 2 ? zeroBC2D : zeroBC3D, flag, 0, domain, "Dirichlet", dim);
+        }
+
+        // ---- 2b. the interface and the distances to it (the driver has one domain: it is its own "other" side) ----
+        if (!interfaceFlags.empty()) {
+            domain->identifyInterfaceParallelAndDistance(domain, interfaceFlags);
+            int have = 0;
+            int64_t nInterface = 0;
+            feddCheck(fedd_interface_distance_info(ctx, &have, &nInterface, nullptr), "fedd_interface_distance_info");
+            std::cout << "interface nodes " << nInterface << std::endl;
         }
 
         // ---- 3. the extension ----

@@ -11,7 +11,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libfedd_hip.so")
 
-FORM_LAPLACE, FORM_LAPLACE_VEC, FORM_MASS, FORM_MASS_VEC, FORM_LINELAS, FORM_BDSTAB, FORM_STRESS = range(7)
+FORM_LAPLACE, FORM_LAPLACE_VEC, FORM_MASS, FORM_MASS_VEC, FORM_LINELAS, FORM_BDSTAB, FORM_STRESS, FORM_LAPLACE_XDIM = range(8)
 BLOCK_SCALAR, BLOCK_DIAG, BLOCK_FULL = range(3)
 COMBINE_RESTRICTED, COMBINE_AVERAGING, COMBINE_FULL = range(3)
 (T_SYMBOLIC, T_ASSEMBLE, T_RHS, T_DIRICHLET, T_SPMV, T_SCHWARZ_SETUP, T_SCHWARZ_APPLY, T_ORTHO, T_COARSE_SETUP,
@@ -19,7 +19,7 @@ COMBINE_RESTRICTED, COMBINE_AVERAGING, COMBINE_FULL = range(3)
 TIMER_NAMES = ["symbolic", "assemble", "rhs", "dirichlet", "spmv", "schwarz_setup", "schwarz_apply", "ortho",
                "coarse_setup", "coarse_apply", "halo", "allreduce", "spmv_setup", "gs_dot", "gs_update", "gs_fused",
                "full_park_mfma", "full_park", "full_gather", "cg_pq", "cg_xr", "cg_rz", "cg_p", "newmark_state", "block_apply", "multistep_state", "blockprec_bt",
-               "newton_residual", "newton_update", "mesh_move", "move_check"]
+               "newton_residual", "newton_update", "mesh_move", "move_check", "interface_distance"]
 COARSE_Q1 = 1
 COARSE_GDSW = 2
 COARSE_RGDSW = 3
@@ -95,6 +95,12 @@ SIGNATURES = {
     "fedd_mesh_velocity_set": [C.c_void_p, _f64p],
     "fedd_mesh_velocity_diff": [C.c_void_p, _f64p, _f64p, C.c_double],
     "fedd_mesh_velocity_get": [C.c_void_p, _f64p],
+    "fedd_interface_distance": [C.c_void_p, C.c_int, _i32p, _i64p],
+    "fedd_interface_distance_points": [C.c_void_p, C.c_int64, _f64p],
+    "fedd_interface_distance_set": [C.c_void_p, _f64p],
+    "fedd_interface_distance_get": [C.c_void_p, _f64p],
+    "fedd_interface_distance_info": [C.c_void_p, _ip, _i64p, _ip],
+    "fedd_laplace_scale_get": [C.c_void_p, _f64p],
     "fedd_assemble_advection_ale": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int],
     "fedd_assemble_hyperelastic": [C.c_void_p, C.c_int, _f64p, C.c_int, C.c_int],
     "fedd_hyperelastic_force_get": [C.c_void_p, _f64p],
@@ -548,6 +554,7 @@ class Context:
         self.n_own = gid_uni.shape[0]
         self._dim = dim
         self._n_rep = xyz.shape[0]
+        self._n_elem = conn.shape[0]
 
     def mesh_set_dict(self, m):
         self.mesh_set(m["dim"], m["conn"], m["xyz"], m["gid_rep"], m["gid_uni"], m["flag_uni"],
@@ -681,6 +688,51 @@ class Context:
         n = getattr(self, "_n_rep", 0)
         out = np.zeros((max(n, 1), getattr(self, "_dim", 1)))
         _chk(self._L.fedd_mesh_velocity_get(self._h, _p(out, _f64p)))
+        return out[:n]
+
+    def interface_distance(self, flags):
+        """distances of every repeated node to the nodes whose flag is in `flags`, at the coordinates in force, capped at 1000
+        (fedd_interface_distance); returns the number of interface nodes"""
+        fl = np.ascontiguousarray(np.atleast_1d(flags), dtype=np.int32)
+        n = C.c_int64()
+        _chk(self._L.fedd_interface_distance(self._h, fl.shape[0], _p(fl, _i32p), C.byref(n)))
+        return n.value
+
+    def interface_distance_points(self, pts):
+        """the same against points of the caller's, [n_pts, dim] (fedd_interface_distance_points)"""
+        p = np.ascontiguousarray(pts, dtype=np.float64)
+        dim = getattr(self, "_dim", 1)
+        if p.size % dim:
+            raise FeddError("interface_distance_points: %d coordinates are no multiple of the dimension %d" % (p.size, dim))
+        _chk(self._L.fedd_interface_distance_points(self._h, p.size // dim, _p(p.ravel(), _f64p)))
+
+    def interface_distance_set(self, dist_rep):
+        """distances of the caller's on the repeated map of mesh_set, [n_rep]; None releases them (fedd_interface_distance_set)"""
+        d = None
+        if dist_rep is not None:
+            d = np.ascontiguousarray(dist_rep, dtype=np.float64).ravel()
+            n = getattr(self, "_n_rep", None)
+            if n is not None and d.shape[0] != n:
+                raise FeddError("interface_distance_set: %d distances, the repeated map has %d nodes" % (d.shape[0], n))
+        _chk(self._L.fedd_interface_distance_set(self._h, _p(d, _f64p)))
+
+    def interface_distances(self):
+        """the distances held, [n_rep] on the repeated map of mesh_set (fedd_interface_distance_get)"""
+        n = getattr(self, "_n_rep", 0)
+        out = np.zeros(max(n, 1))
+        _chk(self._L.fedd_interface_distance_get(self._h, _p(out, _f64p)))
+        return out[:n]
+
+    def interface_distance_info(self):
+        h, n, t = C.c_int(), C.c_int64(), C.c_int()
+        _chk(self._L.fedd_interface_distance_info(self._h, C.byref(h), C.byref(n), C.byref(t)))
+        return {"have": bool(h.value), "n_interface": n.value, "tile_points": t.value}
+
+    def laplace_scale(self):
+        """the coefficient per element of the last FORM_LAPLACE_XDIM assembly, [n_elem] (fedd_laplace_scale_get)"""
+        n = getattr(self, "_n_elem", 0)
+        out = np.zeros(max(n, 1))
+        _chk(self._L.fedd_laplace_scale_get(self._h, _p(out, _f64p)))
         return out[:n]
 
     def assemble_advection_ale(self, kind, scale=1.0, slot_add=-1, slot_out=4):

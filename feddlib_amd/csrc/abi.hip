@@ -188,6 +188,10 @@ static int mesh_set_impl(fedd_ctx* c, int dim, int nen, int64_t n_elem, const in
     c->have_vel = false;
     c->have_mvel = false;   // ... and so did the mesh velocity, whose buffer goes with them
     c->d_mvel.release();
+    c->have_idist = c->have_lscale = false;   // ... and the interface distances and the coefficients made from them
+    c->n_interface = 0;
+    c->d_idist.release();
+    c->d_lscale.release();
     c->hy_lists = c->have_hy_f = false;   // ... and the lists and the force vector of the hyperelastic path
     c->nw_active = c->nw_have_src = c->nw_f_fresh = false;   // ... and the Newton state (newton.hip)
     c->nw_n = -1;
@@ -344,6 +348,53 @@ extern "C" int fedd_mesh_coords_get(fedd_ctx* c, double* xyz_rep) {
     return mesh_coords_get(c, xyz_rep);
 }
 
+extern "C" int fedd_interface_distance(fedd_ctx* c, int n_flags, const int32_t* flags, int64_t* n_interface) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(c->n_node > 0, "fedd_interface_distance: call fedd_mesh_set first");
+    FEDD_CHECK(n_flags >= 0, "fedd_interface_distance: negative number of flags %d", n_flags);
+    FEDD_CHECK(n_flags == 0 || flags, "fedd_interface_distance: null flag list");
+    FEDD_HIP(hipSetDevice(c->device));
+    return interface_distance_flags(c, n_flags, flags, n_interface);
+}
+
+extern "C" int fedd_interface_distance_points(fedd_ctx* c, int64_t n_pts, const double* xyz_pts) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(c->n_node > 0, "fedd_interface_distance_points: call fedd_mesh_set first");
+    FEDD_CHECK(n_pts >= 0, "fedd_interface_distance_points: negative number of points %lld", (long long)n_pts);
+    FEDD_CHECK(n_pts == 0 || xyz_pts, "fedd_interface_distance_points: null point array");
+    FEDD_HIP(hipSetDevice(c->device));
+    return interface_distance_points(c, n_pts, xyz_pts);
+}
+
+extern "C" int fedd_interface_distance_set(fedd_ctx* c, const double* dist_rep) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(c->n_node > 0, "fedd_interface_distance_set: call fedd_mesh_set first");
+    FEDD_HIP(hipSetDevice(c->device));
+    return interface_distance_set(c, dist_rep);
+}
+
+extern "C" int fedd_interface_distance_get(fedd_ctx* c, double* dist_rep) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(dist_rep, "fedd_interface_distance_get: null pointer");
+    FEDD_HIP(hipSetDevice(c->device));
+    return interface_distance_get(c, dist_rep);
+}
+
+extern "C" int fedd_interface_distance_info(fedd_ctx* c, int* have, int64_t* n_interface, int* tile_points) {
+    FEDD_CHECK(c, "fedd_interface_distance_info: null context");
+    if (have) *have = c->have_idist ? 1 : 0;
+    if (n_interface) *n_interface = c->n_interface;
+    if (tile_points) *tile_points = interface_distance_tile();
+    return 0;
+}
+
+extern "C" int fedd_laplace_scale_get(fedd_ctx* c, double* f_elem) {
+    NEED_DEVICE(c);
+    FEDD_CHECK(f_elem, "fedd_laplace_scale_get: null pointer");
+    FEDD_HIP(hipSetDevice(c->device));
+    return laplace_scale_get(c, f_elem);
+}
+
 extern "C" int fedd_pattern_build(fedd_ctx* c, int dofs_per_node, int block_mode, int64_t* nnz_out) {
     NEED_DEVICE(c);
     FEDD_CHECK(c->n_node > 0, "fedd_pattern_build: call fedd_mesh_set first");
@@ -369,6 +420,8 @@ static const char* const NO_ADJACENCY = "this context has not built the node -> 
 
 extern "C" int fedd_assemble(fedd_ctx* c, int form, const double* params) {
     NEED_DEVICE(c);
+    if (form == FEDD_FORM_LAPLACE_XDIM)     // (before the pattern: a context of several ranks is refused whatever it holds)
+        FEDD_CHECK(c->nranks == 1, "fedd_assemble(FEDD_FORM_LAPLACE_XDIM): one rank only (a context with %d ranks was given)", c->nranks);
     FEDD_CHECK(c->have_pattern, "fedd_assemble: call fedd_pattern_build first");
     FEDD_CHECK(c->have_adj, "fedd_assemble: %s", NO_ADJACENCY);
     FEDD_HIP(hipSetDevice(c->device));

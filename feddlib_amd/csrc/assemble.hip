@@ -586,7 +586,10 @@ __global__ void k_dirichlet_nodes(const int32_t* __restrict__ nodes, const int32
 // instead of re-deriving it: the pair kernels alone evaluate every P2 element ten times, 11.4 ms at a 64^3-cell cube against
 // the figure in DESIGN.md section 4 with this kernel) -- in adjacency order, no atomics: bitwise reproducible as before.
 // ---------------------------------------------------------------------------------------------
-template <int DIM, int NEN, int FORM>
+// SCALED (a compile-time switch; F_LAPLACE only): the element carries a coefficient f = a.fscale[e], the scaled vector
+// Laplacian of FE::assemblyLaplaceXDim (FE_def.hpp:2225-2402): val += (f w_k) (grad phi_j . grad phi_i), |det B| last, and no
+// doSetZeros.  The unscaled instantiations keep their code and their bits.
+template <int DIM, int NEN, int FORM, bool SCALED = false>
 __global__ __launch_bounds__(256) void k_elem_matrix(AsmArgs a, int64_t n_elem, double* __restrict__ ke) {
     extern __shared__ double sm[];
     const int nq = a.nq, ntab = nq * (1 + NEN + NEN * DIM + DIM + 1);
@@ -630,7 +633,18 @@ __global__ __launch_bounds__(256) void k_elem_matrix(AsmArgs a, int64_t n_elem, 
             for (int t = lane; t < NEN * NEN; t += 64) {
                 const int i = t / NEN, j = t - i * NEN;
                 double v = 0.0;
-                if constexpr (FORM == F_LAPLACE) {
+                if constexpr (SCALED) {
+                    const double f = a.fscale[e];
+                    for (int q = 0; q < nq; ++q) {
+                        const double* gi = Gs + (q * NEN + i) * DIM;
+                        const double* gj = Gs + (q * NEN + j) * DIM;
+                        double dot = 0.0;
+#pragma unroll
+                        for (int d = 0; d < DIM; ++d) dot += gj[d] * gi[d];
+                        v += (f * s_w[q]) * dot;
+                    }
+                    out[t] = absdet * v;
+                } else if constexpr (FORM == F_LAPLACE) {
                     for (int q = 0; q < nq; ++q) {
                         const double* gi = Gs + (q * NEN + i) * DIM;
                         const double* gj = Gs + (q * NEN + j) * DIM;
@@ -649,14 +663,14 @@ __global__ __launch_bounds__(256) void k_elem_matrix(AsmArgs a, int64_t n_elem, 
 }
 
 // element matrices of the whole mesh into c->d_ke (P2, F_LAPLACE / F_MASS); returns the args with ke set
-template <int DIM, int NEN, int FORM>
+template <int DIM, int NEN, int FORM, bool SCALED = false>
 int launch_elem_matrices(fedd_ctx* c, AsmArgs& a, int ntab) {
     FEDD_TRY(c->d_ke.ensure((size_t)c->n_elem * NEN * NEN));
     const size_t lds = ((size_t)ntab + (ntab & 1) + 4 * (size_t)a.nq * NEN * DIM) * sizeof(double);
     FEDD_CHECK(lds <= 64 * 1024, "element matrices: quadrature tables of %d points do not fit the LDS", a.nq);
     const int64_t nwg = std::min<int64_t>((c->n_elem + 3) / 4, 256 * 8);
     ScopedTimer t(c, FEDD_T_ASSEMBLE);
-    hipLaunchKernelGGL((k_elem_matrix<DIM, NEN, FORM>), dim3((unsigned)nwg), dim3(256), lds, c->stream, a, c->n_elem, c->d_ke.p);
+    hipLaunchKernelGGL((k_elem_matrix<DIM, NEN, FORM, SCALED>), dim3((unsigned)nwg), dim3(256), lds, c->stream, a, c->n_elem, c->d_ke.p);
     t.stop();
     FEDD_HIP(hipGetLastError());
     a.ke = c->d_ke.p;
@@ -1040,10 +1054,39 @@ int launch_stress(fedd_ctx* c, const AsmArgs& a) {
     return 0;
 }
 
+// The scaled vector Laplacian (FEDD_FORM_LAPLACE_XDIM), all four element types on ONE path: the element matrices with the
+// element's coefficient (k_elem_matrix<..., SCALED>, one element per wavefront), the rows summed from them through the
+// node-level gather lists of k_p2_lists (built once per mesh, kept by a move), each value written to the dim diagonal-block
+// slots.  P1 takes this path too, not the tiles: the tile kernel keeps no per-element scalar in its blobs, and one path has
+// one summation order to state and to test (DESIGN.md section 4 "Interface distances" has what it costs).
+template <int DIM, int NEN>
+int launch_laplace_xdim(fedd_ctx* c, AsmArgs a, int ntab) {
+    if (c->n_elem == 0 || c->n_own == 0) {
+        FEDD_HIP(hipMemsetAsync(c->d_val.p, 0, (size_t)c->nnz_ext * sizeof(double), c->stream));
+        return 0;
+    }
+    {
+        ScopedTimer t(c, FEDD_T_ASSEMBLE);
+        // byte model on top of the unscaled pass: four distances per element through the connectivity (shared lines), one
+        // coefficient written and read per element
+        t.bytes((double)c->n_elem * ((DIM + 1) * 4.0 + 16.0) + (double)c->n_node * 8.0);
+        FEDD_TRY(laplace_scale(c, a.p0, a.p1));
+    }
+    a.fscale = c->d_lscale.p;
+    FEDD_TRY((launch_elem_matrices<DIM, NEN, F_LAPLACE, true>(c, a, ntab)));
+    const double keep_ms = c->tl_build_ms;
+    const int rc = launch_p2_gather<NEN>(c);
+    if constexpr (NEN == DIM + 1) c->tl_build_ms = keep_ms;     // (on a P1 mesh that figure is the tile build's)
+    FEDD_CHECK(rc >= 0, "fedd_assemble(FEDD_FORM_LAPLACE_XDIM): the gather lists do not fit this mesh (a node with more than %d "
+                        "incident elements)", 65535 / NEN);
+    return rc;
+}
+
 // The dispatch: the stress form, tiles, then P2 element matrices + gather lists, then launch_matrix.
 template <int DIM, int NEN>
-int launch_assemble(fedd_ctx* c, int kform, AsmArgs a, int ntab) {
+int launch_assemble(fedd_ctx* c, int kform, AsmArgs a, int ntab, bool xdim = false) {
     if (kform == F_STRESS) return launch_stress<DIM, NEN>(c, a);
+    if (xdim) return launch_laplace_xdim<DIM, NEN>(c, a, ntab);
     if constexpr (NEN == DIM + 1) {
         // element-major tiles for the P1 forms they cover (option "asm_tiles" 0: the pair kernels)
         if (c->asm_kind == 0 && c->asm_tiles && a.nq == 1 && (kform == F_LAPLACE || kform == F_LINELAS)) {
@@ -1796,6 +1839,14 @@ int assemble_matrix(fedd_ctx* c, int form, const double* params, const double* c
                        "fedd_assemble_stress: assemblyStress needs a FULL pattern with dim dofs per node "
                        "(fedd_pattern_build(dim, FEDD_BLOCK_FULL)) as system matrix");
             kform = F_STRESS; degree = dg + dg; break;
+        case FEDD_FORM_LAPLACE_XDIM:
+            FEDD_CHECK(!c->merged && c->dofs == dim && c->block_mode == FEDD_BLOCK_DIAG && c->n_rowg == 0,
+                       "assemblyLaplaceXDim needs a DIAG pattern with dim dofs per node (fedd_pattern_build(dim, FEDD_BLOCK_DIAG)) "
+                       "as system matrix");
+            FEDD_CHECK(params, "assemblyLaplaceXDim needs params = {distance, coefficient} (\"Distance Laplace\", \"Coefficient Laplace\")");
+            FEDD_CHECK(c->have_idist, "assemblyLaplaceXDim needs the distances to the interface: call fedd_interface_distance "
+                                      "(or fedd_interface_distance_points / fedd_interface_distance_set) first");
+            kform = F_LAPLACE; degree = dg + dg; break;
         default:
             FEDD_CHECK(false, "fedd_assemble: unknown form %d", form);
     }
@@ -1829,14 +1880,15 @@ int assemble_matrix(fedd_ctx* c, int form, const double* params, const double* c
         a.tab = c->d_hy_tab.p;
         a.coeff = coeff_q && n_coeff > 0 ? c->d_dtmp0.p : nullptr;
     }
+    const bool xdim = form == FEDD_FORM_LAPLACE_XDIM;
     if (kform == F_MASS) {   // the constant the Bochev-Dohrmann block takes off every mass entry: |ref. element| x scale (FE_def.hpp:2183-2192)
         a.p0 = form == FEDD_FORM_BDSTAB ? (dim == 2 ? 0.5 : 1.0 / 6.0) : 0.0;
         a.p1 = form == FEDD_FORM_BDSTAB ? (dim == 2 ? 1.0 / 9.0 : 1.0 / 16.0) : 0.0;
     }
-    if (dim == 2 && nen == 3) return launch_assemble<2, 3>(c, kform, a, ntab);
-    if (dim == 2 && nen == 6) return launch_assemble<2, 6>(c, kform, a, ntab);
-    if (dim == 3 && nen == 4) return launch_assemble<3, 4>(c, kform, a, ntab);
-    return launch_assemble<3, 10>(c, kform, a, ntab);
+    if (dim == 2 && nen == 3) return launch_assemble<2, 3>(c, kform, a, ntab, xdim);
+    if (dim == 2 && nen == 6) return launch_assemble<2, 6>(c, kform, a, ntab, xdim);
+    if (dim == 3 && nen == 4) return launch_assemble<3, 4>(c, kform, a, ntab, xdim);
+    return launch_assemble<3, 10>(c, kform, a, ntab, xdim);
 }
 
 int assemble_rhs(fedd_ctx* c, int dofs, const double* f_const, int extra_degree) {

@@ -27,6 +27,7 @@ struct AsmArgs {
     double zero_eps; // > 0: element contributions of magnitude below it are set to zero before they are added (the reference's
                      // optional setZeros_ / myeps_, FE_def.hpp:74-79, 719-721, 2002-2004, 2032-2034: vector Laplacian, B, B^T)
     const double* coeff = nullptr;  // F_STRESS: c(x_k) per element and quadrature point [E][nq]; nullptr: c = 1
+    const double* fscale = nullptr; // FEDD_FORM_LAPLACE_XDIM: the coefficient f per element [E] (k_elem_matrix<..., SCALED>)
 };
 
 namespace {

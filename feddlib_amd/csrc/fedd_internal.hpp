@@ -232,6 +232,13 @@ struct fedd_ctx {
     int64_t n_moves = 0;                        // moves committed since the last fedd_mesh_set*
     uint64_t geometry_id = 0;                   // moves committed since the context was made: which coordinates a result belongs to
     double min_det_ratio = 1.0;                 // smallest |det B| / |det B_ref| of the last committed move
+    // ---- interface distances and the scaled-Laplace coefficient (interface_distance.hip; one rank) ----
+    bool have_idist = false;                    // d_idist holds distances: kept by fedd_mesh_move (nodal values), released by fedd_mesh_set*
+    fedd::DevBuf<double> d_idist;               // [n_node] distance of every node to the interface, column-local numbering
+    fedd::DevBuf<double> d_ipts;                // [dim][n_interface] the interface points of the last computing call, structure-of-arrays
+    int64_t n_interface = 0;                    // ... and their number (0 after fedd_interface_distance_set)
+    bool have_lscale = false;                   // d_lscale holds the coefficients of the last FEDD_FORM_LAPLACE_XDIM assembly on this mesh
+    fedd::DevBuf<double> d_lscale;              // [n_elem] f per element (k_laplace_scale)
 
     // ---- node -> (element, local index) adjacency of owned nodes ----
     fedd::DevBuf<int32_t> d_n2e_ptr, d_n2e;     // [n_own+1], [sum]
@@ -695,6 +702,15 @@ int assemble_advection(fedd_ctx* c, int kind, double scale, int slot_add, int sl
 // soff [node-level nnz + 2], src [adjacency entries * nen + 2]; `who` names the caller in the error text
 int build_gather_lists(fedd_ctx* c, const int32_t* rowptr, const int32_t* colind, int dofs, int full, uint16_t* soff, uint16_t* src,
                        const char* who);
+
+// interface_distance.hip
+int interface_distance_tile();
+int interface_distance_flags(fedd_ctx* c, int n_flags, const int32_t* flags, int64_t* n_interface);
+int interface_distance_points(fedd_ctx* c, int64_t n_pts, const double* xyz_pts);
+int interface_distance_set(fedd_ctx* c, const double* dist_rep);    // nullptr releases
+int interface_distance_get(fedd_ctx* c, double* dist_rep);
+int laplace_scale(fedd_ctx* c, double distance, double coefficient);   // f per element into d_lscale, in the stream
+int laplace_scale_get(fedd_ctx* c, double* f_elem);
 
 // mesh_move.hip
 int mesh_move(fedd_ctx* c, const double* disp_rep);     // nullptr: back to the reference coordinates

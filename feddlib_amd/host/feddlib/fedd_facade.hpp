@@ -24,6 +24,7 @@
 #include <cmath>
 #include <functional>
 #include <iostream>
+#include <limits>
 #include <fstream>
 #include <cstring>
 #include <string>
@@ -52,6 +53,7 @@ typedef Teuchos::RCP<Teuchos::ParameterList> ParameterListPtr_Type;
 typedef std::function<void(double* x, double* res, double* parameters)> RhsFunc_Type;
 typedef std::function<void(double* x, double* res, double t, const double* parameters)> BC_func_Type;
 typedef std::function<double(double* x, int* parameters)> CoeffFunc_Type;                      // FEDDCore.hpp:115
+typedef std::function<double(double* x, double* parameters)> CoeffFuncDbl_Type;                // FEDDCore.hpp:116
 // the coefficient Stokes and NavierStokes hand to FE::assemblyStress (Stokes_def.hpp:21-24, NavierStokes_def.hpp:33-36)
 inline double OneFunction(double* x, int* parameter) { (void)x; (void)parameter; return 1.0; }
 
@@ -586,6 +588,7 @@ public:
         feddCheck(fedd_mesh_set(dev->ctx, dim_, nen_, (int64_t)(conn_.size() / nen_), conn_.data(), (int64_t)grep.size(), ref.data(), grep.data(),
                                 (int64_t)guni.size(), guni.data(), flagUni_.data()), "fedd_mesh_set");
         if (!disp_.empty()) feddCheck(fedd_mesh_move(dev->ctx, disp_.data()), "fedd_mesh_move");
+        if (!dist_.empty()) feddCheck(fedd_interface_distance_set(dev->ctx, dist_.data()), "fedd_interface_distance_set");
         uploads_.push_back(dev.shared());
     }
     // Domain::moveMesh (Domain_def.hpp:673-676 -> Mesh::moveMesh, Mesh_def.hpp:297-330): points = reference points + displacement,
@@ -608,6 +611,49 @@ public:
         disp_.assign(d.begin(), d.end());
         for (size_t k = 0; k < xyz_.size(); ++k) xyz_[k] = xyzRef_[k] + disp_[k];
     }
+    // Domain::identifyInterfaceParallelAndDistance (Domain_def.hpp:553-566 -> MeshUnstructured::buildMeshInterfaceParallelAndDistance
+    // -> MeshInterface_def.hpp:217-491): the interface of this domain is its set of nodes with one of the flags.  Per flag both
+    // domains must hold the same number of such nodes (the reference's check, MeshInterface_def.hpp:254).  The matched index
+    // tables (indicesGlobalMatched_) and the interface maps are NOT built: nothing here reads them.  The distances of every
+    // repeated node to the interface are computed on the device, on the points in force, and given to every context the
+    // domain is uploaded to, now and at a later uploadMeshTo.  One rank (the device call says so).
+    void identifyInterfaceParallelAndDistance(Teuchos::RCP<Domain> domainOther, vec_int_Type interfaceID_vec) {
+        TEUCHOS_TEST_FOR_EXCEPTION(domainOther.is_null(), std::runtime_error, "identifyInterfaceParallelAndDistance: domainOther is null.");
+        for (size_t k = 0; k < interfaceID_vec.size(); ++k) {
+            const int flag = interfaceID_vec[k];
+            const long nThis = (long)std::count(flagUni_.begin(), flagUni_.end(), flag);
+            const long nOther = (long)std::count(domainOther->flagUni_.begin(), domainOther->flagUni_.end(), flag);
+            TEUCHOS_TEST_FOR_EXCEPTION(nThis != nOther, std::runtime_error,
+                                       "DetermineInterfaceInParallel failed. ThisMesh and OtherMesh seem to have different numbers of interface nodes."
+                                       " (flag " << flag << ": " << nThis << " against " << nOther << ")");
+        }
+        interfaceFlags_.assign(interfaceID_vec.begin(), interfaceID_vec.end());
+        haveInterfaceFlags_ = true;
+        calculateDistancesToInterface();
+    }
+    // Domain::calculateDistancesToInterface (Domain_def.hpp:568-648) with the flags of the last identify call
+    void calculateDistancesToInterface() {
+        TEUCHOS_TEST_FOR_EXCEPTION(!haveInterfaceFlags_, std::runtime_error,
+                                   "Domain::calculateDistancesToInterface: no interface; call identifyInterfaceParallelAndDistance first");
+        int64_t nInterface = 0;
+        feddCheck(fedd_interface_distance(dev_->ctx, (int)interfaceFlags_.size(), interfaceFlags_.data(), &nInterface), "fedd_interface_distance");
+        dist_.assign((size_t)mapRepeated_->getNodeNumElements(), 0.);
+        feddCheck(fedd_interface_distance_get(dev_->ctx, dist_.data()), "fedd_interface_distance_get");
+        distributeDistances();
+    }
+    // on the repeated map, in this facade's local order (the order of getPointsRepeated)
+    vec_dbl_ptr_Type getDistancesToInterface() const {
+        TEUCHOS_TEST_FOR_EXCEPTION(dist_.empty(), std::runtime_error, "Domain::getDistancesToInterface: no distances; call identifyInterfaceParallelAndDistance first");
+        return Teuchos::rcp(new vec_dbl_Type(dist_.begin(), dist_.end()));
+    }
+    void setDistancesToInterface(vec_dbl_ptr_Type dist) {
+        TEUCHOS_TEST_FOR_EXCEPTION(dist.is_null() || dist->size() != (size_t)mapRepeated_->getNodeNumElements(), std::runtime_error,
+                                   "Domain::setDistancesToInterface: the distances do not live on the repeated map");
+        dist_.assign(dist->begin(), dist->end());
+        feddCheck(fedd_interface_distance_set(dev_->ctx, dist_.data()), "fedd_interface_distance_set");
+        distributeDistances();
+    }
+    bool hasDistancesToInterface() const { return !dist_.empty(); }
     vec2D_dbl_ptr_Type getPointsRepeatedRef() const { return points(xyzRef_.empty() ? xyz_ : xyzRef_, (size_t)mapRepeated_->getNodeNumElements(), nullptr); }
     vec2D_dbl_ptr_Type getPointsUniqueRef() const { return points(xyzRef_.empty() ? xyz_ : xyzRef_, (size_t)mapUnique_->getNodeNumElements(), &uniOfRep_); }
     int nodesPerElement() const { return nen_; }
@@ -709,6 +755,10 @@ private:
             feddCheck(fedd_mesh_set(dev_->ctx, dim_, nen_, (int64_t)(conn_.size() / nen_), conn_.data(), (int64_t)grep.size(), xyz_.data(),
                                     grep.data(), (int64_t)guni.size(), guni.data(), flagUni_.data()), "fedd_mesh_set");
     }
+    void distributeDistances() {     // to the contexts of uploadMeshTo, as moveMesh does for the displacement
+        for (auto& w : uploads_)
+            if (auto child = w.lock()) feddCheck(fedd_interface_distance_set(child->ctx, dist_.data()), "fedd_interface_distance_set (child context)");
+    }
     void uploadSurfaces() {      // with the mesh: the boundary elements the surface load vectors integrate over
         feddCheck(fedd_surface_set(dev_->ctx, surfNsn_, (int64_t)surfFlag_.size(), surf_.data(), surfFlag_.data()), "fedd_surface_set");
     }
@@ -727,6 +777,9 @@ private:
     std::string FEType_;
     std::vector<int32_t> conn_, flagRep_, flagUni_, uniOfRep_, surf_, surfFlag_, rowGhostRep_, rowGhostFlag_, elemFlag_;
     std::vector<double> xyz_;
+    std::vector<double> dist_;                  // distances to the interface on the repeated map (empty: none)
+    std::vector<int32_t> interfaceFlags_;       // the flags of the last identifyInterfaceParallelAndDistance
+    bool haveInterfaceFlags_ = false;
     std::vector<double> xyzRef_, disp_;         // moveMesh: the points the mesh was built with, the displacement in force (empty: never moved)
     mutable std::vector<std::weak_ptr<DeviceContext> > uploads_;     // contexts of uploadMeshTo
     int volumeID_ = 10;
@@ -784,6 +837,31 @@ public:
         TEUCHOS_TEST_FOR_EXCEPTION(FEType == "P0", std::logic_error, "Not implemented for P0");
         const double p[2] = {lambda, mu};
         assembleInto(checkFE(dim, FEType), dim, FEDD_BLOCK_FULL, FEDD_FORM_LINELAS, p, A, callFillComplete);
+    }
+    // FE::assemblyLaplaceXDim (FE_def.hpp:2225-2402): the vector Laplacian with func(mean distance of the element's vertices to the
+    // interface) per element, on the DIAG pattern, no doSetZeros.  The device applies HeuristicScaling (Geometry_def.hpp:24-34)
+    // itself from parameters = {distance, coefficient}; func is therefore CHECKED, not used: it must return parameters[1] below
+    // parameters[0] and 1.0 at and above it.  Another function is refused with what is built.
+    void assemblyLaplaceXDim(int dim, std::string FEType, MatrixPtr_Type& A, CoeffFuncDbl_Type func, double* parameters, bool callFillComplete = true) {
+        TEUCHOS_TEST_FOR_EXCEPTION(FEType == "P0", std::logic_error, "Not implemented for P0");
+        TEUCHOS_TEST_FOR_EXCEPTION(!func || !parameters, std::runtime_error, "assemblyLaplaceXDim: func or parameters is null.");
+        auto dom = domainVec_.at(checkFE(dim, FEType));
+        TEUCHOS_TEST_FOR_EXCEPTION(!dom->hasDistancesToInterface(), std::logic_error,
+                                   "assemblyLaplaceXDim needs the distances to the interface: call Domain::identifyInterfaceParallelAndDistance first");
+        const double dist = parameters[0], coeff = parameters[1];
+        const double below = std::nextafter(dist, -std::numeric_limits<double>::infinity()), above = std::nextafter(dist, std::numeric_limits<double>::infinity());
+        double probes[5] = {below, 0.5 * dist, dist, above, 2. * dist + 1.};
+        bool same = true;
+        for (int k = 0; k < 5; ++k) {
+            double x[1] = {probes[k]};
+            const double want = x[0] < dist ? coeff : 1.0;
+            const double got = func(x, parameters);
+            same = same && got == want;
+        }
+        TEUCHOS_TEST_FOR_EXCEPTION(!same, std::logic_error,
+                                   "assemblyLaplaceXDim: func is not HeuristicScaling (parameters[1] where x[0] < parameters[0], else 1.0); what is built is "
+                                   "the scaled Laplacian with that function, which the device evaluates itself from parameters = {distance, coefficient}");
+        assembleInto(checkFE(dim, FEType), dim, FEDD_BLOCK_DIAG, FEDD_FORM_LAPLACE_XDIM, parameters, A, callFillComplete);
     }
     // FE::assemblyStress (FE_def.hpp:2407-2733): int func(x) grad v : (grad u + grad u^T), the velocity block in stress form, on
     // the FULL pattern.  func is evaluated on the host at x_k = B xi_k + p_1 of every element and quadrature point of the rule
@@ -1812,8 +1890,13 @@ public:
 
 // Geometry (feddlib/problems/specific/Geometry_def.hpp:37-101): the extension of a boundary displacement into the fluid mesh,
 // one variable d_f.  "Model" = "Elasticity": assemblyLinElasXDim with the reference's lambda from "Poisson Ratio" (default 0.3)
-// and "Mu".  "Model" = "Laplace" (the reference's default when the key is absent) scales the Laplacian by the distance of an
-// element to the FSI interface, which this code has no notion of: an error that names "Elasticity".
+// and "Mu".  "Model" = "Laplace" (the reference's default when the key is absent): assemblyLaplaceXDim with HeuristicScaling and
+// "Distance Laplace" (default 0.03), "Coefficient Laplace" (default 1000), the Laplacian scaled where the mean distance of an
+// element's vertices to the FSI interface is small.  It needs the distances of Domain::identifyInterfaceParallelAndDistance; on a
+// domain without them it is an error that names "Elasticity" and that call.
+// HeuristicScaling (Geometry_def.hpp:24-34)
+inline double HeuristicScaling(double* x, double* parameter) { return x[0] < parameter[0] ? parameter[1] : 1.0; }
+
 template <class SC = default_sc, class LO = default_lo, class GO = default_go, class NO = default_no>
 class Geometry : public Problem<SC, LO, GO, NO> {
 public:
@@ -1830,9 +1913,23 @@ public:
     void assemble(std::string type = "") const override {
         (void)type;
         const std::string model = this->parameterList_->sublist("Parameter").get("Model", "Laplace");
-        TEUCHOS_TEST_FOR_EXCEPTION(model == "Laplace", std::logic_error,
-                                   "Geometry: \"Model\" = \"Laplace\" (also the default when the key is absent) scales the Laplacian by the distance to an FSI "
-                                   "interface, which is not built here; set \"Model\" to \"Elasticity\".");
+        if (model == "Laplace") {
+            TEUCHOS_TEST_FOR_EXCEPTION(!this->getDomain(0)->hasDistancesToInterface(), std::logic_error,
+                                       "Geometry: \"Model\" = \"Laplace\" (also the default when the key is absent) scales the Laplacian by the distance to an FSI "
+                                       "interface: it needs Domain::identifyInterfaceParallelAndDistance first; without an interface set \"Model\" to \"Elasticity\".");
+            if (this->verbose_) std::cout << "-- Assembly Geometry (scaled Laplace)... " << std::flush;
+            double parameter[2] = {this->parameterList_->sublist("Parameter").get("Distance Laplace", 0.03),
+                                   this->parameterList_->sublist("Parameter").get("Coefficient Laplace", 1000.)};
+            if (this->verbose_) std::cout << "\n    Distance Laplace = " << parameter[0] << "  coefficient Laplace = " << parameter[1] << " ... " << std::flush;
+            MatrixPtr_Type H = Teuchos::rcp(new Matrix_Type(this->getDomain(0)->getMapVecFieldUnique(),
+                                                            this->getDomain(0)->getDimension() * this->getDomain(0)->getApproxEntriesPerRow()));
+            this->feFactory_->assemblyLaplaceXDim(this->dim_, this->getDomain(0)->getFEType(), H, HeuristicScaling, parameter);
+            this->system_->addBlock(H, 0, 0);
+            this->assembleSourceTerm(0.);
+            this->addToRhs(this->sourceTerm_);
+            if (this->verbose_) std::cout << "done -- " << std::endl;
+            return;
+        }
         TEUCHOS_TEST_FOR_EXCEPTION(model != "Elasticity", std::logic_error, "Unknown model for geometry.");
         if (this->verbose_) std::cout << "-- Assembly Geometry (linear elasticity)... " << std::flush;
         const double poissonRatio = this->parameterList_->sublist("Parameter").get("Poisson Ratio", 0.3);

@@ -36,8 +36,11 @@ enum fedd_form {
     FEDD_FORM_BDSTAB      = 5, /* FE::assemblyBDStabilization  FE_def.hpp:2151-2220 (dofs 1, P1 only): the Bochev-Dohrmann
                                   pressure block of P1/P1 Stokes, C_ij = |det B| (sum_q w_q phi_i phi_j - |ref| scale),
                                   scaled by -1/viscosity by the caller (Stokes_def.hpp:98-105)        */
-    FEDD_FORM_STRESS      = 6  /* FE::assemblyStress           FE_def.hpp:2407-2733 (dofs dim, full): the velocity block in
+    FEDD_FORM_STRESS      = 6, /* FE::assemblyStress           FE_def.hpp:2407-2733 (dofs dim, full): the velocity block in
                                   stress form with c = 1; fedd_assemble_stress takes a coefficient     */
+    FEDD_FORM_LAPLACE_XDIM = 7 /* FE::assemblyLaplaceXDim      FE_def.hpp:2225-2402 (dofs dim, diag): the vector Laplacian with
+                                  one coefficient per element from the interface distances; params = {distance, coefficient}
+                                  (section "Interface distances")                                       */
 };
 
 /* ---- what fedd_assemble_advection builds from the velocity of fedd_velocity_set ---- */
@@ -103,7 +106,8 @@ enum fedd_timer {
     FEDD_T_NEWTON_UPDATE = 28,   /* ... the iterate's update: k_newton_update                      */
     FEDD_T_MESH_MOVE = 29,  /* fedd_mesh_move: k_mesh_move, candidate = x_ref + d (mesh_move.hip)  */
     FEDD_T_MOVE_CHECK = 30, /* ... k_move_check + k_move_min, det B of every element against the reference */
-    FEDD_T_COUNT    = 31
+    FEDD_T_INTERFACE_DIST = 31, /* fedd_interface_distance*: k_interface_distance (interface_distance.hip) */
+    FEDD_T_COUNT    = 32
 };
 
 /* ------------------------------------------------------------------------------------------------
@@ -319,6 +323,8 @@ int fedd_mesh_set_rows(fedd_ctx* ctx, int dim, int nen, int64_t n_elem, const in
  *   - the advection / stress / hyperelastic scratch and reference tables, the velocity of fedd_velocity_set and the mesh
  *     velocity of fedd_mesh_velocity_set / fedd_mesh_velocity_diff (section "ALE convection"; nodal values, they read no
  *     coordinate);
+ *   - the interface distances of fedd_interface_distance* (section "Interface distances"; nodal values: the reference never
+ *     recomputes them on the moved mesh) and the coefficients of the last FEDD_FORM_LAPLACE_XDIM assembly;
  *   - the surface set of fedd_surface_set;
  *   - the Dirichlet flag tables (boundary flags of the nodes);
  *   - the halo plan;
@@ -337,7 +343,7 @@ int fedd_mesh_set_rows(fedd_ctx* ctx, int dim, int nen, int64_t n_elem, const in
  * the Schwarz inverses and fingerprints, the CG setup.
  *
  * Errors: a host-only context ("needs a GPU context"), no mesh, more than one rank.
- * Left out: interface distances (the scaled-Laplace extension), more than one rank.
+ * Left out: more than one rank.
  *
  * fedd_mesh_move_info: moves committed since the last fedd_mesh_set*, moves committed since the context was made, the ratio
  * above (0, 0, 1.0 on a fresh context).  Needs no device; outputs may be NULL.
@@ -346,6 +352,56 @@ int fedd_mesh_set_rows(fedd_ctx* ctx, int dim, int nen, int64_t n_elem, const in
 int fedd_mesh_move(fedd_ctx* ctx, const double* disp_rep);
 int fedd_mesh_move_info(fedd_ctx* ctx, int64_t* n_moves, int64_t* geometry_id, double* min_det_ratio);
 int fedd_mesh_coords_get(fedd_ctx* ctx, double* xyz_rep);
+
+/* ------------------------------------------------------------------------------------------------
+ * Interface distances and the scaled vector Laplacian of the mesh extension (one rank).
+ * Replaces Domain::calculateDistancesToInterface (feddlib/core/FE/Domain_def.hpp:568-648), the distance loop of
+ * MeshInterface::buildMeshInterfaceParallelAndDistance (feddlib/core/Mesh/MeshInterface_def.hpp:473-491) and
+ * FE::assemblyLaplaceXDim (feddlib/core/FE/FE_def.hpp:2225-2402) with HeuristicScaling
+ * (feddlib/problems/specific/Geometry_def.hpp:24-34), the default model of the Geometry problem (Geometry_def.hpp:63-76).
+ *
+ * NORMATIVE -- the distances (Domain_def.hpp:621-647), for every node i of the repeated map, ghost nodes included:
+ *     dist[i] = min(1000.0, min_j sqrt(sum_k (x_i[k] - p_j[k])^2))
+ *   - the difference, then its square, per coordinate; the squares summed in ascending k; every product and every sum is
+ *     rounded on its own (no fused multiply-add);
+ *   - the kernel takes the minimum of the SQUARED distances and one sqrt per node: a correctly rounded sqrt is monotone, so
+ *     the bits are those of the minimum of the roots;
+ *   - a minimum does not depend on order: the result is independent of the order of the interface points and of the tiling;
+ *   - no floating-point atomic; two calls agree bit for bit;
+ *   - with no interface point every entry is 1000.0 and n_interface = 0; that is not an error.
+ * fedd_interface_distance: the interface points are the nodes of this context whose node flag (bcflag_uni of fedd_mesh_set)
+ * is one of flags[n_flags], at the coordinates IN FORCE at the call, i.e. after any fedd_mesh_move.  *n_interface (may be
+ * NULL) receives their number.
+ * fedd_interface_distance_points: the same against n_pts points of the caller's, xyz_pts[n_pts * dim].
+ * fedd_interface_distance_set: distances of the caller's on the repeated map, dist_rep[n_rep]; NULL releases them.
+ * fedd_interface_distance_get: dist_rep[n_rep] on the repeated map; an error without distances.
+ * fedd_interface_distance_info: whether distances are held, the number of interface points of the last computing call (0
+ * after _set), and the number of points the kernel stages in LDS per tile.  Needs no device; outputs may be NULL.
+ * Lifetime: the distances are nodal values.  fedd_mesh_move KEEPS them (the reference never recomputes them on the moved
+ * mesh); fedd_mesh_set* releases them.
+ *
+ * NORMATIVE -- fedd_assemble(ctx, FEDD_FORM_LAPLACE_XDIM, params = {distance, coefficient}), on the pattern of
+ * FEDD_FORM_LAPLACE_VEC (fedd_pattern_build(dim, FEDD_BLOCK_DIAG)), on the coordinates in force:
+ *   - per element (FE_def.hpp:2273-2278, 2343-2349): mean = (d_0 + d_1 + d_2) / 3.0 in 2D, (d_0 + d_1 + d_2 + d_3) / 4.0 in
+ *     3D, summed left to right over the FIRST dim + 1 nodes of the element (P2 mid-edge nodes do not enter);
+ *     f = coefficient if mean < distance (strict), else f = 1.0;
+ *   - K[(i,a),(j,a)] = |det B| sum_k (f w_k) (grad phi_j . grad phi_i) for every component a: k ascending, the dot product
+ *     summed in ascending coordinate, f w_k formed first, |det B| multiplied last; rule determineDegree(dim, FE, FE, Grad, Grad);
+ *   - NO doSetZeros: the reference's routine has none (unlike assemblyLaplaceVecField), option "asm_zero_eps" does not apply;
+ *   - the rows are summed in adjacency order through gather lists, no floating-point atomic: two calls agree bit for bit.
+ * fedd_laplace_scale_get: f_elem[n_elem], the coefficients of the last such assembly on this mesh.
+ *
+ * Errors: a host-only context ("needs a GPU context"), no mesh, more than one rank, n_pts < 0, n_flags < 0, _get without
+ * distances; the assembly without distances (the message names fedd_interface_distance), with params == NULL, on another
+ * pattern.  Each is a message, never a device fault.
+ * Left out: the matched interface index tables and interface maps, recomputing the distances on the moved mesh, more than one rank.
+ * ---------------------------------------------------------------------------------------------- */
+int fedd_interface_distance(fedd_ctx* ctx, int n_flags, const int32_t* flags, int64_t* n_interface);
+int fedd_interface_distance_points(fedd_ctx* ctx, int64_t n_pts, const double* xyz_pts);
+int fedd_interface_distance_set(fedd_ctx* ctx, const double* dist_rep);
+int fedd_interface_distance_get(fedd_ctx* ctx, double* dist_rep);
+int fedd_interface_distance_info(fedd_ctx* ctx, int* have, int64_t* n_interface, int* tile_points);
+int fedd_laplace_scale_get(fedd_ctx* ctx, double* f_elem);
 
 /* symbolic CSR on the owned (unique-map) rows: what Tpetra's dynamic insert + fillComplete
  * discover (feddlib/core/LinearAlgebra/Matrix_def.hpp:88-92,192-199). */
