@@ -19,7 +19,8 @@ COMBINE_RESTRICTED, COMBINE_AVERAGING, COMBINE_FULL = range(3)
 TIMER_NAMES = ["symbolic", "assemble", "rhs", "dirichlet", "spmv", "schwarz_setup", "schwarz_apply", "ortho",
                "coarse_setup", "coarse_apply", "halo", "allreduce", "spmv_setup", "gs_dot", "gs_update", "gs_fused",
                "full_park_mfma", "full_park", "full_gather", "cg_pq", "cg_xr", "cg_rz", "cg_p", "newmark_state", "block_apply", "multistep_state", "blockprec_bt",
-               "newton_residual", "newton_update", "mesh_move", "move_check", "interface_distance"]
+               "newton_residual", "newton_update", "mesh_move", "move_check", "interface_distance", "fsi_match", "fsi_merge",
+               "fsi_apply"]
 COARSE_Q1 = 1
 COARSE_GDSW = 2
 COARSE_RGDSW = 3
@@ -186,6 +187,16 @@ SIGNATURES = {
     "fedd_block_prec_attach": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int],
     "fedd_block_prec_detach": [C.c_void_p],
     "fedd_block_prec_info": [C.c_void_p, _ip, _f64p, _ip, _i64p],
+    "fedd_interface_match": [C.c_void_p, C.c_void_p, C.c_int, _i32p],
+    "fedd_interface_match_sizes": [C.c_void_p, _i64p, _ip, _ip],
+    "fedd_interface_match_get": [C.c_void_p, _i32p, _i32p, _i64p],
+    "fedd_interface_match_info": [C.c_void_p, _ip, _i64p, _f64p, _ip],
+    "fedd_fsi_merge": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_uint8)],
+    "fedd_fsi_interface_rhs": [C.c_void_p, _f64p],
+    "fedd_fsi_info": [C.c_void_p, _i64p, _i64p, _i64p, _i64p, _i64p, _ip, _i64p],
+    "fedd_fsi_prec_attach": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "fedd_fsi_prec_detach": [C.c_void_p],
+    "fedd_fsi_prec_info": [C.c_void_p, _ip, _i64p],
 }
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, _i32p, _i64p, _f64p, _i64p, _f64p, C.c_int)
@@ -850,6 +861,64 @@ class Context:
         k, sl, n, sc = C.c_int(), C.c_int(), C.c_int64(), C.c_double()
         _chk(self._L.fedd_block_prec_info(self._h, C.byref(k), C.byref(sc), C.byref(sl), C.byref(n)))
         return {"kind": k.value, "schur_scale": sc.value, "slot_bt": sl.value, "applies": n.value}
+
+    def interface_match(self, other, flags):
+        """this context is the fluid, `other` the structure: the nodes that carry each of `flags`, at the reference coordinates,
+        ordered lexicographically and paired by rank (fedd_interface_match); returns the number of pairs"""
+        fl = np.ascontiguousarray(np.atleast_1d(flags), dtype=np.int32)
+        _chk(self._L.fedd_interface_match(self._h, None if other is None else other._h, fl.shape[0], _p(fl, _i32p)))
+        return self.interface_match_info()["n_pairs"]
+
+    def interface_match_table(self):
+        """(iface_fluid, iface_structure, flag_ptr): owned node ids of pair k on both sides, the flags concatenated"""
+        n, nf, d = C.c_int64(), C.c_int(), C.c_int()
+        _chk(self._L.fedd_interface_match_sizes(self._h, C.byref(n), C.byref(nf), C.byref(d)))
+        f = np.zeros(n.value, dtype=np.int32)
+        s = np.zeros(n.value, dtype=np.int32)
+        ptr = np.zeros(nf.value + 1, dtype=np.int64)
+        _chk(self._L.fedd_interface_match_get(self._h, _p(f, _i32p), _p(s, _i32p), _p(ptr, _i64p)))
+        return f, s, ptr
+
+    def interface_match_info(self):
+        h, n, d, t = C.c_int(), C.c_int64(), C.c_double(), C.c_int()
+        _chk(self._L.fedd_interface_match_info(self._h, C.byref(h), C.byref(n), C.byref(d), C.byref(t)))
+        return {"have": bool(h.value), "n_pairs": n.value, "max_pair_distance": d.value, "tile_points": t.value}
+
+    def fsi_merge(self, fluid, structure, dt, coupled_mask=None):
+        """this (mesh-less) context's system <- the four-block coupled system of the children's current systems and the
+        coupling entries of their matched interface (fedd_fsi_merge); coupled_mask: one byte per interface dof, 0 = uncoupled"""
+        m = None if coupled_mask is None else np.ascontiguousarray(coupled_mask, dtype=np.uint8)
+        _chk(self._L.fedd_fsi_merge(self._h, None if fluid is None else fluid._h, None if structure is None else structure._h,
+                                    float(dt), _p(m, C.POINTER(C.c_uint8))))
+
+    def fsi_interface_rhs(self, d_old):
+        """rhs_lambda <- C2 d_old on the coupled interface dofs, 0 elsewhere (fedd_fsi_interface_rhs); d_old: [n_s]"""
+        d = np.ascontiguousarray(d_old, dtype=np.float64).ravel()
+        n_s = self.fsi_info()["n_s"]
+        if d.shape[0] != n_s:
+            raise FeddError("fsi_interface_rhs: %d entries, the structure block has %d" % (d.shape[0], n_s))
+        _chk(self._L.fedd_fsi_interface_rhs(self._h, _p(d, _f64p)))
+
+    def fsi_info(self):
+        a, b, c, d, lv, nv = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int(), C.c_int64()
+        off = np.zeros(4, dtype=np.int64)
+        _chk(self._L.fedd_fsi_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d), _p(off, _i64p), C.byref(lv), C.byref(nv)))
+        return {"n_u": a.value, "n_p": b.value, "n_s": c.value, "n_l": d.value, "offsets": off,
+                "last_values_only": bool(lv.value), "n_values_only": nv.value}
+
+    def fsi_prec_attach(self, fluid, structure):
+        """FaCSI preconditioner of this context's coupled system out of the two child contexts, which are not owned"""
+        _chk(self._L.fedd_fsi_prec_attach(self._h, None if fluid is None else fluid._h, None if structure is None else structure._h))
+        self._fp_children = (fluid, structure)      # keeps them alive while attached
+
+    def fsi_prec_detach(self):
+        _chk(self._L.fedd_fsi_prec_detach(self._h))
+        self._fp_children = None
+
+    def fsi_prec_info(self):
+        a, n = C.c_int(), C.c_int64()
+        _chk(self._L.fedd_fsi_prec_info(self._h, C.byref(a), C.byref(n)))
+        return {"attached": bool(a.value), "applies": n.value}
 
     def newmark_begin(self):
         """u_n <- the current solution, v = w = 0; the next advance is the first step"""

@@ -136,6 +136,9 @@ extern "C" void fedd_ctx_destroy(fedd_ctx* c) {
     if (!c) return;
     block_prec_child_gone(c);   // parents that apply this context as a block are detached (their streams finished first)
     block_prec_unlink(c);       // ... and this context's own children forget it
+    fsi_prec_child_gone(c);     // the same for the coupled contexts that apply this one inside their FaCSI preconditioner
+    fsi_prec_unlink(c);
+    iface_release(c);           // the other side of a match finds it released
     if (c->device >= 0) {
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
@@ -148,6 +151,7 @@ extern "C" void fedd_ctx_destroy(fedd_ctx* c) {
         if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
         if (c->ev_join) (void)hipEventDestroy(c->ev_join);
         if (c->bp_ev) (void)hipEventDestroy(c->bp_ev);
+        if (c->fp_ev) (void)hipEventDestroy(c->fp_ev);
         if (c->stream2) (void)hipStreamDestroy(c->stream2);
         (void)hipStreamDestroy(c->stream);
     }
@@ -160,6 +164,8 @@ extern "C" int fedd_sync(fedd_ctx* c) {
     // an attached block preconditioner runs its children's applies in this stream; their own streams hold their setups
     if (c->bp_kind && c->bp_vel && c->bp_vel->device >= 0) FEDD_HIP(hipStreamSynchronize(c->bp_vel->stream));
     if (c->bp_kind && c->bp_schur && c->bp_schur->device >= 0) FEDD_HIP(hipStreamSynchronize(c->bp_schur->stream));
+    if (c->fp_on && c->fp_fluid && c->fp_fluid->device >= 0) FEDD_HIP(hipStreamSynchronize(c->fp_fluid->stream));
+    if (c->fp_on && c->fp_struct && c->fp_struct->device >= 0) FEDD_HIP(hipStreamSynchronize(c->fp_struct->stream));
     return 0;
 }
 
@@ -192,6 +198,8 @@ static int mesh_set_impl(fedd_ctx* c, int dim, int nen, int64_t n_elem, const in
     c->n_interface = 0;
     c->d_idist.release();
     c->d_lscale.release();
+    iface_release(c);       // ... and the matched interface, on both sides (a coupled system built on it finds it released)
+    c->fsi_coupled = false; // (a coupled context that is given a mesh is an ordinary context again)
     c->hy_lists = c->have_hy_f = false;   // ... and the lists and the force vector of the hyperelastic path
     c->nw_active = c->nw_have_src = c->nw_f_fresh = false;   // ... and the Newton state (newton.hip)
     c->nw_n = -1;
@@ -415,6 +423,9 @@ extern "C" int fedd_pattern_build(fedd_ctx* c, int dofs_per_node, int block_mode
 }
 
 // (an imported system, or a merge of blocks of an earlier mesh, has a pattern without the adjacency the assembly kernels walk)
+// (the coupled context of fedd_fsi_merge holds a system and never a mesh)
+static const char* const NO_MESH = "this context carries no mesh (a coupled context of fedd_fsi_merge never does): the call needs "
+                                   "the nodes of a fedd_mesh_set";
 static const char* const NO_ADJACENCY = "this context has not built the node -> element adjacency of its mesh (the system matrix "
                                         "was imported or merged, not built here): fedd_pattern_build builds it";
 
@@ -486,6 +497,7 @@ extern "C" int fedd_assemble_surface_values(fedd_ctx* c, int dofs_per_node, cons
 extern "C" int fedd_dirichlet(fedd_ctx* c, int n_bc, const int32_t* flags, const int32_t* comp_mask, const double* values) {
     NEED_DEVICE(c);
     FEDD_CHECK(c->have_pattern, "fedd_dirichlet: call fedd_pattern_build first");
+    FEDD_CHECK(c->n_node > 0, "fedd_dirichlet: %s", NO_MESH);
     FEDD_CHECK(n_bc >= 0 && n_bc <= MAX_BC, "fedd_dirichlet: at most %d boundary conditions", MAX_BC);
     FEDD_CHECK(n_bc == 0 || (flags && values), "fedd_dirichlet: null array");
     FEDD_HIP(hipSetDevice(c->device));
@@ -496,6 +508,7 @@ extern "C" int fedd_dirichlet_nodes(fedd_ctx* c, int64_t n, const int32_t* owned
                                     const double* values) {
     NEED_DEVICE(c);
     FEDD_CHECK(c->have_pattern, "fedd_dirichlet_nodes: call fedd_pattern_build first");
+    FEDD_CHECK(c->n_node > 0, "fedd_dirichlet_nodes: %s", NO_MESH);
     FEDD_CHECK(n >= 0 && (n == 0 || (owned_nodes && values)), "fedd_dirichlet_nodes: null array");
     FEDD_HIP(hipSetDevice(c->device));
     return apply_dirichlet_nodes(c, n, owned_nodes, comp_mask, values);
@@ -865,6 +878,7 @@ extern "C" int fedd_schwarz_set_target(fedd_ctx* c, int target_nodes, double sca
 extern "C" int fedd_schwarz_setup(fedd_ctx* c, int overlap, int combine, int two_level, int coarse_kind) {
     NEED_DEVICE(c);
     FEDD_CHECK(c->have_pattern, "fedd_schwarz_setup: assemble the matrix first");
+    FEDD_CHECK(c->n_node > 0, "fedd_schwarz_setup: %s (its preconditioner is fedd_fsi_prec_attach)", NO_MESH);
     FEDD_CHECK(overlap >= 0 && overlap <= 4, "fedd_schwarz_setup: overlap %d", overlap);
     FEDD_CHECK(combine >= 0 && combine <= 2, "fedd_schwarz_setup: combine mode %d", combine);
     FEDD_CHECK(two_level == 0 || coarse_kind == FEDD_COARSE_Q1 || coarse_kind == FEDD_COARSE_GDSW || coarse_kind == FEDD_COARSE_RGDSW,
@@ -963,8 +977,8 @@ extern "C" int fedd_spmv_reuse_info(fedd_ctx* c, int* last_reused, int64_t* n_re
 
 extern "C" int fedd_schwarz_apply(fedd_ctx* c, const double* r_owned, double* z_owned) {
     NEED_DEVICE(c);
-    FEDD_CHECK((c->have_schwarz || c->bp_kind) && r_owned && z_owned, "fedd_schwarz_apply: no preconditioner / null pointer");
-    if (c->bp_kind) FEDD_TRY(block_prec_check(c, "fedd_schwarz_apply"));
+    FEDD_CHECK((c->have_schwarz || has_attached_prec(c)) && r_owned && z_owned, "fedd_schwarz_apply: no preconditioner / null pointer");
+    if (has_attached_prec(c)) FEDD_TRY(attached_prec_check(c, "fedd_schwarz_apply"));
     else FEDD_TRY(levels_check(c, "fedd_schwarz_apply"));
     FEDD_HIP(hipSetDevice(c->device));
     FEDD_TRY(c->d_dtmp0.ensure((size_t)c->n_rows * 2));
@@ -979,8 +993,8 @@ extern "C" int fedd_schwarz_apply(fedd_ctx* c, const double* r_owned, double* z_
 
 extern "C" int fedd_schwarz_apply_device(fedd_ctx* c, int reps) {
     NEED_DEVICE(c);
-    FEDD_CHECK(c->have_schwarz || c->bp_kind, "fedd_schwarz_apply_device: no preconditioner");
-    if (c->bp_kind) FEDD_TRY(block_prec_check(c, "fedd_schwarz_apply_device"));
+    FEDD_CHECK(c->have_schwarz || has_attached_prec(c), "fedd_schwarz_apply_device: no preconditioner");
+    if (has_attached_prec(c)) FEDD_TRY(attached_prec_check(c, "fedd_schwarz_apply_device"));
     else FEDD_TRY(levels_check(c, "fedd_schwarz_apply_device"));
     FEDD_HIP(hipSetDevice(c->device));
     FEDD_TRY(c->d_dtmp0.ensure((size_t)c->n_rows * 2));
@@ -997,9 +1011,9 @@ static int gmres_entry(fedd_ctx* c, const char* who, bool x0, const double* b_ow
                        int restart, int use_prec, int* its_out, double* relres_out) {
     NEED_DEVICE(c);
     FEDD_CHECK(c->have_pattern, "%s: no matrix", who);
-    FEDD_CHECK(!use_prec || c->bp_kind || c->have_schwarz, "%s: preconditioner requested but fedd_schwarz_setup was not called", who);
+    FEDD_CHECK(!use_prec || has_attached_prec(c) || c->have_schwarz, "%s: preconditioner requested but fedd_schwarz_setup was not called", who);
     FEDD_CHECK(rtol > 0 && max_it >= 1 && restart >= 1 && restart <= 1000, "%s: bad rtol/max_it/restart", who);
-    if (use_prec && c->bp_kind) FEDD_TRY(block_prec_check(c, who));     // (and again at every apply)
+    if (use_prec && has_attached_prec(c)) FEDD_TRY(attached_prec_check(c, who));     // (and again at every apply)
     else if (use_prec) FEDD_TRY(levels_check(c, who));
     FEDD_HIP(hipSetDevice(c->device));
     const size_t bytes = (size_t)c->n_rows * sizeof(double);

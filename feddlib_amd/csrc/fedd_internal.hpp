@@ -6,6 +6,7 @@
 #include <vector>
 #include <cstdio>
 #include <cstdarg>
+#include <memory>
 #include "../../include/fedd_hip.h"
 
 struct ncclComm;
@@ -198,6 +199,21 @@ struct SpmvStream {
     // ---- build scratch: written and read inside one build only ----
     DevBuf<int32_t> d_wincnt;                   // kept entries per window of the parity CSR -> their offsets
     DevBuf<uint64_t> d_clskey;                  // keys of the class hash table
+};
+
+// The matched interface of a fluid and a structure context (fsi.hip fedd_interface_match): both contexts hold the same table.
+// fedd_mesh_set* on either side marks it released (valid = false) and lets go of its own reference; a coupled context that was
+// merged on it keeps a reference of its own and finds it released at its next merge or apply.
+struct IfaceTable {
+    bool valid = true;
+    int device = -1, dim = 0;
+    int64_t n = 0;                              // pairs
+    uint64_t uid_f = 0, uid_s = 0;              // fedd_ctx::uid of the two sides
+    uint64_t id = 0;                            // process-wide: which match this is
+    std::vector<int32_t> h_f, h_s;              // [n] owned node ids of pair k, fluid / structure side (read back from the device)
+    std::vector<int32_t> flags;                 // the flags of the match, in the order given
+    std::vector<int64_t> flag_ptr;              // [flags + 1] pairs of flag i: [flag_ptr[i], flag_ptr[i + 1])
+    double max_dist = 0.0;                      // largest distance between paired points
 };
 
 }  // namespace fedd
@@ -492,6 +508,31 @@ struct fedd_ctx {
     uint64_t imp_mesh_id = 0, imp_pattern_id = 0, imp_pattern_gen = 0;
     std::vector<fedd_ctx*> bp_parents;          // contexts that hold this one as a child of their block preconditioner
 
+    // ---- FSI coupling (fsi.hip; one rank) ----
+    std::shared_ptr<fedd::IfaceTable> iface;    // the matched interface this context is one side of (fedd_interface_match)
+    // a coupled context: the system matrix is the four-block system of fedd_fsi_merge (the context carries no mesh)
+    bool fsi_coupled = false;
+    std::shared_ptr<fedd::IfaceTable> fsi_table;   // the match the merge was built on
+    uint64_t fsi_uid_f = 0, fsi_uid_s = 0;      // the children of the merge: uid, and their mesh_gen / pattern_gen at the merge
+    uint64_t fsi_mesh_gen_f = 0, fsi_mesh_gen_s = 0, fsi_pat_gen_f = 0, fsi_pat_gen_s = 0;
+    uint64_t fsi_pat_gen = 0;                   // ... and the pattern_gen the merge left here
+    int64_t fsi_nu = 0, fsi_np = 0, fsi_ns = 0, fsi_nl = 0;   // block sizes: velocity, pressure, structure, lambda
+    double fsi_dt = 0.0;
+    std::vector<uint8_t> fsi_mask;              // [fsi_nl] 1 = coupled lambda-dof
+    fedd::DevBuf<int32_t> d_fsi_fdof, d_fsi_sdof;   // [fsi_nl] fluid / structure dof of lambda-dof k (-1: uncoupled)
+    fedd::DevBuf<int32_t> d_fsi_lam_f, d_fsi_lam_s; // [n_u + n_p], [n_s] lambda-dof of a fluid / structure dof (-1: none)
+    int fsi_last_values_only = 0;               // the last merge moved values only
+    int64_t fsi_values_only_count = 0;          // merges that did since the context was made
+    // the FaCSI preconditioner: two child contexts this one does not own
+    bool fp_on = false;
+    fedd_ctx* fp_fluid = nullptr;
+    fedd_ctx* fp_struct = nullptr;
+    fedd::DevBuf<double> d_fp_t;                // [n_u + n_p] t of the apply
+    hipEvent_t fp_ev = nullptr;                 // orders a child's own stream before this one after the child was set up again
+    uint64_t fp_seen_f = 0, fp_seen_s = 0;      // the children's sw_setup_gen at the last such ordering
+    int64_t fp_applies = 0;
+    std::vector<fedd_ctx*> fp_parents;          // coupled contexts that hold this one as a child of their FaCSI preconditioner
+
     // ---- coarse level (two-level Schwarz) ----
     int sw_two_level = 0;
     int sw_levels = FEDD_LEVELS_ADDITIVE;       // fedd_schwarz_set_level_combination, read at apply time
@@ -544,7 +585,7 @@ struct fedd_ctx {
     fedd::DevBuf<int32_t> d_rs_hist;            // radix sort: digit histograms [256][tiles]
     fedd::DevBuf<double> d_dtmp0;
     fedd::DevBuf<uint64_t> d_u64tmp;            // hashes and hash-table keys of a build in progress (SpMV dictionary, tile shapes)
-    fedd::DevBuf<int32_t> d_flags;              // [16] device flags: 0 max scratch, 1 bad pivot, 2 DGKS gate, 3-5 coarse setup, 8-11 Schwarz setup counters, 12 s-step block length, 13 SpMV stream keep
+    fedd::DevBuf<int32_t> d_flags;              // [16] device flags: 0 max scratch, 1 bad pivot, 2 DGKS gate, 3-5 coarse setup, 8-11 Schwarz setup counters, 12 s-step block length, 13 SpMV stream keep, 14 interface match twin, 15 coupled merge row check
 
     fedd::HaloPlan halo;
 
@@ -738,7 +779,16 @@ void block_prec_unlink(fedd_ctx* c);                   // c gives up its childre
 void block_prec_child_gone(fedd_ctx* child);           // a child is being destroyed: its parents are detached first
 // the preconditioner of the context: the attached block operator, else its own Schwarz preconditioner
 int schwarz_apply(fedd_ctx* c, const double* d_r_owned, double* d_z_owned, bool r_has_tail);
+// fsi.hip: matched interface, the coupled four-block system, the FaCSI preconditioner out of two child contexts
+void iface_release(fedd_ctx* c);                       // fedd_mesh_set* / destroy: the match of this context is released on both sides
+int fsi_prec_check(fedd_ctx* c, const char* who);      // everything an apply needs, with errors that name the child
+int fsi_prec_apply(fedd_ctx* c, const double* d_r_owned, double* d_z_owned);
+void fsi_prec_unlink(fedd_ctx* c);
+void fsi_prec_child_gone(fedd_ctx* child);
+inline bool has_attached_prec(const fedd_ctx* c) { return c->bp_kind != 0 || c->fp_on; }
+inline int attached_prec_check(fedd_ctx* c, const char* who) { return c->fp_on ? fsi_prec_check(c, who) : block_prec_check(c, who); }
 inline int prec_apply(fedd_ctx* c, const double* d_r_owned, double* d_z_owned, bool r_has_tail) {
+    if (c->fp_on) return fsi_prec_apply(c, d_r_owned, d_z_owned);
     return c->bp_kind ? block_prec_apply(c, d_r_owned, d_z_owned) : schwarz_apply(c, d_r_owned, d_z_owned, r_has_tail);
 }
 

@@ -616,6 +616,10 @@ extern "C" int fedd_dirichlet_rhs(fedd_ctx* c, int n_bc, const int32_t* flags, c
     NEED_DEVICE(c);
     ONE_RANK(c, "fedd_dirichlet_rhs");
     FEDD_CHECK(c->have_pattern && !c->merged, "fedd_dirichlet_rhs: no single-block system");
+    // (the kernel reads the flag of every row's node: a coupled context of fedd_fsi_merge has rows and no nodes)
+    FEDD_CHECK(c->n_node > 0 && c->n_rows <= (int64_t)c->dofs * c->n_node,
+               "fedd_dirichlet_rhs: this context carries no mesh (a coupled context of fedd_fsi_merge never does), or its system has "
+               "more rows than its mesh has dofs: the call needs the flags of the nodes of a fedd_mesh_set");
     FEDD_CHECK(n_bc >= 0 && n_bc <= MAX_BC, "fedd_dirichlet_rhs: at most %d boundary conditions", MAX_BC);
     FEDD_CHECK(n_bc == 0 || (flags && values), "fedd_dirichlet_rhs: null array");
     FEDD_HIP(hipSetDevice(c->device));

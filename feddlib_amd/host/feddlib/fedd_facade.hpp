@@ -48,6 +48,10 @@ typedef std::vector<std::vector<double>> vec2D_dbl_Type;
 typedef Teuchos::RCP<vec_dbl_Type> vec_dbl_ptr_Type;
 typedef Teuchos::RCP<vec_int_Type> vec_int_ptr_Type;
 typedef Teuchos::RCP<vec2D_dbl_Type> vec2D_dbl_ptr_Type;
+typedef std::vector<default_go> vec_GO_Type;
+typedef std::vector<vec_GO_Type> vec2D_GO_Type;
+typedef std::vector<vec2D_GO_Type> vec3D_GO_Type;
+typedef Teuchos::RCP<vec3D_GO_Type> vec3D_GO_ptr_Type;
 typedef Teuchos::RCP<Teuchos::ParameterList> ParameterListPtr_Type;
 // feddlib/core/FEDDCore.hpp:115-118 (boost::function there)
 typedef std::function<void(double* x, double* res, double* parameters)> RhsFunc_Type;
@@ -613,10 +617,16 @@ public:
     }
     // Domain::identifyInterfaceParallelAndDistance (Domain_def.hpp:553-566 -> MeshUnstructured::buildMeshInterfaceParallelAndDistance
     // -> MeshInterface_def.hpp:217-491): the interface of this domain is its set of nodes with one of the flags.  Per flag both
-    // domains must hold the same number of such nodes (the reference's check, MeshInterface_def.hpp:254).  The matched index
-    // tables (indicesGlobalMatched_) and the interface maps are NOT built: nothing here reads them.  The distances of every
-    // repeated node to the interface are computed on the device, on the points in force, and given to every context the
-    // domain is uploaded to, now and at a later uploadMeshTo.  One rank (the device call says so).
+    // domains must hold the same number of such nodes (the reference's check, MeshInterface_def.hpp:254).  The two sides are
+    // matched on the device (fedd_interface_match: per flag, both sides ordered lexicographically by their reference
+    // coordinates and paired by rank); the tables (indicesGlobalMatched_) and the interface maps (buildInterfaceMaps) are kept.
+    // This domain is the FLUID side of the device's table and domainOther the structure side, unless domainOther has already
+    // identified its interface against this domain with the same flags: then that table stands and is read with the sides
+    // exchanged, so that fluid->identify(structure) followed by structure->identify(fluid), as the reference's FSI main
+    // calls them, leaves ONE table with the fluid as its fluid side.  A domain given as its own other side (the geometry
+    // driver) has nobody to be paired with: no tables, and the getters below say so.  The distances of every repeated node to
+    // the interface are computed on the device, on the points in force, and given to every context the domain is uploaded
+    // to, now and at a later uploadMeshTo.  One rank (the device calls say so).
     void identifyInterfaceParallelAndDistance(Teuchos::RCP<Domain> domainOther, vec_int_Type interfaceID_vec) {
         TEUCHOS_TEST_FOR_EXCEPTION(domainOther.is_null(), std::runtime_error, "identifyInterfaceParallelAndDistance: domainOther is null.");
         for (size_t k = 0; k < interfaceID_vec.size(); ++k) {
@@ -627,10 +637,102 @@ public:
                                        "DetermineInterfaceInParallel failed. ThisMesh and OtherMesh seem to have different numbers of interface nodes."
                                        " (flag " << flag << ": " << nThis << " against " << nOther << ")");
         }
+        matchInterface(*domainOther, interfaceID_vec);
         interfaceFlags_.assign(interfaceID_vec.begin(), interfaceID_vec.end());
         haveInterfaceFlags_ = true;
         calculateDistancesToInterface();
     }
+    bool hasMatchedInterface() const { return !indicesGlobalMatched_.empty(); }
+    bool isFluidSideOfMatch() const { return matchThisIsFluid_; }
+    // MeshInterface::getIndicesGlobalMatched (MeshInterface_def.hpp:539-553): [flag][0: this domain, 1: the other domain][j],
+    // global node ids of pair j of the flag, each in its own domain's numbering.  On one rank the reference's "origin" and
+    // "unique" tables are this table.
+    vec3D_GO_ptr_Type getIndicesGlobalMatched() const {
+        needMatch("getIndicesGlobalMatched");
+        return Teuchos::rcp(new vec3D_GO_Type(indicesGlobalMatched_));
+    }
+    vec3D_GO_ptr_Type getIndicesGlobalMatchedOrigin() const { return getIndicesGlobalMatched(); }
+    vec3D_GO_ptr_Type getIndicesGlobalMatchedUnique() const { return getIndicesGlobalMatched(); }
+    // the same pairs as the device holds them: local unique node ids of this domain, the flags concatenated (interface
+    // dof dim * k + c is component c of pair k); what fedd_dirichlet_nodes wants for the FaCSI rows of the fluid
+    const std::vector<int32_t>& interfaceNodesLocal() const { needMatch("interfaceNodesLocal"); return interfaceLocal_; }
+    // Domain::setPartialCoupling (Domain_def.hpp:766-771 -> MeshInterface::setPartialCoupling): interface nodes of this
+    // flag couple only in the components the type names.  The interface maps are built again if they stand.
+    void setPartialCoupling(int flag, std::string type) {
+        partialCouplingFlag_.push_back(flag);
+        partialCouplingType_.push_back(type);
+        if (hasMatchedInterface()) buildInterfaceMaps();
+    }
+    // Domain::buildInterfaceMaps (Domain_def.hpp:774-876) on one rank; identifyInterfaceParallelAndDistance has called it.
+    //   interface map            0 .. n-1, the interface numbering (position in the concatenated table)
+    //   global interface map     this domain's global node id of every interface node, in interface order
+    //   other global ...         the other domain's global node id of the same pair
+    // and their vector-field maps dim * id + c.  With partial coupling the vector-field maps still list every component (the
+    // uncoupled ones are the dummy dofs of assemblyDummyCoupling), the interface vector-field map is 0 .. dim n - 1, and the
+    // "partial" maps list the coupled components only; the type the reference builds is "X_Y" in 3D.
+    void buildInterfaceMaps() {
+        needMatch("buildInterfaceMaps");
+        std::vector<GO> vecGlobal, vecOther, vecInterface;
+        std::vector<int> vecFlag;
+        LO localID = 0;
+        for (size_t i = 0; i < indicesGlobalMatched_.size(); ++i)
+            for (size_t j = 0; j < indicesGlobalMatched_[i][0].size(); ++j) {
+                const LO index = mapUnique_->getLocalElement(indicesGlobalMatched_[i][0][j]);
+                if (index != (LO)-1) {
+                    vecGlobal.push_back(indicesGlobalMatched_[i][0][j]);
+                    vecOther.push_back(indicesGlobalMatched_[i][1][j]);
+                    vecInterface.push_back((GO)localID);
+                    vecFlag.push_back(flagUni_[(size_t)index]);
+                }
+                ++localID;
+            }
+        globalInterfaceMapUnique_ = Teuchos::rcp(new Map_Type(vecGlobal, comm_));
+        interfaceMapUnique_ = Teuchos::rcp(new Map_Type(vecInterface, comm_));
+        otherGlobalInterfaceMapUnique_ = Teuchos::rcp(new Map_Type(vecOther, comm_));
+        partialGlobalInterfaceVecFieldMap_ = Teuchos::null;
+        otherPartialGlobalInterfaceVecFieldMap_ = Teuchos::null;
+        interfaceCoupled_.assign(vecGlobal.size() * (size_t)dim_, 1);
+        if (partialCouplingFlag_.empty()) {
+            globalInterfaceMapVecFieldUnique_ = globalInterfaceMapUnique_->buildVecFieldMap(dim_);
+            interfaceMapVecFieldUnique_ = interfaceMapUnique_->buildVecFieldMap(dim_);
+            otherGlobalInterfaceMapVecFieldUnique_ = otherGlobalInterfaceMapUnique_->buildVecFieldMap(dim_);
+            return;
+        }
+        const GO numDofs = dim_;
+        std::vector<GO> field, fieldPartial, otherField, otherFieldPartial, fieldInterface;
+        for (size_t i = 0; i < vecGlobal.size(); ++i) {
+            const int loc = isPartialCouplingFlag(vecFlag[i]);
+            TEUCHOS_TEST_FOR_EXCEPTION(loc > -1 && !(partialCouplingType_[(size_t)loc] == "X_Y" && dim_ == 3), std::runtime_error,
+                                       "Implement other partial coupling types.");
+            for (GO dof = 0; dof < numDofs; ++dof) {
+                const bool coupled = loc < 0 || dof < 2;        // "X_Y": the z component is a dummy dof
+                field.push_back(numDofs * vecGlobal[i] + dof);
+                otherField.push_back(numDofs * vecOther[i] + dof);
+                fieldInterface.push_back((GO)fieldInterface.size());
+                if (coupled) {
+                    fieldPartial.push_back(numDofs * vecGlobal[i] + dof);
+                    otherFieldPartial.push_back(numDofs * vecOther[i] + dof);
+                }
+                interfaceCoupled_[i * (size_t)dim_ + (size_t)dof] = coupled ? 1 : 0;
+            }
+        }
+        globalInterfaceMapVecFieldUnique_ = Teuchos::rcp(new Map_Type(field, comm_));
+        otherGlobalInterfaceMapVecFieldUnique_ = Teuchos::rcp(new Map_Type(otherField, comm_));
+        interfaceMapVecFieldUnique_ = Teuchos::rcp(new Map_Type(fieldInterface, comm_));
+        partialGlobalInterfaceVecFieldMap_ = Teuchos::rcp(new Map_Type(fieldPartial, comm_));
+        otherPartialGlobalInterfaceVecFieldMap_ = Teuchos::rcp(new Map_Type(otherFieldPartial, comm_));
+    }
+    MapConstPtr_Type getInterfaceMapUnique() const { needMatch("getInterfaceMapUnique"); return interfaceMapUnique_; }
+    MapConstPtr_Type getInterfaceMapVecFieldUnique() const { needMatch("getInterfaceMapVecFieldUnique"); return interfaceMapVecFieldUnique_; }
+    MapConstPtr_Type getGlobalInterfaceMapUnique() const { needMatch("getGlobalInterfaceMapUnique"); return globalInterfaceMapUnique_; }
+    MapConstPtr_Type getGlobalInterfaceMapVecFieldUnique() const { needMatch("getGlobalInterfaceMapVecFieldUnique"); return globalInterfaceMapVecFieldUnique_; }
+    MapConstPtr_Type getOtherGlobalInterfaceMapUnique() const { needMatch("getOtherGlobalInterfaceMapUnique"); return otherGlobalInterfaceMapUnique_; }
+    MapConstPtr_Type getOtherGlobalInterfaceMapVecFieldUnique() const { needMatch("getOtherGlobalInterfaceMapVecFieldUnique"); return otherGlobalInterfaceMapVecFieldUnique_; }
+    // null without partial coupling, as in the reference (FSI::assemble asks is_null())
+    MapConstPtr_Type getGlobalInterfaceMapVecFieldPartial() const { return partialGlobalInterfaceVecFieldMap_; }
+    MapConstPtr_Type getOtherGlobalInterfaceMapVecFieldPartial() const { return otherPartialGlobalInterfaceVecFieldMap_; }
+    // one byte per interface dof, 0 = a dummy dof of the partial coupling: the coupled_mask of fedd_fsi_merge
+    const std::vector<uint8_t>& interfaceCoupledMask() const { needMatch("interfaceCoupledMask"); return interfaceCoupled_; }
     // Domain::calculateDistancesToInterface (Domain_def.hpp:568-648) with the flags of the last identify call
     void calculateDistancesToInterface() {
         TEUCHOS_TEST_FOR_EXCEPTION(!haveInterfaceFlags_, std::runtime_error,
@@ -737,6 +839,7 @@ private:
             uniOfRep_[i] = it->second;
         }
         dev_ = Teuchos::rcp(new DeviceContext(comm_));
+        clearMatch();       // (a new mesh: the device has released the table with the old context)
         rowGhostRep_.clear();
         rowGhostFlag_.clear();
         if (rowGhost) {     // their repeated-local ids (coordinates) and flags: the Dirichlet treatment covers their rows too
@@ -754,6 +857,63 @@ private:
         else
             feddCheck(fedd_mesh_set(dev_->ctx, dim_, nen_, (int64_t)(conn_.size() / nen_), conn_.data(), (int64_t)grep.size(), xyz_.data(),
                                     grep.data(), (int64_t)guni.size(), guni.data(), flagUni_.data()), "fedd_mesh_set");
+    }
+    void needMatch(const char* who) const {
+        TEUCHOS_TEST_FOR_EXCEPTION(indicesGlobalMatched_.empty(), std::runtime_error,
+                                   "Domain::" << who << ": no matched interface; call identifyInterfaceParallelAndDistance with the other "
+                                   "domain first (a domain given as its own other side is not matched)");
+    }
+    int isPartialCouplingFlag(int flag) const {      // MeshInterface::isPartialCouplingFlag: the position, or -1
+        auto it = std::find(partialCouplingFlag_.begin(), partialCouplingFlag_.end(), flag);
+        return it == partialCouplingFlag_.end() ? -1 : (int)std::distance(partialCouplingFlag_.begin(), it);
+    }
+    void clearMatch() {
+        indicesGlobalMatched_.clear();
+        interfaceLocal_.clear();
+        interfaceCoupled_.clear();
+        matchFlags_.clear();
+        matchPartner_.reset();
+        matchThisIsFluid_ = false;
+        interfaceMapUnique_ = interfaceMapVecFieldUnique_ = globalInterfaceMapUnique_ = globalInterfaceMapVecFieldUnique_ = Teuchos::null;
+        otherGlobalInterfaceMapUnique_ = otherGlobalInterfaceMapVecFieldUnique_ = Teuchos::null;
+        partialGlobalInterfaceVecFieldMap_ = otherPartialGlobalInterfaceVecFieldMap_ = Teuchos::null;
+    }
+    // the device's table between this domain's context and the other's, into indicesGlobalMatched_ and the maps
+    void matchInterface(Domain& other, const vec_int_Type& interfaceID_vec) {
+        if (&other == this) {
+            clearMatch();
+            return;
+        }
+        fedd_ctx *mine = dev_->ctx, *theirs = other.dev_->ctx;
+        const std::vector<int32_t> flags(interfaceID_vec.begin(), interfaceID_vec.end());
+        int haveMine = 0, haveTheirs = 0;
+        feddCheck(fedd_interface_match_info(mine, &haveMine, nullptr, nullptr, nullptr), "fedd_interface_match_info");
+        feddCheck(fedd_interface_match_info(theirs, &haveTheirs, nullptr, nullptr, nullptr), "fedd_interface_match_info");
+        // the other domain matched itself (as the fluid side) against this one with these flags, and both contexts still hold it
+        const bool stands = haveMine && haveTheirs && other.matchThisIsFluid_ && other.matchFlags_ == flags &&
+                            other.matchPartner_.lock().get() == dev_.get() && other.hasMatchedInterface();
+        clearMatch();
+        if (!stands) feddCheck(fedd_interface_match(mine, theirs, (int)flags.size(), flags.data()), "fedd_interface_match");
+        int64_t nPairs = 0;
+        int nFlags = 0;
+        feddCheck(fedd_interface_match_sizes(mine, &nPairs, &nFlags, nullptr), "fedd_interface_match_sizes");
+        TEUCHOS_TEST_FOR_EXCEPTION(nFlags != (int)flags.size(), std::logic_error, "identifyInterfaceParallelAndDistance: the device's table has other flags");
+        std::vector<int32_t> idFluid((size_t)nPairs), idStructure((size_t)nPairs);
+        std::vector<int64_t> ptr((size_t)nFlags + 1);
+        feddCheck(fedd_interface_match_get(mine, idFluid.data(), idStructure.data(), ptr.data()), "fedd_interface_match_get");
+        const std::vector<int32_t>& idThis = stands ? idStructure : idFluid;
+        const std::vector<int32_t>& idOther = stands ? idFluid : idStructure;
+        indicesGlobalMatched_.assign((size_t)nFlags, vec2D_GO_Type(2));
+        for (int q = 0; q < nFlags; ++q)
+            for (int64_t k = ptr[(size_t)q]; k < ptr[(size_t)q + 1]; ++k) {     // device node id = local id of the unique map
+                indicesGlobalMatched_[(size_t)q][0].push_back(mapUnique_->getGlobalElement((LO)idThis[(size_t)k]));
+                indicesGlobalMatched_[(size_t)q][1].push_back(other.mapUnique_->getGlobalElement((LO)idOther[(size_t)k]));
+            }
+        interfaceLocal_ = idThis;
+        matchFlags_ = flags;
+        matchPartner_ = other.dev_.shared();
+        matchThisIsFluid_ = !stands;
+        buildInterfaceMaps();
     }
     void distributeDistances() {     // to the contexts of uploadMeshTo, as moveMesh does for the displacement
         for (auto& w : uploads_)
@@ -780,6 +940,18 @@ private:
     std::vector<double> dist_;                  // distances to the interface on the repeated map (empty: none)
     std::vector<int32_t> interfaceFlags_;       // the flags of the last identifyInterfaceParallelAndDistance
     bool haveInterfaceFlags_ = false;
+    // the matched interface (identifyInterfaceParallelAndDistance against another domain; empty: none)
+    vec3D_GO_Type indicesGlobalMatched_;        // [flag][0: this, 1: other][j] global node ids
+    std::vector<int32_t> interfaceLocal_;       // this side of the device's table: local unique node ids, flags concatenated
+    std::vector<int32_t> matchFlags_;
+    std::weak_ptr<DeviceContext> matchPartner_; // the other domain's context at the time of the match
+    bool matchThisIsFluid_ = false;             // this domain's context is the fluid side of the device's table
+    vec_int_Type partialCouplingFlag_;
+    std::vector<std::string> partialCouplingType_;
+    std::vector<uint8_t> interfaceCoupled_;
+    Teuchos::RCP<Map_Type> interfaceMapUnique_, interfaceMapVecFieldUnique_, globalInterfaceMapUnique_, globalInterfaceMapVecFieldUnique_,
+        otherGlobalInterfaceMapUnique_, otherGlobalInterfaceMapVecFieldUnique_, partialGlobalInterfaceVecFieldMap_,
+        otherPartialGlobalInterfaceVecFieldMap_;
     std::vector<double> xyzRef_, disp_;         // moveMesh: the points the mesh was built with, the displacement in force (empty: never moved)
     mutable std::vector<std::weak_ptr<DeviceContext> > uploads_;     // contexts of uploadMeshTo
     int volumeID_ = 10;

@@ -107,7 +107,10 @@ enum fedd_timer {
     FEDD_T_MESH_MOVE = 29,  /* fedd_mesh_move: k_mesh_move, candidate = x_ref + d (mesh_move.hip)  */
     FEDD_T_MOVE_CHECK = 30, /* ... k_move_check + k_move_min, det B of every element against the reference */
     FEDD_T_INTERFACE_DIST = 31, /* fedd_interface_distance*: k_interface_distance (interface_distance.hip) */
-    FEDD_T_COUNT    = 32
+    FEDD_T_FSI_MATCH = 32,  /* fedd_interface_match: k_iface_rank + k_iface_scatter (fsi.hip)            */
+    FEDD_T_FSI_MERGE = 33,  /* fedd_fsi_merge: count / fill / values kernels of the four-block system     */
+    FEDD_T_FSI_APPLY = 34,  /* FaCSI apply: k_facsi_inject + k_facsi_rows (the children's applies are SCHWARZ_APPLY of theirs) */
+    FEDD_T_COUNT    = 35
 };
 
 /* ------------------------------------------------------------------------------------------------
@@ -394,7 +397,8 @@ int fedd_mesh_coords_get(fedd_ctx* ctx, double* xyz_rep);
  * Errors: a host-only context ("needs a GPU context"), no mesh, more than one rank, n_pts < 0, n_flags < 0, _get without
  * distances; the assembly without distances (the message names fedd_interface_distance), with params == NULL, on another
  * pattern.  Each is a message, never a device fault.
- * Left out: the matched interface index tables and interface maps, recomputing the distances on the moved mesh, more than one rank.
+ * Left out: recomputing the distances on the moved mesh, more than one rank.  (The matched interface tables are "FSI coupling"
+ * below.)
  * ---------------------------------------------------------------------------------------------- */
 int fedd_interface_distance(fedd_ctx* ctx, int n_flags, const int32_t* flags, int64_t* n_interface);
 int fedd_interface_distance_points(fedd_ctx* ctx, int64_t n_pts, const double* xyz_pts);
@@ -1055,6 +1059,102 @@ int fedd_matrix_import(fedd_ctx* dst, fedd_ctx* src, int src_slot);
 int fedd_block_prec_attach(fedd_ctx* ctx, int kind, fedd_ctx* velocity, fedd_ctx* schur, double schur_scale, int slot_bt);
 int fedd_block_prec_detach(fedd_ctx* ctx);
 int fedd_block_prec_info(fedd_ctx* ctx, int* kind, double* schur_scale, int* slot_bt, int64_t* n_applies);
+
+/* ------------------------------------------------------------------------------------------------
+ * FSI coupling (one rank, geometry-explicit, four blocks): the matched interface of a fluid and a structure context, the
+ * coupled system, and the FaCSI preconditioner.  Replaces MeshInterface::determineInterfaceParallelAndDistance
+ * (feddlib/core/Mesh/MeshInterface_def.hpp), FE::assemblyFSICoupling / FE::assemblyDummyCoupling as FSI::assemble places them
+ * (feddlib/problems/specific/FSI_def.hpp:223-318), FSI::addInterfaceBlockRHS, Preconditioner::buildPreconditionerFaCSI
+ * (Preconditioner_def.hpp:789-971) and the geometry-explicit branch of PrecOpFaCSI::applyImpl (PrecOpFaCSI_def.hpp:367-589).
+ * The FSI problem class, its TimeProblem and advanceInTimeFSI are NOT built; these entries are what they will call.
+ *
+ *     [ F    B^T  0    C1^T ] [u]        C1   : n_l x n_u, +1 at (lambda-dof, fluid interface dof)
+ *     [ B    C    0    0    ] [p]        C1^T : its transpose
+ *     [ 0    0    S    C3^T ] [d]        C2   : -(1/dt) at (lambda-dof, structure interface dof)
+ *     [ C1   0    C2   D    ] [l]        C3^T : -1 at (structure interface dof, lambda-dof)
+ *                                        D    : 1 on the diagonal of uncoupled lambda-dofs (assemblyDummyCoupling), else no entry
+ *
+ * NORMATIVE -- the match.  fedd_interface_match(fluid, structure, n_flags, flags): per flag, in the order given, the nodes of
+ * each context that carry the flag (bcflag_uni of fedd_mesh_set), at the REFERENCE coordinates (those of the last
+ * fedd_mesh_set*, not the moved ones), ordered lexicographically by (x, y[, z]) with exact double comparison and paired by
+ * rank -- the reference's std::sort on vec_dbl followed by pairing by position.  The result is two tables of owned
+ * (unique-map) node ids in interface order, iface_f[k] and iface_s[k], the flags concatenated; interface dof dim * k + c is
+ * component c of pair k.  They are formed on the device (rank, then scatter) and read back once: what is kept are the host
+ * copies, which fedd_interface_match_get serves and from which fedd_fsi_merge derives the dof maps its kernels read; no kernel
+ * reads the tables themselves.  Both contexts keep a reference to the same table.  The call first releases the earlier match of
+ * BOTH contexts; a call that then fails (unequal counts, identical coordinates, ...) leaves both without one.  The rank is formed by counting,
+ * rank_i = #{ j : p_j <lex p_i }, one lane per interface node against LDS tiles of 1024 points: deterministic, quadratic in the
+ * interface only.  Paired points need NOT coincide (the reference does not check it): fedd_interface_match_info returns the
+ * largest Euclidean distance between paired points so that a caller can.
+ *   fedd_interface_match_sizes  pairs, flags of the match, dofs per interface node (= dim); on either context of the match.
+ *   fedd_interface_match_get    iface_f[n], iface_s[n], flag_ptr[n_flags + 1] (the pairs of flag i are [flag_ptr[i], flag_ptr[i + 1]));
+ *                               outputs may be NULL.
+ *   fedd_interface_match_info   have (0 / 1), pairs, the largest pair distance, the points per LDS tile.  Needs no device.
+ * Lifetime: fedd_mesh_move KEEPS the table; fedd_mesh_set* on either context releases it on both, and a coupled system built on
+ * it is an error at the next fedd_fsi_merge and at the next FaCSI apply -- never a dangling pointer.  At the apply a
+ * fedd_mesh_set* on a child is reported as "the merge is older than the <child>'s mesh", a table released by a new
+ * fedd_interface_match as "the matched interface ... has been released".
+ * Errors that name the cause: different counts per flag (the flag and both counts), two nodes of one side with identical
+ * coordinates (both node ids), an empty interface, contexts on different devices, more than one rank, a host-only context
+ * ("needs a GPU context"), a context without a mesh, the same context twice, meshes of different dimension.
+ *
+ * The coupled context is an ordinary fedd_ctx that never gets a mesh: system matrix, right-hand side, solution and Dirichlet
+ * marks are those of the four-block system; fedd_gmres*, fedd_spmv, fedd_csr_get, fedd_rhs_* work on it as on any system; the
+ * entries that need a mesh refuse it by name.
+ *   fedd_fsi_merge(cpl, fluid, structure, dt, coupled_mask)
+ *       cpl's system <- the merged CSR of fluid's current system (the merged [F B^T; B C] of fedd_block_merge with its wall
+ *       Dirichlet rows applied; an unmerged fluid is an error), structure's current system, and the coupling entries; device to
+ *       device, ordered as fedd_matrix_import orders its copies; columns ascending within a row.  Rows that are Dirichlet rows of
+ *       fluid / structure stay unit rows and get NO C1^T / C3^T entry (setBoundariesSystem on the block system); their marks are
+ *       copied, lambda-rows carry none.  The children's right-hand sides are copied, the lambda part is zero, the solution is
+ *       zeroed.  coupled_mask[n_l] (bytes; NULL = all coupled): 0 makes lambda-dof k uncoupled -- no entries in C1, C1^T, C2, C3^T
+ *       and a 1 on the lambda diagonal.  The coupling values are exactly 1.0, -1.0 and -(1.0 / dt).  A second merge of the same
+ *       children whose patterns, Dirichlet marks on the interface, match and mask have not changed moves values only and keeps
+ *       cpl's pattern generation (the rule of fedd_matrix_import); fedd_fsi_info reports it.
+ *       Errors: dt <= 0, no match between exactly these two contexts (or a released one), a child without a system, an
+ *       unmerged fluid, more than one rank, other devices, a host-only context.
+ *   fedd_fsi_interface_rhs(cpl, d_old_structure[n_s])
+ *       rhs_l[k] = (-(1.0 / dt)) * d_old[sdof(k)] on coupled dofs, 0 elsewhere (FSI::addInterfaceBlockRHS, C2 d_s^n); the
+ *       coefficient is formed first, the product rounded once.
+ *   fedd_fsi_info  n_u, n_p, n_s, n_l, offsets[4] of the blocks u, p, d, l in the vectors, whether the last merge moved values
+ *       only, merges that did since the context was made.  Needs no device; outputs may be NULL.
+ *
+ * NORMATIVE -- FaCSI.  fedd_fsi_prec_attach(cpl, fluid, structure) / _detach / _info, with the ownership and ordering rules of
+ * fedd_block_prec_attach: the children are not owned, destroying an attached child detaches, the children's apply kernels run
+ * in cpl's stream behind one event per child setup, no host synchronisation in the Krylov loop.  While attached, fedd_gmres[_x0]
+ * with use_prec = 1 and fedd_schwarz_apply[_device] on cpl apply (PrecOpFaCSI_def.hpp:414-589), with S~ and F~ the children's
+ * Schwarz applies (F~ the monolithic one on fluid's merged velocity-pressure system), c2 = -(1.0 / dt):
+ *     y_d       = S~(x_d)
+ *     g_k       = x_l,k - c2 * y_d[sdof(k)]                      coupled k   (Y_l = X_l - C2 Y_s; the product is rounded first)
+ *     t         = [x_u; x_p] with t_u[fdof(k)] <- g_k            coupled k   (the two C1^T updates of :504-507)
+ *     [y_u;y_p] = F~(t)
+ *     z_r       = (x_u,r - (B^T y_p)_r) - (F y_u)_r              on the rows r = fdof(k) only; F, B^T as they stand in cpl's CSR
+ *     y_l,k     = z_fdof(k)                                      coupled k
+ *     y_l,k     = x_l,k                                          uncoupled k
+ * The last line DEVIATES from the reference, which returns 0 there and so makes the operator singular.  The C3^T coupling of
+ * the d block is dropped, as in the reference: with exact child inverses A P^-1 x equals x in the u, p and l blocks and differs
+ * by C3^T y_l in the d block.  g and the injection are one kernel; z and y_l are one kernel with a group of 8 lanes (16 for rows
+ * of more than 32 entries) per interface row over cpl's CSR, columns < n_u + n_p only: the two row sums are formed separately,
+ * each lane adds its products in ascending column order, one fixed tree per sum, no contraction -- two applies agree bit for bit
+ * whenever the children's do.  Only n_l rows of F and B^T are read, not the whole blocks.
+ * The caller gives fluid homogeneous Dirichlet rows on the interface velocity dofs AFTER the merge and BEFORE
+ * fedd_schwarz_setup(fluid): the reference's faCSIBCFactory_.  On the merged fluid system that is fedd_dirichlet_rows with the
+ * rows dim * iface_f[k] + c of the table of fedd_interface_match_get (fedd_dirichlet_nodes addresses one dof per node of a
+ * merged system).  The attach does not do it.
+ * Checked at every apply, with errors that name the child: a child without a current fedd_schwarz_setup, sizes that no longer
+ * fit the merge, a merge older than a child's mesh, a released match, FEDD_LEVELS_MULTIPLICATIVE children.
+ * ---------------------------------------------------------------------------------------------- */
+int fedd_interface_match(fedd_ctx* fluid, fedd_ctx* structure, int n_flags, const int32_t* flags);
+int fedd_interface_match_sizes(fedd_ctx* ctx, int64_t* n_pairs, int* n_flags, int* dofs_per_node);
+int fedd_interface_match_get(fedd_ctx* ctx, int32_t* iface_fluid, int32_t* iface_structure, int64_t* flag_ptr);
+int fedd_interface_match_info(fedd_ctx* ctx, int* have, int64_t* n_pairs, double* max_pair_distance, int* tile_points);
+int fedd_fsi_merge(fedd_ctx* cpl, fedd_ctx* fluid, fedd_ctx* structure, double dt, const uint8_t* coupled_mask);
+int fedd_fsi_interface_rhs(fedd_ctx* cpl, const double* d_old_structure);
+int fedd_fsi_info(fedd_ctx* cpl, int64_t* n_u, int64_t* n_p, int64_t* n_s, int64_t* n_l, int64_t* offsets, int* last_values_only,
+                  int64_t* n_values_only);
+int fedd_fsi_prec_attach(fedd_ctx* cpl, fedd_ctx* fluid, fedd_ctx* structure);
+int fedd_fsi_prec_detach(fedd_ctx* cpl);
+int fedd_fsi_prec_info(fedd_ctx* cpl, int* attached, int64_t* n_applies);
 /* The structures that depend on the mesh alone are built once per mesh, at the first call that needs them, and reused by every
  * later assembly: the node -> element adjacency (fedd_pattern_build) and the element-major tile structures of the assembly
  * kernel (fedd_assemble, P1 forms).  Their wall time (ms, device synchronised before and after) is not part of a steady-state
