@@ -163,6 +163,9 @@ SIGNATURES = {
     "fedd_timing_get": [C.c_void_p, C.c_int, _f64p, _i64p],
     "fedd_timing_get_sampled": [C.c_void_p, C.c_int, _f64p, _i64p, _f64p],
     "fedd_gmres_info": [C.c_void_p, _ip, _ip, _ip, _ip],
+    "fedd_gmres_capture_arm": [C.c_void_p, C.c_int],
+    "fedd_gmres_capture_info": [C.c_void_p, _i64p],
+    "fedd_gmres_capture_get": [C.c_void_p, C.c_char_p, _f64p, C.c_int64],
     "fedd_gmres_fused_blocks": [C.c_void_p, C.POINTER(C.c_int)],
     "fedd_gmres_x0": [C.c_void_p, _f64p, _f64p, C.c_double, C.c_int, C.c_int, C.c_int, _ip, _f64p],
     "fedd_gmres_status": [C.c_void_p, _ip, _f64p],
@@ -1220,6 +1223,39 @@ class Context:
         _chk(self._L.fedd_gmres_info(self._h, C.byref(k), C.byref(s), C.byref(nb), C.byref(nc)))
         _chk(self._L.fedd_gmres_fused_blocks(self._h, C.byref(nf)))
         return {"kind": k.value, "s": s.value, "blocks": nb.value, "cut_blocks": nc.value, "fused_blocks": nf.value}
+
+    CAPTURE_PIECES = ("V0", "C0", "P1", "CF1", "RI1", "SA1", "W1", "P2", "CF2", "RI2", "SA2", "TH", "W2", "H", "VEND")
+
+    def gmres_capture_arm(self, block):
+        """copy the block-th orthogonalised block of the next s-step solve stage by stage (block < 0: disarm, free the copies)"""
+        if int(block) != block:
+            raise ValueError("gmres_capture_arm: block must be an integer, got %r" % (block,))
+        _chk(self._L.fedd_gmres_capture_arm(self._h, int(block)))
+
+    def gmres_capture_info(self):
+        v = np.zeros(8, dtype=np.int64)
+        _chk(self._L.fedd_gmres_capture_info(self._h, _p(v, _i64p)))
+        names = ("captured", "n", "ldv", "k", "sa_req", "S", "m", "fused")
+        return {k: int(x) for k, x in zip(names, v)}
+
+    def gmres_capture_get(self, what, cap=None):
+        """one piece of the captured block, shaped: basis pieces (ldv, columns) column-major, coefficient pieces (rows, S),
+        H (m + 1, columns) column-major, SA1 / SA2 / TH flat.  cap: doubles to make room for (default: what the piece takes)"""
+        if what not in self.CAPTURE_PIECES:
+            raise ValueError("gmres_capture_get: no piece is named %r (pieces: %s)" % (what, " ".join(self.CAPTURE_PIECES)))
+        i = self.gmres_capture_info()
+        k, sa, S, ldv, m = i["k"], i["sa_req"], i["S"], i["ldv"], i["m"]
+        can = 1 if k + sa <= m else 0
+        sa2 = 0
+        if what in ("H", "VEND") and i["captured"]:
+            sa2 = int(self.gmres_capture_get("SA2")[0])
+        shape = {"V0": (k + sa, ldv), "C0": (1, ldv), "P1": (k + sa, S), "P2": (k + sa, S), "CF1": (k, S), "CF2": (k, S),
+                 "RI1": (S, S), "RI2": (S, S), "SA1": (1,), "SA2": (2,), "TH": (S,), "W1": (sa + can, ldv), "W2": (sa + can, ldv),
+                 "H": (k - 1 + max(sa2, 1), m + 1), "VEND": (k + sa2, ldv)}[what]
+        out = np.zeros(max(int(np.prod(shape)) if cap is None else int(cap), 1))
+        _chk(self._L.fedd_gmres_capture_get(self._h, what.encode(), _p(out, _f64p), out.shape[0] if cap is None else int(cap)))
+        out = out[:int(np.prod(shape))].reshape(shape)
+        return out.T if what in ("V0", "C0", "W1", "W2", "H", "VEND") else out
 
     def read_bandwidth(self, nbytes=2 << 30, reps=10):
         """GB/s of a read-only stream on this GPU (roofline calibration)."""

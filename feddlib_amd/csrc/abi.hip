@@ -1319,6 +1319,24 @@ extern "C" int fedd_gmres_fused_blocks(fedd_ctx* c, int* blocks) {
     return 0;
 }
 
+extern "C" int fedd_gmres_capture_arm(fedd_ctx* c, int block) {
+    FEDD_CHECK(c, "fedd_gmres_capture_arm: null context");
+    return fedd::gmres_capture_arm(c, block);
+}
+
+extern "C" int fedd_gmres_capture_info(fedd_ctx* c, int64_t* out) {
+    FEDD_CHECK(c && out, "fedd_gmres_capture_info: null argument");
+    const fedd::GmresCapture& g = c->gm_cap;
+    const int64_t v[8] = {g.captured ? 1 : 0, g.n, g.ldv, g.k, g.sa_req, g.S, g.m, g.fused};
+    std::copy(v, v + 8, out);
+    return 0;
+}
+
+extern "C" int fedd_gmres_capture_get(fedd_ctx* c, const char* what, double* out, int64_t cap) {
+    FEDD_CHECK(c && what && out, "fedd_gmres_capture_get: null argument");
+    return fedd::gmres_capture_get(c, what, out, cap);
+}
+
 extern "C" int fedd_halo_plan_sizes(fedd_ctx* c, int* n_peers, int64_t* n_send_total, int64_t* n_recv_total) {
     FEDD_CHECK(c, "null context");
     if (n_peers) *n_peers = (int)c->halo.peers.size();

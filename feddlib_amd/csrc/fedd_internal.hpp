@@ -216,6 +216,20 @@ struct IfaceTable {
     double max_dist = 0.0;                      // largest distance between paired points
 };
 
+// One block of an s-step solve, copied stage by stage (fedd_gmres_capture_*): device-to-device copies on the solver's stream
+// between the launches the block makes anyway.  `buf` holds the pieces one behind the other, piece i at off[i] with len[i]
+// doubles (the two d_sa values are stored as int32 in a double's slot); len 0 = not captured.
+struct GmresCapture {
+    enum Piece { V0, C0, P1, CF1, RI1, SA1, W1, P2, CF2, RI2, SA2, TH, W2, H, VEND, NPIECE };
+    int armed = -1;                             // block of the next s-step solve to copy (counted by gmres_blocks); -1: none
+    bool captured = false;
+    int64_t n = 0, ldv = 0;
+    int k = 0, sa_req = 0, S = 0, m = 0, fused = 0;
+    int canary = 0;                             // the basis has a column behind the block (k + sa_req <= m): W1 / W2 carry it
+    size_t off[NPIECE] = {}, len[NPIECE] = {};
+    DevBuf<double> buf;
+};
+
 }  // namespace fedd
 
 struct fedd_ctx {
@@ -572,6 +586,7 @@ struct fedd_ctx {
     int multi_ch = 4;                           // option "multi_ch": matrix-core steps per flight of gathers in k_apply_multi (4, 8, 16)
     int pat_hash = 1;                           // option "pat_hash": 1 = hashed node-pattern merge for vertex-only elements (symbolic.hip)
     int gmres_fused_blocks = 0;                 // blocks of the last s-step solve whose first update and second dot ran as one sweep
+    fedd::GmresCapture gm_cap;                  // fedd_gmres_capture_*: one block of an s-step solve, stage by stage (tests)
     int gmres_fuse = -1;                        // option "gmres_fuse": s-step solver, first update and second dot of a block in one sweep (k_blockfuse); -1 = from 4 M rows on
     int gdsw_rot = 0;                           // option "gdsw_rotations": rotations in the null space of vector problems (dofs = dim)
     int co_nns = 1;                             // coarse functions per entity of the last GDSW setup (dofs, or dofs + rotations)
@@ -853,6 +868,8 @@ struct GmresCall {
     int nr = 1;                     // > 1: stacked vectors X[row * nr + j] (multi.hip; the GDSW extension solves)
 };
 int gmres_solve(fedd_ctx* c, const GmresCall& call, int* its_out, double* relres_out);
+int gmres_capture_arm(fedd_ctx* c, int block);
+int gmres_capture_get(fedd_ctx* c, const char* what, double* out, int64_t cap);
 int allreduce_sum(fedd_ctx* c, double* d_buf, int n);
 
 // cg.hip

@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 
 namespace fedd {
 namespace {
@@ -1777,6 +1778,8 @@ static void leja_order(double* v, int n) {
 template <int S>
 static int gmres_solve_sstep(fedd_ctx* c, const GmresCall& call, int s, int* its_out, double* relres_out) {
     Frame f;
+    const int cap_block = c->gm_cap.armed;   // fedd_gmres_capture_arm: the block to copy, -1 (no block's number) when unarmed;
+    c->gm_cap.armed = -1;                    // this solve consumes the arm
     FEDD_TRY(f.setup(c, call, true));
     const int nr = f.nr;
     FEDD_CHECK(nr == 1 || (nr == MULTI_NR && call.use_prec && multi_rhs_ok(c)), "gmres: stacked solve with %d right-hand sides", nr);
@@ -1894,6 +1897,38 @@ static int gmres_solve_sstep(fedd_ctx* c, const GmresCall& call, int s, int* its
     c->gmres_blocks = 0;
     c->gmres_cut_blocks = 0;
     c->gmres_fused_blocks = 0;
+    // fedd_gmres_capture_*: the armed block is copied piece by piece, device to device on the solver's stream, between the
+    // launches it makes anyway (no launch is added, moved or given other arguments); grab_* run for that one block only
+    GmresCapture& gc = c->gm_cap;
+    auto grab_begin = [&](int k, int sa) -> int {
+        typedef GmresCapture G;
+        gc.captured = false;
+        gc.n = n; gc.ldv = ldv; gc.k = k; gc.sa_req = sa; gc.S = S; gc.m = m; gc.fused = 0;
+        gc.canary = k + sa <= m ? 1 : 0;
+        const size_t cols = (size_t)(k + sa), L = (size_t)ldv;
+        for (int p = 0; p < G::NPIECE; ++p) gc.len[p] = 0;
+        gc.len[G::V0] = gc.len[G::VEND] = cols * L;
+        gc.len[G::C0] = gc.canary * L;
+        gc.len[G::P1] = gc.len[G::P2] = cols * S;
+        gc.len[G::CF1] = gc.len[G::CF2] = (size_t)k * S;
+        gc.len[G::RI1] = gc.len[G::RI2] = (size_t)S * S;
+        gc.len[G::SA1] = 1;
+        gc.len[G::SA2] = 2;
+        gc.len[G::TH] = S;
+        gc.len[G::W1] = gc.len[G::W2] = (size_t)(sa + gc.canary) * L;
+        gc.len[G::H] = (cols - 1) * (size_t)(m + 1);
+        size_t tot = 0;
+        for (int p = 0; p < G::NPIECE; ++p) {
+            gc.off[p] = tot;
+            tot += gc.len[p];
+        }
+        FEDD_TRY(gc.buf.ensure(tot));
+        return 0;
+    };
+    auto grab = [&](int piece, const void* src, size_t count, size_t elem = sizeof(double), size_t at = 0) -> int {
+        FEDD_HIP(hipMemcpyAsync(gc.buf.p + gc.off[piece] + at, src, count * elem, hipMemcpyDeviceToDevice, st));
+        return 0;
+    };
     bool first_cycle = true;
     while (!done && its < max_it) {
         if (project && !first_cycle) {   // r = b - A x is the true residual here (trial): project it, x += Pc r, r = b - A x
@@ -1920,6 +1955,12 @@ static int gmres_solve_sstep(fedd_ctx* c, const GmresCall& call, int s, int* its
                 FEDD_TRY(f.apply(V + (int64_t)(k - 1 + i) * ldv, V + (int64_t)(k + i) * ldv, false, have_shifts ? theta[(size_t)i] : 0.0));
             {
                 ScopedTimer t(c, FEDD_T_ORTHO);
+                typedef GmresCapture G;
+                const bool cap = cap_block == c->gmres_blocks;
+                if (cap) {
+                    FEDD_TRY(grab_begin(k, sa));
+                    FEDD_TRY(grab(G::V0, V, (size_t)(k + sa + gc.canary) * ldv));   // (the canary column C0 lies right behind)
+                }
                 const int ncg = (k + sa + dot_cg - 1) / dot_cg;
                 const dim3 gd(nblkd, std::min(gy_dot, ncg));
                 auto launch_dot = [&](const int32_t* dsa) {
@@ -1939,7 +1980,13 @@ static int gmres_solve_sstep(fedd_ctx* c, const GmresCall& call, int s, int* its
                 hipLaunchKernelGGL(k_reduce_cols, dim3((k + sa) * S), blk, 0, st, (const double*)c->d_part.p, Sx + o3.P, nblkd,
                                    (const int32_t*)nullptr);
                 FEDD_TRY(allreduce_sum(c, Sx + o3.P, (k + sa) * S));
+                if (cap) FEDD_TRY(grab(G::P1, Sx + o3.P, gc.len[G::P1]));
                 hipLaunchKernelGGL(k_ss_pass1<S>, dim3(1), blk, 0, st, Sx, o3, k, sa, chol_tol, d_sa);
+                if (cap) {
+                    FEDD_TRY(grab(G::CF1, Sx + o3.cf1, gc.len[G::CF1]));
+                    FEDD_TRY(grab(G::RI1, Sx + o3.ri1, gc.len[G::RI1]));
+                    FEDD_TRY(grab(G::SA1, d_sa, 1, sizeof(int32_t)));
+                }
                 bool fused = false;
                 // (auto: long vectors only -- at 9.9 M rows the step gains 1.1 ms, at the 1.26 M rows of the N = 8 share the two
                 //  separate kernels are 0.15 ms ahead: their second read finds much of the basis in the Infinity Cache anyway)
@@ -1958,6 +2005,7 @@ static int gmres_solve_sstep(fedd_ctx* c, const GmresCall& call, int s, int* its
                             hipLaunchKernelGGL((k_blockfuse<S, false>), dim3(nblk2), blk, 0, st, V, ldv, n, k, sa, (const int32_t*)d_sa,
                                                (const double*)(Sx + o3.cf1), (const double*)(Sx + o3.ri1), c->d_part.p, nblk2);
                     }
+                    if (cap) FEDD_TRY(grab(G::W1, V + (int64_t)k * ldv, gc.len[G::W1]));
                 } else {
                     {
                         ScopedTimer tu(c, FEDD_T_GS_UPDATE);
@@ -1965,6 +2013,7 @@ static int gmres_solve_sstep(fedd_ctx* c, const GmresCall& call, int s, int* its
                         hipLaunchKernelGGL(k_blockaxpy<S>, dim3(nblk2), blk, 0, st, V, ldv, n, k, sa, (const int32_t*)d_sa,
                                            (const double*)(Sx + o3.cf1), (const double*)(Sx + o3.ri1));
                     }
+                    if (cap) FEDD_TRY(grab(G::W1, V + (int64_t)k * ldv, gc.len[G::W1]));
                     {
                         ScopedTimer td(c, FEDD_T_GS_DOT);
                         td.bytes(dot_bytes);
@@ -1974,8 +2023,20 @@ static int gmres_solve_sstep(fedd_ctx* c, const GmresCall& call, int s, int* its
                 hipLaunchKernelGGL(k_reduce_cols, dim3((k + sa) * S), blk, 0, st, (const double*)c->d_part.p, Sx + o3.P, fused ? nblk2 : nblkd,
                                    (const int32_t*)nullptr);
                 FEDD_TRY(allreduce_sum(c, Sx + o3.P, (k + sa) * S));
+                if (cap) {
+                    gc.fused = fused ? 1 : 0;
+                    FEDD_TRY(grab(G::P2, Sx + o3.P, gc.len[G::P2]));
+                }
                 hipLaunchKernelGGL(k_ss_pass2<S>, dim3(1), blk, pass2_lds, st, Sx, o, o3, k, sa, m,
                                    chol_tol, d_sa, hout_dev);
+                if (cap) {
+                    FEDD_TRY(grab(G::CF2, Sx + o3.cf2, gc.len[G::CF2]));
+                    FEDD_TRY(grab(G::RI2, Sx + o3.ri2, gc.len[G::RI2]));
+                    FEDD_TRY(grab(G::SA2, d_sa, 1, sizeof(int32_t)));
+                    FEDD_TRY(grab(G::SA2, Sx + o.misc + 4, 1, sizeof(double), 1));   // the accepted count as the host reads it
+                    FEDD_TRY(grab(G::TH, Sx + o3.th, gc.len[G::TH]));
+                    FEDD_TRY(grab(G::H, Sx + o3.Hraw, gc.len[G::H]));
+                }
                 if (!hout_dev) {
                     FEDD_HIP(hipMemcpyAsync(hout, Sx + o.misc + 4, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
                     FEDD_HIP(hipMemcpyAsync(hout + 2, Sx + o3.res, S * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -2000,6 +2061,11 @@ static int gmres_solve_sstep(fedd_ctx* c, const GmresCall& call, int s, int* its
                     tu.bytes(upd_bytes);
                     hipLaunchKernelGGL(k_blockaxpy<S>, dim3(nblk2), blk, 0, st, V, ldv, n, k, sa, (const int32_t*)d_sa,
                                        (const double*)(Sx + o3.cf2), (const double*)(Sx + o3.ri2));
+                }
+                if (cap) {
+                    FEDD_TRY(grab(G::W2, V + (int64_t)k * ldv, gc.len[G::W2]));
+                    FEDD_TRY(grab(G::VEND, V, gc.len[G::VEND]));
+                    gc.captured = true;
                 }
                 t.stop();
             }
@@ -2234,6 +2300,12 @@ int gmres_solve(fedd_ctx* c, const GmresCall& call, int* its_out, double* relres
     c->gmres_floor = 0;
     c->gmres_rec_relres = -1.0;
     FEDD_CHECK(call.nr <= 1 || c->gmres_kind == 2, "gmres: a stacked solve (%d right-hand sides) needs the s-step solver (gmres_kind 2)", call.nr);
+    if (c->gm_cap.armed >= 0 && (c->gmres_kind != 2 || call.nr > 1 || c->nranks > 1)) {
+        c->gm_cap.armed = -1;
+        FEDD_CHECK(c->nranks == 1, "gmres capture: one rank only (this context has %d)", c->nranks);
+        FEDD_CHECK(call.nr <= 1, "gmres capture: not for the stacked solve (%d right-hand sides)", call.nr);
+        FEDD_CHECK(false, "gmres capture: the s-step solver only (gmres_kind 2; %d is set and keeps no raw Hessenberg matrix)", c->gmres_kind);
+    }
     if (c->gmres_kind == 0) return gmres_solve_dcgs2(c, call, its_out, relres_out);
     if (c->gmres_kind == 1) return gmres_solve_cgs2(c, call, its_out, relres_out);
     // block length: "gmres_s" 0 = by the vector length per rank -- 16-vector (Newton-basis) blocks where the sweeps over the
@@ -2261,6 +2333,51 @@ int gmres_solve(fedd_ctx* c, const GmresCall& call, int* its_out, double* relres
     if (s <= 4) return gmres_solve_sstep<4>(c, call, s, its_out, relres_out);
     if (s <= 8) return gmres_solve_sstep<8>(c, call, s, its_out, relres_out);
     return gmres_solve_sstep<16>(c, call, s, its_out, relres_out);
+}
+
+int gmres_capture_arm(fedd_ctx* c, int block) {
+    GmresCapture& g = c->gm_cap;
+    if (block < 0) {
+        g.armed = -1;
+        g.captured = false;
+        g.buf.release();
+        return 0;
+    }
+    FEDD_CHECK(c->nranks == 1, "fedd_gmres_capture_arm: one rank only (this context has %d)", c->nranks);
+    FEDD_CHECK(c->device >= 0, "this call needs a GPU context (fedd_ctx_create with device >= 0); there is no CPU fallback");
+    g.armed = block;
+    g.captured = false;
+    return 0;
+}
+
+static const char* const capture_names[GmresCapture::NPIECE] = {"V0", "C0", "P1", "CF1", "RI1", "SA1", "W1", "P2",
+                                                                "CF2", "RI2", "SA2", "TH", "W2", "H", "VEND"};
+
+int gmres_capture_get(fedd_ctx* c, const char* what, double* out, int64_t cap) {
+    typedef GmresCapture G;
+    G& g = c->gm_cap;
+    int p = 0;
+    while (p < G::NPIECE && strcmp(what, capture_names[p]) != 0) ++p;
+    FEDD_CHECK(p < G::NPIECE, "fedd_gmres_capture_get: no piece is named '%s'", what);
+    FEDD_CHECK(g.captured, "fedd_gmres_capture_get: nothing captured (fedd_gmres_capture_arm, then an s-step solve that reaches that block)");
+    FEDD_CHECK(g.len[p] > 0, "fedd_gmres_capture_get: '%s' was not captured (block at k %d with %d of %d columns asked)", what, g.k, g.sa_req,
+               g.m + 1);
+    FEDD_HIP(hipStreamSynchronize(c->stream));
+    size_t cnt = g.len[p];
+    int32_t sa[2] = {0, 0};
+    if (p == G::SA1 || p == G::SA2 || p == G::H || p == G::VEND)
+        FEDD_HIP(hipMemcpy(sa, g.buf.p + g.off[p == G::SA1 ? G::SA1 : G::SA2], sizeof(sa), hipMemcpyDeviceToHost));
+    // the pieces taken after pass 2 end at the columns it accepted (a breakdown still writes Hessenberg column k - 1)
+    if (p == G::H) cnt = (size_t)(g.k - 1 + std::max(sa[0], 1)) * (g.m + 1);
+    if (p == G::VEND) cnt = (size_t)(g.k + sa[0]) * g.ldv;
+    FEDD_CHECK(cap >= (int64_t)cnt, "fedd_gmres_capture_get: '%s' has %lld values, the buffer holds %lld", what, (long long)cnt, (long long)cap);
+    if (p == G::SA1 || p == G::SA2) {
+        out[0] = (double)sa[0];
+        if (p == G::SA2) FEDD_HIP(hipMemcpy(out + 1, g.buf.p + g.off[p] + 1, sizeof(double), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    FEDD_HIP(hipMemcpy(out, g.buf.p + g.off[p], cnt * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 }  // namespace fedd

@@ -1179,6 +1179,30 @@ int fedd_schwarz_coarse_apply(fedd_ctx* ctx, const double* r_owned, double* z_ow
 int fedd_gmres_info(fedd_ctx* ctx, int* kind, int* s, int* blocks, int* cut_blocks);
 /* blocks of the last s-step solve orthogonalised with three sweeps instead of four (option "gmres_fuse": k_blockfuse) */
 int fedd_gmres_fused_blocks(fedd_ctx* ctx, int* blocks);
+/* One block of an s-step solve (gmres_kind 2), copied stage by stage for the tests.  block >= 0 arms the capture for the
+ * block-th orthogonalised block of the next s-step solve (counted as fedd_gmres_info counts blocks, from 0); that solve
+ * consumes the arm whether it reaches the block or not.  block < 0 disarms and frees the copies.  The armed solve makes the
+ * launches of an unarmed one, with the same arguments in the same order; the copies are device-to-device on its stream
+ * between them.  One rank, one right-hand side: an arm on a context of several ranks and an armed stacked solve are errors.
+ * fedd_gmres_capture_info: out = { captured (0/1), n, ldv, k, sa_req, S, m, fused } -- rows and leading dimension of the
+ * basis, final basis vectors before the block, block columns asked for, block size of the kernels, restart length, and
+ * whether k_blockfuse ran.
+ * fedd_gmres_capture_get copies one piece to the host (cap: doubles `out` holds; too few is an error).  Column-major
+ * pieces have ldv rows per column (rows n .. ldv - 1 are padding), coefficient pieces are row-wise with S entries a row:
+ *   "V0"   basis columns 0 .. k + sa_req - 1 before the first dot sweep;  "C0" the column behind them (the canary; not
+ *          captured when the block ends at the last column of the basis, k + sa_req = m + 1)
+ *   "P1" / "P2"   [Q W]^T W after the first / second reduction, (k + sa_req) x S
+ *   "CF1" "RI1" "SA1"   after pass 1: coefficients k x S, inverse factor S x S, accepted columns
+ *   "W1"   block columns k .. k + sa_req - 1 after the first update, then the canary column if there is one;  columns
+ *          SA1 .. sa_req - 1 of a cut block are not written by the updates: they still hold the operator's products
+ *   "CF2" "RI2" "TH"   after pass 2, TH = the S shifts;  "SA2" two values: accepted columns on the device and as the host reads them
+ *   "W2"   as W1, after the last update
+ *   "H"    raw Hessenberg columns 0 .. k + max(SA2, 1) - 2, leading dimension m + 1 (shifts folded in; the solver neither
+ *          writes nor reads below the sub-diagonal: whatever the array held stays there)
+ *   "VEND" basis columns 0 .. k + SA2 - 1 after the last update */
+int fedd_gmres_capture_arm(fedd_ctx* ctx, int block);
+int fedd_gmres_capture_info(fedd_ctx* ctx, int64_t* out);
+int fedd_gmres_capture_get(fedd_ctx* ctx, const char* what, double* out, int64_t cap);
 
 /* "apply_gather" 0 (default) = fedd_schwarz_apply and GMRES keep the atomicAdd combine for Full and Averaging, 1 = they use the
  * park + gather kernels (bitwise reproducible); "apply_full_kind" 0 = the matrix-core park kernel for subdomains that share their
