@@ -857,14 +857,14 @@ bool multi_rhs_ok(const fedd_ctx* c);
 int spmm_owned(fedd_ctx* c, double* d_X, double* d_Y, const double* mk, const double* alt);
 int schwarz_apply_multi(fedd_ctx* c, double* d_R, double* d_Z, const double* mk);
 
-// gmres.hip
+// gmres.hip (dispatcher, one-vector solvers), gmres_sstep.hip (s-step solver, capture)
 struct GmresCall {
     const double* b;                // right-hand side (device, owned rows)
     double* x;                      // solution; the initial guess if x0
     double rtol;
     int max_it, restart, use_prec;
     bool x0 = false;                // start from the vector in x ("Zero Initial Guess" = false) instead of zero
-    const double* mask = nullptr;   // != nullptr: the constrained system (dofs with mask 0 held), see Frame in gmres.hip
+    const double* mask = nullptr;   // != nullptr: the constrained system (dofs with mask 0 held), see Frame in gmres_frame.hpp
     int nr = 1;                     // > 1: stacked vectors X[row * nr + j] (multi.hip; the GDSW extension solves)
 };
 int gmres_solve(fedd_ctx* c, const GmresCall& call, int* its_out, double* relres_out);

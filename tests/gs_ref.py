@@ -1,4 +1,4 @@
-"""Plain reference of one block of the s-step Gram-Schmidt (BCGS-PIP2, csrc/gmres.hip): numpy only, no GPU.
+"""Plain reference of one block of the s-step Gram-Schmidt (BCGS-PIP2, csrc/gmres_sstep.hip): numpy only, no GPU.
 
 The two sweeps over the basis have longdouble references (64-bit significand on x86) with the product of absolute values beside
 them, which is what a rounding bound of a dot product or an update is stated against.  The small matrix work between the

@@ -1,6 +1,6 @@
 """The s-step Gram-Schmidt kernels stage by stage, inside a real solve.
 
-fedd_gmres_capture_* copies one block of gmres_solve_sstep piece by piece (the basis before the block, the reduced products,
+fedd_gmres_capture_* copies one block of the s-step solve (csrc/gmres_sstep.hip, SStep::orthogonalise) piece by piece (the basis before the block, the reduced products,
 the coefficients of both passes, the block after each update, the raw Hessenberg columns); every piece is compared here with
 tests/gs_ref.py: the two sweeps with their longdouble references under bounds that hold for any summation order
 (u = 2^-53, elementwise, against the product of absolute values), the small matrix work with the float64 restatement of the

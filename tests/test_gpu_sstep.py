@@ -1,4 +1,4 @@
-"""GPU tests of the s-step GMRES (fedd_set_option "gmres_kind" 2; gmres.hip): in exact arithmetic its iterates are those of
+"""GPU tests of the s-step GMRES (fedd_set_option "gmres_kind" 2; gmres_sstep.hip): in exact arithmetic its iterates are those of
 the one-vector-at-a-time solver, so it is held against that solver (same iteration count at the reference's tolerance), against
 the oracle's GMRES on the same preconditioner definition, and against a direct solve with both sides driven to 1e-13
 (north_star: solution within 1e-10).  Stands in for Belos "Block GMRES", parametersSolver.xml:5-15."""

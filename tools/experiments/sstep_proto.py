@@ -1,4 +1,4 @@
-"""Prototype (numpy) of the s-step GMRES with BCGS-PIP2 block orthogonalisation that gmres.hip's gmres_kind 2
+"""Prototype (numpy) of the s-step GMRES with BCGS-PIP2 block orthogonalisation that gmres_sstep.hip's gmres_kind 2
 implements: validates the Hessenberg recovery formulas and the conditioning of the monomial block basis.
 Development tool; reads only oracle/ (test infrastructure)."""
 import math

@@ -1,6 +1,6 @@
 // Does a second read of a workgroup's row block, right after the first, come back faster than HBM (L2 / Infinity Cache)?
 // Layout of the Krylov basis: K columns of n doubles (column-major, ld = n); a workgroup takes 512 rows (2 per lane) of all K columns --
-// the access pattern of the block Gram-Schmidt sweeps (gmres.hip k_blockaxpy / k_blockdot).  once: one pass over the columns;
+// the access pattern of the block Gram-Schmidt sweeps (gmres_sstep.hip k_blockaxpy / k_blockdot).  once: one pass over the columns;
 // twice: two passes over the same rows (what a fused update + dot sweep would do); the gain of fusing = 2 x once - twice.
 #include <hip/hip_runtime.h>
 #include <cstdio>
