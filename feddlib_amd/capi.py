@@ -149,6 +149,7 @@ SIGNATURES = {
     "fedd_schwarz_reuse_info": [C.c_void_p, _ip, _i64p],
     "fedd_pattern_reuse_info": [C.c_void_p, _ip, _i64p],
     "fedd_spmv_reuse_info": [C.c_void_p, _ip, _i64p],
+    "fedd_setup_fused_info": [C.c_void_p, _i64p, _i64p, _i64p],
     "fedd_schwarz_unique": [C.c_void_p, _i64p],
     "fedd_schwarz_sizes": [C.c_void_p, _i64p, _i64p],
     "fedd_schwarz_conforming": [C.c_void_p, _i64p],
@@ -1109,6 +1110,12 @@ class Context:
         a, n = C.c_int(), C.c_int64()
         _chk(self._L.fedd_pattern_reuse_info(self._h, C.byref(a), C.byref(n)))
         return {"last_reused": bool(a.value), "n_reused": n.value}
+
+    def setup_fused_info(self):
+        """what option "setup_fused" has done on this context (fedd_setup_fused_info)"""
+        a, b, d = C.c_int64(), C.c_int64(), C.c_int64()
+        _chk(self._L.fedd_setup_fused_info(self._h, C.byref(a), C.byref(b), C.byref(d)))
+        return {"n_walks": a.value, "n_checks_used": b.value, "n_absdet_kept": d.value}
 
     def spmv_reuse_info(self):
         """whether the solver's SpMV stream in use was kept from the matrix before (verified, not built), and how often it was"""

@@ -207,6 +207,8 @@ static int mesh_set_impl(fedd_ctx* c, int dim, int nen, int64_t n_elem, const in
     c->n_surf = 0;
     for (auto& id : c->adv_pattern_id) id = 0;
     c->d_adv_ke.release();   // the element-block scratch is sized by the mesh (the largest buffer of the advection path)
+    c->absdet_valid = false; // ... and so is |det B| of the old elements (assemble_rhs, option "setup_fused")
+    c->d_absdet.release();
     ++c->mesh_id;
     c->nm_n = -1;           // the Newmark state belonged to the old rows
     c->ms_order = c->ms_count = 0;   // ... and so did the multistep history, whose buffers go with it
@@ -975,6 +977,14 @@ extern "C" int fedd_spmv_reuse_info(fedd_ctx* c, int* last_reused, int64_t* n_re
     return 0;
 }
 
+extern "C" int fedd_setup_fused_info(fedd_ctx* c, int64_t* n_walks, int64_t* n_checks_used, int64_t* n_absdet_kept) {
+    FEDD_CHECK(c, "fedd_setup_fused_info: null context");
+    if (n_walks) *n_walks = c->fused_walks;
+    if (n_checks_used) *n_checks_used = c->fused_checks_used;
+    if (n_absdet_kept) *n_absdet_kept = c->fused_absdet_kept;
+    return 0;
+}
+
 extern "C" int fedd_schwarz_apply(fedd_ctx* c, const double* r_owned, double* z_owned) {
     NEED_DEVICE(c);
     FEDD_CHECK((c->have_schwarz || has_attached_prec(c)) && r_owned && z_owned, "fedd_schwarz_apply: no preconditioner / null pointer");
@@ -1229,6 +1239,8 @@ const Option OPTIONS[] = {
     {"schwarz_reuse", FLAG(sw_reuse), any, 0},
     {"pattern_reuse", FLAG(pat_reuse), any, 0},
     {"spmv_reuse", FLAG(spmv_reuse), any, 0},
+    // (drops the stream check a Schwarz setup may have left for the next SpMV: switched off, that SpMV makes its own)
+    {"setup_fused", FLAG(setup_fused), any, OPT_DROPS_FUSED},
 };
 #undef INT
 #undef FLAG

@@ -1909,18 +1909,33 @@ int assemble_rhs(fedd_ctx* c, int dofs, const double* f_const, int extra_degree)
     }
     for (int d = 0; d < MAX_DOFS; ++d) a.f[d] = d < dofs ? f_const[d] : 0.0;
     const dim3 grid((unsigned)((c->n_own + 255) / 256)), block(256);
-    FEDD_TRY(c->d_dtmp0.ensure(std::max<size_t>((size_t)c->n_elem, c->d_dtmp0.cap)));
+    // |det B_e| follows d_conn and d_xyz alone.  Option "setup_fused" keeps it in a buffer of its own from call to call (a Newton
+    // loop, a time loop and the bench assemble again and again on one geometry) while the two stand: d_conn and d_xyz are
+    // written by fedd_mesh_set* (mesh_gen; a P2 mesh, a second mesh, the sides of an FSI problem all arrive through it) and d_xyz by
+    // a committed fedd_mesh_move (geometry_id; the ALE and FSI geometry steps move the mesh through it), and by nothing else.
+    const bool keep = c->setup_fused != 0;
+    const bool kept = keep && c->absdet_valid && c->absdet_mesh_gen == c->mesh_gen && c->absdet_geometry_id == c->geometry_id &&
+                      c->d_absdet.cap >= (size_t)c->n_elem;
+    if (keep) FEDD_TRY(c->d_absdet.ensure((size_t)c->n_elem));
+    else FEDD_TRY(c->d_dtmp0.ensure(std::max<size_t>((size_t)c->n_elem, c->d_dtmp0.cap)));
+    double* absdet = keep ? c->d_absdet.p : c->d_dtmp0.p;
     const dim3 egrid((unsigned)((c->n_elem + 255) / 256));
     ScopedTimer t(c, FEDD_T_RHS);
-    if (dim == 2)
+    if (!kept && dim == 2)
         hipLaunchKernelGGL(k_elem_absdet<2>, egrid, block, 0, c->stream, (const int32_t*)c->d_conn.p, nen,
-                           (const double*)c->d_xyz.p, c->n_elem, c->d_dtmp0.p);
-    else
+                           (const double*)c->d_xyz.p, c->n_elem, absdet);
+    else if (!kept)
         hipLaunchKernelGGL(k_elem_absdet<3>, egrid, block, 0, c->stream, (const int32_t*)c->d_conn.p, nen,
-                           (const double*)c->d_xyz.p, c->n_elem, c->d_dtmp0.p);
+                           (const double*)c->d_xyz.p, c->n_elem, absdet);
+    if (kept) ++c->fused_absdet_kept;
+    if (keep) {
+        c->absdet_valid = true;
+        c->absdet_mesh_gen = c->mesh_gen;
+        c->absdet_geometry_id = c->geometry_id;
+    }
     const int cap = std::max(256, std::min(RHS_NPB * std::max(1, c->max_deg), 6144));
     hipLaunchKernelGGL(k_rhs, dim3((unsigned)((c->n_own + RHS_NPB - 1) / RHS_NPB)), block, (size_t)cap * sizeof(double),
-                       c->stream, a, (const double*)c->d_dtmp0.p, cap);
+                       c->stream, a, (const double*)absdet, cap);
     t.stop();
     FEDD_HIP(hipGetLastError());
     return 0;

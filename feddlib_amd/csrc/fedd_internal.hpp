@@ -436,6 +436,7 @@ struct fedd_ctx {
     int sw_last_reused = 0;                     // the last setup kept the structure
     int64_t sw_reuse_count = 0;                 // setups that kept it since the context was made
     fedd::DevBuf<int64_t> d_inv_ptr;           // [nsub+1] offsets into d_inv (elements)
+    fedd::DevBuf<int64_t> d_sw_gather;         // [8] scalars of the numeric stage read back in one copy (schwarz.hip k_setup_gather)
     fedd::DevBuf<double> d_inv;                 // per subdomain [n_i][rp_i] column-major slab
     fedd::DevBuf<double> d_mult;                // [n_cols] multiplicity (averaging)
     bool have_schwarz = false;                  // cleared by system_written (below): a parent that applies this context as a block (blockprec.hip)
@@ -499,6 +500,18 @@ struct fedd_ctx {
     uint64_t sys_pattern_id = 0;                // the system slot holds the pattern with this DevCsr::pattern_id (copied by
     uint64_t sys_pattern_gen = 0;               // fedd_matrix_store / fedd_matrix_combine) ... while pattern_gen still has this value
     uint64_t sys_value_gen = 0;                 // bumped by every writer of the system matrix' values (system_written; Dirichlet rows excepted)
+    uint64_t sys_write_count = 0;               // bumped by every system_written, whatever it wrote (Dirichlet rows included)
+    // ---- option "setup_fused" (default 1; 0 = every consumer walks the matrix and the elements for itself) ----
+    int setup_fused = 1;
+    struct SetupWalk {                          // the SpMV stream check, made by the walk that forms the Schwarz row hashes (spmv.hip setup_walk)
+        bool valid = false;
+        uint64_t write_count = 0;               // sys_write_count of the rows that were walked: any write since makes the result stale
+        int32_t bad = 0;                        // what k_cs_reuse leaves in *n_bad
+    } setup_walk;
+    int64_t fused_walks = 0, fused_checks_used = 0, fused_absdet_kept = 0;   // fedd_setup_fused_info
+    fedd::DevBuf<double> d_absdet;              // [n_elem] |det B| of every element (assemble.hip assemble_rhs), kept while the
+    bool absdet_valid = false;                  // connectivity (mesh_gen: fedd_mesh_set*) and the coordinates (geometry_id: fedd_mesh_move)
+    uint64_t absdet_mesh_gen = 0, absdet_geometry_id = 0;   // are the ones it was computed from
     int comb_slot_m = -1, comb_slot_a = -1;     // the last fedd_matrix_combine: slots, coefficients, the slots' value ids
     double comb_cm = 0.0, comb_ca = 0.0;        // and the sys_value_gen it left (none yet: a value sys_value_gen never takes)
     uint64_t comb_id_m = 0, comb_id_a = 0, comb_sys_gen = ~(uint64_t)0;
@@ -628,6 +641,7 @@ enum : unsigned {
                          // SwStructKey::geometry_id, the last combine's record (its matrices belong to the old coordinates)
 };
 inline void system_written(fedd_ctx* c, unsigned what) {
+    ++c->sys_write_count;
     if (what & SYS_GEOMETRY) {
         ++c->geometry_id;
         c->comb_sys_gen = ~(uint64_t)0;        // fedd_matrix_combine_current answers 0
@@ -650,12 +664,17 @@ enum : unsigned {
     OPT_DROPS_SCHWARZ = 2,   // the preconditioner
     OPT_DROPS_TILES = 4,     // the assembly's tile structures
     OPT_DROPS_REPEAT = 8,    // the next fedd_pattern_build builds
+    OPT_DROPS_FUSED = 16,    // what option "setup_fused" keeps from one call for a later one: the stream check, |det B|
 };
 inline void option_drops(fedd_ctx* c, unsigned what) {
-    if (what & OPT_DROPS_STREAM) c->cs.valid = c->cs.key.valid = false;
+    if (what & OPT_DROPS_STREAM) c->cs.valid = c->cs.key.valid = c->setup_walk.valid = false;
     if (what & OPT_DROPS_SCHWARZ) c->have_schwarz = false;
     if (what & OPT_DROPS_TILES) c->tl_state = 0;
     if (what & OPT_DROPS_REPEAT) c->pat_repeatable = false;
+    if (what & OPT_DROPS_FUSED) {
+        c->setup_walk.valid = c->absdet_valid = false;
+        c->d_absdet.release();      // (470 MB at the headline: not held by a context that has switched the option off)
+    }
 }
 
 // RAII-ish helper: records a start event at construction and a stop event at stop().
@@ -820,6 +839,30 @@ int read_bandwidth(fedd_ctx* c, int64_t bytes, int reps, double* gbs);     // re
 // schwarz.hip
 int schwarz_setup(fedd_ctx* c);
 int schwarz_apply(fedd_ctx* c, const double* d_r_owned, double* d_z_owned, bool r_has_tail = false);
+
+// The row hash of the Schwarz fingerprints (schwarz.hip k_row_hash) as the two kernels that form it share it: 128 bits,
+// order-independent (wrapping sums), over (column - row, value quantised to 2^-44 of the row's largest magnitude) of every
+// entry that does not quantise to zero.
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {
+    x ^= x >> 33;
+    x *= 0xff51afd7ed558ccdull;
+    x ^= x >> 33;
+    x *= 0xc4ceb9fe1a85ec53ull;
+    x ^= x >> 33;
+    return x;
+}
+__device__ __forceinline__ double row_hash_scale(double row_max) { return row_max > 0.0 ? 17592186044416.0 / row_max : 0.0; }   // 2^44 / row max
+__device__ __forceinline__ void row_hash_add(double a, double scale, int32_t cidx, int32_t r, uint64_t& h1, uint64_t& h2) {
+    const int64_t qv = (int64_t)llrint(a * scale);
+    if (qv == 0) return;
+    const uint64_t key = (uint64_t)(uint32_t)(cidx - r);
+    h1 += mix64((key + 0x2545f4914f6cdd1dull) * 0x9e3779b97f4a7c15ull + (uint64_t)qv);
+    h2 += mix64((key + 0x632be59bd9b4e019ull) * 0xd6e8feb86659fd93ull ^ ((uint64_t)qv * 0xa0761d6478bd642full));
+}
+// spmv.hip, option "setup_fused": one walk over the finished rows for the Schwarz setup's row maxima and row hashes AND the
+// check of the kept SpMV stream (spmv_reuse_try finds its result in fedd_ctx::setup_walk).  *ran = false: there is no stream to
+// check against (or the rows are not the stream's), nothing was launched and the caller runs its own kernel.
+int setup_walk(fedd_ctx* c, double* d_rmax, uint64_t* d_row_hash, bool* ran);
 // schwarz_sym.hip: Full / Averaging combine by park + gather (no floating-point atomics, fixed summation order)
 int schwarz_sym_setup(fedd_ctx* c);
 int schwarz_apply_sym(fedd_ctx* c, const double* d_r_cols, double* d_z_owned);

@@ -315,13 +315,17 @@ __global__ void k_row_absmax(const int32_t* __restrict__ rowptr, const double* _
     if (r < n_rows && e == 0) rmax[r] = m;
 }
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33;
-    x *= 0xc4ceb9fe1a85ec53ull;
-    x ^= x >> 33;
-    return x;
+// (mix64 and the hash of one row entry: fedd_internal.hpp, shared with the fused walk of spmv.hip)
+
+// the scalars of the numeric stage that the host waits for together (schwarz_setup `gathered`); a null source keeps `nsub` / 0
+__global__ void k_setup_gather(const int32_t* __restrict__ n_rep, const int32_t* __restrict__ n_int, const int64_t* __restrict__ slab_total,
+                               const int32_t* __restrict__ walk_bad, int64_t nsub, int64_t* __restrict__ out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    out[0] = n_rep ? n_rep[0] : nsub;
+    out[1] = n_int ? n_int[0] : 0;
+    out[2] = n_int ? n_int[1] : 0;
+    out[3] = slab_total[0];
+    out[4] = walk_bad ? walk_bad[0] : 0;
 }
 
 // Row maxima and ROW hashes in one coalesced pass over the stored rows (16 lanes per row): 128 bits, order-independent, over
@@ -356,15 +360,9 @@ __global__ void k_row_hash(const int32_t* __restrict__ rowptr, const int32_t* __
         double m = fabs(v0[q]);
         for (int32_t p = p0 + 16 + e; p < p_end; p += 16) m = fmax(m, fabs(val[p]));
         for (int off = 8; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off, 16));
-        const double scale = m > 0.0 ? 17592186044416.0 / m : 0.0;   // 2^44 / row max
+        const double scale = row_hash_scale(m);
         uint64_t h1 = 0, h2 = 0;
-        auto add = [&](double a, int32_t cidx) {
-            const int64_t qv = (int64_t)llrint(a * scale);
-            if (qv == 0) return;
-            const uint64_t key = (uint64_t)(uint32_t)(cidx - r);
-            h1 += mix64((key + 0x2545f4914f6cdd1dull) * 0x9e3779b97f4a7c15ull + (uint64_t)qv);
-            h2 += mix64((key + 0x632be59bd9b4e019ull) * 0xd6e8feb86659fd93ull ^ ((uint64_t)qv * 0xa0761d6478bd642full));
-        };
+        auto add = [&](double a, int32_t cidx) { row_hash_add(a, scale, cidx, r, h1, h2); };
         if (p0 + e < p_end) add(v0[q], c0[q]);
         for (int32_t p = p0 + 16 + e; p < p_end; p += 16) add(val[p], colind[p]);
         for (int off = 8; off > 0; off >>= 1) {
@@ -1796,6 +1794,9 @@ int schwarz_setup(fedd_ctx* c) {
     const int32_t p_off = c->merged ? (int32_t)c->merged_nA : INT32_MAX;
     // ---- equal local matrices share one slab (option "schwarz_dedupe", default on) ----
     const int32_t* sub_n_inv = c->d_sub_n.p;      // sizes as the inversion sees them: 0 = not a representative
+    const bool one_wait = c->setup_fused != 0;    // option "setup_fused": the scalars of this stage that can travel together do (`gather` below)
+    const int32_t* d_n_rep = nullptr;
+    bool walked = false;
     c->sw_nrep = nsub;
     if (c->sw_dedupe) {
         const dim3 gs((unsigned)((nsub + 255) / 256));
@@ -1804,10 +1805,13 @@ int schwarz_setup(fedd_ctx* c) {
         const bool by_rows = c->sw_fp_kind == 0;
         FEDD_TRY(c->d_sw_fp.ensure((size_t)(2 * nsub + 2 * tsize) + (by_rows ? 2 * (size_t)n_stored : 0)));
         uint64_t* row_hash = c->d_sw_fp.p + 2 * nsub + 2 * tsize;
-        if (by_rows)
+        // option "setup_fused": the walk that forms the row hashes also checks the kept SpMV stream against these rows, when
+        // there is one (the solver's first SpMV would read the same finished rows again for that, spmv_reuse_try)
+        if (by_rows && c->setup_fused) FEDD_TRY(setup_walk(c, c->d_sw_rmax.p, row_hash, &walked));
+        if (by_rows && !walked)
             hipLaunchKernelGGL(k_row_hash, dim3((unsigned)((n_stored + 16 * RH_R - 1) / (16 * RH_R))), blk, 0, c->stream, (const int32_t*)c->d_rowptr.p,
                                (const int32_t*)c->d_colind.p, (const double*)c->d_val.p, n_stored, c->d_sw_rmax.p, row_hash);
-        else
+        else if (!by_rows)
             hipLaunchKernelGGL(k_row_absmax, dim3((unsigned)((n_stored + 15) / 16)), blk, 0, c->stream, (const int32_t*)c->d_rowptr.p,
                                (const double*)c->d_val.p, n_stored, c->d_sw_rmax.p);
         FEDD_TRY(c->d_sw_rep.ensure((size_t)(3 * nsub + tsize + 4)));
@@ -1833,11 +1837,37 @@ int schwarz_setup(fedd_ctx* c) {
         hipLaunchKernelGGL(k_fp_resolve, gs, blk, 0, c->stream, (const int32_t*)slot_of, (const int32_t*)tmin,
                            (const int32_t*)c->d_sub_n.p, (int32_t)nsub, rep, n_inv, n_rep);
         sub_n_inv = n_inv;
-        int32_t h_nrep = 0;
-        FEDD_HIP(hipMemcpyAsync(&h_nrep, n_rep, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        FEDD_HIP(hipStreamSynchronize(c->stream));
-        c->sw_nrep = h_nrep;
+        d_n_rep = n_rep;
+        if (!one_wait) {
+            int32_t h_nrep = 0;
+            FEDD_HIP(hipMemcpyAsync(&h_nrep, n_rep, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            FEDD_HIP(hipStreamSynchronize(c->stream));
+            c->sw_nrep = h_nrep;
+        }   // (else n_rep and the walk's flag are read back with the counters of the order and the slab total: `gather` below)
     }
+    // ---- slab offsets (they follow the sizes alone: formed here, so that their total travels with the scalars above) ----
+    FEDD_TRY(c->d_inv_ptr.ensure((size_t)nsub + 1));
+    if (one_wait) {
+        hipLaunchKernelGGL(k_slab_sizes, dim3((unsigned)((nsub + 255) / 256)), blk, 0, c->stream, sub_n_inv,
+                           (const int32_t*)c->d_sub_nown.p, (int32_t)nsub, restricted, c->d_inv_ptr.p);
+        FEDD_TRY(exclusive_scan_i64(c, c->d_inv_ptr.p, c->d_inv_ptr.p, nsub, nullptr));
+    }
+    // One read-back for the scalars the host needs before it can size and shape what follows: representatives, interior and
+    // conforming subdomains, slab total, the walk's stream check.  Each used to be a copy and a wait of its own with the device
+    // idle meanwhile.  (The scan totals of the batch table, of the dense path and the pivot flag come later: each is produced by
+    // launches that the one before it sizes.)
+    int64_t gathered[5] = {nsub, 0, 0, 0, 0};
+    auto gather = [&](const int32_t* n_int) -> int {
+        FEDD_TRY(c->d_sw_gather.ensure(8));
+        hipLaunchKernelGGL(k_setup_gather, dim3(1), dim3(64), 0, c->stream, d_n_rep, n_int, (const int64_t*)(c->d_inv_ptr.p + nsub), walked ? (const int32_t*)(c->d_flags.p + 13) : nullptr, (int64_t)nsub,
+                           c->d_sw_gather.p);
+        FEDD_HIP(hipMemcpyAsync(gathered, c->d_sw_gather.p, sizeof(gathered), hipMemcpyDeviceToHost, c->stream));
+        FEDD_HIP(hipStreamSynchronize(c->stream));
+        c->sw_nrep = gathered[0];
+        if (walked) c->setup_walk = {true, c->sys_write_count, (int32_t)gathered[4]};
+        return 0;
+    };
+    bool gathered_done = false;
     // ---- the order the apply walks the subdomains in: sorted by representative (stable: lattice order within one); with
     // several ranks and option "halo_overlap" the subdomains without ghost dofs first ----
     c->sw_nint = -1;
@@ -1875,11 +1905,18 @@ int schwarz_setup(fedd_ctx* c) {
                                (const int32_t*)c->d_sub_n.p, (const int32_t*)c->d_sub_nown.p, (const int32_t*)c->d_sub_dofs.p,
                                (int32_t)nsub, (int4*)(ord + 4 * nsub), n_int + 1);
             c->sw_order_off = 4 * (int64_t)nsub;
-            int32_t h[2] = {0, 0};
-            FEDD_HIP(hipMemcpyAsync(h, n_int, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-            FEDD_HIP(hipStreamSynchronize(c->stream));
-            if (split) c->sw_nint = h[0];
-            c->sw_nconf = h[1];
+            if (one_wait) {
+                FEDD_TRY(gather(n_int));
+                gathered_done = true;
+            } else {
+                int32_t h[2] = {0, 0};
+                FEDD_HIP(hipMemcpyAsync(h, n_int, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+                FEDD_HIP(hipStreamSynchronize(c->stream));
+                gathered[1] = h[0];
+                gathered[2] = h[1];
+            }
+            if (split) c->sw_nint = gathered[1];
+            c->sw_nconf = gathered[2];
             // batch table of k_apply_bt: when every subdomain conforms (structured meshes) and the inverses are shared
             c->sw_nbatch = 0;
             c->sw_nbatch_int = 0;
@@ -1915,12 +1952,14 @@ int schwarz_setup(fedd_ctx* c) {
             }
         }
     }
-    // ---- slab offsets ----
-    FEDD_TRY(c->d_inv_ptr.ensure((size_t)nsub + 1));
-    hipLaunchKernelGGL(k_slab_sizes, dim3((unsigned)((nsub + 255) / 256)), blk, 0, c->stream, sub_n_inv,
-                       (const int32_t*)c->d_sub_nown.p, (int32_t)nsub, restricted, c->d_inv_ptr.p);
-    int64_t total = 0;
-    FEDD_TRY(exclusive_scan_i64(c, c->d_inv_ptr.p, c->d_inv_ptr.p, nsub, &total));
+    if (one_wait) {
+        if (!gathered_done) FEDD_TRY(gather(nullptr));
+    } else {
+        hipLaunchKernelGGL(k_slab_sizes, dim3((unsigned)((nsub + 255) / 256)), blk, 0, c->stream, sub_n_inv,
+                           (const int32_t*)c->d_sub_nown.p, (int32_t)nsub, restricted, c->d_inv_ptr.p);
+        FEDD_TRY(exclusive_scan_i64(c, c->d_inv_ptr.p, c->d_inv_ptr.p, nsub, &gathered[3]));
+    }
+    const int64_t total = gathered[3];
     c->sw_inv_elems = total;
     FEDD_TRY(c->d_inv.ensure((size_t)total + 16));
     if (c->sw_dedupe)

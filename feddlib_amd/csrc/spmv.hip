@@ -865,16 +865,25 @@ __global__ __launch_bounds__(256) void k_cls_verify(const int32_t* __restrict__ 
 // fly together and the differences are OR-ed, no short-circuit (see k_cls_rows); the second round of loads -- what to compare
 // with -- needs the positions, i.e. the row's threshold, i.e. its values.
 // ------------------------------------------------------------------------------------------------
-template <bool REFRESH>
+// HASH (option "setup_fused"): the same walk also serves the row pass of the Schwarz setup (schwarz.hip k_row_hash).  The Schwarz
+// setup runs first and reads the finished rows for their maxima and hashes; the solver's first SpMV would then read the same
+// rows again for the check above.  With HASH the entries a row's lanes hold serve both, and nothing of the check changes:
+//   - rmax[r] is the largest |value| of the row -- a maximum, so the same number whichever lanes form it.  k_row_hash starts
+//     its maximum from |first entry| and not from 0, so that a row of sixteen or more entries that are ALL NaN gets a NaN there:
+//     here such a row gets the canonical quiet NaN (`nan_row`), there the payload of one of its entries.  Nothing reads the
+//     payload: the hash scale of a NaN maximum is 0 and the subdomain's maximum passes a NaN by;
+//   - the hashes are wrapping 64-bit sums of row_hash_add over the row's entries: the same bits in any order.
+template <bool REFRESH, bool HASH>
 __global__ __launch_bounds__(256) void k_cs_reuse(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
                                                   const double* __restrict__ val, int32_t n, double tol,
                                                   const int32_t* __restrict__ cs_rowptr, const int32_t* __restrict__ cs_col,
                                                   double* cs_val, const uint16_t* __restrict__ pat,
                                                   const int32_t* __restrict__ pdelta, const uint32_t* __restrict__ cls,
-                                                  const double* __restrict__ cls_val, int cl, int32_t* __restrict__ n_bad) {
-    constexpr int NV = 4;                   // chunks of eight entries held in registers; longer rows read their tail twice
+                                                  const double* __restrict__ cls_val, int cl, int32_t* __restrict__ n_bad,
+                                                  double* __restrict__ rmax, uint64_t* __restrict__ rh) {
+    constexpr int NV = 4;
     const int e = threadIdx.x & 7;
-    const int gsh = threadIdx.x & 56;       // first lane of the row's group in its wave
+    const int gsh = threadIdx.x & 56;
     uint32_t bad = 0;
     for (int64_t r64 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 3; r64 < n; r64 += ((int64_t)gridDim.x * blockDim.x) >> 3) {
         const int32_t r = (int32_t)r64;
@@ -890,23 +899,35 @@ __global__ __launch_bounds__(256) void k_cs_reuse(const int32_t* __restrict__ ro
             v[u] = j < len ? __builtin_nontemporal_load(val + b + j) : 0.0;
             cc[u] = j < len ? __builtin_nontemporal_load(colind + b + j) : 0;
         }
-        double mx = 0.0;                    // (the maximum does not depend on the order; fmax passes a NaN by, as there)
+        double mx = 0.0;
+        bool num = false;                   // HASH: some entry of the row is a number
 #pragma unroll
-        for (int u = 0; u < NV; ++u) mx = fmax(mx, fabs(v[u]));
-        for (int32_t j = e + 8 * NV; j < len; j += 8) mx = fmax(mx, fabs(val[b + j]));
+        for (int u = 0; u < NV; ++u) {
+            mx = fmax(mx, fabs(v[u]));
+            if (HASH) num = num || (e + 8 * u < len && v[u] == v[u]);
+        }
+        for (int32_t j = e + 8 * NV; j < len; j += 8) {
+            const double vj = val[b + j];
+            mx = fmax(mx, fabs(vj));
+            if (HASH) num = num || vj == vj;
+        }
         for (int off = 4; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off, 8));
+        const bool nan_row = HASH && len >= 16 && (((uint32_t)(__ballot(num) >> gsh) & 0xffu) == 0u);
         const double thr = tol * mx;
         const bool dict = pid != SPAT_EXPL, classed = w != CLS_NONE;
-        // (a row with a pattern has at most SPAT_L stream entries and one with a class at most cl: its build verified that)
         const int32_t lim = min(clen, min(dict ? SPAT_L : clen, classed ? cl : clen));
         const int32_t* __restrict__ dl = pdelta + (dict ? (int)pid : 0) * SPAT_L;
         const double* tv = classed ? cls_val + (size_t)(w >> 8) * cl : cs_val + cb;
-        int32_t base = 0;                   // kept entries of the row before this chunk
+        // (the hash scale of a NaN maximum is 0, as row_hash_scale gives it)
+        const double hmax = nan_row ? __longlong_as_double(0x7ff8000000000000ll) : mx, scale = row_hash_scale(hmax);
+        uint64_t h1 = 0, h2 = 0;
+        int32_t base = 0;
         auto chunk = [&](int32_t j, double vj, int32_t cj) {
             const bool keep = j < len && !(fabs(vj) <= thr);
             const uint32_t m8 = (uint32_t)(__ballot(keep) >> gsh) & 0xffu;
             const int32_t pos = base + __popc(m8 & ((1u << e) - 1u));
             base += __popc(m8);
+            if (HASH && j < len) row_hash_add(vj, scale, cj, r, h1, h2);
             if (keep) {
                 const bool in = pos < lim;
                 const int32_t q = in ? pos : 0;
@@ -922,13 +943,22 @@ __global__ __launch_bounds__(256) void k_cs_reuse(const int32_t* __restrict__ ro
         };
 #pragma unroll
         for (int u = 0; u < NV; ++u) chunk(e + 8 * u, v[u], cc[u]);
-        for (int32_t j0 = 8 * NV; j0 < len; j0 += 8) {      // (uniform over the row's lanes)
+        for (int32_t j0 = 8 * NV; j0 < len; j0 += 8) {
             const int32_t j = j0 + e;
             const double vj = j < len ? val[b + j] : 0.0;
             const int32_t cj = j < len ? colind[b + j] : 0;
             chunk(j, vj, cj);
         }
         bad |= base != clen ? 1u : 0u;
+        for (int off = 4; HASH && off > 0; off >>= 1) {
+            h1 += __shfl_xor(h1, off, 8);
+            h2 += __shfl_xor(h2, off, 8);
+        }
+        if (HASH && e == 0) {
+            rmax[r] = hmax;
+            rh[2 * (int64_t)r] = h1;
+            rh[2 * (int64_t)r + 1] = h2;
+        }
     }
     const uint64_t any = __ballot(bad != 0u);
     if (any && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(any)) atomicOr(n_bad, 1);
@@ -1366,7 +1396,8 @@ struct LprRow { double max_avg; int lpr; decltype(&k_spmv<4>) kernel; };    // t
 struct ClsLdsRow { int max_len, rpt; decltype(&k_spmv_cls_lds<4, 8>) kernel; };     // the same rows per workgroup, row by row, as SPMV_CLS
 constexpr ClsLdsRow SPMV_CLS_LDS[] = {{8, 4, k_spmv_cls_lds<4, 8>}, {16, 4, k_spmv_cls_lds<4, 16>}, {SPAT_L, 2, k_spmv_cls_lds<2, SPAT_L>}};
 constexpr LprRow SPMV_LPR[] = {{4.0, 4, k_spmv<4>}, {10.0, 8, k_spmv<8>}, {24.0, 16, k_spmv<16>}, {48.0, 32, k_spmv<32>}, {1e300, 64, k_spmv<64>}};
-constexpr decltype(&k_cs_reuse<false>) CS_REUSE[2] = {k_cs_reuse<false>, k_cs_reuse<true>};     // [REFRESH]
+constexpr decltype(&k_cs_reuse<false, false>) CS_REUSE[2][2] = {{k_cs_reuse<false, false>, k_cs_reuse<true, false>},      // [HASH][REFRESH]
+                                                                {k_cs_reuse<false, true>, k_cs_reuse<true, true>}};
 
 // when the matrix takes the windowed kernels, and with them the solver's stream
 bool spmv_windowed(const fedd_ctx* c) { return c->spmv_kind == 0 && c->max_row_nnz <= 256 && c->nnz > 0; }
@@ -1404,26 +1435,40 @@ static void cs_record_path(SpmvStream& s) {
 
 // The matrix changed, its graph and the options did not (cs.key): one pass over the assembled rows instead of the build, see
 // k_cs_reuse.  *kept = false: some row differs (or there is nothing to keep), the caller builds.
+static bool cs_key_stands(const fedd_ctx* c) {
+    const SpmvStream::Key& k = c->cs.key;
+    return c->spmv_reuse && k.valid && k.pattern_gen == c->pattern_gen && k.n == c->n_rows && k.n_cols == c->n_cols && k.nnz == c->nnz &&
+           k.drop_tol == c->spmv_drop_tol;
+}
+
 static int spmv_reuse_try(fedd_ctx* c, bool* kept) {
     *kept = false;
     SpmvStream& s = c->cs;
     const SpmvStream::Key& k = s.key;
-    if (!c->spmv_reuse || !k.valid) return 0;
-    if (k.pattern_gen != c->pattern_gen || k.n != c->n_rows || k.n_cols != c->n_cols || k.nnz != c->nnz || k.drop_tol != c->spmv_drop_tol)
-        return 0;
+    if (!cs_key_stands(c)) return 0;
     const int32_t n = (int32_t)c->n_rows;
     const bool dict = s.npat > 0, classes = dict && s.ncls > 0;
     ScopedTimer ts(c, FEDD_T_SPMV_SETUP);
-    FEDD_TRY(c->d_flags.ensure(16));
-    int32_t* flag = c->d_flags.p + 13;
-    FEDD_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), c->stream));
-    // (a build that ran the class stage decided by the values: they have to be the same; else they are written)
-    hipLaunchKernelGGL(CS_REUSE[k.cls_tried ? 0 : 1], dim3(std::min(rows_x8(n), 8192u)), dim3(256), 0, c->stream, c->d_rowptr.p, c->d_colind.p,
-                       c->d_val.p, n, c->spmv_drop_tol, s.d_rowptr.p, s.d_col.p, s.d_val.p, dict ? s.d_pat.p : nullptr,
-                       dict ? pat_layout(c, n).pdelta : nullptr, classes ? s.d_cls.p : nullptr, classes ? s.d_clsval.p : nullptr, s.cls_len, flag);
     int32_t h_bad = 0;
-    FEDD_HIP(hipMemcpyAsync(&h_bad, flag, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    FEDD_HIP(hipStreamSynchronize(c->stream));
+    // option "setup_fused": the Schwarz setup's walk over these rows made the check (setup_walk below) and nothing wrote the
+    // matrix since; used once
+    const bool ready = c->setup_fused && c->setup_walk.valid && c->setup_walk.write_count == c->sys_write_count;
+    c->setup_walk.valid = false;
+    if (ready) {
+        h_bad = c->setup_walk.bad;
+        ++c->fused_checks_used;
+    } else {
+        FEDD_TRY(c->d_flags.ensure(16));
+        int32_t* flag = c->d_flags.p + 13;
+        FEDD_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), c->stream));
+        // (a build that ran the class stage decided by the values: they have to be the same; else they are written)
+        hipLaunchKernelGGL(CS_REUSE[0][k.cls_tried ? 0 : 1], dim3(std::min(rows_x8(n), 8192u)), dim3(256), 0, c->stream, c->d_rowptr.p, c->d_colind.p,
+                           c->d_val.p, n, c->spmv_drop_tol, s.d_rowptr.p, s.d_col.p, s.d_val.p, dict ? s.d_pat.p : nullptr,
+                           dict ? pat_layout(c, n).pdelta : nullptr, classes ? s.d_cls.p : nullptr, classes ? s.d_clsval.p : nullptr, s.cls_len, flag,
+                           (double*)nullptr, (uint64_t*)nullptr);
+        FEDD_HIP(hipMemcpyAsync(&h_bad, flag, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        FEDD_HIP(hipStreamSynchronize(c->stream));
+    }
     ts.stop();
     FEDD_HIP(hipGetLastError());
     if (h_bad) return 0;
@@ -1431,6 +1476,29 @@ static int spmv_reuse_try(fedd_ctx* c, bool* kept) {
     s.last_reused = 1;
     ++s.reuse_count;
     *kept = true;
+    return 0;
+}
+
+// Option "setup_fused", called by the Schwarz setup where it would launch k_row_hash: when the solver's next SpMV would go
+// through spmv_reuse_try with the matrix as it stands now -- the stream is stale, its key stands, and the rows Schwarz hashes are
+// the stream's rows (no row ghosts) -- k_cs_reuse<., HASH = true> forms the maxima and hashes and makes that check in the same walk.  The caller
+// reads d_flags[13] back with its next wait and records it in fedd_ctx::setup_walk with the write count.
+int setup_walk(fedd_ctx* c, double* d_rmax, uint64_t* d_row_hash, bool* ran) {
+    *ran = false;
+    c->setup_walk.valid = false;
+    SpmvStream& s = c->cs;
+    if (s.valid || !c->spmv_compact || !spmv_windowed(c) || !cs_key_stands(c) || c->n_rows_ext != c->n_rows || c->n_rows <= 0) return 0;
+    const int32_t n = (int32_t)c->n_rows;
+    const bool dict = s.npat > 0, classes = dict && s.ncls > 0;
+    FEDD_TRY(c->d_flags.ensure(16));
+    int32_t* flag = c->d_flags.p + 13;
+    FEDD_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), c->stream));
+    hipLaunchKernelGGL(CS_REUSE[1][s.key.cls_tried ? 0 : 1], dim3(std::min(rows_x8(n), 8192u)), dim3(256), 0, c->stream, c->d_rowptr.p,
+                       c->d_colind.p, c->d_val.p, n, c->spmv_drop_tol, s.d_rowptr.p, s.d_col.p, s.d_val.p, dict ? s.d_pat.p : nullptr,
+                       dict ? pat_layout(c, n).pdelta : nullptr, classes ? s.d_cls.p : nullptr, classes ? s.d_clsval.p : nullptr, s.cls_len, flag,
+                       d_rmax, d_row_hash);
+    ++c->fused_walks;
+    *ran = true;
     return 0;
 }
 

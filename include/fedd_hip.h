@@ -1270,6 +1270,12 @@ int fedd_gmres_capture_get(fedd_ctx* ctx, const char* what, double* out, int64_t
  * "pattern_reuse" 1 (default) = a fedd_pattern_build that repeats the last one keeps the pattern arrays (see
  * fedd_pattern_reuse_info), 0 = every call builds them; "spmv_reuse" 1 (default) = the solver's SpMV stream is verified
  * against the reassembled matrix in one pass and kept (see fedd_spmv_reuse_info), 0 = built for every matrix;
+ * "setup_fused" 1 (default) = work of the setup side that two calls would each do is done once: fedd_schwarz_setup's walk over
+ * the finished rows (row maxima and hashes of "schwarz_fp_kind" 0) also makes the "spmv_reuse" check the next SpMV would walk
+ * them again for, used only while nothing has written the system matrix in between; fedd_assemble_rhs keeps |det B| of every
+ * element (8 bytes per element) until fedd_mesh_set* or fedd_mesh_move changes the geometry; fedd_schwarz_setup reads the
+ * counts it has before its first host decision back in one copy; 0 = every call for itself, every count with a wait of its
+ * own (the same bits everywhere; the A/B switch);
  * "schwarz_fp_kind" 0 (default) = the fingerprints of that sharing are built from one hash per matrix ROW (column offsets and
  * quantised values of all its entries) and the rows' positions in the subdomain, 1 = entry by entry over the entries inside the
  * subdomain (the round-2 form; finds the same classes on the structured grids, four times slower);
@@ -1335,6 +1341,11 @@ int fedd_spmv_cls_blocks(fedd_ctx* ctx, int64_t* n_blocks_lds, int64_t* n_blocks
  * written to their places (same graph, new numbers: Newton steps, time loops).  Any mismatch runs the full build.
  * last_reused: 1 if the stream in use was kept; n_reused: keeps since the context was made.  Outputs may be NULL. */
 int fedd_spmv_reuse_info(fedd_ctx* ctx, int* last_reused, int64_t* n_reused);
+/* What option "setup_fused" (fedd_set_option) has done since the context was made: n_walks = Schwarz setups whose row walk also
+ * made the SpMV stream check; n_checks_used = of those, the checks the next SpMV found still valid (no write to the system matrix
+ * in between) and used in place of a walk of its own; n_absdet_kept = fedd_assemble_rhs calls that found |det B| of the elements
+ * kept from an earlier call.  Outputs may be NULL. */
+int fedd_setup_fused_info(fedd_ctx* ctx, int64_t* n_walks, int64_t* n_checks_used, int64_t* n_absdet_kept);
 /* bytes per column index of the solver's SpMV stream: 0 = column patterns in use (above), 2 = 16-bit offsets from a base per
  * window of the stream (option "spmv_col16", default 1; 10 instead of 12 bytes per entry) in every window whose columns span less
  * than 65536 -- any mesh numbered with some locality; entries_with_32bit_columns (nullable) = the entries of the windows that
