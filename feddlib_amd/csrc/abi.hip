@@ -189,9 +189,8 @@ static int mesh_set_impl(fedd_ctx* c, int dim, int nen, int64_t n_elem, const in
     system_written(c, SYS_VALUES | SYS_PATTERN | SYS_GONE);
     c->have_adj = false;
     c->tl_state = 0;     // the assembly's tile structures belong to the old mesh
-    c->p2_state = 0;     // ... and so do the gather lists of the P2 row sums
-    c->adv_state = 0;    // ... and the pattern and lists of the advection matrices; the velocity belonged to the old nodes
-    c->have_vel = false;
+    gather_lists_reset(c);  // ... and so do the gather lists (with gl_adv: the pattern and tables of the advection matrices)
+    c->have_vel = false;    // the velocity belonged to the old nodes
     c->have_mvel = false;   // ... and so did the mesh velocity, whose buffer goes with them
     c->d_mvel.release();
     c->have_idist = c->have_lscale = false;   // ... and the interface distances and the coefficients made from them
@@ -200,7 +199,7 @@ static int mesh_set_impl(fedd_ctx* c, int dim, int nen, int64_t n_elem, const in
     c->d_lscale.release();
     iface_release(c);       // ... and the matched interface, on both sides (a coupled system built on it finds it released)
     c->fsi_coupled = false; // (a coupled context that is given a mesh is an ordinary context again)
-    c->hy_lists = c->have_hy_f = false;   // ... and the lists and the force vector of the hyperelastic path
+    c->have_hy_f = false;   // ... and the force vector of the hyperelastic path
     c->nw_active = c->nw_have_src = c->nw_f_fresh = false;   // ... and the Newton state (newton.hip)
     c->nw_n = -1;
     c->have_surf = false;   // ... and the surface elements
@@ -1107,8 +1106,8 @@ extern "C" int fedd_mesh_setup_info(fedd_ctx* c, double* adjacency_ms, double* t
     FEDD_CHECK(c, "fedd_mesh_setup_info: null context");
     if (adjacency_ms) *adjacency_ms = c->have_adj ? c->adj_build_ms : 0.0;
     // (P2 meshes: the gather lists of the row sums take the place of the tile structures)
-    if (tiles_ms) *tiles_ms = (c->tl_state != 0 || c->p2_state != 0) ? c->tl_build_ms : 0.0;
-    if (tiles_state) *tiles_state = c->tl_state != 0 ? c->tl_state : c->p2_state;
+    if (tiles_ms) *tiles_ms = (c->tl_state != 0 || c->gl_p2.state != 0) ? c->tl_build_ms : 0.0;
+    if (tiles_state) *tiles_state = c->tl_state != 0 ? c->tl_state : c->gl_p2.state;
     if (n_tiles) *n_tiles = c->tl_state == 1 ? c->tl_ntile : 0;
     return 0;
 }

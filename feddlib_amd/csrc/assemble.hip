@@ -22,6 +22,7 @@
 // Quadrature points/weights and reference basis values/gradients are staged in LDS once per
 // workgroup.  The forms, the kernel arguments and the simplex geometry are in assemble_common.hpp.
 #include "assemble_common.hpp"
+#include "gather_lists.hpp"
 #include <algorithm>
 #include <array>
 #include <chrono>
@@ -748,13 +749,10 @@ int launch_matrix(fedd_ctx* c, const AsmArgs& a, int ntab, int64_t n_rows, int r
 }
 
 // ---------------------------------------------------------------------------------------------
-// Row sums of the P2 scalar forms from the element matrices of k_elem_matrix, by GATHER LISTS built once per mesh
-// (k_p2_lists): for every node-level nonzero (node p, slot s) the (adjacency entry q, local column j) pairs that contribute
-// to it, in adjacency order -- 16 bits each, q << 4 | j, behind a 16-bit start per nonzero; a node's list starts at
-// NEN x its adjacency start, no scan needed.  k_p2_gather: a wave per node, a lane per slot, every lane adds its few (2.6 on
-// average) element-matrix entries in list order and writes its CSR slot(s): no search, no atomics, bitwise reproducible, and
-// the summation order of the pair kernels.  (The pair kernels spend their time searching the row for every one of the 157 M
-// contributions of a 64^3-cell P2 cube: 11.4 ms with or without the element matrices.)
+// Row sums of the P2 scalar forms from the element matrices of k_elem_matrix, by GATHER LISTS built once per mesh (k_p2_lists;
+// gather_lists.hpp).  k_p2_gather: every lane adds its few (2.6 on average) element-matrix entries in list order, the summation
+// order of the pair kernels.  (Those spend their time searching the row for every one of the 157 M contributions of a 64^3-cell
+// P2 cube: 11.4 ms with or without the element matrices.)
 // ---------------------------------------------------------------------------------------------
 template <int NEN>
 __global__ __launch_bounds__(256) void k_p2_lists(const int32_t* __restrict__ conn, const int32_t* __restrict__ n2e_ptr,
@@ -764,11 +762,10 @@ __global__ __launch_bounds__(256) void k_p2_lists(const int32_t* __restrict__ co
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int64_t p = (int64_t)blockIdx.x * 4 + w; p < nn; p += (int64_t)gridDim.x * 4) {
         const int32_t ab = n2e_ptr[p], deg = n2e_ptr[p + 1] - ab;
-        const int32_t row = (int32_t)p * dofs, rs = rowptr[row], len = rowptr[row + 1] - rs;
-        const int nslot = full ? len / dofs : len, step = full ? dofs : 1;
-        const int32_t nbn = dofs == 1 ? rs : (full ? rs / (dofs * dofs) : rs / dofs);
+        const GatherRow r = GatherRows{rowptr, dofs, full}(p);
+        const int32_t rs = r.rs, nbn = r.nb, nslot = r.nslot, step = full ? dofs : 1;
         const int64_t base = (int64_t)ab * NEN;
-        if (deg > 4095 || deg * NEN > 65535) {
+        if (deg > GATHER_MAX_DEG || deg * NEN > GATHER_MAX_SRC) {
             if (lane == 0) atomicMax(bad, 1);
             continue;
         }
@@ -796,62 +793,30 @@ __global__ __launch_bounds__(256) void k_p2_lists(const int32_t* __restrict__ co
                     const int32_t* __restrict__ en = conn + (int64_t)(n2e[ab + q] / NEN) * NEN;
 #pragma unroll
                     for (int j = 0; j < NEN; ++j)
-                        if (en[j] == v) src[base + k++] = (uint16_t)((q << 4) | j);
+                        if (en[j] == v) src[base + k++] = gather_pack(q, j);
                 }
             running += __shfl(incl, 63, 64);
         }
     }
 }
 
+// one element-matrix entry per source; the sum goes to the slot of every component's row (scalar rows or diagonal blocks)
+template <int NEN>
+struct P2Sum : GatherBlockSum<NEN, 1> {
+    const int32_t* rowptr;
+    int dofs;
+    double* val;
+    __device__ void store(const GatherRow& r, int sl) {
+        for (int comp = 0; comp < dofs; ++comp) val[rowptr[r.row + comp] + sl] = this->acc[0];
+    }
+};
+
 template <int NEN>
 __global__ __launch_bounds__(256) void k_p2_gather(const int32_t* __restrict__ n2e_ptr, const int32_t* __restrict__ n2e,
                                                    const int32_t* __restrict__ rowptr, int dofs, int32_t nn,
                                                    const uint16_t* __restrict__ soff, const uint16_t* __restrict__ src,
                                                    const double* __restrict__ ke, double* __restrict__ val) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int64_t p = (int64_t)blockIdx.x * 4 + w; p < nn; p += (int64_t)gridDim.x * 4) {
-        const int32_t ab = n2e_ptr[p], deg = n2e_ptr[p + 1] - ab;
-        const int32_t row = (int32_t)p * dofs, rs = rowptr[row], nslot = rowptr[row + 1] - rs;     // (scalar or diagonal blocks)
-        const int32_t nbn = dofs == 1 ? rs : rs / dofs;
-        const uint16_t* __restrict__ sp = src + (int64_t)ab * NEN;
-        const int total = deg * NEN;
-        for (int sl = lane; sl < nslot; sl += 64) {
-            const int b = soff[nbn + sl], e2 = sl + 1 < nslot ? (int)soff[nbn + sl + 1] : total;
-            double acc = 0.0;
-            for (int k = b; k < e2; ++k) {
-                const uint32_t sr = sp[k];
-                acc += ke[(int64_t)n2e[ab + (sr >> 4)] * NEN + (sr & 15u)];
-            }
-            for (int comp = 0; comp < dofs; ++comp) val[rowptr[row + comp] + sl] = acc;
-        }
-    }
-}
-
-// the gather lists of the current mesh (built at the first P2 assembly that uses them); c->p2_state = -1: not applicable
-template <int NEN>
-int p2_lists_build(fedd_ctx* c) {
-    c->p2_state = -1;
-    const int64_t nn = c->n_own + c->n_rowg;
-    if (!c->have_pattern || !c->have_adj || c->block_mode == FEDD_BLOCK_FULL || nn <= 0) return 0;
-    int32_t n2e_total = 0;
-    FEDD_HIP(hipMemcpyAsync(&n2e_total, c->d_n2e_ptr.p + nn, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    FEDD_HIP(hipStreamSynchronize(c->stream));
-    const int64_t node_nnz = c->nnz_ext / c->dofs;      // scalar: nnz; diagonal blocks: dofs rows of the node-level length each
-    FEDD_TRY(c->d_p2_soff.ensure((size_t)node_nnz + 2));
-    FEDD_TRY(c->d_p2_src.ensure((size_t)n2e_total * NEN + 2));
-    FEDD_TRY(c->d_flags.ensure(16));
-    int32_t* bad = c->d_flags.p + 6;
-    FEDD_HIP(hipMemsetAsync(bad, 0, sizeof(int32_t), c->stream));
-    const int nwg = (int)std::min<int64_t>((nn + 3) / 4, 256 * 32);
-    hipLaunchKernelGGL(k_p2_lists<NEN>, dim3((unsigned)nwg), dim3(256), 0, c->stream, (const int32_t*)c->d_conn.p,
-                       (const int32_t*)c->d_n2e_ptr.p, (const int32_t*)c->d_n2e.p, (const int32_t*)c->d_rowptr.p,
-                       (const int32_t*)c->d_colind.p, c->dofs, 0, (int32_t)nn, c->d_p2_soff.p, c->d_p2_src.p, bad);
-    int32_t h_bad = 0;
-    FEDD_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    FEDD_HIP(hipStreamSynchronize(c->stream));
-    FEDD_HIP(hipGetLastError());
-    if (!h_bad) c->p2_state = 1;
-    return 0;
+    gather_walk<NEN>(n2e_ptr, n2e, soff, src, nn, GatherRows{rowptr, dofs, 0}, P2Sum<NEN>{{ke}, rowptr, dofs, val});
 }
 
 // f(std::integral_constant<int, FORM>()) for the matrix form kform (F_LAPLACE, F_MASS or F_LINELAS)
@@ -862,26 +827,25 @@ int with_form(int kform, F&& f) {
     return f(std::integral_constant<int, F_LINELAS>());
 }
 
-// rows of the P2 scalar forms from the element matrices in c->d_ke through the gather lists (scalar rows or diagonal
-// blocks); returns -1 (without error) where the lists do not apply
+// rows of the P2 scalar forms (scalar or diagonal blocks) from c->d_ke through the gather lists; -1 (no error) where they do not apply
 template <int NEN>
 int launch_p2_gather(fedd_ctx* c) {
     if (c->block_mode == FEDD_BLOCK_FULL) return -1;
-    if (c->p2_state == 0) {
+    // the lists of the current mesh, built at the first P2 assembly that uses them: of the node-level pattern, which the scalar
+    // and the DIAG patterns of a mesh share (nnz of a scalar pattern; diagonal blocks have dofs rows of that length each)
+    GatherLists& gl = c->gl_p2;
+    const int64_t nn = c->n_own + c->n_rowg;
+    if (gl.state == GatherLists::NOT_BUILT) {
         FEDD_HIP(hipStreamSynchronize(c->stream));
         const auto t0 = std::chrono::steady_clock::now();
-        FEDD_TRY(p2_lists_build<NEN>(c));
+        FEDD_TRY(gather_lists_ensure(c, gl, GATHER_NODE_PATTERN, c->d_rowptr.p, c->d_colind.p, c->dofs, 0, nn, c->nnz_ext / c->dofs, nullptr));
         FEDD_HIP(hipStreamSynchronize(c->stream));
         c->tl_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
-    if (c->p2_state != 1) return -1;
-    const int64_t nn = c->n_own + c->n_rowg;
-    const int nwg = (int)std::min<int64_t>((nn + 3) / 4, 256 * 32);
+    if (gl.state != GatherLists::READY) return -1;
     ScopedTimer t(c, FEDD_T_ASSEMBLE);
-    hipLaunchKernelGGL(k_p2_gather<NEN>, dim3((unsigned)nwg), dim3(256), 0, c->stream, (const int32_t*)c->d_n2e_ptr.p,
-                       (const int32_t*)c->d_n2e.p, (const int32_t*)c->d_rowptr.p, c->dofs, (int32_t)nn,
-                       (const uint16_t*)c->d_p2_soff.p, (const uint16_t*)c->d_p2_src.p, (const double*)c->d_ke.p,
-                       c->d_val.p);
+    hipLaunchKernelGGL(k_p2_gather<NEN>, dim3((unsigned)gather_grid(nn)), dim3(256), 0, c->stream, c->d_n2e_ptr.p, c->d_n2e.p,
+                       c->d_rowptr.p, c->dofs, (int32_t)nn, gl.soff.p, gl.src.p, c->d_ke.p, c->d_val.p);
     t.stop();
     FEDD_HIP(hipGetLastError());
     return 0;
@@ -898,8 +862,7 @@ int launch_p2_gather(fedd_ctx* c) {
 // S_ij[a][b] = |det B| (O[b][a] + delta_ab tr O) as one contiguous stream [pair][a][b]: 8 * n_elem * NEN (NEN + 1) / 2 * dim^2
 // bytes of scratch (d_adv_ke; 3960 bytes per P2 tetrahedron, 55 % of a full element matrix).
 // The rows are then summed through the gather lists of the system's FULL pattern (full_lists_ensure, shared with the
-// hyperelastic tangent): a wave per node, a lane per node-level nonzero, the element blocks added in adjacency order, read
-// transposed where the row's local index is the larger one.  No atomics, bitwise reproducible.
+// hyperelastic tangent; gather_lists.hpp), the element blocks read transposed where the row's local index is the larger one.
 // Operation order per pair: k ascending; (c_k w_k) d_b phi_i, times d_a phi_j, accumulated; the trace added; times |det B|.
 // ---------------------------------------------------------------------------------------------
 template <int DIM, int NEN>
@@ -981,53 +944,46 @@ __global__ __launch_bounds__(256) void k_stress_elem(AsmArgs a, int64_t n_elem, 
     }
 }
 
-// rows of the system's FULL pattern from the packed pair blocks of k_stress_elem
+// rows of the system's FULL pattern from the packed pair blocks of k_stress_elem: one per source, read transposed where the
+// row's local index is the larger one
+template <int DIM, int NEN>
+struct StressSum : GatherBlockSum<NEN, DIM * DIM> {
+    static constexpr int DD = DIM * DIM, NP = NEN * (NEN + 1) / 2;
+    double* val;
+    __device__ void add(int32_t at, int j) {
+        const int32_t el = at / NEN;
+        const int i = at - el * NEN;
+        const int lo = i < j ? i : j, hi = i < j ? j : i;
+        const double* __restrict__ kb = this->ke + ((int64_t)el * NP + (lo * NEN - lo * (lo - 1) / 2 + (hi - lo))) * DD;
+        if (i <= j) {
+#pragma unroll
+            for (int m = 0; m < DD; ++m) this->acc[m] += kb[m];
+        } else {
+#pragma unroll
+            for (int r = 0; r < DIM; ++r)
+#pragma unroll
+                for (int cc = 0; cc < DIM; ++cc) this->acc[r * DIM + cc] += kb[cc * DIM + r];
+        }
+    }
+    __device__ void store(const GatherRow& g, int sl) {
+#pragma unroll
+        for (int r = 0; r < DIM; ++r) {
+            const int64_t to = (int64_t)g.rs + (int64_t)r * g.nslot * DIM + (int64_t)sl * DIM;
+#pragma unroll
+            for (int cc = 0; cc < DIM; ++cc) val[to + cc] = this->acc[r * DIM + cc];
+        }
+    }
+};
+
 template <int DIM, int NEN>
 __global__ __launch_bounds__(256) void k_stress_gather(const int32_t* __restrict__ n2e_ptr, const int32_t* __restrict__ n2e,
                                                        const int32_t* __restrict__ rowptr, int32_t nn,
                                                        const uint16_t* __restrict__ soff, const uint16_t* __restrict__ src,
                                                        const double* __restrict__ ke, double* __restrict__ val) {
-    constexpr int DD = DIM * DIM, NP = NEN * (NEN + 1) / 2;
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int64_t p = (int64_t)blockIdx.x * 4 + w; p < nn; p += (int64_t)gridDim.x * 4) {
-        const int32_t ab = n2e_ptr[p], deg = n2e_ptr[p + 1] - ab;
-        const int32_t row = (int32_t)p * DIM, rs = rowptr[row];
-        const int32_t nslot = (rowptr[row + 1] - rs) / DIM, nb = rs / DD;
-        const uint16_t* __restrict__ sp = src + (int64_t)ab * NEN;
-        const int total = deg * NEN;
-        for (int sl = lane; sl < nslot; sl += 64) {
-            const int b = soff[nb + sl], e2 = sl + 1 < nslot ? (int)soff[nb + sl + 1] : total;
-            double acc[DD];
-#pragma unroll
-            for (int m = 0; m < DD; ++m) acc[m] = 0.0;
-            for (int k = b; k < e2; ++k) {
-                const uint32_t sr = sp[k];
-                const int32_t at = n2e[ab + (sr >> 4)];         // element * NEN + local index of node p in it
-                const int32_t el = at / NEN;
-                const int i = at - el * NEN, j = (int)(sr & 15u);
-                const int lo = i < j ? i : j, hi = i < j ? j : i;
-                const double* __restrict__ kb = ke + ((int64_t)el * NP + (lo * NEN - lo * (lo - 1) / 2 + (hi - lo))) * DD;
-                if (i <= j) {
-#pragma unroll
-                    for (int m = 0; m < DD; ++m) acc[m] += kb[m];
-                } else {
-#pragma unroll
-                    for (int r = 0; r < DIM; ++r)
-#pragma unroll
-                        for (int cc = 0; cc < DIM; ++cc) acc[r * DIM + cc] += kb[cc * DIM + r];
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < DIM; ++r) {
-                const int64_t to = (int64_t)rs + (int64_t)r * nslot * DIM + (int64_t)sl * DIM;
-#pragma unroll
-                for (int cc = 0; cc < DIM; ++cc) val[to + cc] = acc[r * DIM + cc];
-            }
-        }
-    }
+    gather_walk<NEN>(n2e_ptr, n2e, soff, src, nn, GatherRows{rowptr, DIM, 1}, StressSum<DIM, NEN>{{ke}, val});
 }
 
-// a.tab / a.nq: the tables of full_lists_ensure (w | dphi); the lists are c->d_hy_soff / d_hy_src
+// a.tab / a.nq: the tables of full_lists_ensure (w | dphi); the lists are c->gl_full
 template <int DIM, int NEN>
 int launch_stress(fedd_ctx* c, const AsmArgs& a) {
     constexpr int DD = DIM * DIM, NP = NEN * (NEN + 1) / 2;
@@ -1045,10 +1001,8 @@ int launch_stress(fedd_ctx* c, const AsmArgs& a) {
         const int64_t nwg = std::min<int64_t>((c->n_elem + 3) / 4, 256 * 8);
         hipLaunchKernelGGL((k_stress_elem<DIM, NEN>), dim3((unsigned)nwg), dim3(256), lds, c->stream, a, c->n_elem, c->d_adv_ke.p);
     }
-    const int nwg2 = (int)std::max<int64_t>(1, std::min<int64_t>((nn + 3) / 4, 256 * 32));
-    hipLaunchKernelGGL((k_stress_gather<DIM, NEN>), dim3((unsigned)nwg2), dim3(256), 0, c->stream, (const int32_t*)c->d_n2e_ptr.p,
-                       (const int32_t*)c->d_n2e.p, (const int32_t*)c->d_rowptr.p, (int32_t)nn, (const uint16_t*)c->d_hy_soff.p,
-                       (const uint16_t*)c->d_hy_src.p, (const double*)c->d_adv_ke.p, c->d_val.p);
+    hipLaunchKernelGGL((k_stress_gather<DIM, NEN>), dim3((unsigned)gather_grid(nn)), dim3(256), 0, c->stream, c->d_n2e_ptr.p,
+                       c->d_n2e.p, c->d_rowptr.p, (int32_t)nn, c->gl_full.soff.p, c->gl_full.src.p, c->d_adv_ke.p, c->d_val.p);
     t.stop();
     FEDD_HIP(hipGetLastError());
     return 0;
@@ -1078,7 +1032,7 @@ int launch_laplace_xdim(fedd_ctx* c, AsmArgs a, int ntab) {
     const int rc = launch_p2_gather<NEN>(c);
     if constexpr (NEN == DIM + 1) c->tl_build_ms = keep_ms;     // (on a P1 mesh that figure is the tile build's)
     FEDD_CHECK(rc >= 0, "fedd_assemble(FEDD_FORM_LAPLACE_XDIM): the gather lists do not fit this mesh (a node with more than %d "
-                        "incident elements)", 65535 / NEN);
+                        "incident elements)", GATHER_MAX_SRC / NEN);
     return rc;
 }
 
@@ -1235,16 +1189,11 @@ int assemble_div(fedd_ctx* c, int64_t n_p, int slot_b, int slot_bt) {
     AsmArgs ab = a, at = a;
     ab.rowptr = B.rowptr.p; ab.colind = B.colind.p; ab.val = B.val.p; ab.n_rows = (int32_t)n_p; ab.dofs = 1;
     at.rowptr = BT.rowptr.p; at.colind = BT.colind.p; at.val = BT.val.p; at.n_rows = (int32_t)BT.n_rows; at.dofs = dim;
-#define DIV_LAUNCH(D, N)                                                                               \
-    do {                                                                                               \
-        FEDD_TRY((launch_matrix<D, N, F_DIV>(c, ab, ntab, n_p, B.max_row_nnz)));                       \
-        FEDD_TRY((launch_matrix<D, N, F_DIVT>(c, at, ntab, BT.n_rows, BT.max_row_nnz)));               \
-    } while (0)
-    if (dim == 2 && nen == 3) DIV_LAUNCH(2, 3);
-    else if (dim == 2 && nen == 6) DIV_LAUNCH(2, 6);
-    else if (dim == 3 && nen == 4) DIV_LAUNCH(3, 4);
-    else DIV_LAUNCH(3, 10);
-#undef DIV_LAUNCH
+    FEDD_TRY(with_element(dim, nen, [&](auto d, auto n) {
+        constexpr int D = decltype(d)::value, N = decltype(n)::value;
+        FEDD_TRY((launch_matrix<D, N, F_DIV>(c, ab, ntab, n_p, B.max_row_nnz)));
+        return launch_matrix<D, N, F_DIVT>(c, at, ntab, BT.n_rows, BT.max_row_nnz);
+    }));
     B.valid = BT.valid = true;
     B.pattern_id = ++c->pattern_counter;
     BT.pattern_id = ++c->pattern_counter;
@@ -1266,8 +1215,7 @@ namespace {
 // reference-space vector w_q B^-1 u_h) and w_q grad u_h at the quadrature points into LDS, and then take the NEN^2 node pairs:
 // n_ij and the dim x dim block of W are summed in registers and leave as one contiguous stream, [i][j][dim x dim] (N alone:
 // [i][j]).  ADV_NEWTON adds n_ij to the diagonal of the block, so N + W costs one pass over the geometry and u.
-// The rows are then summed by gather lists (k_p2_lists on the node-level pattern, built once per mesh): a wave per node, a lane
-// per node-level nonzero, the element blocks added in adjacency order -- no atomics, bitwise reproducible -- and written as
+// The rows are then summed by gather lists on the node-level pattern (gather_lists.hpp; built once per mesh) and written as
 // scale * block + M[slot_add] into the FULL pattern, whose positions follow from the node-level pattern in closed form.
 //
 // ALE convection on a moved mesh (fedd_assemble_advection_ale; template parameter ALE, 0 = the fixed-mesh kinds above, whose
@@ -1454,52 +1402,44 @@ __global__ __launch_bounds__(256) void k_adv_elem(AdvArgs a, int64_t n_elem, dou
     }
 }
 
-// rows of the FULL pattern from the element blocks: val = scale * sum + M[slot_add] (add_full: M has the FULL pattern, else DIAG)
+// one BLK block per source (BLK 1: a scalar for the diagonal of the block); val = scale * sum + M[slot_add] (add_full: M has the
+// FULL pattern, else DIAG), under the compiler's default contraction
+template <int DIM, int NEN, int BLK>
+struct AdvSum : GatherBlockSum<NEN, BLK> {
+    double scale;
+    const double* addval;
+    int add_full;
+    double* val;
+    __device__ void store(const GatherRow& g, int sl) {
+        const int32_t nb = g.nb, nslot = g.nslot;
+#pragma unroll
+        for (int r = 0; r < DIM; ++r) {
+            const int64_t rs = (int64_t)nb * DIM * DIM + (int64_t)r * nslot * DIM + (int64_t)sl * DIM;
+#pragma unroll
+            for (int cc = 0; cc < DIM; ++cc) {
+                double v = scale * (BLK == 1 ? (r == cc ? this->acc[0] : 0.0) : this->acc[(r * DIM + cc) % BLK]);
+                if (addval) {
+                    if (add_full) v += addval[rs + cc];
+                    else if (r == cc) v += addval[(int64_t)nb * DIM + (int64_t)r * nslot + sl];
+                }
+                val[rs + cc] = v;
+            }
+        }
+    }
+};
+
 template <int DIM, int NEN, int BLK>
 __global__ __launch_bounds__(256) void k_adv_gather(const int32_t* __restrict__ n2e_ptr, const int32_t* __restrict__ n2e,
                                                     const int32_t* __restrict__ nptr, int32_t nn, const uint16_t* __restrict__ soff,
                                                     const uint16_t* __restrict__ src, const double* __restrict__ ke, double scale,
                                                     const double* __restrict__ addval, int add_full, double* __restrict__ val) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int64_t p = (int64_t)blockIdx.x * 4 + w; p < nn; p += (int64_t)gridDim.x * 4) {
-        const int32_t ab = n2e_ptr[p], deg = n2e_ptr[p + 1] - ab;
-        const int32_t nb = nptr[p], nslot = nptr[p + 1] - nb;
-        const uint16_t* __restrict__ sp = src + (int64_t)ab * NEN;
-        const int total = deg * NEN;
-        for (int sl = lane; sl < nslot; sl += 64) {
-            const int b = soff[nb + sl], e2 = sl + 1 < nslot ? (int)soff[nb + sl + 1] : total;
-            double acc[BLK];
-#pragma unroll
-            for (int m = 0; m < BLK; ++m) acc[m] = 0.0;
-            for (int k = b; k < e2; ++k) {
-                const uint32_t sr = sp[k];
-                const double* __restrict__ kb = ke + ((int64_t)n2e[ab + (sr >> 4)] * NEN + (sr & 15u)) * BLK;
-#pragma unroll
-                for (int m = 0; m < BLK; ++m) acc[m] += kb[m];
-            }
-#pragma unroll
-            for (int r = 0; r < DIM; ++r) {
-                const int64_t rs = (int64_t)nb * DIM * DIM + (int64_t)r * nslot * DIM + (int64_t)sl * DIM;
-#pragma unroll
-                for (int cc = 0; cc < DIM; ++cc) {
-                    double v = scale * (BLK == 1 ? (r == cc ? acc[0] : 0.0) : acc[(r * DIM + cc) % BLK]);
-                    if (addval) {
-                        if (add_full) v += addval[rs + cc];
-                        else if (r == cc) v += addval[(int64_t)nb * DIM + (int64_t)r * nslot + sl];
-                    }
-                    val[rs + cc] = v;
-                }
-            }
-        }
-    }
+    gather_walk<NEN>(n2e_ptr, n2e, soff, src, nn, GatherRows{nptr, 1, 0}, AdvSum<DIM, NEN, BLK>{{ke}, scale, addval, add_full, val});
 }
 
 // the per-mesh structures: node-level pattern, gather lists, quadrature tables (determineDegree, FE_def.hpp:1770-1772, 1859-1861:
 // P2 5 / 5; P1 2 / 3, remapped by fe_quadrature)
-template <int NEN>
 int adv_setup(fedd_ctx* c) {
     const int dim = c->dim, nen = c->nen;
-    const int64_t nn = c->n_own;
     {
         ScopedTimer t(c, FEDD_T_SYMBOLIC);
         int32_t mx = 0;
@@ -1507,24 +1447,10 @@ int adv_setup(fedd_ctx* c) {
         c->adv_max_nn = mx;
         FEDD_CHECK(c->adv_node_nnz * dim * dim < ((int64_t)1 << 31), "advection: %lld nonzeros exceed 32-bit local offsets",
                    (long long)(c->adv_node_nnz * dim * dim));
-        int32_t n2e_total = 0;
-        FEDD_HIP(hipMemcpyAsync(&n2e_total, c->d_n2e_ptr.p + nn, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        FEDD_HIP(hipStreamSynchronize(c->stream));
-        FEDD_TRY(c->d_adv_soff.ensure((size_t)c->adv_node_nnz + 2));
-        FEDD_TRY(c->d_adv_src.ensure((size_t)n2e_total * NEN + 2));
-        FEDD_TRY(c->d_flags.ensure(16));
-        int32_t* bad = c->d_flags.p + 6;
-        FEDD_HIP(hipMemsetAsync(bad, 0, sizeof(int32_t), c->stream));
-        const int nwg = (int)std::min<int64_t>((nn + 3) / 4, 256 * 32);
-        hipLaunchKernelGGL(k_p2_lists<NEN>, dim3((unsigned)nwg), dim3(256), 0, c->stream, (const int32_t*)c->d_conn.p,
-                           (const int32_t*)c->d_n2e_ptr.p, (const int32_t*)c->d_n2e.p, (const int32_t*)c->d_adv_nptr.p,
-                           (const int32_t*)c->d_adv_ncol.p, 1, 0, (int32_t)nn, c->d_adv_soff.p, c->d_adv_src.p, bad);
-        int32_t h_bad = 0;
-        FEDD_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        FEDD_HIP(hipStreamSynchronize(c->stream));
-        FEDD_HIP(hipGetLastError());
-        FEDD_CHECK(!h_bad, "advection: a node with more than 4095 incident elements does not fit the gather lists");
+        FEDD_TRY(gather_lists_ensure(c, c->gl_adv, GATHER_NODE_PATTERN, c->d_adv_nptr.p, c->d_adv_ncol.p, 1, 0, c->n_own, c->adv_node_nnz,
+                                     "advection"));
     }
+    c->gl_adv.reset();      // ready when the tables are
     const bool p2 = nen > dim + 1;
     const int deg_n = p2 ? 5 : 2, deg_w = p2 ? 5 : 3;
     FeTables tn, tw;
@@ -1545,7 +1471,7 @@ int adv_setup(fedd_ctx* c) {
     FEDD_TRY(c->d_adv_tab.ensure(host.size()));
     FEDD_HIP(hipMemcpyAsync(c->d_adv_tab.p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     FEDD_HIP(hipStreamSynchronize(c->stream));  // `host` is a local
-    c->adv_state = 1;
+    c->gl_adv.state = GatherLists::READY;
     return 0;
 }
 
@@ -1567,12 +1493,10 @@ int launch_advection(fedd_ctx* c, double scale, const DevCsr* add, DevCsr& out) 
         const int64_t nwg = std::min<int64_t>((c->n_elem + 3) / 4, 256 * 8);
         hipLaunchKernelGGL((k_adv_elem<DIM, NEN, KIND, ALE>), dim3((unsigned)nwg), dim3(256), lds, c->stream, a, c->n_elem, c->d_adv_ke.p);
     }
-    const int nwg2 = (int)std::min<int64_t>((nn + 3) / 4, 256 * 32);
     const int add_full = add && add->block_mode == FEDD_BLOCK_FULL ? 1 : 0;
-    hipLaunchKernelGGL((k_adv_gather<DIM, NEN, BLK>), dim3((unsigned)nwg2), dim3(256), 0, c->stream, (const int32_t*)c->d_n2e_ptr.p,
-                       (const int32_t*)c->d_n2e.p, (const int32_t*)c->d_adv_nptr.p, (int32_t)nn, (const uint16_t*)c->d_adv_soff.p,
-                       (const uint16_t*)c->d_adv_src.p, (const double*)c->d_adv_ke.p, scale, add ? (const double*)add->val.p : nullptr,
-                       add_full, out.val.p);
+    hipLaunchKernelGGL((k_adv_gather<DIM, NEN, BLK>), dim3((unsigned)gather_grid(nn)), dim3(256), 0, c->stream, c->d_n2e_ptr.p,
+                       c->d_n2e.p, c->d_adv_nptr.p, (int32_t)nn, c->gl_adv.soff.p, c->gl_adv.src.p, c->d_adv_ke.p, scale,
+                       add ? (const double*)add->val.p : nullptr, add_full, out.val.p);
     // byte model: geometry, u and connectivity once per element, the element blocks written and read once, the FULL values written;
     // the fused ALE kinds read one more nodal field, w (P alone reads w in the place of u)
     t.bytes(((double)c->n_elem * (NEN * 4.0 + 2.0 * NEN * NEN * BLK * 8.0) + (double)c->n_node * DIM * (ALE == ALE_FUSED ? 24.0 : 16.0) +
@@ -1605,27 +1529,34 @@ __global__ __launch_bounds__(256) void k_mesh_velocity_diff(const double* __rest
 
 }  // namespace
 
-int build_gather_lists(fedd_ctx* c, const int32_t* rowptr, const int32_t* colind, int dofs, int full, uint16_t* soff, uint16_t* src,
-                       const char* who) {
-    const int64_t nn = c->n_own;
-    FEDD_TRY(c->d_flags.ensure(16));
-    int32_t* bad = c->d_flags.p + 6;
-    FEDD_HIP(hipMemsetAsync(bad, 0, sizeof(int32_t), c->stream));
-    const int nwg = (int)std::max<int64_t>(1, std::min<int64_t>((nn + 3) / 4, 256 * 32));
-    auto go = [&](auto nen) {
-        hipLaunchKernelGGL(k_p2_lists<decltype(nen)::value>, dim3((unsigned)nwg), dim3(256), 0, c->stream, (const int32_t*)c->d_conn.p,
-                           (const int32_t*)c->d_n2e_ptr.p, (const int32_t*)c->d_n2e.p, rowptr, colind, dofs, full, (int32_t)nn, soff,
-                           src, bad);
-    };
-    if (c->nen == 3) go(std::integral_constant<int, 3>());
-    else if (c->nen == 4) go(std::integral_constant<int, 4>());
-    else if (c->nen == 6) go(std::integral_constant<int, 6>());
-    else go(std::integral_constant<int, 10>());
-    int32_t h_bad = 0;
-    FEDD_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    FEDD_HIP(hipStreamSynchronize(c->stream));
-    FEDD_HIP(hipGetLastError());
-    FEDD_CHECK(!h_bad, "%s: a node with more than 4095 incident elements does not fit the gather lists", who);
+int gather_lists_ensure(fedd_ctx* c, GatherLists& gl, uint64_t pattern, const int32_t* rowptr, const int32_t* colind, int dofs,
+                        int full, int64_t nn, int64_t node_nnz, const char* who) {
+    if (!gl.ready_for(c->mesh_id, pattern)) {
+        gl.mesh_id = c->mesh_id;
+        gl.pattern = pattern;
+        gl.state = GatherLists::NO_FIT;
+        if (!who && (!c->have_pattern || !c->have_adj || nn <= 0)) return 0;
+        int32_t n2e_total = 0, h_bad = 0;
+        FEDD_HIP(hipMemcpyAsync(&n2e_total, c->d_n2e_ptr.p + nn, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        FEDD_HIP(hipStreamSynchronize(c->stream));
+        FEDD_TRY(gl.soff.ensure((size_t)node_nnz + 2));
+        FEDD_TRY(gl.src.ensure((size_t)n2e_total * c->nen + 2));
+        FEDD_TRY(c->d_flags.ensure(16));
+        int32_t* bad = c->d_flags.p + 6;
+        FEDD_HIP(hipMemsetAsync(bad, 0, sizeof(int32_t), c->stream));
+        with_nen(c->nen, [&](auto nen) {
+            hipLaunchKernelGGL(k_p2_lists<decltype(nen)::value>, dim3((unsigned)gather_grid(nn)), dim3(256), 0, c->stream,
+                               (const int32_t*)c->d_conn.p, (const int32_t*)c->d_n2e_ptr.p, (const int32_t*)c->d_n2e.p, rowptr, colind,
+                               dofs, full, (int32_t)nn, gl.soff.p, gl.src.p, bad);
+            return 0;
+        });
+        FEDD_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        FEDD_HIP(hipStreamSynchronize(c->stream));
+        FEDD_HIP(hipGetLastError());
+        if (!h_bad) gl.state = GatherLists::READY;
+    }
+    FEDD_CHECK(gl.state == GatherLists::READY || !who, "%s: a node with more than %d incident elements does not fit the gather lists",
+               who, GATHER_MAX_DEG);
     return 0;
 }
 
@@ -1633,17 +1564,12 @@ int build_gather_lists(fedd_ctx* c, const int32_t* rowptr, const int32_t* colind
 // Grad) (P1 0 + 0 -> 1, FE_def.hpp:5508-5509; P2 1 + 1), built once per (mesh, pattern) and kept: one copy for the hyperelastic
 // tangent and the stress form, which sum their element blocks into the same rows from the same rule.
 int full_lists_ensure(fedd_ctx* c, const char* who) {
-    if (c->hy_lists && c->hy_mesh_id == c->mesh_id && c->hy_pattern_gen == c->pattern_gen) return 0;
+    if (c->gl_full.ready_for(c->mesh_id, c->pattern_gen)) return 0;
     const int dim = c->dim, nen = c->nen;
-    c->hy_lists = false;
     ScopedTimer t(c, FEDD_T_SYMBOLIC);
-    int32_t n2e_total = 0;
-    FEDD_HIP(hipMemcpyAsync(&n2e_total, c->d_n2e_ptr.p + c->n_own, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    FEDD_HIP(hipStreamSynchronize(c->stream));
-    FEDD_TRY(c->d_hy_soff.ensure((size_t)(c->nnz / (dim * dim)) + 2));
-    FEDD_TRY(c->d_hy_src.ensure((size_t)n2e_total * nen + 2));
-    FEDD_TRY(build_gather_lists(c, c->d_rowptr.p, c->d_colind.p, dim, 1, c->d_hy_soff.p, c->d_hy_src.p, who));
+    FEDD_TRY(gather_lists_ensure(c, c->gl_full, c->pattern_gen, c->d_rowptr.p, c->d_colind.p, dim, 1, c->n_own, c->nnz / (dim * dim), who));
     t.stop();
+    c->gl_full.reset();     // ready when the tables are
     int degree = 2 * fe_degree(nen, dim, true);
     if (degree == 0) degree = 1;
     FeTables tb;
@@ -1654,9 +1580,7 @@ int full_lists_ensure(fedd_ctx* c, const char* who) {
     FEDD_HIP(hipMemcpyAsync(c->d_hy_tab.p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     FEDD_HIP(hipStreamSynchronize(c->stream));  // `host` is a local
     c->hy_nq = tb.nq;
-    c->hy_mesh_id = c->mesh_id;
-    c->hy_pattern_gen = c->pattern_gen;
-    c->hy_lists = true;
+    c->gl_full.state = GatherLists::READY;
     return 0;
 }
 
@@ -1744,12 +1668,7 @@ static int advection_into_slot(fedd_ctx* c, const char* who, bool ale, int kind,
         ScopedTimer t(c, FEDD_T_SYMBOLIC);
         FEDD_TRY(build_adjacency(c));
     }
-    if (c->adv_state == 0) {
-        if (nen == 3) FEDD_TRY(adv_setup<3>(c));
-        else if (nen == 4) FEDD_TRY(adv_setup<4>(c));
-        else if (nen == 6) FEDD_TRY(adv_setup<6>(c));
-        else FEDD_TRY(adv_setup<10>(c));
-    }
+    if (c->gl_adv.state != GatherLists::READY) FEDD_TRY(adv_setup(c));
     const int64_t n_rows = c->n_own * dim, nnz = c->adv_node_nnz * dim * dim;
     const DevCsr* add = slot_add >= 0 ? &c->aux[slot_add] : nullptr;
     if (add) {
@@ -1776,17 +1695,10 @@ static int advection_into_slot(fedd_ctx* c, const char* who, bool ale, int kind,
     out.dofs = dim;
     out.block_mode = FEDD_BLOCK_FULL;
     out.mesh_id = c->mesh_id;
-    if (ale) {
-        if (dim == 2 && nen == 3) FEDD_TRY((advection_ale_kind<2, 3>(c, kind, scale, add, out)));
-        else if (dim == 2 && nen == 6) FEDD_TRY((advection_ale_kind<2, 6>(c, kind, scale, add, out)));
-        else if (dim == 3 && nen == 4) FEDD_TRY((advection_ale_kind<3, 4>(c, kind, scale, add, out)));
-        else FEDD_TRY((advection_ale_kind<3, 10>(c, kind, scale, add, out)));
-    } else {
-        if (dim == 2 && nen == 3) FEDD_TRY((advection_kind<2, 3>(c, kind, scale, add, out)));
-        else if (dim == 2 && nen == 6) FEDD_TRY((advection_kind<2, 6>(c, kind, scale, add, out)));
-        else if (dim == 3 && nen == 4) FEDD_TRY((advection_kind<3, 4>(c, kind, scale, add, out)));
-        else FEDD_TRY((advection_kind<3, 10>(c, kind, scale, add, out)));
-    }
+    FEDD_TRY(with_element(dim, nen, [&](auto d, auto n) {
+        constexpr int D = decltype(d)::value, N = decltype(n)::value;
+        return ale ? advection_ale_kind<D, N>(c, kind, scale, add, out) : advection_kind<D, N>(c, kind, scale, add, out);
+    }));
     out.valid = true;
     out.value_id = ++c->value_counter;
     return 0;
@@ -1885,10 +1797,9 @@ int assemble_matrix(fedd_ctx* c, int form, const double* params, const double* c
         a.p0 = form == FEDD_FORM_BDSTAB ? (dim == 2 ? 0.5 : 1.0 / 6.0) : 0.0;
         a.p1 = form == FEDD_FORM_BDSTAB ? (dim == 2 ? 1.0 / 9.0 : 1.0 / 16.0) : 0.0;
     }
-    if (dim == 2 && nen == 3) return launch_assemble<2, 3>(c, kform, a, ntab, xdim);
-    if (dim == 2 && nen == 6) return launch_assemble<2, 6>(c, kform, a, ntab, xdim);
-    if (dim == 3 && nen == 4) return launch_assemble<3, 4>(c, kform, a, ntab, xdim);
-    return launch_assemble<3, 10>(c, kform, a, ntab, xdim);
+    return with_element(dim, nen, [&](auto d, auto n) {
+        return launch_assemble<decltype(d)::value, decltype(n)::value>(c, kform, a, ntab, xdim);
+    });
 }
 
 int assemble_rhs(fedd_ctx* c, int dofs, const double* f_const, int extra_degree) {

@@ -1,6 +1,7 @@
 #pragma once
 // What the assembly translation units share: the forms, the kernel arguments and the affine geometry of a simplex.
 #include "fedd_internal.hpp"
+#include <type_traits>
 
 namespace fedd {
 
@@ -31,6 +32,24 @@ struct AsmArgs {
 };
 
 namespace {
+
+// f(std::integral_constant<int, DIM>(), std::integral_constant<int, NEN>()) for the element of the mesh: P1 / P2 simplices in
+// 2D and 3D (fedd_mesh_set admits no other); with_nen where the code depends on NEN alone
+template <class F>
+int with_element(int dim, int nen, F&& f) {
+    if (dim == 2 && nen == 3) return f(std::integral_constant<int, 2>(), std::integral_constant<int, 3>());
+    if (dim == 2 && nen == 6) return f(std::integral_constant<int, 2>(), std::integral_constant<int, 6>());
+    if (dim == 3 && nen == 4) return f(std::integral_constant<int, 3>(), std::integral_constant<int, 4>());
+    return f(std::integral_constant<int, 3>(), std::integral_constant<int, 10>());
+}
+
+template <class F>
+int with_nen(int nen, F&& f) {
+    if (nen == 3) return f(std::integral_constant<int, 3>());
+    if (nen == 4) return f(std::integral_constant<int, 4>());
+    if (nen == 6) return f(std::integral_constant<int, 6>());
+    return f(std::integral_constant<int, 10>());
+}
 
 __device__ __forceinline__ double zero_small(const AsmArgs& a, double v) { return (a.zero_eps > 0.0 && fabs(v) < a.zero_eps) ? 0.0 : v; }
 

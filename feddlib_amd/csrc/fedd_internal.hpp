@@ -70,6 +70,21 @@ struct DevBuf {
     }
 };
 
+// Gather lists of an element-major assembly path (gather_lists_ensure below, gather_lists.hpp; DESIGN.md section 4 "Gather lists
+// and the row walk" has the format): soff [node-level nnz + 2], src [adjacency entries * nen + 2], and the mesh and pattern they
+// were built for (pattern_gen, or GATHER_NODE_PATTERN for a node-level pattern, which follows from the mesh alone)
+constexpr int GATHER_MAX_DEG = 4095;        // incident elements of a node: the adjacency entry has 12 bits
+constexpr int GATHER_MAX_SRC = 65535;       // sources of a node, deg * nen: the starts have 16 bits
+constexpr uint64_t GATHER_NODE_PATTERN = ~(uint64_t)0;
+struct GatherLists {
+    enum { NOT_BUILT = 0, READY = 1, NO_FIT = -1 };   // NO_FIT: a node beyond the limits above, or nothing to build the lists on
+    DevBuf<uint16_t> soff, src;
+    uint64_t mesh_id = 0, pattern = 0;
+    int state = NOT_BUILT;
+    bool ready_for(uint64_t m, uint64_t p) const { return state == READY && mesh_id == m && pattern == p; }
+    void reset() { state = NOT_BUILT; }     // (the buffers stay: the next mesh is usually of the same size)
+};
+
 constexpr int MAX_BC = 16;
 constexpr int MAX_DOFS = 3;
 constexpr int SPMV_PAT_LMAX = 48;       // longest offset list of the SpMV pattern table (spmv.hip SPAT_L)
@@ -308,8 +323,7 @@ struct fedd_ctx {
     int asm_kind = 0;                           // option "asm_kind": 0 = the default dispatch (assemble.hip launch_assemble), 2 = the pair sweep always, 3 = slot-addressed where it fits
     // element-major tile structures of the current mesh (assemble_tiles.hip build_tiles): 0 = not built, 1 = ready, -1 = mesh does not fit
     int asm_p2_elem = 1;                        // option "asm_p2_elem": P2 scalar forms take their element matrices from k_elem_matrix (one element per wavefront); 0 = pair kernels alone
-    int p2_state = 0;                           // gather lists of the P2 row sums (assemble.hip k_p2_lists): 0 = not built, 1 = ready, -1 = not applicable
-    fedd::DevBuf<uint16_t> d_p2_soff, d_p2_src; // per node-level nonzero the start of its sources; the sources (adjacency entry << 4 | local column)
+    fedd::GatherLists gl_p2;                    // of the node-level system pattern: row sums of the P2 scalar forms, FEDD_FORM_LAPLACE_XDIM (NO_FIT: the pair kernels)
     fedd::DevBuf<double> d_ke;                  // [n_elem * nen * nen] element matrices of the assembly in progress (P2)
     double asm_zero_eps = 0.0;                  // option "asm_zero_eps": FE::doSetZeros(eps) -- element contributions below eps are dropped (vector Laplacian, B, B^T); 0 = off
     int asm_tiles_host = 0;                     // option "asm_tiles_host": 1 = the tile structures are built on the host (the round-3 builder; A/B and tests), 0 = on the device
@@ -349,11 +363,10 @@ struct fedd_ctx {
     bool have_vel = false;
     fedd::DevBuf<double> d_mvel;                // [n_node * dim] mesh velocity w at the nodes, same numbering (fedd_mesh_velocity_set / _diff)
     bool have_mvel = false;
-    int adv_state = 0;                          // per-mesh structures below: 0 = not built, 1 = ready
+    fedd::GatherLists gl_adv;                   // of the node-level pattern below; READY: every per-mesh structure below is built
     int64_t adv_node_nnz = 0;                   // nonzeros of the node-level pattern
     int adv_max_nn = 0;                         // its longest row
     fedd::DevBuf<int32_t> d_adv_nptr, d_adv_ncol;   // node-level pattern [n_own + 1], [adv_node_nnz]: the FULL dof pattern follows in closed form
-    fedd::DevBuf<uint16_t> d_adv_soff, d_adv_src;   // gather lists of the node-level nonzeros (k_p2_lists)
     fedd::DevBuf<double> d_adv_tab;             // quadrature tables of N, then of W where its rule differs (w | phi | dphi each)
     int adv_nq[2] = {0, 0}, adv_tab_off_w = 0;
     fedd::DevBuf<double> d_adv_ke;              // [n_elem][nen][nen][1 | dim * dim] element blocks of the assembly in progress
@@ -361,9 +374,7 @@ struct fedd_ctx {
     // ---- hyperelastic tangent and forces (hyperelastic.hip assemble_hyperelastic; one rank): u is d_vel, the element blocks
     //      pass through d_adv_ke, the tangent goes into the system matrix.  The lists and tables (full_lists_ensure) also serve
     //      the stress form (assemble.hip k_stress_elem, k_stress_gather), whose packed pair blocks pass through d_adv_ke too ----
-    bool hy_lists = false;                      // the gather lists and tables below belong to hy_mesh_id / hy_pattern_gen
-    uint64_t hy_mesh_id = 0, hy_pattern_gen = 0;
-    fedd::DevBuf<uint16_t> d_hy_soff, d_hy_src; // gather lists of the node-level nonzeros of the system's FULL pattern (k_p2_lists)
+    fedd::GatherLists gl_full;                  // of the system's FULL pattern; the tables below are uploaded with them
     fedd::DevBuf<double> d_hy_tab;              // w | dphi of the rule determineDegree(Grad, Grad)
     int hy_nq = 0;
     fedd::DevBuf<double> d_hy_fe;               // [n_elem][nen][dim] element forces of the assembly in progress
@@ -658,6 +669,9 @@ inline void system_written(fedd_ctx* c, unsigned what) {
     if (what & SYS_GONE) c->have_pattern = false;
 }
 
+// ... what a new mesh does to the gather lists (a fedd_mesh_move keeps them: they follow connectivity and patterns, not coordinates)
+inline void gather_lists_reset(fedd_ctx* c) { c->gl_p2.reset(), c->gl_adv.reset(), c->gl_full.reset(); }
+
 // ... and what an option drops when it is set (fedd_set_option's table names one of these per key)
 enum : unsigned {
     OPT_DROPS_STREAM = 1,    // the solver's SpMV stream and the key it is kept by
@@ -754,7 +768,7 @@ int expand_node_pattern(fedd_ctx* c, const int32_t* nptr, const int32_t* ncol, i
 // (coeff_q / n_coeff: the coefficient array of FEDD_FORM_STRESS, nullptr = 1; the other forms ignore them)
 int assemble_matrix(fedd_ctx* c, int form, const double* params, const double* coeff_q = nullptr, int64_t n_coeff = 0);
 // gather lists of the system's FULL pattern + the tables w | dphi of the (Grad, Grad) rule, kept per (mesh, pattern) in
-// d_hy_soff / d_hy_src / d_hy_tab / hy_nq: shared by the hyperelastic tangent and the stress form
+// gl_full / d_hy_tab / hy_nq: shared by the hyperelastic tangent and the stress form
 int full_lists_ensure(fedd_ctx* c, const char* who);
 int assemble_rhs(fedd_ctx* c, int dofs, const double* f_const, int extra_degree);
 int surface_set(fedd_ctx* c, int nsn, int64_t n_surf, const int32_t* surf, const int32_t* sflag);
@@ -773,10 +787,11 @@ int mesh_velocity_diff(fedd_ctx* c, const double* d_new_rep, const double* d_old
 int mesh_velocity_get(fedd_ctx* c, double* w_rep);
 int assemble_advection_ale(fedd_ctx* c, int kind, double scale, int slot_add, int slot_out);
 int assemble_advection(fedd_ctx* c, int kind, double scale, int slot_add, int slot_out);
-// k_p2_lists on a pattern of the caller's (rows of the first dof of every owned node; full: FULL blocks, else scalar / DIAG):
-// soff [node-level nnz + 2], src [adjacency entries * nen + 2]; `who` names the caller in the error text
-int build_gather_lists(fedd_ctx* c, const int32_t* rowptr, const int32_t* colind, int dofs, int full, uint16_t* soff, uint16_t* src,
-                       const char* who);
+// The one builder of gather lists (k_p2_lists): gl for the first nn nodes of a pattern of the caller's with node_nnz node-level
+// nonzeros (full: FULL blocks, else scalar / DIAG); nothing to do where gl is ready for this mesh and `pattern`.  Lists that do not
+// fit are an error naming `who`; who == nullptr (the caller has another path): no error, NO_FIT also without pattern, adjacency or nodes
+int gather_lists_ensure(fedd_ctx* c, GatherLists& gl, uint64_t pattern, const int32_t* rowptr, const int32_t* colind, int dofs,
+                        int full, int64_t nn, int64_t node_nnz, const char* who);
 
 // interface_distance.hip
 int interface_distance_tile();

@@ -25,11 +25,12 @@
 //   3  lanes over (p, j, d1, k):     H_j[d1][k][d2] = sum_l w_p A[d1][k][d2][l] g_j,l
 //   4  lanes over (i, j):            the dim x dim block sum_p sum_k g_i,k H_j[d1][k][d2], times |det B| -> ke[T][i][j][d1][d2];
 //      lanes over (i, d):            sum_p sum_k w_p P_dk g_i,k, times |det B|                           -> fe[T][i][d]
-// The rows are then summed by gather lists (k_p2_lists on the system's FULL pattern, built once per pattern): the tangent as in
+// The rows are then summed by gather lists (gather_lists.hpp; on the system's FULL pattern, built once per pattern): the tangent as in
 // k_adv_gather, the force by a thread per node over its adjacency.  Every sum runs in a fixed order and there is no
 // floating-point atomic: two calls agree bit for bit, and so do tangent-only and force-only calls with the combined one (the
 // same instructions produce each).  The one atomic is the integer minimum that records an inverted element.
 #include "assemble_common.hpp"
+#include "gather_lists.hpp"
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -310,66 +311,53 @@ struct HyMass {
     int64_t nnz = 0;
 };
 
+// one DIM x DIM block per source (gather_lists.hpp).  This struct stays below the pragma above: store() forms cm * M and + K as
+// two roundings.  The mass entries of the slot are loaded before its sources are walked.
+template <int DIM, int NEN, int MASS>
+struct HyperSum : GatherBlockSum<NEN, DIM * DIM> {
+    const int32_t* m_rowptr;
+    const double* m_val;
+    double cm;
+    double* val;
+    double mv[MASS == 1 ? DIM * DIM : DIM];
+    __device__ void init(const GatherRow& g, int sl) {
+#pragma unroll
+        for (int r = 0; r < DIM; ++r) {
+            if (MASS == 1) {
+#pragma unroll
+                for (int cc = 0; cc < DIM; ++cc) mv[r * DIM + cc] = m_val[(int64_t)g.rs + (int64_t)r * g.nslot * DIM + (int64_t)sl * DIM + cc];
+            }
+            if (MASS == 2) {
+                const int32_t ms = m_rowptr[g.row + r];
+                mv[r] = sl < m_rowptr[g.row + r + 1] - ms ? m_val[ms + sl] : 0.0;
+            }
+        }
+        this->zero();
+    }
+    __device__ void store(const GatherRow& g, int sl) {
+#pragma unroll
+        for (int r = 0; r < DIM; ++r) {
+            const int64_t at = (int64_t)g.rs + (int64_t)r * g.nslot * DIM + (int64_t)sl * DIM;
+#pragma unroll
+            for (int cc = 0; cc < DIM; ++cc) {
+                double v = this->acc[r * DIM + cc];
+                if (MASS != 0) {
+                    const double pm = cm * (MASS == 1 ? mv[r * DIM + cc] : cc == r ? mv[r] : 0.0);
+                    v = pm + v;
+                }
+                val[at + cc] = v;
+            }
+        }
+    }
+};
+
 template <int DIM, int NEN, int MASS>
 __global__ __launch_bounds__(256) void k_hyper_gather(const int32_t* __restrict__ n2e_ptr, const int32_t* __restrict__ n2e,
                                                       const int32_t* __restrict__ rowptr, int32_t nn,
                                                       const uint16_t* __restrict__ soff, const uint16_t* __restrict__ src,
                                                       const double* __restrict__ ke, const int32_t* __restrict__ m_rowptr,
                                                       const double* __restrict__ m_val, double cm, double* __restrict__ val) {
-    constexpr int DD = DIM * DIM;
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int64_t p = (int64_t)blockIdx.x * 4 + w; p < nn; p += (int64_t)gridDim.x * 4) {
-        const int32_t ab = n2e_ptr[p], deg = n2e_ptr[p + 1] - ab;
-        const int32_t row = (int32_t)p * DIM, rs = rowptr[row];
-        const int32_t nslot = (rowptr[row + 1] - rs) / DIM, nb = rs / DD;
-        const uint16_t* __restrict__ sp = src + (int64_t)ab * NEN;
-        const int total = deg * NEN;
-        int32_t ms[DIM], mlen[DIM];
-        if (MASS == 2) {
-#pragma unroll
-            for (int r = 0; r < DIM; ++r) {
-                ms[r] = m_rowptr[row + r];
-                mlen[r] = m_rowptr[row + r + 1] - ms[r];
-            }
-        }
-        for (int sl = lane; sl < nslot; sl += 64) {
-            const int b = soff[nb + sl], e2 = sl + 1 < nslot ? (int)soff[nb + sl + 1] : total;
-            double mv[MASS == 1 ? DD : DIM];
-            if (MASS == 1) {
-#pragma unroll
-                for (int r = 0; r < DIM; ++r)
-#pragma unroll
-                    for (int cc = 0; cc < DIM; ++cc)
-                        mv[r * DIM + cc] = m_val[(int64_t)rs + (int64_t)r * nslot * DIM + (int64_t)sl * DIM + cc];
-            }
-            if (MASS == 2) {
-#pragma unroll
-                for (int r = 0; r < DIM; ++r) mv[r] = sl < mlen[r] ? m_val[ms[r] + sl] : 0.0;
-            }
-            double acc[DD];
-#pragma unroll
-            for (int m = 0; m < DD; ++m) acc[m] = 0.0;
-            for (int k = b; k < e2; ++k) {
-                const uint32_t sr = sp[k];
-                const double* __restrict__ kb = ke + ((int64_t)n2e[ab + (sr >> 4)] * NEN + (sr & 15u)) * DD;
-#pragma unroll
-                for (int m = 0; m < DD; ++m) acc[m] += kb[m];
-            }
-#pragma unroll
-            for (int r = 0; r < DIM; ++r) {
-                const int64_t at = (int64_t)rs + (int64_t)r * nslot * DIM + (int64_t)sl * DIM;
-#pragma unroll
-                for (int cc = 0; cc < DIM; ++cc) {
-                    double v = acc[r * DIM + cc];
-                    if (MASS != 0) {
-                        const double pm = cm * (MASS == 1 ? mv[r * DIM + cc] : cc == r ? mv[r] : 0.0);
-                        v = pm + v;
-                    }
-                    val[at + cc] = v;
-                }
-            }
-        }
-    }
+    gather_walk<NEN>(n2e_ptr, n2e, soff, src, nn, GatherRows{rowptr, DIM, 1}, HyperSum<DIM, NEN, MASS>{{ke}, m_rowptr, m_val, cm, val});
 }
 
 // f_(p,d) = sum over the adjacency of node p, in its order, of the element forces
@@ -425,20 +413,13 @@ int launch_hyper(fedd_ctx* c, HyArgs a, const HyMass& mass, const char* who) {
     t.resume();
     if (a.what & FEDD_HYPER_TANGENT) {
         system_written(c, SYS_VALUES);
-        const int nwg2 = (int)std::max<int64_t>(1, std::min<int64_t>((nn + 3) / 4, 256 * 32));
-        const dim3 grid2((unsigned)nwg2), blk(256);
+        const dim3 grid2((unsigned)gather_grid(nn)), blk(256);
         const int32_t *n2e_ptr = c->d_n2e_ptr.p, *n2e = c->d_n2e.p, *rowptr = c->d_rowptr.p;
-        const uint16_t *soff = c->d_hy_soff.p, *src = c->d_hy_src.p;
+        const uint16_t *soff = c->gl_full.soff.p, *src = c->gl_full.src.p;
         const double* ke = c->d_adv_ke.p;
-        if (mass.kind == 0)
-            hipLaunchKernelGGL((k_hyper_gather<DIM, NEN, 0>), grid2, blk, 0, c->stream, n2e_ptr, n2e, rowptr, (int32_t)nn, soff, src, ke,
-                               (const int32_t*)nullptr, (const double*)nullptr, 0.0, c->d_val.p);
-        else if (mass.kind == 1)
-            hipLaunchKernelGGL((k_hyper_gather<DIM, NEN, 1>), grid2, blk, 0, c->stream, n2e_ptr, n2e, rowptr, (int32_t)nn, soff, src, ke,
-                               mass.rowptr, mass.val, mass.cm, c->d_val.p);
-        else
-            hipLaunchKernelGGL((k_hyper_gather<DIM, NEN, 2>), grid2, blk, 0, c->stream, n2e_ptr, n2e, rowptr, (int32_t)nn, soff, src, ke,
-                               mass.rowptr, mass.val, mass.cm, c->d_val.p);
+        auto kern = mass.kind == 0 ? k_hyper_gather<DIM, NEN, 0> : mass.kind == 1 ? k_hyper_gather<DIM, NEN, 1> : k_hyper_gather<DIM, NEN, 2>;
+        hipLaunchKernelGGL(kern, grid2, blk, 0, c->stream, n2e_ptr, n2e, rowptr, (int32_t)nn, soff, src, ke, mass.rowptr, mass.val,
+                           mass.cm, c->d_val.p);       // (without a mass: null pointers and cm = 0, which that kernel does not read)
     }
     if (a.what & FEDD_HYPER_FORCE) {
         hipLaunchKernelGGL(k_hyper_force<DIM>, dim3((unsigned)std::max<int64_t>(1, (nn + 255) / 256)), dim3(256), 0, c->stream,
@@ -494,10 +475,7 @@ int assemble_hyper(fedd_ctx* c, int model, const double* params, int n_params, i
     a.conn = c->d_conn.p; a.xyz = c->d_xyz.p; a.u = c->d_vel.p; a.tab = c->d_hy_tab.p;
     a.nq = c->hy_nq;
     a.flag = c->d_hy_flag.p;
-    if (dim == 2 && nen == 3) return launch_hyper<2, 3>(c, a, mass, who);
-    if (dim == 2 && nen == 6) return launch_hyper<2, 6>(c, a, mass, who);
-    if (dim == 3 && nen == 4) return launch_hyper<3, 4>(c, a, mass, who);
-    return launch_hyper<3, 10>(c, a, mass, who);
+    return with_element(dim, nen, [&](auto d, auto n) { return launch_hyper<decltype(d)::value, decltype(n)::value>(c, a, mass, who); });
 }
 
 }  // namespace
