@@ -31,7 +31,7 @@ def _stale(obj: str, src: str) -> bool:
         return True
     t = os.path.getmtime(obj)
     deps = [src, os.path.join(CSRC, "fedd_internal.hpp"), os.path.join(CSRC, "assemble_common.hpp"),
-            os.path.join(CSRC, "gather_lists.hpp"), os.path.join(CSRC, "gmres_frame.hpp"), os.path.join(CSRC, "gmres_stop_rule.hpp"),
+            os.path.join(CSRC, "gather_lists.hpp"), os.path.join(CSRC, "stored_rows.hpp"), os.path.join(CSRC, "gmres_frame.hpp"), os.path.join(CSRC, "gmres_stop_rule.hpp"),
             os.path.join(HERE, "..", "include", "fedd_hip.h"), os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 

@@ -41,10 +41,6 @@ int timing_flush(fedd_ctx* c) {
 
 using namespace fedd;
 
-#define NEED_DEVICE(c)                                                                           \
-    FEDD_CHECK((c) && (c)->device >= 0,                                                          \
-               "this call needs a GPU context (fedd_ctx_create with device >= 0); there is no CPU fallback")
-
 extern "C" const char* fedd_last_error(void) { return g_err.c_str(); }
 
 extern "C" int fedd_nccl_unique_id(void* id128) {
@@ -134,10 +130,8 @@ extern "C" int fedd_ctx_create(fedd_ctx** out, int device, const void* nccl_uniq
 
 extern "C" void fedd_ctx_destroy(fedd_ctx* c) {
     if (!c) return;
-    block_prec_child_gone(c);   // parents that apply this context as a block are detached (their streams finished first)
-    block_prec_unlink(c);       // ... and this context's own children forget it
-    fsi_prec_child_gone(c);     // the same for the coupled contexts that apply this one inside their FaCSI preconditioner
-    fsi_prec_unlink(c);
+    prec_child_gone(c);         // parents that apply this context as a block (block preconditioner, FaCSI) are detached, their
+    prec_unlink(c);             // streams finished first ... and this context's own children forget it
     iface_release(c);           // the other side of a match finds it released
     if (c->device >= 0) {
         (void)hipSetDevice(c->device);
@@ -150,8 +144,7 @@ extern "C" void fedd_ctx_destroy(fedd_ctx* c) {
         if (c->h_pinned) (void)hipHostFree(c->h_pinned);
         if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
         if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-        if (c->bp_ev) (void)hipEventDestroy(c->bp_ev);
-        if (c->fp_ev) (void)hipEventDestroy(c->fp_ev);
+        if (c->prec.ev) (void)hipEventDestroy(c->prec.ev);
         if (c->stream2) (void)hipStreamDestroy(c->stream2);
         (void)hipStreamDestroy(c->stream);
     }
@@ -161,11 +154,9 @@ extern "C" void fedd_ctx_destroy(fedd_ctx* c) {
 extern "C" int fedd_sync(fedd_ctx* c) {
     NEED_DEVICE(c);
     FEDD_HIP(hipStreamSynchronize(c->stream));
-    // an attached block preconditioner runs its children's applies in this stream; their own streams hold their setups
-    if (c->bp_kind && c->bp_vel && c->bp_vel->device >= 0) FEDD_HIP(hipStreamSynchronize(c->bp_vel->stream));
-    if (c->bp_kind && c->bp_schur && c->bp_schur->device >= 0) FEDD_HIP(hipStreamSynchronize(c->bp_schur->stream));
-    if (c->fp_on && c->fp_fluid && c->fp_fluid->device >= 0) FEDD_HIP(hipStreamSynchronize(c->fp_fluid->stream));
-    if (c->fp_on && c->fp_struct && c->fp_struct->device >= 0) FEDD_HIP(hipStreamSynchronize(c->fp_struct->stream));
+    // an attached preconditioner runs its children's applies in this stream; their own streams hold their setups
+    for (const PrecChild& ch : c->prec.child)
+        if (ch.ctx && ch.ctx->device >= 0) FEDD_HIP(hipStreamSynchronize(ch.ctx->stream));
     return 0;
 }
 
@@ -522,8 +513,6 @@ extern "C" int fedd_dirichlet_rows(fedd_ctx* c, int64_t n, const int32_t* rows, 
     FEDD_HIP(hipSetDevice(c->device));
     return apply_dirichlet_rows(c, n, rows, values);
 }
-
-#define CHECK_SLOT(s) FEDD_CHECK((s) >= 0 && (s) < fedd::MAX_AUX, "matrix slot %d out of range", (s))
 
 extern "C" int fedd_matrix_store(fedd_ctx* c, int slot) {
     NEED_DEVICE(c);

@@ -536,24 +536,14 @@ __global__ __launch_bounds__(256) void k_rhs(RhsArgs a, const double* __restrict
         for (int d = 0; d < a.dofs; ++d) a.rhs[(int64_t)node * a.dofs + d] = sum * a.f[d];
 }
 
-struct BcArgs {
-    int n, dofs;
-    int32_t flag[MAX_BC];
-    int32_t mask[MAX_BC * MAX_DOFS];
-    double value[MAX_BC * MAX_DOFS];
-};
-
-__global__ void k_dirichlet(BcArgs b, const int32_t* __restrict__ nflag, const int32_t* __restrict__ rowptr,
+__global__ void k_dirichlet(BcTable b, const int32_t* __restrict__ nflag, const int32_t* __restrict__ rowptr,
                             const int32_t* __restrict__ colind, double* val, double* rhs, int32_t* isdir,
                             int32_t n_rows) {
     const int32_t row = blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= n_rows) return;
     const int32_t node = row / b.dofs;
     const int comp = row - node * b.dofs;
-    const int32_t f = nflag[node];
-    int hit = -1;
-    for (int k = 0; k < b.n; ++k)
-        if (hit < 0 && b.flag[k] == f && b.mask[k * b.dofs + comp]) hit = k;
+    const int hit = bc_hit(b, nflag[node], comp);
     if (hit < 0) return;
     for (int32_t p = rowptr[row]; p < rowptr[row + 1]; ++p) val[p] = colind[p] == row ? 1.0 : 0.0;
     rhs[row] = b.value[hit * b.dofs + comp];
@@ -1900,16 +1890,7 @@ int apply_dirichlet_rows(fedd_ctx* c, int64_t n, const int32_t* rows, const doub
 
 int apply_dirichlet(fedd_ctx* c, int n_bc, const int32_t* flags, const int32_t* comp_mask, const double* values) {
     system_written(c, SYS_DIRICHLET);
-    BcArgs b;
-    b.n = n_bc;
-    b.dofs = c->dofs;
-    for (int k = 0; k < n_bc; ++k) {
-        b.flag[k] = flags[k];
-        for (int d = 0; d < c->dofs; ++d) {
-            b.mask[k * c->dofs + d] = comp_mask ? comp_mask[k * c->dofs + d] : 1;
-            b.value[k * c->dofs + d] = values[k * c->dofs + d];
-        }
-    }
+    const BcTable b = bc_table_fill(c->dofs, n_bc, flags, comp_mask, values);
     // row-ghost rows get the same treatment as owned ones (their flags follow the owned flags in d_flag)
     const dim3 grid((unsigned)((c->n_rows_ext + 255) / 256)), block(256);
     ScopedTimer t(c, FEDD_T_DIRICHLET);

@@ -8,10 +8,14 @@
 // pointers it does not own.
 //
 // One kernel of its own: k_bt_sub, t = r_u - B^T (scale * s) over the rectangular CSR of the stored B^T with the Dirichlet mask
-// of the merged system and the scale of z_p fused in.  Its row sums are those of k_block_apply (timestep.hip): the same lane
-// groups, ascending columns per lane, four trips in flight, the same shuffle tree, every product rounded before it is added.
+// of the merged system and the scale of z_p fused in.  Its row sums are the lane-group row walk of stored_rows.hpp, as
+// k_block_apply (timestep.hip) makes them, with x_j = scale * s[j] rounded before it is used.
 // The normative operation order is in include/fedd_hip.h.
-#include "fedd_internal.hpp"
+//
+// The child link ("a child context applied as a block") that this preconditioner and FaCSI (fsi.hip) share is also here:
+// attach, unlink, the destroy of a child, the ordering of a child's own stream, its apply in the parent's stream, and the
+// checks both kinds make of a child.
+#include "stored_rows.hpp"
 #include <algorithm>
 #include <cassert>
 
@@ -22,7 +26,7 @@ namespace {
 
 // G lanes per row of B^T (rows < n_rows, columns < n_p by the shape check of block_prec_check).  s = S(r_p), unscaled.
 //   x_j   = scale * s[j]                                 (rounded: the entry z_p[j] this kernel also stores)
-//   acc   = sum_k val[k] * x_col[k]                      (k_block_apply's order)
+//   acc   = sum_k val[k] * x_col[k]                      (the row walk; a Dirichlet row walks with len = 0)
 //   t[i]  = isdir[i] ? r_u[i] : r_u[i] - acc
 // The first n_p threads of the grid (grid-stride) write z_p = scale * s: s and z_p are different buffers, so no lane reads what
 // another one writes.
@@ -39,24 +43,7 @@ __global__ __launch_bounds__(256) void k_bt_sub(const int32_t* __restrict__ rowp
     const bool dir = live ? isdir[row] != 0 : false;
     const int32_t st = live ? rowptr[row] : 0;
     const int32_t len = (live && !dir) ? rowptr[row + 1] - st : 0;
-    double acc = 0.0;
-    for (int32_t k0 = g; k0 < len; k0 += 4 * G) {
-        int32_t cc[4];
-        double vv[4], xx[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int32_t k = k0 + u * G;
-            const bool in = k < len;
-            cc[u] = in ? colind[st + k] : -1;
-            vv[u] = in ? val[st + k] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) xx[u] = cc[u] >= 0 ? scale * s[cc[u]] : 0.0;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc += vv[u] * xx[u];
-    }
-#pragma unroll
-    for (int o = G / 2; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, G);
+    const double acc = row_sum<G>(colind, val, st, len, g, [=](int32_t col) { return scale * s[col]; });
     if (live && g == 0) {
         const double ru = r_u[row];
         t[row] = dir ? ru : ru - acc;
@@ -68,45 +55,58 @@ __global__ __launch_bounds__(256) void k_scale_vec(double* __restrict__ v, int64
     if (i < n) v[i] = a * v[i];
 }
 
-const char* child_name(const fedd_ctx* c, const fedd_ctx* ch) { return ch == c->bp_vel ? "velocity" : "Schur complement"; }
+const char* const BP = "block preconditioner";
 
-int child_check(fedd_ctx* c, fedd_ctx* ch, int64_t n_expected, const char* who) {
-    const char* nm = child_name(c, ch);
-    FEDD_CHECK(ch->device >= 0, "%s: block preconditioner: the %s child is a host-only context", who, nm);
-    FEDD_CHECK(ch->nranks == 1, "%s: block preconditioner: one rank only (the %s child has %d ranks)", who, nm, ch->nranks);
-    FEDD_CHECK(ch->device == c->device, "%s: block preconditioner: the %s child is on device %d, the parent on device %d", who, nm,
-               ch->device, c->device);
+int child_check(fedd_ctx* c, int which, int64_t n_expected, const char* who) {
+    const fedd_ctx* ch = c->prec.child[which].ctx;
+    const char* nm = which == 0 ? "velocity" : "Schur complement";
+    FEDD_TRY(child_check_context(c, ch, who, BP, nm, "parent"));
     FEDD_CHECK(ch->have_pattern && !ch->merged, "%s: block preconditioner: the %s child holds no single-block system", who, nm);
     FEDD_CHECK(ch->n_rows == n_expected && ch->n_cols == n_expected,
                "%s: block preconditioner: wrong sizes: the %s child's system has %lld rows, the parent's block row %lld", who, nm,
                (long long)ch->n_rows, (long long)n_expected);
-    FEDD_CHECK(ch->have_schwarz,
-               "%s: block preconditioner: the %s child has no current fedd_schwarz_setup (never set up, or its matrix changed since)",
-               who, nm);
-    FEDD_CHECK(ch->sw_levels != FEDD_LEVELS_MULTIPLICATIVE,
-               "%s: block preconditioner: the %s child asks for FEDD_LEVELS_MULTIPLICATIVE, whose operator (I - Pc A) M1^-1 is singular "
-               "and is not built as a block of a block preconditioner; use FEDD_LEVELS_ADDITIVE",
-               who, nm);
+    return child_check_schwarz(ch, who, BP, nm, " (I - Pc A) M1^-1");
+}
+
+}  // namespace
+
+// ---- the child link -------------------------------------------------------------------------------------------------------
+int child_check_context(const fedd_ctx* c, const fedd_ctx* ch, const char* who, const char* label, const char* nm, const char* parent) {
+    FEDD_CHECK(ch->device >= 0, "%s: %s: the %s child is a host-only context", who, label, nm);
+    FEDD_CHECK(ch->nranks == 1, "%s: %s: one rank only (the %s child has %d ranks)", who, label, nm, ch->nranks);
+    FEDD_CHECK(ch->device == c->device, "%s: %s: the %s child is on device %d, the %s on device %d", who, label, nm, ch->device, parent,
+               c->device);
     return 0;
 }
 
-// The child's kernels go into the parent's stream: the three applies and k_bt_sub are then ordered by the stream itself, with no
-// event and no host synchronisation inside the Krylov loop, and fedd_sync(parent) covers them.  What the child put into its
-// OWN stream before (fedd_matrix_import, fedd_dirichlet, fedd_schwarz_setup) is ordered in front by an event: after every setup of the child, and whenever its stream is not idle.
-int child_order(fedd_ctx* c, fedd_ctx* ch, uint64_t* seen) {
+int child_check_schwarz(const fedd_ctx* ch, const char* who, const char* label, const char* nm, const char* mult_operator) {
+    FEDD_CHECK(ch->have_schwarz, "%s: %s: the %s child has no current fedd_schwarz_setup (never set up, or its matrix changed since)", who,
+               label, nm);
+    FEDD_CHECK(ch->sw_levels != FEDD_LEVELS_MULTIPLICATIVE,
+               "%s: %s: the %s child asks for FEDD_LEVELS_MULTIPLICATIVE, whose operator%s is singular and is not built as a block of a "
+               "block preconditioner; use FEDD_LEVELS_ADDITIVE",
+               who, label, nm, mult_operator);
+    return 0;
+}
+
+// The child's kernels go into the parent's stream (child_apply): the applies and the parent's own kernels between them are then
+// ordered by the stream itself, with no event and no host synchronisation inside the Krylov loop, and fedd_sync(parent) covers
+// them.  What the child put into its OWN stream before (fedd_matrix_import, a merge, fedd_dirichlet, fedd_schwarz_setup) is
+// ordered in front by an event: after every setup of the child, and whenever its stream is not idle.
+int child_order(fedd_ctx* c, PrecChild& ch) {
     // (the query costs no device work; it covers whatever else may have gone into the child's stream since its setup)
-    // Both children share the one event bp_ev: a hipStreamWaitEvent captures the record made before it, so the next record does
-    // not disturb a wait already enqueued.
-    if (*seen == ch->sw_setup_gen) {
-        const hipError_t q = hipStreamQuery(ch->stream);
+    // Both children share the one event: a hipStreamWaitEvent captures the record made before it, so the next record does not
+    // disturb a wait already enqueued.
+    if (ch.seen == ch.ctx->sw_setup_gen) {
+        const hipError_t q = hipStreamQuery(ch.ctx->stream);
         if (q == hipSuccess) return 0;
         if (q != hipErrorNotReady) FEDD_HIP(q);     // a real error is reported, not cleared
         (void)hipGetLastError();                    // hipErrorNotReady is an answer, not a failure
     }
-    if (!c->bp_ev) FEDD_HIP(hipEventCreateWithFlags(&c->bp_ev, hipEventDisableTiming));
-    FEDD_HIP(hipEventRecord(c->bp_ev, ch->stream));
-    FEDD_HIP(hipStreamWaitEvent(c->stream, c->bp_ev, 0));
-    *seen = ch->sw_setup_gen;
+    if (!c->prec.ev) FEDD_HIP(hipEventCreateWithFlags(&c->prec.ev, hipEventDisableTiming));
+    FEDD_HIP(hipEventRecord(c->prec.ev, ch.ctx->stream));
+    FEDD_HIP(hipStreamWaitEvent(c->stream, c->prec.ev, 0));
+    ch.seen = ch.ctx->sw_setup_gen;
     return 0;
 }
 
@@ -118,17 +118,51 @@ int child_apply(fedd_ctx* c, fedd_ctx* ch, const double* r, double* z) {
     return rc;
 }
 
-}  // namespace
+void prec_attach(fedd_ctx* c, int kind, fedd_ctx* first, fedd_ctx* second) {
+    c->prec.kind = kind;
+    c->prec.applies = 0;
+    for (int i = 0; i < 2; ++i) {
+        fedd_ctx* ch = i == 0 ? first : second;
+        ch->prec_parents.push_back(c);
+        c->prec.child[i] = {ch, ~(uint64_t)0};      // the first apply orders the children's streams in front
+    }
+}
 
+void prec_unlink(fedd_ctx* c) {
+    for (PrecChild& ch : c->prec.child) {
+        if (ch.ctx) {       // c is a parent of ch once: one entry goes, those of ch's other parents stay
+            auto it = std::find(ch.ctx->prec_parents.begin(), ch.ctx->prec_parents.end(), c);
+            if (it != ch.ctx->prec_parents.end()) ch.ctx->prec_parents.erase(it);
+        }
+        ch = PrecChild();
+    }
+    c->prec.kind = AttachedPrec::NONE;
+    c->bp_kind = 0;
+    c->bp_slot_bt = -1;
+    c->bp_scale = 1.0;
+}
+
+// The child's buffers may still be read by kernels in a parent's stream: each parent finishes them, then lets go of both children.
+void prec_child_gone(fedd_ctx* child) {
+    while (!child->prec_parents.empty()) {
+        fedd_ctx* p = child->prec_parents.back();
+        if (p->device >= 0 && hipSetDevice(p->device) == hipSuccess) (void)hipStreamSynchronize(p->stream);
+        prec_unlink(p);     // erases p from child->prec_parents: p held the child as one of its two
+        assert(child->prec_parents.empty() || child->prec_parents.back() != p);
+    }
+}
+
+// ---- the block preconditioner ----------------------------------------------------------------------------------------------
 int block_prec_check(fedd_ctx* c, const char* who) {
-    FEDD_CHECK(c->bp_kind == FEDD_BLOCKPREC_DIAGONAL || c->bp_kind == FEDD_BLOCKPREC_TRIANGULAR, "%s: no block preconditioner attached", who);
+    FEDD_CHECK(c->prec.kind == AttachedPrec::BLOCK && (c->bp_kind == FEDD_BLOCKPREC_DIAGONAL || c->bp_kind == FEDD_BLOCKPREC_TRIANGULAR),
+               "%s: no block preconditioner attached", who);
     FEDD_CHECK(c->nranks == 1, "%s: block preconditioner: one rank only (a context with %d ranks was given)", who, c->nranks);
-    FEDD_CHECK(c->bp_vel && c->bp_schur, "%s: block preconditioner: null child", who);
+    FEDD_CHECK(c->prec.child[0].ctx && c->prec.child[1].ctx, "%s: block preconditioner: null child", who);
     FEDD_CHECK(c->have_pattern && c->merged,
                "%s: block preconditioner: unmerged parent: the context does not hold a merged 2 x 2 system (fedd_block_merge first)", who);
     const int64_t nA = c->merged_nA, nP = c->n_rows - c->merged_nA;
-    FEDD_TRY(child_check(c, c->bp_vel, nA, who));
-    FEDD_TRY(child_check(c, c->bp_schur, nP, who));
+    FEDD_TRY(child_check(c, 0, nA, who));
+    FEDD_TRY(child_check(c, 1, nP, who));
     if (c->bp_kind == FEDD_BLOCKPREC_TRIANGULAR) {
         FEDD_CHECK(c->bp_slot_bt >= 0 && c->bp_slot_bt < MAX_AUX, "%s: block preconditioner: matrix slot %d out of range", who, c->bp_slot_bt);
         const DevCsr& bt = c->aux[c->bp_slot_bt];
@@ -142,11 +176,11 @@ int block_prec_check(fedd_ctx* c, const char* who) {
 
 int block_prec_apply(fedd_ctx* c, const double* r, double* z) {
     FEDD_TRY(block_prec_check(c, "block preconditioner apply"));
-    fedd_ctx *V = c->bp_vel, *S = c->bp_schur;
+    fedd_ctx *V = c->prec.child[0].ctx, *S = c->prec.child[1].ctx;
     const int64_t nA = c->merged_nA, nP = c->n_rows - nA;
-    FEDD_TRY(child_order(c, V, &c->bp_seen_vel));
-    FEDD_TRY(child_order(c, S, &c->bp_seen_schur));
-    ++c->bp_applies;
+    FEDD_TRY(child_order(c, c->prec.child[0]));
+    FEDD_TRY(child_order(c, c->prec.child[1]));
+    ++c->prec.applies;
     const double* r_u = r;
     const double* r_p = r + nA;
     double* z_u = z;
@@ -175,53 +209,21 @@ int block_prec_apply(fedd_ctx* c, const double* r, double* z) {
         ScopedTimer tm(c, FEDD_T_BLOCKPREC_BT);
         // values and columns, row pointer, Dirichlet marks, r_u and t, s (read once from memory, then cache resident) and z_p
         tm.bytes(12.0 * (double)bt.nnz + 4.0 * (double)(nA + 1) + 4.0 * (double)nA + 16.0 * (double)nA + 16.0 * (double)nP);
-        const int32_t n = (int32_t)nA;
-        if (bt.max_row_nnz <= 32) {     // the lane groups of block_apply_device (timestep.hip)
-            constexpr int G = 8;
-            hipLaunchKernelGGL(k_bt_sub<G>, dim3((unsigned)(((int64_t)n * G + 255) / 256)), dim3(256), 0, c->stream,
-                               (const int32_t*)bt.rowptr.p, (const int32_t*)bt.colind.p, (const double*)bt.val.p, (const double*)s,
-                               c->bp_scale, (const int32_t*)c->d_isdir.p, r_u, n, (int32_t)nP, t, z_p);
-        } else {
-            constexpr int G = 16;
-            hipLaunchKernelGGL(k_bt_sub<G>, dim3((unsigned)(((int64_t)n * G + 255) / 256)), dim3(256), 0, c->stream,
-                               (const int32_t*)bt.rowptr.p, (const int32_t*)bt.colind.p, (const double*)bt.val.p, (const double*)s,
-                               c->bp_scale, (const int32_t*)c->d_isdir.p, r_u, n, (int32_t)nP, t, z_p);
-        }
+        with_row_groups(bt.max_row_nnz, nA, [&](auto G, unsigned grid) {
+            hipLaunchKernelGGL(k_bt_sub<decltype(G)::value>, dim3(grid), dim3(256), 0, c->stream, (const int32_t*)bt.rowptr.p,
+                               (const int32_t*)bt.colind.p, (const double*)bt.val.p, (const double*)s, c->bp_scale,
+                               (const int32_t*)c->d_isdir.p, r_u, (int32_t)nA, (int32_t)nP, t, z_p);
+            return 0;
+        });
         tm.stop();
         FEDD_HIP(hipGetLastError());
     }
     return child_apply(c, V, t, z_u);
 }
 
-void block_prec_unlink(fedd_ctx* c) {
-    for (fedd_ctx* ch : {c->bp_vel, c->bp_schur})
-        if (ch) {
-            auto it = std::find(ch->bp_parents.begin(), ch->bp_parents.end(), c);
-            if (it != ch->bp_parents.end()) ch->bp_parents.erase(it);
-        }
-    c->bp_kind = 0;
-    c->bp_vel = c->bp_schur = nullptr;
-    c->bp_slot_bt = -1;
-    c->bp_scale = 1.0;
-}
-
-// The child's buffers may still be read by kernels in a parent's stream: each parent finishes them, then lets go of both children.
-void block_prec_child_gone(fedd_ctx* child) {
-    while (!child->bp_parents.empty()) {
-        fedd_ctx* p = child->bp_parents.back();
-        if (p->device >= 0 && hipSetDevice(p->device) == hipSuccess) (void)hipStreamSynchronize(p->stream);
-        block_prec_unlink(p);   // erases p from child->bp_parents: p held the child as bp_vel or bp_schur
-        assert(child->bp_parents.empty() || child->bp_parents.back() != p);
-    }
-}
-
 }  // namespace fedd
 
 using namespace fedd;
-
-#define NEED_DEVICE(c)                                                                           \
-    FEDD_CHECK((c) && (c)->device >= 0,                                                          \
-               "this call needs a GPU context (fedd_ctx_create with device >= 0); there is no CPU fallback")
 
 extern "C" int fedd_matrix_import(fedd_ctx* dst, fedd_ctx* src, int src_slot) {
     FEDD_CHECK(dst && src, "fedd_matrix_import: null context");
@@ -264,26 +266,9 @@ extern "C" int fedd_matrix_import(fedd_ctx* dst, fedd_ctx* src, int src_slot) {
     int rc = 0;
     auto body = [&]() -> int {
         if (!values_only) {
-            ScopedTimer t(c, FEDD_T_SYMBOLIC);
-            c->have_pattern = false;
-            FEDD_TRY(c->d_rowptr.ensure(n + 1));
-            FEDD_TRY(c->d_colind.ensure((size_t)m.nnz));
-            FEDD_TRY(c->d_val.ensure((size_t)m.nnz));
-            FEDD_TRY(c->d_rhs.ensure(n));
-            FEDD_TRY(c->d_x.ensure(n));
-            FEDD_TRY(c->d_xcol.ensure(n));
-            FEDD_TRY(c->d_isdir.ensure(n));
-            FEDD_HIP(hipMemcpyAsync(c->d_rowptr.p, m.rowptr.p, (n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
-            FEDD_HIP(hipMemcpyAsync(c->d_colind.p, m.colind.p, (size_t)m.nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
-            c->dofs = (int)dofs;
-            c->block_mode = m.block_mode >= 0 ? m.block_mode : (dofs == 1 ? FEDD_BLOCK_SCALAR : FEDD_BLOCK_FULL);
-            c->n_rows = c->n_rows_ext = m.n_rows;
-            c->n_cols = m.n_cols;
-            c->nnz = c->nnz_ext = m.nnz;
-            c->max_row_nnz = m.max_row_nnz;
-            c->merged = false;
-            c->sys_pattern_id = 0;      // the system slot holds the pattern of none of this context's own slots
-            c->sys_pattern_gen = c->pattern_gen;
+            // (the system slot then holds the pattern of none of this context's own slots: pattern id 0)
+            FEDD_TRY(system_adopt_pattern(c, m, (int)dofs, m.block_mode >= 0 ? m.block_mode : (dofs == 1 ? FEDD_BLOCK_SCALAR : FEDD_BLOCK_FULL),
+                                          n, false, 0));
         }
         FEDD_HIP(hipMemcpyAsync(c->d_val.p, m.val.p, (size_t)m.nnz * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         // reset as by a merge
@@ -331,16 +316,11 @@ extern "C" int fedd_block_prec_attach(fedd_ctx* c, int kind, fedd_ctx* velocity,
     FEDD_CHECK(velocity->device == c->device && schur->device == c->device,
                "fedd_block_prec_attach: contexts on different devices (parent %d, velocity %d, Schur complement %d)", c->device,
                velocity->device, schur->device);
-    block_prec_unlink(c);       // (an earlier attach)
-    velocity->bp_parents.push_back(c);
-    schur->bp_parents.push_back(c);
+    prec_unlink(c);             // (an earlier attach, of either kind)
+    prec_attach(c, AttachedPrec::BLOCK, velocity, schur);
     c->bp_kind = kind;
-    c->bp_vel = velocity;
-    c->bp_schur = schur;
     c->bp_scale = schur_scale;
     c->bp_slot_bt = kind == FEDD_BLOCKPREC_TRIANGULAR ? slot_bt : -1;
-    c->bp_seen_vel = c->bp_seen_schur = ~(uint64_t)0;   // the first apply orders the children's streams in front
-    c->bp_applies = 0;
     return 0;
 }
 
@@ -350,7 +330,7 @@ extern "C" int fedd_block_prec_detach(fedd_ctx* c) {
         FEDD_HIP(hipSetDevice(c->device));
         FEDD_HIP(hipStreamSynchronize(c->stream));
     }
-    block_prec_unlink(c);
+    if (c->bp_kind) prec_unlink(c);
     return 0;
 }
 
@@ -359,6 +339,6 @@ extern "C" int fedd_block_prec_info(fedd_ctx* c, int* kind, double* schur_scale,
     if (kind) *kind = c->bp_kind;
     if (schur_scale) *schur_scale = c->bp_scale;
     if (slot_bt) *slot_bt = c->bp_slot_bt;
-    if (n_applies) *n_applies = c->bp_applies;
+    if (n_applies) *n_applies = c->bp_kind ? c->prec.applies : 0;
     return 0;
 }

@@ -38,6 +38,13 @@ void set_error(const char* fmt, ...);
         if (r__) return r__;                                                                    \
     } while (0)
 
+// the argument checks of the entry points (fsi.hip words its own for calls that take several contexts)
+#define NEED_DEVICE(c)                                                                           \
+    FEDD_CHECK((c) && (c)->device >= 0,                                                          \
+               "this call needs a GPU context (fedd_ctx_create with device >= 0); there is no CPU fallback")
+#define ONE_RANK(c, who) FEDD_CHECK((c)->nranks == 1, "%s: one rank only (a context with %d ranks was given)", who, (c)->nranks)
+#define CHECK_SLOT(s) FEDD_CHECK((s) >= 0 && (s) < fedd::MAX_AUX, "matrix slot %d out of range", (s))
+
 // A device allocation that remembers its size; grows on demand, never shrinks.
 template <class T>
 struct DevBuf {
@@ -87,6 +94,35 @@ struct GatherLists {
 
 constexpr int MAX_BC = 16;
 constexpr int MAX_DOFS = 3;
+
+// The Dirichlet conditions of a call, by value into its kernel: condition k holds on the nodes with flag[k], for the components
+// with mask[k * dofs + comp] != 0 (no mask given: all), with value[k * dofs + comp].  The first condition that fits decides.
+struct BcTable {
+    int n, dofs;
+    int32_t flag[MAX_BC];
+    int32_t mask[MAX_BC * MAX_DOFS];
+    double value[MAX_BC * MAX_DOFS];
+};
+inline BcTable bc_table_fill(int dofs, int n_bc, const int32_t* flags, const int32_t* comp_mask, const double* values) {
+    BcTable b;
+    b.n = n_bc;
+    b.dofs = dofs;
+    for (int k = 0; k < n_bc; ++k) {
+        b.flag[k] = flags[k];
+        for (int d = 0; d < dofs; ++d) {
+            b.mask[k * dofs + d] = comp_mask ? comp_mask[k * dofs + d] : 1;
+            b.value[k * dofs + d] = values[k * dofs + d];
+        }
+    }
+    return b;
+}
+// the condition of component comp of a node with this flag, -1: none
+__device__ __forceinline__ int bc_hit(const BcTable& b, int32_t flag, int comp) {
+    int hit = -1;
+    for (int k = 0; k < b.n; ++k)
+        if (hit < 0 && b.flag[k] == flag && b.mask[k * b.dofs + comp]) hit = k;
+    return hit;
+}
 constexpr int SPMV_PAT_LMAX = 48;       // longest offset list of the SpMV pattern table (spmv.hip SPAT_L)
 constexpr int SCHWARZ_NMAX = 256;  // largest overlapping subdomain (dofs) the register / LDS dense kernels take
 constexpr int SCHWARZ_NMAX_BIG = 1024;  // ... and the batched matrix-core inversion of the large-subdomain path
@@ -229,6 +265,20 @@ struct IfaceTable {
     std::vector<int32_t> flags;                 // the flags of the match, in the order given
     std::vector<int64_t> flag_ptr;              // [flags + 1] pairs of flag i: [flag_ptr[i], flag_ptr[i + 1])
     double max_dist = 0.0;                      // largest distance between paired points
+};
+
+// A preconditioner of a context out of two child contexts applied as blocks (DESIGN.md section 4 "Stored blocks: the lane-group
+// row walk and child contexts").  The children are not owned; each keeps its parents in fedd_ctx::prec_parents.
+struct PrecChild {
+    fedd_ctx* ctx = nullptr;
+    uint64_t seen = 0;                          // the child's sw_setup_gen when its own stream was last ordered before the parent's
+};
+struct AttachedPrec {
+    enum { NONE = 0, BLOCK = 1, FACSI = 2 };
+    int kind = NONE;
+    PrecChild child[2];                         // BLOCK: velocity, Schur complement; FACSI: fluid, structure
+    hipEvent_t ev = nullptr;                    // orders a child's own stream before the parent's (one event serves both children)
+    int64_t applies = 0;                        // applies since the attach
 };
 
 // One block of an s-step solve, copied stage by stage (fedd_gmres_capture_*): device-to-device copies on the solver's stream
@@ -527,24 +577,20 @@ struct fedd_ctx {
     double comb_cm = 0.0, comb_ca = 0.0;        // and the sys_value_gen it left (none yet: a value sys_value_gen never takes)
     uint64_t comb_id_m = 0, comb_id_a = 0, comb_sys_gen = ~(uint64_t)0;
 
-    // ---- block preconditioner of a merged 2 x 2 system (blockprec.hip; one rank): the two Schwarz preconditioners live in child
-    //      contexts that this one does not own ----
+    // ---- a preconditioner out of two child contexts that this one does not own (blockprec.hip "child link"; one rank): the
+    //      block preconditioner of a merged 2 x 2 system (blockprec.hip) or FaCSI of a coupled system (fsi.hip) ----
+    fedd::AttachedPrec prec;
+    std::vector<fedd_ctx*> prec_parents;        // contexts that hold this one as a child of their attached preconditioner
     int bp_kind = 0;                            // 0 = none attached, FEDD_BLOCKPREC_DIAGONAL / FEDD_BLOCKPREC_TRIANGULAR
-    fedd_ctx* bp_vel = nullptr;                 // V: preconditioner of block (0,0)
-    fedd_ctx* bp_schur = nullptr;               // S: preconditioner of the Schur complement's stand-in
     double bp_scale = 1.0;                      // z_p = bp_scale * S(r_p)
     int bp_slot_bt = -1;                        // B^T of the Triangular form
     fedd::DevBuf<double> d_bp_ws;               // [n_rows] S(r_p) | t of the Triangular form
-    hipEvent_t bp_ev = nullptr;                 // orders a child's own stream before this one after the child was set up again
-    uint64_t bp_seen_vel = 0, bp_seen_schur = 0;   // the children's sw_setup_gen at the last such ordering
-    int64_t bp_applies = 0;                     // applies of the block operator since it was attached
     uint64_t sw_setup_gen = 0;                  // counts the fedd_schwarz_setup calls of this context
     // the system matrix is an import (fedd_matrix_import) of this block: the source context's uid, its mesh, the block's pattern id, and the
     // pattern_gen the import left here -- while all four stand, the next import of that block moves values only
     uint64_t uid = 0;                           // process-wide unique id of this context (fedd_ctx_create): an address can come back
     uint64_t imp_src_uid = 0;                   // ... after a destroy, this number cannot
     uint64_t imp_mesh_id = 0, imp_pattern_id = 0, imp_pattern_gen = 0;
-    std::vector<fedd_ctx*> bp_parents;          // contexts that hold this one as a child of their block preconditioner
 
     // ---- FSI coupling (fsi.hip; one rank) ----
     std::shared_ptr<fedd::IfaceTable> iface;    // the matched interface this context is one side of (fedd_interface_match)
@@ -561,15 +607,7 @@ struct fedd_ctx {
     fedd::DevBuf<int32_t> d_fsi_lam_f, d_fsi_lam_s; // [n_u + n_p], [n_s] lambda-dof of a fluid / structure dof (-1: none)
     int fsi_last_values_only = 0;               // the last merge moved values only
     int64_t fsi_values_only_count = 0;          // merges that did since the context was made
-    // the FaCSI preconditioner: two child contexts this one does not own
-    bool fp_on = false;
-    fedd_ctx* fp_fluid = nullptr;
-    fedd_ctx* fp_struct = nullptr;
-    fedd::DevBuf<double> d_fp_t;                // [n_u + n_p] t of the apply
-    hipEvent_t fp_ev = nullptr;                 // orders a child's own stream before this one after the child was set up again
-    uint64_t fp_seen_f = 0, fp_seen_s = 0;      // the children's sw_setup_gen at the last such ordering
-    int64_t fp_applies = 0;
-    std::vector<fedd_ctx*> fp_parents;          // coupled contexts that hold this one as a child of their FaCSI preconditioner
+    fedd::DevBuf<double> d_fp_t;                // [n_u + n_p] t of the FaCSI apply (the children: `prec` above)
 
     // ---- coarse level (two-level Schwarz) ----
     int sw_two_level = 0;
@@ -820,25 +858,36 @@ int tiles_refresh_coords(fedd_ctx* c);   // the coordinate copies at the head of
 int matrix_store(fedd_ctx* c, int slot);
 int matrix_scale(fedd_ctx* c, int slot, double alpha);
 int block_merge(fedd_ctx* c, int slot_a, int slot_bt, int slot_b, int slot_c);
+// timestep.hip: the system slot adopts the pattern of the stored block m (fedd_matrix_combine, fedd_matrix_import): buffers, row
+// pointers and columns (copied in c's stream), sizes; the values are the caller's.  n_xcol = the length of d_xcol;
+// zero_other_len: a right-hand side and a solution of another length are zeroed; pattern_id = what sys_pattern_id becomes
+int system_adopt_pattern(fedd_ctx* c, const DevCsr& m, int dofs, int block_mode, size_t n_xcol, bool zero_other_len, uint64_t pattern_id);
 
 // blockprec.hip: Diagonal / Triangular block preconditioner of a merged system out of two child contexts
 int block_prec_check(fedd_ctx* c, const char* who);    // everything an apply needs, with errors that name the child
 int block_prec_apply(fedd_ctx* c, const double* d_r_owned, double* d_z_owned);
-void block_prec_unlink(fedd_ctx* c);                   // c gives up its children (detach, re-attach, destroy of c)
-void block_prec_child_gone(fedd_ctx* child);           // a child is being destroyed: its parents are detached first
+// ... and the child link that the block preconditioner and FaCSI share.  `label` is the kind as the messages name it, `nm` the
+// child, `parent` the parent; a kind's own checks of the child's system stand between the two halves of the check
+void prec_attach(fedd_ctx* c, int kind, fedd_ctx* first, fedd_ctx* second);   // (after prec_unlink of an earlier attach)
+void prec_unlink(fedd_ctx* c);                         // c gives up its children (detach, re-attach, destroy of c)
+void prec_child_gone(fedd_ctx* child);                 // a child is being destroyed: its parents are detached first
+int child_check_context(const fedd_ctx* c, const fedd_ctx* ch, const char* who, const char* label, const char* nm, const char* parent);
+int child_check_schwarz(const fedd_ctx* ch, const char* who, const char* label, const char* nm, const char* mult_operator);
+int child_order(fedd_ctx* c, PrecChild& ch);           // the child's own stream is ordered before c's, where that is needed
+int child_apply(fedd_ctx* c, fedd_ctx* ch, const double* d_r, double* d_z);   // the child's Schwarz apply, in c's stream
 // the preconditioner of the context: the attached block operator, else its own Schwarz preconditioner
 int schwarz_apply(fedd_ctx* c, const double* d_r_owned, double* d_z_owned, bool r_has_tail);
 // fsi.hip: matched interface, the coupled four-block system, the FaCSI preconditioner out of two child contexts
 void iface_release(fedd_ctx* c);                       // fedd_mesh_set* / destroy: the match of this context is released on both sides
 int fsi_prec_check(fedd_ctx* c, const char* who);      // everything an apply needs, with errors that name the child
 int fsi_prec_apply(fedd_ctx* c, const double* d_r_owned, double* d_z_owned);
-void fsi_prec_unlink(fedd_ctx* c);
-void fsi_prec_child_gone(fedd_ctx* child);
-inline bool has_attached_prec(const fedd_ctx* c) { return c->bp_kind != 0 || c->fp_on; }
-inline int attached_prec_check(fedd_ctx* c, const char* who) { return c->fp_on ? fsi_prec_check(c, who) : block_prec_check(c, who); }
+inline bool has_attached_prec(const fedd_ctx* c) { return c->prec.kind != AttachedPrec::NONE; }
+inline int attached_prec_check(fedd_ctx* c, const char* who) {
+    return c->prec.kind == AttachedPrec::FACSI ? fsi_prec_check(c, who) : block_prec_check(c, who);
+}
 inline int prec_apply(fedd_ctx* c, const double* d_r_owned, double* d_z_owned, bool r_has_tail) {
-    if (c->fp_on) return fsi_prec_apply(c, d_r_owned, d_z_owned);
-    return c->bp_kind ? block_prec_apply(c, d_r_owned, d_z_owned) : schwarz_apply(c, d_r_owned, d_z_owned, r_has_tail);
+    if (c->prec.kind == AttachedPrec::FACSI) return fsi_prec_apply(c, d_r_owned, d_z_owned);
+    return c->prec.kind ? block_prec_apply(c, d_r_owned, d_z_owned) : schwarz_apply(c, d_r_owned, d_z_owned, r_has_tail);
 }
 
 // spmv.hip

@@ -19,15 +19,13 @@
 //                    pattern in place (the Dirichlet marks of the children decide whether a row has its C1^T / C3^T entry).
 //   k_facsi_inject   t = [x_u; x_p] with t[fdof(k)] = x_l,k - c2 * y_d[sdof(k)]: g and the injection, one lane per fluid dof
 //                    through the dof -> lambda map, so no two lanes write the same entry.
-//   k_facsi_rows     z and y_l: G lanes per interface row over cpl's CSR, columns < n_f only, the sums over F (columns < n_u)
-//                    and over B^T (columns in [n_u, n_f)) formed separately, each lane adding in ascending column order, one
-//                    fixed tree per sum, no contraction.
+//   k_facsi_rows     z and y_l: the lane-group row walk of stored_rows.hpp per interface row over cpl's CSR, columns < n_f only,
+//                    with two sums, over F (columns < n_u) and over B^T (columns in [n_u, n_f)), one fixed tree per sum.
 //                    Bytes of an apply beside the children's: inject 8 (2 n_f) + 4 n_f + 20 n_l; rows 12 nnz(rows fdof(k) of
 //                    cpl) + 8 n_l (row pointers) + 4 n_l + 24 n_l -- n_l rows of F and B^T, not the whole blocks.
-#include "fedd_internal.hpp"
+#include "stored_rows.hpp"
 #include <algorithm>
 #include <atomic>
-#include <cassert>
 #include <cmath>
 
 #pragma clang fp contract(off)
@@ -182,6 +180,24 @@ __global__ __launch_bounds__(256) void k_facsi_inject(const double* __restrict__
     }
 }
 
+// the two sums of a fluid row of cpl: the C1^T entry of the row lies behind n_f and is dropped
+struct FacsiSums {
+    const double* __restrict__ y;
+    int32_t n_u, n_f;
+    double sF = 0.0, sB = 0.0;
+    __device__ bool keep(int32_t col) const { return col < n_f; }
+    __device__ double x(int32_t col) const { return y[col]; }
+    __device__ void add(int32_t col, double p) {
+        if (col >= 0 && col < n_u) sF += p;
+        if (col >= n_u) sB += p;
+    }
+    template <int G>
+    __device__ void fold(int o) {
+        sF += __shfl_xor(sF, o, G);
+        sB += __shfl_xor(sB, o, G);
+    }
+};
+
 // G lanes per lambda-dof k.  y = [y_u; y_p] (the first n_f entries of the output vector), x as above.
 //   sF = sum over the columns < n_u of row fdof(k), sB = sum over the columns in [n_u, n_f)      (cpl's CSR, as it stands)
 //   y_l,k = (x_u[fdof(k)] - sB) - sF        coupled;      y_l,k = x_l,k        uncoupled
@@ -197,31 +213,9 @@ __global__ __launch_bounds__(256) void k_facsi_rows(const int32_t* __restrict__ 
     const int32_t r = live ? fdof[k] : -1;
     const int32_t st = r >= 0 ? rowptr[r] : 0;
     const int32_t len = r >= 0 ? rowptr[r + 1] - st : 0;
-    double sF = 0.0, sB = 0.0;
-    for (int32_t k0 = g; k0 < len; k0 += 4 * G) {
-        int32_t cc[4];
-        double vv[4], yy[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int32_t q = k0 + u * G;
-            const int32_t col = q < len ? colind[st + q] : n_f;
-            cc[u] = col < n_f ? col : -1;       // the C1^T entry of the row lies behind n_f
-            vv[u] = cc[u] >= 0 ? val[st + q] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) yy[u] = cc[u] >= 0 ? y[cc[u]] : 0.0;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const double prod = vv[u] * yy[u];
-            if (cc[u] >= 0 && cc[u] < n_u) sF += prod;
-            if (cc[u] >= n_u) sB += prod;
-        }
-    }
-#pragma unroll
-    for (int o = G / 2; o >= 1; o >>= 1) {
-        sF += __shfl_xor(sF, o, G);
-        sB += __shfl_xor(sB, o, G);
-    }
+    FacsiSums sums{y, n_u, n_f};
+    row_walk<G>(colind, val, st, len, g, sums);
+    const double sF = sums.sF, sB = sums.sB;
     if (live && g == 0) {
         if (r >= 0) {
             const double a = x[r] - sB;
@@ -300,51 +294,18 @@ int side_rank(fedd_ctx* run, const char* name, int flag, int dim, const Side& s,
     return 0;
 }
 
-const char* child_name(const fedd_ctx* c, const fedd_ctx* ch) { return ch == c->fp_fluid ? "fluid" : "structure"; }
-
-// as blockprec.hip child_order: what the child put into its OWN stream (merge, Dirichlet rows, setup) is ordered in front of this
-// stream by an event, after every setup of the child and whenever its stream is not idle
-int child_order(fedd_ctx* c, fedd_ctx* ch, uint64_t* seen) {
-    if (*seen == ch->sw_setup_gen) {
-        const hipError_t q = hipStreamQuery(ch->stream);
-        if (q == hipSuccess) return 0;
-        if (q != hipErrorNotReady) FEDD_HIP(q);
-        (void)hipGetLastError();
-    }
-    if (!c->fp_ev) FEDD_HIP(hipEventCreateWithFlags(&c->fp_ev, hipEventDisableTiming));
-    FEDD_HIP(hipEventRecord(c->fp_ev, ch->stream));
-    FEDD_HIP(hipStreamWaitEvent(c->stream, c->fp_ev, 0));
-    *seen = ch->sw_setup_gen;
-    return 0;
-}
-
-int child_apply(fedd_ctx* c, fedd_ctx* ch, const double* r, double* z) {
-    hipStream_t own = ch->stream;
-    ch->stream = c->stream;
-    const int rc = schwarz_apply(ch, r, z, false);
-    ch->stream = own;
-    return rc;
-}
-
-int child_check(fedd_ctx* c, fedd_ctx* ch, int64_t n_expected, uint64_t uid, uint64_t mesh_gen, const char* who) {
-    const char* nm = child_name(c, ch);
-    FEDD_CHECK(ch->device >= 0, "%s: FaCSI: the %s child is a host-only context", who, nm);
-    FEDD_CHECK(ch->nranks == 1, "%s: FaCSI: one rank only (the %s child has %d ranks)", who, nm, ch->nranks);
-    FEDD_CHECK(ch->device == c->device, "%s: FaCSI: the %s child is on device %d, the coupled context on device %d", who, nm,
-               ch->device, c->device);
+// (the checks in the order of the messages: a fedd_mesh_set* on a child says more than its sizes)
+int child_check(fedd_ctx* c, int which, int64_t n_expected, uint64_t uid, uint64_t mesh_gen, const char* who) {
+    const fedd_ctx* ch = c->prec.child[which].ctx;
+    const char* nm = which == 0 ? "fluid" : "structure";
+    FEDD_TRY(child_check_context(c, ch, who, "FaCSI", nm, "coupled context"));
     FEDD_CHECK(ch->uid == uid, "%s: FaCSI: the %s child is not the %s context the coupled system was merged from", who, nm, nm);
     FEDD_CHECK(ch->mesh_gen == mesh_gen,
                "%s: FaCSI: the merge is older than the %s child's mesh (fedd_mesh_set since the last fedd_fsi_merge)", who, nm);
     FEDD_CHECK(ch->have_pattern && ch->n_rows == n_expected && ch->n_cols == n_expected,
                "%s: FaCSI: wrong sizes: the %s child's system has %lld rows, the coupled system's block %lld", who, nm,
                (long long)(ch->have_pattern ? ch->n_rows : 0), (long long)n_expected);
-    FEDD_CHECK(ch->have_schwarz,
-               "%s: FaCSI: the %s child has no current fedd_schwarz_setup (never set up, or its matrix changed since)", who, nm);
-    FEDD_CHECK(ch->sw_levels != FEDD_LEVELS_MULTIPLICATIVE,
-               "%s: FaCSI: the %s child asks for FEDD_LEVELS_MULTIPLICATIVE, whose operator is singular and is not built as a block "
-               "of a block preconditioner; use FEDD_LEVELS_ADDITIVE",
-               who, nm);
-    return 0;
+    return child_check_schwarz(ch, who, "FaCSI", nm, "");
 }
 
 }  // namespace
@@ -355,33 +316,34 @@ void iface_release(fedd_ctx* c) {
 }
 
 int fsi_prec_check(fedd_ctx* c, const char* who) {
-    FEDD_CHECK(c->fp_on && c->fp_fluid && c->fp_struct, "%s: no FaCSI preconditioner attached", who);
+    FEDD_CHECK(c->prec.kind == AttachedPrec::FACSI && c->prec.child[0].ctx && c->prec.child[1].ctx, "%s: no FaCSI preconditioner attached", who);
     FEDD_CHECK(c->nranks == 1, "%s: FaCSI: one rank only (a context with %d ranks was given)", who, c->nranks);
     FEDD_CHECK(c->have_pattern && c->fsi_coupled && c->pattern_gen == c->fsi_pat_gen,
                "%s: FaCSI: the context does not hold a coupled system (fedd_fsi_merge first)", who);
     // (the children first: a fedd_mesh_set* on a child also releases the table, and the message that names the child and its
     // mesh says more than the one about the table, which is left for a table released by a new fedd_interface_match)
-    FEDD_TRY(child_check(c, c->fp_fluid, c->fsi_nu + c->fsi_np, c->fsi_uid_f, c->fsi_mesh_gen_f, who));
-    FEDD_TRY(child_check(c, c->fp_struct, c->fsi_ns, c->fsi_uid_s, c->fsi_mesh_gen_s, who));
+    FEDD_TRY(child_check(c, 0, c->fsi_nu + c->fsi_np, c->fsi_uid_f, c->fsi_mesh_gen_f, who));
+    FEDD_TRY(child_check(c, 1, c->fsi_ns, c->fsi_uid_s, c->fsi_mesh_gen_s, who));
     FEDD_CHECK(c->fsi_table && c->fsi_table->valid,
                "%s: FaCSI: the matched interface the coupled system was built on has been released (a new fedd_interface_match of a "
                "child since the last fedd_fsi_merge)",
                who);
-    FEDD_CHECK(c->fp_fluid->merged && c->fp_fluid->merged_nA == c->fsi_nu,
+    const fedd_ctx* F = c->prec.child[0].ctx;
+    FEDD_CHECK(F->merged && F->merged_nA == c->fsi_nu,
                "%s: FaCSI: wrong sizes: the fluid child's velocity block has %lld rows, the coupled system's %lld", who,
-               (long long)(c->fp_fluid->merged ? c->fp_fluid->merged_nA : 0), (long long)c->fsi_nu);
+               (long long)(F->merged ? F->merged_nA : 0), (long long)c->fsi_nu);
     return 0;
 }
 
 int fsi_prec_apply(fedd_ctx* c, const double* x, double* y) {
     FEDD_TRY(fsi_prec_check(c, "FaCSI apply"));
-    fedd_ctx *F = c->fp_fluid, *S = c->fp_struct;
+    fedd_ctx *F = c->prec.child[0].ctx, *S = c->prec.child[1].ctx;
     const int32_t n_u = (int32_t)c->fsi_nu, n_f = (int32_t)(c->fsi_nu + c->fsi_np), n_s = (int32_t)c->fsi_ns, n_l = (int32_t)c->fsi_nl;
     const int32_t off_l = n_f + n_s;
     const double c2 = -(1.0 / c->fsi_dt);
-    FEDD_TRY(child_order(c, F, &c->fp_seen_f));
-    FEDD_TRY(child_order(c, S, &c->fp_seen_s));
-    ++c->fp_applies;
+    FEDD_TRY(child_order(c, c->prec.child[0]));
+    FEDD_TRY(child_order(c, c->prec.child[1]));
+    ++c->prec.applies;
     FEDD_TRY(c->d_fp_t.ensure((size_t)n_f));
     double* t = c->d_fp_t.p;
     FEDD_TRY(child_apply(c, S, x + n_f, y + n_f));          // y_d = S~(x_d)
@@ -397,41 +359,16 @@ int fsi_prec_apply(fedd_ctx* c, const double* x, double* y) {
     {
         ScopedTimer tm(c, FEDD_T_FSI_APPLY);
         tm.bytes(12.0 * (double)c->max_row_nnz * (double)n_l + 36.0 * (double)n_l);    // (an upper bound: the longest row for every one)
-        if (c->max_row_nnz <= 32) {
-            constexpr int G = 8;
-            hipLaunchKernelGGL(k_facsi_rows<G>, dim3((unsigned)(((int64_t)n_l * G + 255) / 256)), dim3(256), 0, c->stream,
-                               (const int32_t*)c->d_rowptr.p, (const int32_t*)c->d_colind.p, (const double*)c->d_val.p,
-                               (const int32_t*)c->d_fsi_fdof.p, x, (const double*)y, n_u, n_f, off_l, n_l, y + off_l);
-        } else {
-            constexpr int G = 16;
-            hipLaunchKernelGGL(k_facsi_rows<G>, dim3((unsigned)(((int64_t)n_l * G + 255) / 256)), dim3(256), 0, c->stream,
-                               (const int32_t*)c->d_rowptr.p, (const int32_t*)c->d_colind.p, (const double*)c->d_val.p,
-                               (const int32_t*)c->d_fsi_fdof.p, x, (const double*)y, n_u, n_f, off_l, n_l, y + off_l);
-        }
+        with_row_groups(c->max_row_nnz, n_l, [&](auto G, unsigned grid) {
+            hipLaunchKernelGGL(k_facsi_rows<decltype(G)::value>, dim3(grid), dim3(256), 0, c->stream, (const int32_t*)c->d_rowptr.p,
+                               (const int32_t*)c->d_colind.p, (const double*)c->d_val.p, (const int32_t*)c->d_fsi_fdof.p, x,
+                               (const double*)y, n_u, n_f, off_l, n_l, y + off_l);
+            return 0;
+        });
         tm.stop();
         FEDD_HIP(hipGetLastError());
     }
     return 0;
-}
-
-void fsi_prec_unlink(fedd_ctx* c) {
-    for (fedd_ctx* ch : {c->fp_fluid, c->fp_struct})
-        if (ch) {
-            auto it = std::find(ch->fp_parents.begin(), ch->fp_parents.end(), c);
-            if (it != ch->fp_parents.end()) ch->fp_parents.erase(it);
-        }
-    c->fp_on = false;
-    c->fp_fluid = c->fp_struct = nullptr;
-}
-
-// The child's buffers may still be read by kernels in a parent's stream: each parent finishes them, then lets go of both children.
-void fsi_prec_child_gone(fedd_ctx* child) {
-    while (!child->fp_parents.empty()) {
-        fedd_ctx* p = child->fp_parents.back();
-        if (p->device >= 0 && hipSetDevice(p->device) == hipSuccess) (void)hipStreamSynchronize(p->stream);
-        fsi_prec_unlink(p);     // erases p from child->fp_parents
-        assert(child->fp_parents.empty() || child->fp_parents.back() != p);
-    }
 }
 
 }  // namespace fedd
@@ -772,31 +709,27 @@ extern "C" int fedd_fsi_prec_attach(fedd_ctx* c, fedd_ctx* fluid, fedd_ctx* stru
                "fedd_fsi_prec_attach: the context does not hold a coupled system (fedd_fsi_merge first)");
     FEDD_CHECK(c->fsi_uid_f == fluid->uid && c->fsi_uid_s == structure->uid,
                "fedd_fsi_prec_attach: the coupled system was merged from other contexts than these two");
-    FEDD_CHECK(c->bp_kind == 0, "fedd_fsi_prec_attach: a block preconditioner is attached (fedd_block_prec_detach first)");
-    fsi_prec_unlink(c);         // (an earlier attach)
-    fluid->fp_parents.push_back(c);
-    structure->fp_parents.push_back(c);
-    c->fp_on = true;
-    c->fp_fluid = fluid;
-    c->fp_struct = structure;
-    c->fp_seen_f = c->fp_seen_s = ~(uint64_t)0;     // the first apply orders the children's streams in front
-    c->fp_applies = 0;
+    FEDD_CHECK(c->prec.kind != AttachedPrec::BLOCK, "fedd_fsi_prec_attach: a block preconditioner is attached (fedd_block_prec_detach first)");
+    prec_unlink(c);             // (an earlier attach)
+    prec_attach(c, AttachedPrec::FACSI, fluid, structure);
     return 0;
 }
 
 extern "C" int fedd_fsi_prec_detach(fedd_ctx* c) {
     FEDD_CHECK(c, "fedd_fsi_prec_detach: null context");
-    if (c->fp_on && c->device >= 0) {       // the children's kernels run in this context's stream: let them finish
+    const bool on = c->prec.kind == AttachedPrec::FACSI;
+    if (on && c->device >= 0) {             // the children's kernels run in this context's stream: let them finish
         FEDD_HIP(hipSetDevice(c->device));
         FEDD_HIP(hipStreamSynchronize(c->stream));
     }
-    fsi_prec_unlink(c);
+    if (on) prec_unlink(c);
     return 0;
 }
 
 extern "C" int fedd_fsi_prec_info(fedd_ctx* c, int* attached, int64_t* n_applies) {
     FEDD_CHECK(c, "fedd_fsi_prec_info: null context");
-    if (attached) *attached = c->fp_on ? 1 : 0;
-    if (n_applies) *n_applies = c->fp_applies;
+    const bool on = c->prec.kind == AttachedPrec::FACSI;
+    if (attached) *attached = on ? 1 : 0;
+    if (n_applies) *n_applies = on ? c->prec.applies : 0;
     return 0;
 }

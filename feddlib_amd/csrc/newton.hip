@@ -9,15 +9,15 @@
 //
 // Three kernels:
 //   k_newton_residual  r = ((b - f) + s) - cm (M u_k), Dirichlet rows r = g - u_k, and the workgroup's share of |r|^2 in one pass:
-//                      the row walk is k_block_apply's (timestep.hip: G lanes per row, the loads of four trips in flight, the
-//                      fixed shuffle tree), so cm (M u_k) carries the bits of fedd_matrix_apply(slot_m, cm, u_k); the lane that
-//                      finishes a row has loaded its b, f, s, u_k and node flag before the walk starts
+//                      the row walk is the one of stored_rows.hpp, as k_block_apply (timestep.hip) makes it, so cm (M u_k)
+//                      carries the bits of fedd_matrix_apply(slot_m, cm, u_k); the lane that finishes a row has loaded its b, f,
+//                      s, u_k and node flag before the walk starts
 //   k_newton_update    u_k <- u_k + alpha delta, nodal vector field <- u_k, the workgroup's share of |delta|^2: a pure stream of
 //                      16-byte accesses over the row pairs (32 bytes per row), one scalar tail row when n is odd
 //   k_newton_sum       the partial sums of either kernel added by one workgroup in a fixed order
 // The normative operation order is in include/fedd_hip.h; no product is fused with a sum anywhere in this file and there is no
 // floating-point atomic, so the residual can be restated bit for bit on the host and two calls agree bit for bit.
-#include "fedd_internal.hpp"
+#include "stored_rows.hpp"
 #include <algorithm>
 #include <cmath>
 
@@ -25,13 +25,6 @@
 
 namespace fedd {
 namespace {
-
-struct NwBc {
-    int n, dofs;
-    int32_t flag[MAX_BC];
-    int32_t mask[MAX_BC * MAX_DOFS];
-    double value[MAX_BC * MAX_DOFS];
-};
 
 // the workgroup's 256 values added by a fixed tree; the result in red[0]
 __device__ __forceinline__ void wg_sum(double* red, double v) {
@@ -48,7 +41,7 @@ template <int G, bool SRC>
 __global__ __launch_bounds__(256) void k_newton_residual(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
                                                          const double* __restrict__ val, const double* __restrict__ u,
                                                          const double* __restrict__ b, const double* __restrict__ f,
-                                                         const double* __restrict__ src, const int32_t* __restrict__ nflag, NwBc bc,
+                                                         const double* __restrict__ src, const int32_t* __restrict__ nflag, BcTable bc,
                                                          int32_t n_rows, double cm, double* __restrict__ r, double* __restrict__ part) {
     __shared__ double red[256];
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -67,24 +60,7 @@ __global__ __launch_bounds__(256) void k_newton_residual(const int32_t* __restri
         uv = u[row];
         fl = nflag[row / bc.dofs];
     }
-    double acc = 0.0;
-    for (int32_t k0 = g; k0 < len; k0 += 4 * G) {
-        int32_t cc[4];
-        double vv[4], xx[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int32_t k = k0 + q * G;
-            const bool in = k < len;
-            cc[q] = in ? colind[s + k] : -1;
-            vv[q] = in ? val[s + k] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) xx[q] = cc[q] >= 0 ? u[cc[q]] : 0.0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc += vv[q] * xx[q];
-    }
-#pragma unroll
-    for (int o = G / 2; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, G);
+    const double acc = row_sum<G>(colind, val, s, len, g, [=](int32_t col) { return u[col]; });
     double sq = 0.0;
     if (lead) {
         const double m = cm * acc;
@@ -92,9 +68,7 @@ __global__ __launch_bounds__(256) void k_newton_residual(const int32_t* __restri
         if (SRC) rv = rv + sv;
         rv = rv - m;
         const int comp = row - (row / bc.dofs) * bc.dofs;
-        int hit = -1;
-        for (int k = 0; k < bc.n; ++k)
-            if (hit < 0 && bc.flag[k] == fl && bc.mask[k * bc.dofs + comp]) hit = k;
+        const int hit = bc_hit(bc, fl, comp);
         if (hit >= 0) rv = bc.value[hit * bc.dofs + comp] - uv;
         r[row] = rv;
         sq = rv * rv;
@@ -162,11 +136,6 @@ int norm_from_parts(fedd_ctx* c, int32_t n_part, double* norm) {
 
 using namespace fedd;
 
-#define NEED_DEVICE(c)                                                                           \
-    FEDD_CHECK((c) && (c)->device >= 0,                                                          \
-               "this call needs a GPU context (fedd_ctx_create with device >= 0); there is no CPU fallback")
-#define ONE_RANK(c, who) FEDD_CHECK((c)->nranks == 1, "%s: one rank only (a context with %d ranks was given)", who, (c)->nranks)
-#define CHECK_SLOT(s) FEDD_CHECK((s) >= 0 && (s) < fedd::MAX_AUX, "matrix slot %d out of range", (s))
 #define NEED_NEWTON(c, who)                                                                                          \
     FEDD_CHECK((c)->nw_active && (c)->nw_n == (c)->n_rows && (c)->d_nw_u.p,                                          \
                "%s: no Newton state (fedd_newton_begin first; fedd_newton_end and fedd_mesh_set end it)", who)
@@ -230,39 +199,33 @@ extern "C" int fedd_newton_residual(fedd_ctx* c, int slot_m, double cm, int n_bc
                "fedd_newton_residual: the force vector is stale: it is older than the last fedd_newton_begin / fedd_newton_update "
                "(fedd_assemble_hyperelastic* with FEDD_HYPER_FORCE first)");
     FEDD_HIP(hipSetDevice(c->device));
-    NwBc bc;
-    bc.n = n_bc;
-    bc.dofs = c->dofs;
-    for (int k = 0; k < n_bc; ++k) {
-        bc.flag[k] = flags[k];
-        for (int d = 0; d < c->dofs; ++d) {
-            bc.mask[k * c->dofs + d] = comp_mask ? comp_mask[k * c->dofs + d] : 1;
-            bc.value[k * c->dofs + d] = values[k * c->dofs + d];
-        }
-    }
+    const BcTable bc = bc_table_fill(c->dofs, n_bc, flags, comp_mask, values);
     const int32_t n = (int32_t)c->n_rows;
-    const int G = M.max_row_nnz <= 32 ? 8 : 16;     // the grouping of k_block_apply (timestep.hip block_apply_device)
-    const int32_t n_part = (int32_t)std::max<int64_t>(1, ((int64_t)n * G + 255) / 256);
-    FEDD_TRY(c->d_nw_part.ensure((size_t)n_part + 1));
-    if (n > 0) {
+    int32_t n_part = 1;     // one partial sum per workgroup of the walk (one, zero, where there is no row)
+    FEDD_TRY(with_row_groups(M.max_row_nnz, n, [&](auto G, unsigned grid) {
+        n_part = (int32_t)std::max(1u, grid);
+        FEDD_TRY(c->d_nw_part.ensure((size_t)n_part + 1));
+        if (n == 0) {
+            FEDD_HIP(hipMemsetAsync(c->d_nw_part.p, 0, sizeof(double), c->stream));
+            return 0;
+        }
         const bool src = c->nw_have_src;
         ScopedTimer t(c, FEDD_T_NEWTON_RESIDUAL);
         // byte model: the block as k_block_apply counts it (values, columns, row pointers, u_k once), b, f, the source where set
         // and the node flags read, r written
         t.bytes(12.0 * (double)M.nnz + 4.0 * (double)(n + 1) + (src ? 40.0 : 32.0) * (double)n + 4.0 * (double)(n / c->dofs));
-        const dim3 grid((unsigned)n_part), blk(256);
-        const int32_t *rp = M.rowptr.p, *ci = M.colind.p, *nf = c->d_flag.p;
-        const double *mv = M.val.p, *u = c->d_nw_u.p, *b = c->d_nw_b.p, *f = c->d_hy_f.p, *s = c->d_nw_s.p;
-        double *r = c->d_rhs.p, *part = c->d_nw_part.p;
-        if (G == 8 && src) hipLaunchKernelGGL((k_newton_residual<8, true>), grid, blk, 0, c->stream, rp, ci, mv, u, b, f, s, nf, bc, n, cm, r, part);
-        else if (G == 8) hipLaunchKernelGGL((k_newton_residual<8, false>), grid, blk, 0, c->stream, rp, ci, mv, u, b, f, s, nf, bc, n, cm, r, part);
-        else if (src) hipLaunchKernelGGL((k_newton_residual<16, true>), grid, blk, 0, c->stream, rp, ci, mv, u, b, f, s, nf, bc, n, cm, r, part);
-        else hipLaunchKernelGGL((k_newton_residual<16, false>), grid, blk, 0, c->stream, rp, ci, mv, u, b, f, s, nf, bc, n, cm, r, part);
+        auto launch = [&](auto SRC) {
+            hipLaunchKernelGGL((k_newton_residual<decltype(G)::value, decltype(SRC)::value>), dim3(grid), dim3(256), 0, c->stream,
+                               (const int32_t*)M.rowptr.p, (const int32_t*)M.colind.p, (const double*)M.val.p, (const double*)c->d_nw_u.p,
+                               (const double*)c->d_nw_b.p, (const double*)c->d_hy_f.p, (const double*)c->d_nw_s.p,
+                               (const int32_t*)c->d_flag.p, bc, n, cm, c->d_rhs.p, c->d_nw_part.p);
+        };
+        if (src) launch(std::true_type());
+        else launch(std::false_type());
         t.stop();
         FEDD_HIP(hipGetLastError());
-    } else {
-        FEDD_HIP(hipMemsetAsync(c->d_nw_part.p, 0, sizeof(double), c->stream));
-    }
+        return 0;
+    }));
     ++c->nw_residuals;
     double nr = 0.0;
     FEDD_TRY(norm_from_parts(c, n_part, &nr));

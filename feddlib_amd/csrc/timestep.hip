@@ -10,7 +10,7 @@
 // Four kernels:
 //   k_combine_*   system <- cm M + ca A, one lane per stored entry of A; the position of M's entry inside A's row is closed form
 //                 (both patterns expand from the same node-level pattern, symbolic.hip k_expand_pattern)
-//   k_block_apply y = alpha M x on a stored block: G lanes per row, loads of four trips in flight, fixed shuffle tree
+//   k_block_apply y = alpha M x on a stored block: the lane-group row walk of stored_rows.hpp, one sum per row
 //   k_newmark     the vector part of a step in one pass: reads u, u_n, v, w, writes u_n, v, w, t (56 bytes per row)
 //   k_multistep   the history of a BDF loop on a merged (velocity, pressure) system in one pass: reads u and u_0, writes u_0, u_1
 //                 and t = coeff[0] u (+ coeff[1] u_0) (40 bytes per row), zeroes the pressure rows of the right-hand side
@@ -18,7 +18,7 @@
 //                 DAESolverInTime::advanceInTimeNonLinearMultistep, DAESolverInTime_def.hpp:1209-1333)
 // The normative operation order is in include/fedd_hip.h; no product is fused with a sum anywhere in this file, so the
 // combine and the state update can be restated bit for bit on the host.
-#include "fedd_internal.hpp"
+#include "stored_rows.hpp"
 #include <algorithm>
 
 #pragma clang fp contract(off)
@@ -60,10 +60,8 @@ __global__ __launch_bounds__(256) void k_combine_diag(const int32_t* __restrict_
 }
 
 // ---- y = alpha M x on a stored block ---------------------------------------------------------------------------------------
-// G lanes per row; lane g takes entries g, g + G, ... of the row, four trips at a time: the column indices and values of the
-// four trips are loaded first, then the four x entries, then the products are added in trip order (the loads
-// of several trips of a row walk are issued together).  The lane sums are combined by a fixed shuffle tree, so two calls
-// give the same bits.  No stream, dictionary or classes: a stored block is read as it lies.
+// G lanes per row, the walk and its order in stored_rows.hpp.  No stream, dictionary or classes: a stored block is read as it
+// lies.
 template <int G>
 __global__ __launch_bounds__(256) void k_block_apply(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
                                                      const double* __restrict__ val, const double* __restrict__ x, int32_t n_rows,
@@ -74,24 +72,7 @@ __global__ __launch_bounds__(256) void k_block_apply(const int32_t* __restrict__
     const bool live = row < n_rows;
     const int32_t s = live ? rowptr[row] : 0;
     const int32_t len = live ? rowptr[row + 1] - s : 0;
-    double acc = 0.0;
-    for (int32_t k0 = g; k0 < len; k0 += 4 * G) {
-        int32_t cc[4];
-        double vv[4], xx[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int32_t k = k0 + u * G;
-            const bool in = k < len;
-            cc[u] = in ? colind[s + k] : -1;
-            vv[u] = in ? val[s + k] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) xx[u] = cc[u] >= 0 ? x[cc[u]] : 0.0;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc += vv[u] * xx[u];
-    }
-#pragma unroll
-    for (int o = G / 2; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, G);
+    const double acc = row_sum<G>(colind, val, s, len, g, [=](int32_t col) { return x[col]; });
     if (live && g == 0) y[row] = alpha * acc;
 }
 
@@ -217,23 +198,13 @@ __global__ __launch_bounds__(256) void k_axpy(double* __restrict__ y, const doub
     y[i] = y[i] + p;
 }
 
-struct BcRhsArgs {
-    int n, dofs;
-    int32_t flag[MAX_BC];
-    int32_t mask[MAX_BC * MAX_DOFS];
-    double value[MAX_BC * MAX_DOFS];
-};
-
 // the right-hand-side half of k_dirichlet (assemble.hip): the rows are unit rows already
-__global__ void k_dirichlet_rhs(BcRhsArgs b, const int32_t* __restrict__ nflag, double* __restrict__ rhs, int32_t n_rows) {
+__global__ void k_dirichlet_rhs(BcTable b, const int32_t* __restrict__ nflag, double* __restrict__ rhs, int32_t n_rows) {
     const int32_t row = blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= n_rows) return;
     const int32_t node = row / b.dofs;
     const int comp = row - node * b.dofs;
-    const int32_t f = nflag[node];
-    int hit = -1;
-    for (int k = 0; k < b.n; ++k)
-        if (hit < 0 && b.flag[k] == f && b.mask[k * b.dofs + comp]) hit = k;
+    const int hit = bc_hit(b, nflag[node], comp);
     if (hit < 0) return;
     rhs[row] = b.value[hit * b.dofs + comp];
 }
@@ -243,15 +214,11 @@ int block_apply_device(fedd_ctx* c, const DevCsr& m, double alpha, const double*
     if (n == 0) return 0;
     ScopedTimer t(c, FEDD_T_BLOCK_APPLY);
     t.bytes(12.0 * (double)m.nnz + 4.0 * (double)(n + 1) + 16.0 * (double)n);
-    if (m.max_row_nnz <= 32) {
-        constexpr int G = 8;
-        hipLaunchKernelGGL(k_block_apply<G>, dim3((unsigned)(((int64_t)n * G + 255) / 256)), dim3(256), 0, c->stream,
-                           (const int32_t*)m.rowptr.p, (const int32_t*)m.colind.p, (const double*)m.val.p, d_x, n, alpha, d_y);
-    } else {
-        constexpr int G = 16;
-        hipLaunchKernelGGL(k_block_apply<G>, dim3((unsigned)(((int64_t)n * G + 255) / 256)), dim3(256), 0, c->stream,
-                           (const int32_t*)m.rowptr.p, (const int32_t*)m.colind.p, (const double*)m.val.p, d_x, n, alpha, d_y);
-    }
+    with_row_groups(m.max_row_nnz, n, [&](auto G, unsigned grid) {
+        hipLaunchKernelGGL(k_block_apply<decltype(G)::value>, dim3(grid), dim3(256), 0, c->stream, (const int32_t*)m.rowptr.p,
+                           (const int32_t*)m.colind.p, (const double*)m.val.p, d_x, n, alpha, d_y);
+        return 0;
+    });
     t.stop();
     FEDD_HIP(hipGetLastError());
     return 0;
@@ -274,15 +241,40 @@ int newmark_alloc(fedd_ctx* c) {
 }
 
 }  // namespace
+
+int system_adopt_pattern(fedd_ctx* c, const DevCsr& m, int dofs, int block_mode, size_t n_xcol, bool zero_other_len, uint64_t pattern_id) {
+    ScopedTimer t(c, FEDD_T_SYMBOLIC);
+    const size_t n = (size_t)m.n_rows;
+    const bool same_len = c->n_rows == m.n_rows && c->d_rhs.p && c->d_x.p && c->d_rhs.cap >= n && c->d_x.cap >= n;
+    c->have_pattern = false;
+    FEDD_TRY(c->d_rowptr.ensure(n + 1));
+    FEDD_TRY(c->d_colind.ensure((size_t)m.nnz));
+    FEDD_TRY(c->d_val.ensure((size_t)m.nnz));
+    FEDD_TRY(c->d_rhs.ensure(n));
+    FEDD_TRY(c->d_x.ensure(n));
+    FEDD_TRY(c->d_xcol.ensure(n_xcol));
+    FEDD_TRY(c->d_isdir.ensure(n));
+    FEDD_HIP(hipMemcpyAsync(c->d_rowptr.p, m.rowptr.p, (n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    FEDD_HIP(hipMemcpyAsync(c->d_colind.p, m.colind.p, (size_t)m.nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    if (zero_other_len && !same_len) {
+        FEDD_HIP(hipMemsetAsync(c->d_rhs.p, 0, n * sizeof(double), c->stream));
+        FEDD_HIP(hipMemsetAsync(c->d_x.p, 0, n * sizeof(double), c->stream));
+    }
+    c->dofs = dofs;
+    c->block_mode = block_mode;
+    c->n_rows = c->n_rows_ext = m.n_rows;
+    c->n_cols = m.n_cols;
+    c->nnz = c->nnz_ext = m.nnz;
+    c->max_row_nnz = m.max_row_nnz;
+    c->merged = false;
+    c->sys_pattern_id = pattern_id;
+    c->sys_pattern_gen = c->pattern_gen;
+    return 0;
+}
+
 }  // namespace fedd
 
 using namespace fedd;
-
-#define NEED_DEVICE(c)                                                                           \
-    FEDD_CHECK((c) && (c)->device >= 0,                                                          \
-               "this call needs a GPU context (fedd_ctx_create with device >= 0); there is no CPU fallback")
-#define ONE_RANK(c, who) FEDD_CHECK((c)->nranks == 1, "%s: one rank only (a context with %d ranks was given)", who, (c)->nranks)
-#define CHECK_SLOT(s) FEDD_CHECK((s) >= 0 && (s) < fedd::MAX_AUX, "matrix slot %d out of range", (s))
 
 // what a combine of these slots would pair: 0 = same pattern, 1 = DIAG into FULL; errors otherwise
 static int combine_pairing(fedd_ctx* c, int slot_m, int slot_a, int* kind) {
@@ -323,33 +315,8 @@ extern "C" int fedd_matrix_combine(fedd_ctx* c, int slot_m, double cm, int slot_
     const bool in_place = c->have_pattern && !c->merged && c->sys_pattern_id == A.pattern_id && c->sys_pattern_gen == c->pattern_gen &&
                           c->n_rows == A.n_rows && c->nnz == A.nnz;
     system_written(c, in_place ? SYS_VALUES : SYS_VALUES | SYS_PATTERN);
-    if (!in_place) {
-        ScopedTimer t(c, FEDD_T_SYMBOLIC);
-        c->have_pattern = false;
-        const bool same_len = c->n_rows == A.n_rows && c->d_rhs.p && c->d_x.p && c->d_rhs.cap >= n && c->d_x.cap >= n;
-        FEDD_TRY(c->d_rowptr.ensure(n + 1));
-        FEDD_TRY(c->d_colind.ensure((size_t)A.nnz));
-        FEDD_TRY(c->d_val.ensure((size_t)A.nnz));
-        FEDD_TRY(c->d_rhs.ensure(n));
-        FEDD_TRY(c->d_x.ensure(n));
-        FEDD_TRY(c->d_xcol.ensure((size_t)A.n_cols));
-        FEDD_TRY(c->d_isdir.ensure(n));
-        FEDD_HIP(hipMemcpyAsync(c->d_rowptr.p, A.rowptr.p, (n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
-        FEDD_HIP(hipMemcpyAsync(c->d_colind.p, A.colind.p, (size_t)A.nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
-        if (!same_len) {    // vectors of another length are not a right-hand side and a solution of this system
-            FEDD_HIP(hipMemsetAsync(c->d_rhs.p, 0, n * sizeof(double), c->stream));
-            FEDD_HIP(hipMemsetAsync(c->d_x.p, 0, n * sizeof(double), c->stream));
-        }
-        c->dofs = A.dofs;
-        c->block_mode = A.block_mode;
-        c->n_rows = c->n_rows_ext = A.n_rows;
-        c->n_cols = A.n_cols;
-        c->nnz = c->nnz_ext = A.nnz;
-        c->max_row_nnz = A.max_row_nnz;
-        c->merged = false;
-        c->sys_pattern_id = A.pattern_id;
-        c->sys_pattern_gen = c->pattern_gen;
-    }
+    // (vectors of another length are not a right-hand side and a solution of this system: they are zeroed)
+    if (!in_place) FEDD_TRY(system_adopt_pattern(c, A, A.dofs, A.block_mode, (size_t)A.n_cols, true, A.pattern_id));
     FEDD_HIP(hipMemsetAsync(c->d_isdir.p, 0, n * sizeof(int32_t), c->stream));
     {
         ScopedTimer t(c, FEDD_T_ASSEMBLE);
@@ -623,16 +590,7 @@ extern "C" int fedd_dirichlet_rhs(fedd_ctx* c, int n_bc, const int32_t* flags, c
     FEDD_CHECK(n_bc >= 0 && n_bc <= MAX_BC, "fedd_dirichlet_rhs: at most %d boundary conditions", MAX_BC);
     FEDD_CHECK(n_bc == 0 || (flags && values), "fedd_dirichlet_rhs: null array");
     FEDD_HIP(hipSetDevice(c->device));
-    BcRhsArgs b;
-    b.n = n_bc;
-    b.dofs = c->dofs;
-    for (int k = 0; k < n_bc; ++k) {
-        b.flag[k] = flags[k];
-        for (int d = 0; d < c->dofs; ++d) {
-            b.mask[k * c->dofs + d] = comp_mask ? comp_mask[k * c->dofs + d] : 1;
-            b.value[k * c->dofs + d] = values[k * c->dofs + d];
-        }
-    }
+    const BcTable b = bc_table_fill(c->dofs, n_bc, flags, comp_mask, values);
     ScopedTimer t(c, FEDD_T_DIRICHLET);
     if (c->n_rows > 0)
         hipLaunchKernelGGL(k_dirichlet_rhs, dim3((unsigned)((c->n_rows + 255) / 256)), dim3(256), 0, c->stream, b,
