@@ -17,6 +17,8 @@
 // blocked Gauss-Jordan sweep whose rank-64 updates run on the f64 matrix cores
 // (v_mfma_f64_16x16x4_f64) -- the one genuinely dense contraction of the solver.
 // Apply: cell-wise restriction (fixed summation order), dense K0^-1 r0, prolongation.
+// The GDSW / RGDSW spaces on the same lattice follow ("GDSW coarse space" below).  Both setups run through one host frame:
+// make_lattice, group_nodes_by_cell, coarse_mask, invert_k0; gdsw_setup is five named steps between them.
 #include "fedd_internal.hpp"
 #include <algorithm>
 #include <climits>
@@ -469,6 +471,37 @@ __device__ __forceinline__ void gd_coarse_coords(const CoarseGeom& cg, int32_t i
         }
 }
 
+// home cell h = floor(e / 2) of the rows of a node whose entity has the id `id`
+template <int DIM>
+__device__ __forceinline__ void gd_home_cell(const CoarseGeom& cg, int32_t id, int h[3]) {
+    int e[3];
+    gd_entity_coords<DIM>(cg, id, e);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) h[d] = 0;
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) h[d] = e[d] >> 1;
+}
+
+// The cells that see entity e, those with |2 h_d - e_d| <= 1, counted by a = 0 .. 2^DIM - 1: e_d even -> h_d = e_d / 2 (bit d of
+// a must be 0), odd -> (e_d - 1) / 2 + bit d.  false: a names no cell of the lattice.
+template <int DIM>
+__device__ __forceinline__ bool gd_cell_seeing(const CoarseGeom& cg, const int e[3], int a, int h[3]) {
+    bool ok = true;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) h[d] = 0;
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) {
+        const int bit = (a >> d) & 1;
+        if (e[d] & 1) h[d] = (e[d] - 1) / 2 + bit;
+        else {
+            h[d] = e[d] / 2;
+            ok = ok && bit == 0;
+        }
+        ok = ok && h[d] >= 0 && h[d] < cg.g[d];
+    }
+    return ok;
+}
+
 // entity and home cell of every owned node from the cells of its incident elements
 template <int DIM>
 __global__ void k_gd_node_entity(CoarseGeom cg, const int32_t* __restrict__ conn, int nen, const double* __restrict__ xyz,
@@ -669,6 +702,8 @@ __global__ void k_gd_phi_init(CoarseGeom cg, GdAct act, const int32_t* __restric
     imask[r] = cls < 0 ? mask[r] : 0.0;
 }
 
+// The extension solves take NR columns at a time on stacked vectors X[r * NR + j] (multi.hip): NR = 1 a column by itself,
+// NR = MULTI_NR sixteen as one system.
 // v = one column of Phi on the interface rows, 0 on the interior rows
 __global__ void k_gd_gamma_col(const double* __restrict__ phi_col, const double* __restrict__ imask, int64_t n_rows,
                                const double* __restrict__ mask, double* __restrict__ v) {
@@ -677,20 +712,7 @@ __global__ void k_gd_gamma_col(const double* __restrict__ phi_col, const double*
     v[r] = (imask[r] == 0.0 && mask[r] != 0.0) ? phi_col[r] : 0.0;
 }
 
-// b = -imask o w
-__global__ void k_gd_rhs(const double* __restrict__ imask, const double* __restrict__ w, int64_t n_rows, double* __restrict__ b) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < n_rows) b[r] = imask[r] != 0.0 ? -w[r] : 0.0;
-}
-
-// interior rows: Phi column = x
-__global__ void k_gd_store(const double* __restrict__ imask, const double* __restrict__ x, int64_t n_rows, double* __restrict__ phi_col) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < n_rows && imask[r] != 0.0) phi_col[r] = x[r];
-}
-
-// ... the same three steps for MULTI_NR columns at a time on stacked vectors X[r * MULTI_NR + j] (multi.hip): column j is slot
-// slot0 + j, columns j >= nb are zero
+// ... and MULTI_NR of them: column j is slot slot0 + j, columns j >= nb are zero (no template: its arguments cost k_gd_gamma_col 8 SGPRs)
 __global__ void k_gd_gamma_cols(const double* __restrict__ phiT, int64_t ldp, int slot0, int nb, const double* __restrict__ imask,
                                 int64_t n_rows, const double* __restrict__ mask, double* __restrict__ V) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -700,9 +722,17 @@ __global__ void k_gd_gamma_cols(const double* __restrict__ phiT, int64_t ldp, in
     V[t] = (j < nb && imask[r] == 0.0 && mask[r] != 0.0) ? phiT[(int64_t)(slot0 + j) * ldp + r] : 0.0;
 }
 
-__global__ void k_gd_rhs_cols(const double* __restrict__ imask, const double* __restrict__ W, int64_t n_rows, double* __restrict__ B) {
+// B = -imask o W
+template <int NR>
+__global__ void k_gd_rhs(const double* __restrict__ imask, const double* __restrict__ W, int64_t n_rows, double* __restrict__ B) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < n_rows * MULTI_NR) B[t] = imask[t / MULTI_NR] != 0.0 ? -W[t] : 0.0;
+    if (t < n_rows * NR) B[t] = imask[t / NR] != 0.0 ? -W[t] : 0.0;
+}
+
+// interior rows: Phi column = x (one column; the stacked k_gd_store_cols below transposes through LDS)
+__global__ void k_gd_store(const double* __restrict__ imask, const double* __restrict__ x, int64_t n_rows, double* __restrict__ phi_col) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < n_rows && imask[r] != 0.0) phi_col[r] = x[r];
 }
 
 // Sixteen stacked right-hand sides are solved as ONE system, so the solver's tolerance applies to the Frobenius norm of the
@@ -812,7 +842,8 @@ __global__ __launch_bounds__(256) void k_gd_restrict_cells(const int32_t* __rest
     if (tid < CH && s0 + tid < nsd) part[(int64_t)cell * nsd + s0 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
 }
 
-// restriction, step 2: r0[(E, k)] = sum over the cells that see E (fixed order) of their class(E) partial sum
+// restriction, step 2: r0[(E, k)] = sum over the cells that see E (fixed order) of their class(E) partial sum.  (Runs in every
+// apply; no template with k_gd_restrict_ent_cols below: the chunk loop and column index cost it 4 VGPRs, 8 SGPRs in 2D)
 template <int DIM>
 __global__ void k_gd_restrict_ent(CoarseGeom cg, GdAct act, int nns, int64_t n_ent, const double* __restrict__ part,
                                   double* __restrict__ r0) {
@@ -825,21 +856,10 @@ __global__ void k_gd_restrict_ent(CoarseGeom cg, GdAct act, int nns, int64_t n_e
     const int cls = gd_class<DIM>(e);
     double sum = 0.0;
     if (cls >= 0 && act.idx[cls] >= 0) {
-        // cells h with |2 h_d - e_d| <= 1: e_d even -> h_d = e_d / 2; odd -> (e_d - 1) / 2 and (e_d + 1) / 2
-        for (int a = 0; a < (1 << DIM); ++a) {
-            int h[3] = {0, 0, 0};
-            bool ok = true;
 #pragma unroll
-            for (int d = 0; d < DIM; ++d) {
-                const int bit = (a >> d) & 1;
-                if (e[d] & 1) h[d] = (e[d] - 1) / 2 + bit;
-                else {
-                    h[d] = e[d] / 2;
-                    ok = ok && bit == 0;
-                }
-                ok = ok && h[d] >= 0 && h[d] < cg.g[d];
-            }
-            if (ok) sum += part[(int64_t)cell_of<DIM>(cg, h) * (act.n * nns) + act.idx[cls] * nns + k];
+        for (int a = 0; a < (1 << DIM); ++a) {
+            int h[3];
+            if (gd_cell_seeing<DIM>(cg, e, a, h)) sum += part[(int64_t)cell_of<DIM>(cg, h) * (act.n * nns) + act.idx[cls] * nns + k];
         }
     }
     r0[t] = sum;
@@ -852,11 +872,8 @@ __global__ void k_gd_prolong(CoarseGeom cg, GdAct act, const int32_t* __restrict
                              const double* __restrict__ z0, double* __restrict__ z) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_rows) return;
-    const int32_t node = (int32_t)(r / dofs);
-    int e[3], h[3] = {0, 0, 0};
-    gd_entity_coords<DIM>(cg, ent[node], e);
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) h[d] = e[d] >> 1;
+    int h[3];
+    gd_home_cell<DIM>(cg, ent[r / dofs], h);
     double sum = 0.0;
     for (int ai = 0; ai < act.n; ++ai) {
         int ee[3] = {0, 0, 0};
@@ -869,8 +886,6 @@ __global__ void k_gd_prolong(CoarseGeom cg, GdAct act, const int32_t* __restrict
     else z[r] = sum * mask[r];
 }
 
-struct GdCol { int c[3]; };
-
 // Colouring of the coarse dofs for the column-wise Galerkin product: entities whose coordinates agree modulo the period
 // in every direction have supports that no matrix row couples, and every entity couples with at most one of them.
 // GDSW: entities couple within two steps of the doubled lattice -> period 5.  RGDSW: only the coarse nodes (odd
@@ -878,81 +893,47 @@ struct GdCol { int c[3]; };
 // three coarse nodes apart: period 6, and only the odd residues occur: 3^dim colours instead of 5^dim.
 __host__ __device__ __forceinline__ int gd_period(const CoarseGeom& cg) { return cg.reduced ? 6 : 5; }
 
-// v = Phi z0 for z0 = the sum of the unit vectors (E, k) over the interface entities E of one colour (e_d = col_d mod 5):
-// a cell sees three consecutive entity coordinates per direction, so at most one entity of the colour, i.e. a row reads at
-// most ONE entry of Phi (the generic prolongation read all of them, 375 times per setup)
-template <int DIM>
-__global__ void k_gd_prolong_colour(CoarseGeom cg, GdAct act, const int32_t* __restrict__ ent, int dofs, int nns, int64_t n_rows, int64_t ldp,
-                                    const double* __restrict__ phiT, const double* __restrict__ mask, int k, GdCol col,
-                                    double* __restrict__ v) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_rows) return;
-    const int32_t node = (int32_t)(r / dofs);
-    int e[3], h[3] = {0, 0, 0};
-    gd_entity_coords<DIM>(cg, ent[node], e);
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) h[d] = e[d] >> 1;
-    double val = 0.0;
-    for (int ai = 0; ai < act.n; ++ai) {
-        int ee[3] = {0, 0, 0};
-        if (!gd_entity_of<DIM>(cg, h, act.cls[ai], ee)) continue;
-        bool on = gd_coarse_id<DIM>(cg, ee) >= 0;
-#pragma unroll
-        for (int d = 0; d < DIM; ++d) on = on && (ee[d] % gd_period(cg)) == col.c[d];
-        if (on) val = phiT[(int64_t)(ai * nns + k) * ldp + r];
-    }
-    v[r] = val * mask[r];
-}
+// ---- the Galerkin product NR columns at a time (stacked vectors X[r * NR + j], multi.hip; NR = 1: one column per sweep) ----
+template <int NR>
+struct GdCols {
+    int nb;             // columns in use, the others are zero
+    int8_t c[NR][3];    // colour of column j
+    int8_t k[NR];       // function (component) of column j
+};
 
-// K0[(E, a)][(E', k)] = r0[(E, a)] with E' the entity of the colour within two lattice steps of E
+// the entity ep of colour col within two lattice steps of e; false: it lies outside the lattice
 template <int DIM>
-__global__ void k_gd_scatter_col(CoarseGeom cg, int nns, int64_t n_ent, int k, GdCol col, const double* __restrict__ r0,
-                                 double* __restrict__ K, int64_t ld) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_ent * nns) return;
-    const int32_t E = (int32_t)(t / nns);
-    int e[3], ep[3] = {0, 0, 0};
-    gd_coarse_coords<DIM>(cg, E, e);
-    if (gd_class<DIM>(e) < 0) return;
+__device__ __forceinline__ bool gd_colour_near(const CoarseGeom& cg, const int e[3], const int8_t col[3], int ep[3]) {
     bool ok = true;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) ep[d] = 0;
 #pragma unroll
     for (int d = 0; d < DIM; ++d) {
         const int P = gd_period(cg);
-        int dlt = (col.c[d] - e[d] % P + P) % P;   // 0 .. P - 1
+        int dlt = (col[d] - e[d] % P + P) % P;     // 0 .. P - 1
         if (dlt > P / 2) dlt -= P;                 // GDSW -2 .. 2; RGDSW (odd coordinates, odd colours) -2, 0, 2
         ep[d] = e[d] + dlt;
         ok = ok && ep[d] >= 0 && ep[d] <= 2 * cg.g[d] - 2;
     }
-    if (!ok || gd_class<DIM>(ep) < 0) return;
-    const int64_t Ep = gd_coarse_id<DIM>(cg, ep);
-    if (Ep < 0) return;
-    K[t * ld + Ep * nns + k] = r0[t];
+    return ok;
 }
 
-// ---- the Galerkin product MULTI_NR columns at a time (stacked vectors X[r * MULTI_NR + j], multi.hip) ----
-struct GdCols {
-    int nb;
-    int8_t c[MULTI_NR][3];   // colour of column j
-    int8_t k[MULTI_NR];      // component of column j
-};
-
-// V[r][j] = the prolongation of the unit vectors (E, k_j) over the entities E of colour j (k_gd_prolong_colour for each column).
+// V[r][j] = Phi z0 for z0 = the sum of the unit vectors (E, k_j) over the interface entities E of column j's colour (e_d = col_d
+// mod the period): a cell sees three consecutive entity coordinates per direction, so at most one entity of the colour, i.e. a
+// row reads at most ONE entry of Phi per column (the generic prolongation read all of them, 375 times per setup).
 // A thread per row: the entities its home cell sees are worked out once, each column then only compares colours (a thread per
 // (row, column) repeated the entity arithmetic sixteen times: 1.97 ms per launch with the 26 classes of GDSW).
-template <int DIM>
+template <int DIM, int NR>
 __global__ void k_gd_prolong_colours(CoarseGeom cg, GdAct act, const int32_t* __restrict__ ent, int dofs, int nns, int64_t n_rows, int64_t ldp,
-                                     const double* __restrict__ phiT, const double* __restrict__ mask, GdCols cols,
+                                     const double* __restrict__ phiT, const double* __restrict__ mask, GdCols<NR> cols,
                                      double* __restrict__ V) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_rows) return;
-    const int32_t node = (int32_t)(r / dofs);
-    int e[3], h[3] = {0, 0, 0};
-    gd_entity_coords<DIM>(cg, ent[node], e);
+    int h[3];
+    gd_home_cell<DIM>(cg, ent[r / dofs], h);
+    int sel[NR];      // active class whose entity has column j's colour (a cell sees at most one), -1: none
 #pragma unroll
-    for (int d = 0; d < DIM; ++d) h[d] = e[d] >> 1;
-    int sel[MULTI_NR];      // active class whose entity has column j's colour (a cell sees at most one), -1: none
-#pragma unroll
-    for (int j = 0; j < MULTI_NR; ++j) sel[j] = -1;
+    for (int j = 0; j < NR; ++j) sel[j] = -1;
     const int P = gd_period(cg);
     for (int ai = 0; ai < act.n; ++ai) {
         int ee[3] = {0, 0, 0};
@@ -962,7 +943,7 @@ __global__ void k_gd_prolong_colours(CoarseGeom cg, GdAct act, const int32_t* __
 #pragma unroll
         for (int d = 0; d < DIM; ++d) res[d] = ee[d] % P;
 #pragma unroll
-        for (int j = 0; j < MULTI_NR; ++j) {
+        for (int j = 0; j < NR; ++j) {
             bool on = true;
 #pragma unroll
             for (int d = 0; d < DIM; ++d) on = on && res[d] == cols.c[j][d];
@@ -971,10 +952,10 @@ __global__ void k_gd_prolong_colours(CoarseGeom cg, GdAct act, const int32_t* __
     }
     const double m = mask[r];
 #pragma unroll
-    for (int j = 0; j < MULTI_NR; ++j) {
+    for (int j = 0; j < NR; ++j) {
         double val = 0.0;
         if (j < cols.nb && sel[j] >= 0) val = phiT[(int64_t)(sel[j] * nns + cols.k[j]) * ldp + r] * m;
-        V[r * MULTI_NR + j] = val;
+        V[r * NR + j] = val;
     }
 }
 
@@ -1031,20 +1012,10 @@ __global__ void k_gd_restrict_ent_cols(CoarseGeom cg, GdAct act, int nns, int64_
     double sum = 0.0;
     if (cls >= 0 && act.idx[cls] >= 0) {
         const int nsd = act.n * nns;
-        for (int a = 0; a < (1 << DIM); ++a) {
-            int h[3] = {0, 0, 0};
-            bool ok = true;
 #pragma unroll
-            for (int d = 0; d < DIM; ++d) {
-                const int bit = (a >> d) & 1;
-                if (e[d] & 1) h[d] = (e[d] - 1) / 2 + bit;
-                else {
-                    h[d] = e[d] / 2;
-                    ok = ok && bit == 0;
-                }
-                ok = ok && h[d] >= 0 && h[d] < cg.g[d];
-            }
-            if (ok) {
+        for (int a = 0; a < (1 << DIM); ++a) {
+            int h[3];
+            if (gd_cell_seeing<DIM>(cg, e, a, h)) {
                 const int64_t cell = cell_of<DIM>(cg, h);
                 for (int ch = 0; ch < nch; ++ch) sum += part[((cell * nch + ch) * nsd + act.idx[cls] * nns + k) * MULTI_NR + j];
             }
@@ -1054,28 +1025,19 @@ __global__ void k_gd_restrict_ent_cols(CoarseGeom cg, GdAct act, int nns, int64_
 }
 
 // K0[(E, a)][(E', k_j)] = r0[(E, a)][j] with E' the entity of column j's colour within two lattice steps of E
-template <int DIM>
-__global__ void k_gd_scatter_cols(CoarseGeom cg, int nns, int64_t n_ent, GdCols cols, const double* __restrict__ r0,
-                                  double* __restrict__ K, int64_t ld) {
+template <int DIM, int NR>
+__global__ void k_gd_scatter(CoarseGeom cg, int nns, int64_t n_ent, GdCols<NR> cols, const double* __restrict__ r0,
+                             double* __restrict__ K, int64_t ld) {
     const int64_t tt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tt >= n_ent * nns * MULTI_NR) return;
-    const int j = (int)(tt % MULTI_NR);
-    if (j >= cols.nb) return;
-    const int64_t t = tt / MULTI_NR;
+    if (tt >= n_ent * nns * NR) return;
+    const int j = (int)(tt % NR);
+    if (NR > 1 && j >= cols.nb) return;     // (one column: nb = 1)
+    const int64_t t = tt / NR;
     const int32_t E = (int32_t)(t / nns);
-    int e[3], ep[3] = {0, 0, 0};
+    int e[3], ep[3];
     gd_coarse_coords<DIM>(cg, E, e);
     if (gd_class<DIM>(e) < 0) return;
-    bool ok = true;
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) {
-        const int P = gd_period(cg);
-        int dlt = (cols.c[j][d] - e[d] % P + P) % P;
-        if (dlt > P / 2) dlt -= P;
-        ep[d] = e[d] + dlt;
-        ok = ok && ep[d] >= 0 && ep[d] <= 2 * cg.g[d] - 2;
-    }
-    if (!ok || gd_class<DIM>(ep) < 0) return;
+    if (!gd_colour_near<DIM>(cg, e, cols.c[j], ep) || gd_class<DIM>(ep) < 0) return;
     const int64_t Ep = gd_coarse_id<DIM>(cg, ep);
     if (Ep < 0) return;
     K[t * ld + Ep * nns + cols.k[j]] = r0[tt];
@@ -1203,7 +1165,10 @@ __global__ void k_prolong_add(CoarseGeom cg, int dofs, int64_t n_rows, const dou
         if (dim == 3) { KERNEL(3, __VA_ARGS__); }    \
         else { KERNEL(2, __VA_ARGS__); }             \
     } while (0)
-
+// the plain case: KERNEL<dim> (LAUNCH_DX: KERNEL<dim, X>) on GRID workgroups of 256 threads, COARSE_DIM(LAUNCH_D, kernel, grid, arguments);
+// like COARSE_DIM's `dim`, they take the context `c` from the scope they are used in (the host code of this file, to its end)
+#define LAUNCH_D(D, KERNEL, GRID, ...) hipLaunchKernelGGL((KERNEL<D>), GRID, dim3(256), 0, c->stream, __VA_ARGS__)
+#define LAUNCH_DX(D, KERNEL, X, GRID, ...) hipLaunchKernelGGL((KERNEL<D, X>), GRID, dim3(256), 0, c->stream, __VA_ARGS__)
 
 // owned nodes grouped by cell, in node order within a cell: a stable radix sort of (cell, node) over the bits a cell id takes
 // (the in-tree radix sort of scan.hip, 8 bits per pass; rounds 2-3: rocPRIM through hipCUB; round 1: a bit-by-bit split, three
@@ -1216,6 +1181,103 @@ static int sort_nodes_by_cell(fedd_ctx* c, int32_t n_own, int64_t ncell, int* cu
     int32_t* keys[2] = {c->d_co_key[0].p, c->d_co_key[1].p};
     int32_t* vals[2] = {c->d_co_val[0].p, c->d_co_val[1].p};
     return radix_sort_pairs_i32(c, keys, vals, n_own, bits, cur_out);
+}
+
+// ---- the frame of both setups (Q1 lattice, GDSW family): lattice, node grouping, Dirichlet mask, inversion of K0 ----
+struct Lattice {
+    CoarseGeom cg;
+    int64_t ncell = 1, n_ent = 1;   // cells; the coarse index space (Q1: lattice points, GDSW: entities, RGDSW: coarse nodes)
+    int64_t n0 = 0, ld = 0;         // coarse dofs = n_ent x nns, and their number padded to the block size of the inversion
+    void record(fedd_ctx* c) const { c->co_geom = cg, c->co_ncell = ncell, c->co_nlat = n_ent, c->co_n0 = n0, c->co_ld = ld; }   // after the n0 check
+};
+
+// The lattice over the box [lo, hi]: g_d = max(1, floor(L_d / H + 0.5)), H = (V / target)^(1/dim); ents(g) = what the coarse space
+// counts per direction with g cells, nns functions on each.  The caller checks n0, then records it (Lattice::record).
+template <class Ents>
+static Lattice make_lattice(fedd_ctx* c, const double lo[3], const double hi[3], double target, bool reduced, int nns, Ents ents) {
+    const int dim = c->dim;
+    Lattice lt;
+    CoarseGeom& cg = lt.cg;
+    cg.dim = dim;
+    cg.reduced = reduced ? 1 : 0;
+    double V = 1.0;
+    for (int d = 0; d < dim; ++d) V *= (hi[d] - lo[d] > 0 ? hi[d] - lo[d] : 1.0);
+    const double H = std::pow(V / target, 1.0 / dim);
+    for (int d = 0; d < dim; ++d) {     // (the directions beyond dim keep CoarseGeom's defaults: one cell of length 1 at 0)
+        const double Ld = hi[d] - lo[d];
+        cg.lo[d] = lo[d];
+        cg.L[d] = Ld > 0 ? Ld : 1.0;
+        int g = (int)std::floor(cg.L[d] / H + 0.5);
+        if (g < 1 || !(Ld > 0)) g = 1;
+        cg.g[d] = g;
+        cg.np[d] = g + 1;
+        lt.ncell *= g;
+        lt.n_ent *= ents(g);
+    }
+    lt.n0 = lt.n_ent * nns;
+    lt.ld = (lt.n0 + NB - 1) / NB * NB;
+    return lt;
+}
+
+// Owned nodes grouped by cell (stable radix split: node order within a cell): key(grid) launches the coarse space's kernel that
+// writes (cell, node) of every owned node into d_co_key[0], d_co_val[0]; then cell_ptr, and the nodes of a cell in d_co_val[co_sorted]
+template <class KeyKernel>
+static int group_nodes_by_cell(fedd_ctx* c, int64_t ncell, KeyKernel key) {
+    const int32_t n_own = (int32_t)c->n_own;
+    const dim3 blk(256), gn((n_own + 255) / 256);
+    for (int q = 0; q < 2; ++q) {
+        FEDD_TRY(c->d_co_key[q].ensure((size_t)n_own));
+        FEDD_TRY(c->d_co_val[q].ensure((size_t)n_own));
+    }
+    FEDD_TRY(c->d_co_cell_ptr.ensure((size_t)ncell + 1));
+    FEDD_TRY(c->d_itmp0.ensure((size_t)n_own));
+    FEDD_TRY(key(gn));
+    int cur = 0;
+    FEDD_TRY(sort_nodes_by_cell(c, n_own, ncell, &cur));
+    c->co_sorted = cur;
+    hipLaunchKernelGGL(k_cell_bounds, gn, blk, 0, c->stream, (const int32_t*)c->d_co_key[cur].p, n_own, (int32_t)ncell,
+                       c->d_co_cell_ptr.p);
+    return 0;
+}
+
+// Dirichlet mask over the column space (ghost dofs through the halo), and the setup's three device flags reset:
+// d_bad[0] non-neighbour coupling (Q1), [1] K0 not definite, [2] free dofs
+static int coarse_mask(fedd_ctx* c, int32_t** d_bad_out) {
+    FEDD_TRY(c->d_co_mask.ensure((size_t)c->n_cols));
+    FEDD_TRY(c->d_flags.ensure(16));
+    int32_t* d_bad = c->d_flags.p + 3;
+    FEDD_HIP(hipMemsetAsync(d_bad, 0, 3 * sizeof(int32_t), c->stream));
+    hipLaunchKernelGGL(k_mask, dim3((unsigned)((c->n_rows + 255) / 256)), dim3(256), 0, c->stream, (const int32_t*)c->d_isdir.p,
+                       c->n_rows, c->d_co_mask.p, d_bad + 2);
+    if (c->n_cols != c->n_rows || !c->halo.peers.empty()) FEDD_TRY(halo_import(c, c->d_co_mask.p, c->dofs));
+    *d_bad_out = d_bad;
+    return 0;
+}
+
+struct K0Flags {
+    bool coupling = false, indefinite = false;   // d_bad[0], d_bad[1] on any rank
+    double n_free = 0.0;                         // free dofs of all ranks
+};
+
+// K0 <- K0^-1: the diagonal fix, the matrix-core sweep of dense.hip, then the flags read back once and made to agree across the
+// ranks (every rank must take the same decision; the free dofs add up).  What a flag means to its coarse space the caller says.
+static int invert_k0(fedd_ctx* c, const Lattice& lt, int32_t* d_bad, K0Flags* out) {
+    const int64_t n0 = lt.n0, ld = lt.ld;
+    hipLaunchKernelGGL(k_fix_diag, dim3((unsigned)((ld + 3) / 4)), dim3(256), 0, c->stream, c->d_co_K.p, ld, n0);
+    FEDD_TRY(dense_invert_batched(c, c->d_co_K.p, ld, 1, ld * ld, nullptr, (int)(ld / NB), 1, d_bad + 1));
+    int32_t bad[3] = {0, 0, 0};
+    FEDD_HIP(hipMemcpyAsync(bad, d_bad, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    FEDD_HIP(hipStreamSynchronize(c->stream));
+    double hb[3] = {(double)bad[0], (double)bad[1], (double)bad[2]};
+    if (c->nranks > 1) {
+        FEDD_TRY(c->d_co_r0.ensure(std::max<size_t>(3, c->d_co_r0.cap)));
+        FEDD_HIP(hipMemcpyAsync(c->d_co_r0.p, hb, sizeof(hb), hipMemcpyHostToDevice, c->stream));
+        FEDD_TRY(allreduce_sum(c, c->d_co_r0.p, 3));
+        FEDD_HIP(hipMemcpyAsync(hb, c->d_co_r0.p, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
+        FEDD_HIP(hipStreamSynchronize(c->stream));
+    }
+    *out = K0Flags{hb[0] != 0.0, hb[1] != 0.0, hb[2]};
+    return 0;
 }
 
 // ---- GDSW: setup and application (kernels and definitions: "GDSW coarse space" above) ----
@@ -1253,28 +1315,48 @@ static int gdsw_restrict(fedd_ctx* c, const double* d_rv, double* d_r0) {
         hipLaunchKernelGGL(k_gd_restrict_cells, dim3((unsigned)ncell, (unsigned)((nsa + 7) / 8)), dim3(256), 0, c->stream,
                        (const int32_t*)c->d_co_cell_ptr.p, (const int32_t*)c->d_co_val[c->co_sorted].p, dofs, nsa, gdsw_ldp(c),
                        (const double*)c->d_gd_phi.p, d_rv, c->d_co_part.p);
-    const dim3 ge((unsigned)((n_ent * nns + 255) / 256)), blk(256);
-    if (dim == 3) hipLaunchKernelGGL(k_gd_restrict_ent<3>, ge, blk, 0, c->stream, cg, act, nns, n_ent, (const double*)c->d_co_part.p, d_r0);
-    else hipLaunchKernelGGL(k_gd_restrict_ent<2>, ge, blk, 0, c->stream, cg, act, nns, n_ent, (const double*)c->d_co_part.p, d_r0);
+    COARSE_DIM(LAUNCH_D, k_gd_restrict_ent, dim3((unsigned)((n_ent * nns + 255) / 256)), cg, act, nns, n_ent,
+               (const double*)c->d_co_part.p, d_r0);
     return 0;
 }
 
-template <bool ADD>
-static int gdsw_prolong(fedd_ctx* c, const double* d_z0, double* d_z) {
+static int gdsw_prolong_add(fedd_ctx* c, const double* d_z0, double* d_z) {
+    const int dim = c->dim;
     const CoarseGeom cg = c->co_geom;
     const GdAct act = gdsw_active(cg);
-    const dim3 gr((unsigned)((c->n_rows + 255) / 256)), blk(256);
-    if (c->dim == 3)
-        hipLaunchKernelGGL((k_gd_prolong<3, ADD>), gr, blk, 0, c->stream, cg, act, (const int32_t*)c->d_gd_ent.p, c->dofs, c->co_nns, c->n_rows,
-                           gdsw_ldp(c), (const double*)c->d_gd_phi.p, (const double*)c->d_co_mask.p, d_z0, d_z);
-    else
-        hipLaunchKernelGGL((k_gd_prolong<2, ADD>), gr, blk, 0, c->stream, cg, act, (const int32_t*)c->d_gd_ent.p, c->dofs, c->co_nns, c->n_rows,
-                           gdsw_ldp(c), (const double*)c->d_gd_phi.p, (const double*)c->d_co_mask.p, d_z0, d_z);
+    COARSE_DIM(LAUNCH_DX, k_gd_prolong, true, dim3((unsigned)((c->n_rows + 255) / 256)), cg, act, (const int32_t*)c->d_gd_ent.p, c->dofs,
+               c->co_nns, c->n_rows, gdsw_ldp(c), (const double*)c->d_gd_phi.p, (const double*)c->d_co_mask.p, d_z0, d_z);
     return 0;
 }
 
-static int gdsw_setup(fedd_ctx* c) {
-    ScopedTimer timer(c, FEDD_T_COARSE_SETUP);
+// ---- GDSW setup: geometry, interface values of Phi, extensions, Galerkin product, inversion ----
+// the launches of an inner solve belong to the coarse setup (whose timer is open), not to the per-iteration classes of the outer
+// solve: their timers are suspended while one of these lives (the tables double-counted them)
+struct TimersSuspended {
+    fedd_ctx* c;  const bool was;
+    explicit TimersSuspended(fedd_ctx* ctx) : c(ctx), was(ctx->timing) { c->timing = false; }
+    ~TimersSuspended() { c->timing = was; }
+};
+
+struct GdStack {       // d_gd_stack: four stacked vectors X[r * MULTI_NR + j]
+    double *V, *W, *B, *X;      // V [ncs]: column space, the ghost rows behind the owned ones; W, B, X [ns]: owned rows
+};
+
+struct GdswSetup {     // what the steps hand on
+    Lattice lt;
+    GdAct act;
+    bool reduced = false, rot = false, stacked = false;
+    int nns = 0, nsd = 0;       // functions per entity; active slots (compact) = columns of Phi
+    int64_t ldp = 0, nc = 0;    // leading dimension of Phi; length of a column-space vector (ghost tail, rounded up)
+    double ext_tol = 0.0;
+    int32_t* d_bad = nullptr;
+    double *v = nullptr, *w = nullptr, *b = nullptr, *x = nullptr;   // d_gd_tmp: v [nc] column-space vector (ghost tail), w, b, x [n_rows]
+    GdStack st{};               // filled by the stacked extensions
+};
+
+// 1. the coarse decomposition (cells of a regular lattice), entity and home cell of every owned node, the nodes grouped by home
+// cell, the Dirichlet mask
+static int gdsw_geometry(fedd_ctx* c, GdswSetup& S) {
     const int dim = c->dim, dofs = c->dofs;
     const int32_t n_own = (int32_t)c->n_own;
     const int64_t n_rows = c->n_rows;
@@ -1306,255 +1388,241 @@ static int gdsw_setup(fedd_ctx* c) {
             target = std::min(std::pow((double)gmax, (double)dim), std::max(1.0, std::floor(n_global / 1000.0)));
         }
     }
-    CoarseGeom cg;
-    cg.dim = dim;
-    cg.reduced = reduced ? 1 : 0;
-    double V = 1.0;
-    for (int d = 0; d < dim; ++d) V *= (hi[d] - lo[d] > 0 ? hi[d] - lo[d] : 1.0);
-    const double H = std::pow(V / target, 1.0 / dim);
-    int64_t ncell = 1, n_ent = 1;
-    for (int d = 0; d < 3; ++d) {
-        cg.g[d] = 1;
-        cg.np[d] = 1;
-        cg.lo[d] = 0.0;
-        cg.L[d] = 1.0;
-        if (d >= dim) continue;
-        const double Ld = hi[d] - lo[d];
-        cg.lo[d] = lo[d];
-        cg.L[d] = Ld > 0 ? Ld : 1.0;
-        int g = (int)std::floor(cg.L[d] / H + 0.5);
-        if (g < 1 || !(Ld > 0)) g = 1;
-        cg.g[d] = g;
-        cg.np[d] = g + 1;
-        ncell *= g;
-        n_ent *= reduced ? (g >= 2 ? g - 1 : 1) : 2 * g - 1;
-    }
-    const int64_t n0 = n_ent * nns;
-    FEDD_CHECK(n0 <= COARSE_MAX_DOFS, "GDSW setup: %lld coarse dofs ((2g - 1)^dim entities, RGDSW: (g - 1)^dim coarse nodes, x %d), the dense coarse solver takes at "
-               "most %d; lower fedd_schwarz_set_coarse (now %g cells)", (long long)n0, nns, COARSE_MAX_DOFS, target);
-    const int64_t ld = (n0 + NB - 1) / NB * NB;
-    c->co_geom = cg;
-    c->co_ncell = ncell;
-    c->co_nlat = n_ent;     // (the coarse index space: entities of the doubled lattice)
-    c->co_n0 = n0;
-    c->co_ld = ld;
-    const GdAct act = gdsw_active(cg);
-    const int nsd = act.n * nns;            // active slots (compact)
-    const int64_t ldp = gdsw_ldp(c);
-    const dim3 blk(256), gn((n_own + 255) / 256), gr((unsigned)((n_rows + 255) / 256));
+    // (the coarse index space: entities of the doubled lattice, RGDSW: the coarse nodes)
+    S.lt = make_lattice(c, lo, hi, target, reduced, nns, [reduced](int g) { return reduced ? (g >= 2 ? g - 1 : 1) : 2 * g - 1; });
+    FEDD_CHECK(S.lt.n0 <= COARSE_MAX_DOFS, "GDSW setup: %lld coarse dofs ((2g - 1)^dim entities, RGDSW: (g - 1)^dim coarse nodes, x %d), the dense coarse solver takes at "
+               "most %d; lower fedd_schwarz_set_coarse (now %g cells)", (long long)S.lt.n0, nns, COARSE_MAX_DOFS, target);
+    S.lt.record(c);
+    const CoarseGeom cg = S.lt.cg;
+    S.reduced = reduced, S.rot = rot, S.nns = nns;
+    S.act = gdsw_active(cg);
+    S.nsd = S.act.n * nns;
+    S.ldp = gdsw_ldp(c);
     // ---- entity and home cell of every owned node; nodes grouped by home cell (stable radix split) ----
-    for (int q = 0; q < 2; ++q) {
-        FEDD_TRY(c->d_co_key[q].ensure((size_t)n_own));
-        FEDD_TRY(c->d_co_val[q].ensure((size_t)n_own));
-    }
-    FEDD_TRY(c->d_co_cell_ptr.ensure((size_t)ncell + 1));
-    FEDD_TRY(c->d_itmp0.ensure((size_t)n_own));
-    FEDD_TRY(c->d_gd_ent.ensure((size_t)n_own));
-    if (dim == 3)
-        hipLaunchKernelGGL(k_gd_node_entity<3>, gn, blk, 0, c->stream, cg, (const int32_t*)c->d_conn.p, c->nen, (const double*)c->d_xyz.p,
-                           (const int32_t*)c->d_n2e_ptr.p, (const int32_t*)c->d_n2e.p, n_own, c->d_gd_ent.p, c->d_co_key[0].p, c->d_co_val[0].p);
-    else
-        hipLaunchKernelGGL(k_gd_node_entity<2>, gn, blk, 0, c->stream, cg, (const int32_t*)c->d_conn.p, c->nen, (const double*)c->d_xyz.p,
-                           (const int32_t*)c->d_n2e_ptr.p, (const int32_t*)c->d_n2e.p, n_own, c->d_gd_ent.p, c->d_co_key[0].p, c->d_co_val[0].p);
-    int cur = 0;
-    FEDD_TRY(sort_nodes_by_cell(c, n_own, ncell, &cur));
-    c->co_sorted = cur;
-    hipLaunchKernelGGL(k_cell_bounds, gn, blk, 0, c->stream, (const int32_t*)c->d_co_key[cur].p, n_own, (int32_t)ncell,
-                       c->d_co_cell_ptr.p);
-    // ---- Dirichlet mask over the column space ----
-    FEDD_TRY(c->d_co_mask.ensure((size_t)c->n_cols));
-    FEDD_TRY(c->d_flags.ensure(16));
-    int32_t* d_bad = c->d_flags.p + 3;
-    FEDD_HIP(hipMemsetAsync(d_bad, 0, 3 * sizeof(int32_t), c->stream));
-    hipLaunchKernelGGL(k_mask, gr, blk, 0, c->stream, (const int32_t*)c->d_isdir.p, n_rows, c->d_co_mask.p, d_bad + 2);
-    if (c->n_cols != c->n_rows || !c->halo.peers.empty()) FEDD_TRY(halo_import(c, c->d_co_mask.p, dofs));
-    // ---- Phi_Gamma, then the harmonic extensions: one constrained solve per (class, component) ----
-    FEDD_TRY(c->d_gd_phi.ensure((size_t)ldp * std::max(nsd, 1)));
+    FEDD_TRY(group_nodes_by_cell(c, S.lt.ncell, [&](dim3 gn) {
+        FEDD_TRY(c->d_gd_ent.ensure((size_t)n_own));
+        COARSE_DIM(LAUNCH_D, k_gd_node_entity, gn, cg, (const int32_t*)c->d_conn.p, c->nen, (const double*)c->d_xyz.p,
+                   (const int32_t*)c->d_n2e_ptr.p, (const int32_t*)c->d_n2e.p, n_own, c->d_gd_ent.p, c->d_co_key[0].p, c->d_co_val[0].p);
+        return 0;
+    }));
+    return coarse_mask(c, &S.d_bad);
+}
+
+// 2. Phi <- Phi_Gamma, its values on the interface; with rotations, first which functions of every entity are independent on its
+// free interface dofs: Gram matrices (summed over the ranks), selection
+static int gdsw_interface(fedd_ctx* c, GdswSetup& S) {
+    const int dim = c->dim, dofs = c->dofs, nns = S.nns;
+    const int32_t n_own = (int32_t)c->n_own;
+    const int64_t n_rows = c->n_rows, n_ent = S.lt.n_ent;
+    const CoarseGeom cg = S.lt.cg;
+    const dim3 blk(256), gn((n_own + 255) / 256), gr((unsigned)((n_rows + 255) / 256));
+    FEDD_TRY(c->d_gd_phi.ensure((size_t)S.ldp * std::max(S.nsd, 1)));
     FEDD_TRY(c->d_gd_imask.ensure((size_t)n_rows));
-    const int64_t nc = (std::max<int64_t>(n_rows, c->n_cols) + 15) & ~(int64_t)15;
-    FEDD_TRY(c->d_gd_tmp.ensure((size_t)nc + 3 * (size_t)n_rows));
-    double* v = c->d_gd_tmp.p;              // [nc] column-space vector (ghost tail)
-    double* w = v + nc;
-    double* b = w + n_rows;
-    double* x = b + n_rows;
+    S.nc = (std::max<int64_t>(n_rows, c->n_cols) + 15) & ~(int64_t)15;
+    FEDD_TRY(c->d_gd_tmp.ensure((size_t)S.nc + 3 * (size_t)n_rows));
+    S.v = c->d_gd_tmp.p, S.w = S.v + S.nc, S.b = S.w + n_rows, S.x = S.b + n_rows;
     const int32_t* d_keep = nullptr;
-    if (rot) {
-        // which functions of every entity are independent on its free interface dofs: Gram matrices (summed over the ranks), selection
+    if (S.rot) {
         double hmax2 = 0.0;
         for (int d = 0; d < dim; ++d) hmax2 = std::max(hmax2, (cg.L[d] / cg.g[d]) * (cg.L[d] / cg.g[d]));
         FEDD_CHECK(n_ent * GD_NG < ((int64_t)1 << 31), "GDSW setup: %lld entities", (long long)n_ent);
         FEDD_TRY(c->d_gd_gram.ensure((size_t)n_ent * GD_NG));
         FEDD_TRY(c->d_gd_keep.ensure((size_t)n_ent));
         FEDD_HIP(hipMemsetAsync(c->d_gd_gram.p, 0, (size_t)n_ent * GD_NG * sizeof(double), c->stream));
-        if (dim == 3) hipLaunchKernelGGL(k_gd_gram<3>, gn, blk, 0, c->stream, cg, act, (const int32_t*)c->d_gd_ent.p, dofs, nns, n_own, (const double*)c->d_xyz.p, (const double*)c->d_co_mask.p, c->d_gd_gram.p);
-        else hipLaunchKernelGGL(k_gd_gram<2>, gn, blk, 0, c->stream, cg, act, (const int32_t*)c->d_gd_ent.p, dofs, nns, n_own, (const double*)c->d_xyz.p, (const double*)c->d_co_mask.p, c->d_gd_gram.p);
+        COARSE_DIM(LAUNCH_D, k_gd_gram, gn, cg, S.act, (const int32_t*)c->d_gd_ent.p, dofs, nns, n_own, (const double*)c->d_xyz.p,
+                   (const double*)c->d_co_mask.p, c->d_gd_gram.p);
         if (c->nranks > 1) FEDD_TRY(allreduce_sum(c, c->d_gd_gram.p, (int)(n_ent * GD_NG)));
-        hipLaunchKernelGGL(k_gd_select, dim3((unsigned)((n_ent + 255) / 256)), blk, 0, c->stream, (const double*)c->d_gd_gram.p, n_ent, dofs, nns, hmax2, c->d_gd_keep.p);
+        hipLaunchKernelGGL(k_gd_select, dim3((unsigned)((n_ent + 255) / 256)), blk, 0, c->stream, (const double*)c->d_gd_gram.p, n_ent,
+                           dofs, nns, hmax2, c->d_gd_keep.p);
         d_keep = c->d_gd_keep.p;
     }
-    if (dim == 3) hipLaunchKernelGGL(k_gd_phi_init<3>, gr, blk, 0, c->stream, cg, act, (const int32_t*)c->d_gd_ent.p, dofs, nns, n_rows, ldp, (const double*)c->d_xyz.p, d_keep, (const double*)c->d_co_mask.p, c->d_gd_phi.p, c->d_gd_imask.p);
-    else hipLaunchKernelGGL(k_gd_phi_init<2>, gr, blk, 0, c->stream, cg, act, (const int32_t*)c->d_gd_ent.p, dofs, nns, n_rows, ldp, (const double*)c->d_xyz.p, d_keep, (const double*)c->d_co_mask.p, c->d_gd_phi.p, c->d_gd_imask.p);
-    FEDD_TRY(c->d_co_part.ensure((size_t)ncell * std::max(nsd, 1)));
-    FEDD_TRY(c->d_co_r0.ensure(std::max<size_t>((size_t)ld, c->d_co_r0.cap)));
-    FEDD_TRY(c->d_co_z0.ensure((size_t)ld));
-    int its_max = 0;
-    double rel_max = 0.0;
+    COARSE_DIM(LAUNCH_D, k_gd_phi_init, gr, cg, S.act, (const int32_t*)c->d_gd_ent.p, dofs, nns, n_rows, S.ldp, (const double*)c->d_xyz.p,
+               d_keep, (const double*)c->d_co_mask.p, c->d_gd_phi.p, c->d_gd_imask.p);
+    return 0;
+}
+
+// one extension solve on the constrained operator (GmresCall::mask), nr stacked columns; keeps the largest count and residual
+static int gdsw_extension_solve(fedd_ctx* c, const GdswSetup& S, const double* b, double* x, int restart, int nr, int* its_max,
+                                double* rel_max) {
+    int its = 0;
+    double rel = 0.0;
+    GmresCall call{b, x, S.ext_tol, 1000, restart, 1};
+    call.mask = c->d_gd_imask.p;
+    call.nr = nr;
+    TimersSuspended quiet(c);
+    FEDD_TRY(gmres_solve(c, call, &its, &rel));
+    *its_max = std::max(*its_max, its);
+    *rel_max = std::max(*rel_max, rel);
+    return 0;
+}
+
+// 3a. all columns solve with the same constrained operator: MULTI_NR of them at a time as one stacked system (multi.hip) -- the
+// matrix and the local inverses are read once per sweep for all of them; the stacked GMRES minimises the residual of the
+// whole block with one polynomial, columns that are zero stay zero
+static int gdsw_extend_stacked(fedd_ctx* c, GdswSetup& S, int* its_max, double* rel_max) {
+    const int64_t n_rows = c->n_rows, ldp = S.ldp;
+    const int nsd = S.nsd;
+    const int nbatch = (nsd + MULTI_NR - 1) / MULTI_NR, nb_max = (nsd + nbatch - 1) / nbatch;
+    const int64_t ns = n_rows * MULTI_NR, ncs = ((std::max<int64_t>(n_rows, c->n_cols) * MULTI_NR) + 15) & ~(int64_t)15;
+    FEDD_TRY(c->d_gd_stack.ensure((size_t)ncs + 3 * (size_t)ns));
+    double* const p = c->d_gd_stack.p;
+    const GdStack st = S.st = GdStack{p, p + ncs, p + ncs + ns, p + ncs + 2 * ns};
+    const dim3 blk(256), gs((unsigned)((ns + 255) / 256));
+    // the Krylov basis of a stacked solve: restart length by the memory it may take (16 GB), at least 24
+    const int restart_s = (int)std::max<int64_t>(24, std::min<int64_t>(100, (int64_t)(16.0e9 / (8.0 * (double)ns)) - 1));
+    for (int slot0 = 0; slot0 < nsd; slot0 += nb_max) {
+        const int nb = std::min(nb_max, nsd - slot0);
+        hipLaunchKernelGGL(k_gd_gamma_cols, gs, blk, 0, c->stream, (const double*)c->d_gd_phi.p, ldp, slot0, nb,
+                           (const double*)c->d_gd_imask.p, n_rows, (const double*)c->d_co_mask.p, st.V);
+        FEDD_TRY(spmm_owned(c, st.V, st.W, nullptr, nullptr));
+        hipLaunchKernelGGL(k_gd_rhs<MULTI_NR>, gs, blk, 0, c->stream, (const double*)c->d_gd_imask.p, (const double*)st.W, n_rows, st.B);
+        // columns to unit norm (see k_cols_sumsq): the tolerance then holds per column
+        const int ncsb = (int)((n_rows + CS_ROWS - 1) / CS_ROWS);
+        FEDD_TRY(c->d_dtmp0.ensure(std::max<size_t>((size_t)ncsb * MULTI_NR + 4 * MULTI_NR, c->d_dtmp0.cap)));
+        double* csf = c->d_dtmp0.p;                         // [0, 16) 1 / norm, [16, 32) norm
+        double* cspart = csf + 4 * MULTI_NR;
+        hipLaunchKernelGGL(k_cols_sumsq, dim3((unsigned)ncsb), blk, 0, c->stream, (const double*)st.B, n_rows, cspart);
+        hipLaunchKernelGGL(k_cols_sum_parts, dim3(1), dim3(64), 0, c->stream, (const double*)cspart, ncsb, csf);
+        FEDD_TRY(allreduce_sum(c, csf, MULTI_NR));
+        hipLaunchKernelGGL(k_cols_scale_setup, dim3(1), dim3(64), 0, c->stream, csf);
+        hipLaunchKernelGGL(k_cols_scale, gs, blk, 0, c->stream, st.B, ns, (const double*)csf);
+        FEDD_TRY(gdsw_extension_solve(c, S, st.B, st.X, restart_s, MULTI_NR, its_max, rel_max));
+        hipLaunchKernelGGL(k_cols_scale, gs, blk, 0, c->stream, st.X, ns, (const double*)(csf + MULTI_NR));
+        hipLaunchKernelGGL(k_gd_store_cols, dim3((unsigned)((n_rows + 15) / 16)), blk, 0, c->stream, (const double*)c->d_gd_imask.p,
+                           (const double*)st.X, n_rows, c->d_gd_phi.p, ldp, slot0, nb);
+    }
+    return 0;
+}
+
+// 3b. ... or one constrained solve per column
+static int gdsw_extend_single(fedd_ctx* c, GdswSetup& S, int* its_max, double* rel_max) {
+    const int64_t n_rows = c->n_rows;
+    const dim3 blk(256), gr((unsigned)((n_rows + 255) / 256));
+    for (int slot = 0; slot < S.nsd; ++slot) {
+        FEDD_HIP(hipMemsetAsync(S.v, 0, (size_t)S.nc * sizeof(double), c->stream));
+        hipLaunchKernelGGL(k_gd_gamma_col, gr, blk, 0, c->stream, (const double*)(c->d_gd_phi.p + (int64_t)slot * S.ldp),
+                           (const double*)c->d_gd_imask.p, n_rows, (const double*)c->d_co_mask.p, S.v);
+        FEDD_TRY(spmv_owned(c, S.v, S.w, true));
+        hipLaunchKernelGGL(k_gd_rhs<1>, gr, blk, 0, c->stream, (const double*)c->d_gd_imask.p, (const double*)S.w, n_rows, S.b);
+        FEDD_TRY(gdsw_extension_solve(c, S, S.b, S.x, 100, 1, its_max, rel_max));
+        hipLaunchKernelGGL(k_gd_store, gr, blk, 0, c->stream, (const double*)c->d_gd_imask.p, (const double*)S.x, n_rows,
+                           c->d_gd_phi.p + (int64_t)slot * S.ldp);
+    }
+    return 0;
+}
+
+// 3. Phi_I = -K_II^-1 K_IGamma Phi_Gamma: the harmonic extensions, one constrained solve per (class, function)
+static int gdsw_extend(fedd_ctx* c, GdswSetup& S) {
     // tolerance of the extension solves (option "gdsw_tol"; 0 = by coarse space: GDSW 1e-4 -- below that the outer count is that of
     // exact extensions, above it grows: 163 -> 195 at 1e-3 --, RGDSW 1e-3: its outer count barely moves (123 -> 125 at cfg 5's
     // share, 62 -> 68 with the rotations) while the setup loses a third: profiles/r03_gdsw_tol_sweep_stacked.txt,
     // r04_cfg5_extension_tolerance.txt)
-    const double ext_tol = c->gdsw_tol > 0.0 ? c->gdsw_tol : (reduced ? 1e-3 : 1e-4);
-    // all columns solve with the same constrained operator: MULTI_NR of them at a time as one stacked system (multi.hip) -- the
-    // matrix and the local inverses are read once per sweep for all of them; the stacked GMRES minimises the residual of the
-    // whole block with one polynomial, columns that are zero stay zero
-    const bool stacked = c->gdsw_block && c->gmres_kind == 2 && nsd > 1 && multi_rhs_ok(c);
-    if (stacked) {
-        const int nbatch = (nsd + MULTI_NR - 1) / MULTI_NR, nb_max = (nsd + nbatch - 1) / nbatch;
-        const int64_t ns = n_rows * MULTI_NR, ncs = ((std::max<int64_t>(n_rows, c->n_cols) * MULTI_NR) + 15) & ~(int64_t)15;
-        FEDD_TRY(c->d_gd_stack.ensure((size_t)ncs + 3 * (size_t)ns));
-        double* Vs = c->d_gd_stack.p;       // [ncs] with the ghost rows behind the owned ones
-        double* Ws = Vs + ncs;
-        double* Bs = Ws + ns;
-        double* Xs = Bs + ns;
-        const dim3 gs((unsigned)((ns + 255) / 256));
-        // the Krylov basis of a stacked solve: restart length by the memory it may take (16 GB), at least 24
-        const int restart_s = (int)std::max<int64_t>(24, std::min<int64_t>(100, (int64_t)(16.0e9 / (8.0 * (double)ns)) - 1));
-        for (int slot0 = 0; slot0 < nsd; slot0 += nb_max) {
-            const int nb = std::min(nb_max, nsd - slot0);
-            hipLaunchKernelGGL(k_gd_gamma_cols, gs, blk, 0, c->stream, (const double*)c->d_gd_phi.p, ldp, slot0, nb,
-                               (const double*)c->d_gd_imask.p, n_rows, (const double*)c->d_co_mask.p, Vs);
-            FEDD_TRY(spmm_owned(c, Vs, Ws, nullptr, nullptr));
-            hipLaunchKernelGGL(k_gd_rhs_cols, gs, blk, 0, c->stream, (const double*)c->d_gd_imask.p, (const double*)Ws, n_rows, Bs);
-            // columns to unit norm (see k_cols_sumsq): the tolerance then holds per column
-            const int ncsb = (int)((n_rows + CS_ROWS - 1) / CS_ROWS);
-            FEDD_TRY(c->d_dtmp0.ensure(std::max<size_t>((size_t)ncsb * MULTI_NR + 4 * MULTI_NR, c->d_dtmp0.cap)));
-            double* csf = c->d_dtmp0.p;                         // [0, 16) 1 / norm, [16, 32) norm
-            double* cspart = csf + 4 * MULTI_NR;
-            hipLaunchKernelGGL(k_cols_sumsq, dim3((unsigned)ncsb), blk, 0, c->stream, (const double*)Bs, n_rows, cspart);
-            hipLaunchKernelGGL(k_cols_sum_parts, dim3(1), dim3(64), 0, c->stream, (const double*)cspart, ncsb, csf);
-            FEDD_TRY(allreduce_sum(c, csf, MULTI_NR));
-            hipLaunchKernelGGL(k_cols_scale_setup, dim3(1), dim3(64), 0, c->stream, csf);
-            hipLaunchKernelGGL(k_cols_scale, gs, blk, 0, c->stream, Bs, ns, (const double*)csf);
-            int its = 0;
-            double rel = 0.0;
-            GmresCall call{Bs, Xs, ext_tol, 1000, restart_s, 1};
-            call.mask = c->d_gd_imask.p;
-            call.nr = MULTI_NR;
-            const bool timing = c->timing;
-            c->timing = false;
-            const int rc = gmres_solve(c, call, &its, &rel);
-            c->timing = timing;
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_cols_scale, gs, blk, 0, c->stream, Xs, ns, (const double*)(csf + MULTI_NR));
-            its_max = std::max(its_max, its);
-            rel_max = std::max(rel_max, rel);
-            hipLaunchKernelGGL(k_gd_store_cols, dim3((unsigned)((n_rows + 15) / 16)), blk, 0, c->stream, (const double*)c->d_gd_imask.p,
-                               (const double*)Xs, n_rows, c->d_gd_phi.p, ldp, slot0, nb);
-        }
-    }
-    for (int slot = 0; slot < (stacked ? 0 : nsd); ++slot) {
-        FEDD_HIP(hipMemsetAsync(v, 0, (size_t)nc * sizeof(double), c->stream));
-        hipLaunchKernelGGL(k_gd_gamma_col, gr, blk, 0, c->stream, (const double*)(c->d_gd_phi.p + (int64_t)slot * ldp),
-                           (const double*)c->d_gd_imask.p, n_rows, (const double*)c->d_co_mask.p, v);
-        FEDD_TRY(spmv_owned(c, v, w, true));
-        hipLaunchKernelGGL(k_gd_rhs, gr, blk, 0, c->stream, (const double*)c->d_gd_imask.p, (const double*)w, n_rows, b);
-        int its = 0;
-        double rel = 0.0;
-        GmresCall call{b, x, ext_tol, 1000, 100, 1};
-        call.mask = c->d_gd_imask.p;
-        // the launches of these inner solves belong to the coarse setup (whose timer is open), not to the per-iteration
-        // classes of the outer solve: their timers are suspended (the tables double-counted them)
-        const bool timing = c->timing;
-        c->timing = false;
-        const int rc = gmres_solve(c, call, &its, &rel);
-        c->timing = timing;
-        if (rc) return rc;
-        its_max = std::max(its_max, its);
-        rel_max = std::max(rel_max, rel);
-        hipLaunchKernelGGL(k_gd_store, gr, blk, 0, c->stream, (const double*)c->d_gd_imask.p, (const double*)x, n_rows,
-                           c->d_gd_phi.p + (int64_t)slot * ldp);
-    }
+    S.ext_tol = c->gdsw_tol > 0.0 ? c->gdsw_tol : (S.reduced ? 1e-3 : 1e-4);
+    S.stacked = c->gdsw_block && c->gmres_kind == 2 && S.nsd > 1 && multi_rhs_ok(c);
+    int its_max = 0;
+    double rel_max = 0.0;
+    if (S.stacked) FEDD_TRY(gdsw_extend_stacked(c, S, &its_max, &rel_max));
+    else FEDD_TRY(gdsw_extend_single(c, S, &its_max, &rel_max));
     c->gdsw_ext_its = its_max;
     c->gdsw_ext_rel = rel_max;
-    FEDD_CHECK(rel_max <= std::max(1e3 * ext_tol, 1e-6), "GDSW setup: an extension solve stopped at relative residual %.2e "
-               "(tolerance %.1e)", rel_max, ext_tol);
-    // ---- K0 = Phi^T A Phi, a colour (entity coordinates modulo 5) and a component at a time ----
-    FEDD_TRY(c->d_co_K.ensure((size_t)ld * ld));
-    FEDD_HIP(hipMemsetAsync(c->d_co_K.p, 0, (size_t)ld * ld * sizeof(double), c->stream));
-    const dim3 ge((unsigned)((n0 + 255) / 256));
+    FEDD_CHECK(rel_max <= std::max(1e3 * S.ext_tol, 1e-6), "GDSW setup: an extension solve stopped at relative residual %.2e "
+               "(tolerance %.1e)", rel_max, S.ext_tol);
+    return 0;
+}
+
+// The columns of the Galerkin product, (colour, function) pairs, colour by colour: the colours are the residues of the entity
+// coordinates modulo the period that occur -- RGDSW: coarse nodes have odd coordinates in every direction with >= 2 cells (and 0
+// in the others): only those residues
+static std::vector<GdCols<1>> gdsw_columns(const CoarseGeom& cg, int nns) {
+    const int dim = cg.dim;
     int ncol[3] = {1, 1, 1};
     for (int d = 0; d < dim; ++d) ncol[d] = std::min(gd_period(cg), 2 * cg.g[d] - 1);
-    // RGDSW: coarse nodes have odd coordinates in every direction with >= 2 cells (and 0 in the others): only those residues
-    auto colour_used = [&](int d, int cc) { return !reduced || (cg.g[d] >= 2 ? (cc & 1) == 1 : cc == 0); };
-    std::vector<GdCol> colours;
+    auto colour_used = [&](int d, int cc) { return !cg.reduced || (cg.g[d] >= 2 ? (cc & 1) == 1 : cc == 0); };
+    std::vector<GdCols<1>> cols;
     for (int c2 = 0; c2 < ncol[2]; ++c2)
         for (int c1 = 0; c1 < ncol[1]; ++c1)
             for (int c0 = 0; c0 < ncol[0]; ++c0) {
                 if (!(colour_used(0, c0) && (dim < 2 || colour_used(1, c1)) && (dim < 3 || colour_used(2, c2)))) continue;
-                GdCol col;
-                col.c[0] = c0; col.c[1] = c1; col.c[2] = c2;
-                colours.push_back(col);
+                for (int k = 0; k < nns; ++k) cols.push_back(GdCols<1>{1, {{(int8_t)c0, (int8_t)c1, (int8_t)c2}}, {(int8_t)k}});
             }
-    if (stacked) {
-        // MULTI_NR (colour, component) columns per sweep: one SpMM, and Phi read once per sweep by the restriction
-        double* Vs = c->d_gd_stack.p;
-        double* Ws = Vs + (((std::max<int64_t>(n_rows, c->n_cols) * MULTI_NR) + 15) & ~(int64_t)15);
-        // chunks per cell: about 2048 rows each, so that few large cells still spread over the device
-        const int nch = (int)std::min<int64_t>(64, std::max<int64_t>(1, (n_rows / std::max<int64_t>(ncell, 1) + 2047) / 2048));
-        FEDD_TRY(c->d_co_part.ensure((size_t)ncell * nch * std::max(nsd, 1) * MULTI_NR));
-        FEDD_TRY(c->d_co_r0.ensure(std::max<size_t>((size_t)n0 * MULTI_NR, c->d_co_r0.cap)));
-        FEDD_CHECK(n0 * MULTI_NR < ((int64_t)1 << 31), "GDSW setup: coarse space too large for the stacked Galerkin product");
-        const dim3 gs((unsigned)((n_rows + 255) / 256)), ges((unsigned)((n0 * MULTI_NR + 255) / 256));
-        const int64_t npairs = (int64_t)colours.size() * nns;
-        for (int64_t p0 = 0; p0 < npairs; p0 += MULTI_NR) {
-            GdCols cols;
-            cols.nb = (int)std::min<int64_t>(MULTI_NR, npairs - p0);
-            for (int j = 0; j < MULTI_NR; ++j) {
-                const int64_t pj = std::min(p0 + j, npairs - 1);
-                for (int d = 0; d < 3; ++d) cols.c[j][d] = (int8_t)colours[(size_t)(pj / nns)].c[d];
-                cols.k[j] = (int8_t)(pj % nns);
-            }
-            if (dim == 3) hipLaunchKernelGGL(k_gd_prolong_colours<3>, gs, blk, 0, c->stream, cg, act, (const int32_t*)c->d_gd_ent.p, dofs, nns, n_rows, ldp, (const double*)c->d_gd_phi.p, (const double*)c->d_co_mask.p, cols, Vs);
-            else hipLaunchKernelGGL(k_gd_prolong_colours<2>, gs, blk, 0, c->stream, cg, act, (const int32_t*)c->d_gd_ent.p, dofs, nns, n_rows, ldp, (const double*)c->d_gd_phi.p, (const double*)c->d_co_mask.p, cols, Vs);
-            FEDD_TRY(spmm_owned(c, Vs, Ws, nullptr, nullptr));
-            hipLaunchKernelGGL(k_gd_restrict_cells_cols, dim3((unsigned)ncell, (unsigned)((nsd + 15) / 16), (unsigned)nch), blk, 0, c->stream,
-                               (const int32_t*)c->d_co_cell_ptr.p, (const int32_t*)c->d_co_val[c->co_sorted].p, dofs, nsd, nch, ldp,
-                               (const double*)c->d_gd_phi.p, (const double*)Ws, c->d_co_part.p);
-            if (dim == 3) hipLaunchKernelGGL(k_gd_restrict_ent_cols<3>, ges, blk, 0, c->stream, cg, act, nns, n_ent, nch, (const double*)c->d_co_part.p, c->d_co_r0.p);
-            else hipLaunchKernelGGL(k_gd_restrict_ent_cols<2>, ges, blk, 0, c->stream, cg, act, nns, n_ent, nch, (const double*)c->d_co_part.p, c->d_co_r0.p);
-            if (c->nranks > 1) FEDD_TRY(allreduce_sum(c, c->d_co_r0.p, (int)(n0 * MULTI_NR)));
-            if (dim == 3) hipLaunchKernelGGL(k_gd_scatter_cols<3>, ges, blk, 0, c->stream, cg, nns, n_ent, cols, (const double*)c->d_co_r0.p, c->d_co_K.p, ld);
-            else hipLaunchKernelGGL(k_gd_scatter_cols<2>, ges, blk, 0, c->stream, cg, nns, n_ent, cols, (const double*)c->d_co_r0.p, c->d_co_K.p, ld);
+    return cols;
+}
+
+// 4a. MULTI_NR columns per sweep: one SpMM, and Phi read once per sweep by the restriction, nch chunks per cell
+static int gdsw_galerkin_stacked(fedd_ctx* c, const GdswSetup& S, const std::vector<GdCols<1>>& columns, int nch) {
+    const int dim = c->dim, dofs = c->dofs, nns = S.nns, nsd = S.nsd;
+    const int64_t n_rows = c->n_rows, n_ent = S.lt.n_ent, n0 = S.lt.n0, ld = S.lt.ld;
+    const CoarseGeom cg = S.lt.cg;
+    FEDD_CHECK(n0 * MULTI_NR < ((int64_t)1 << 31), "GDSW setup: coarse space too large for the stacked Galerkin product");
+    const dim3 blk(256), gs((unsigned)((n_rows + 255) / 256)), ges((unsigned)((n0 * MULTI_NR + 255) / 256));
+    const int64_t npairs = (int64_t)columns.size();
+    for (int64_t p0 = 0; p0 < npairs; p0 += MULTI_NR) {
+        GdCols<MULTI_NR> cols;
+        cols.nb = (int)std::min<int64_t>(MULTI_NR, npairs - p0);
+        for (int j = 0; j < MULTI_NR; ++j) {
+            const GdCols<1>& one = columns[(size_t)std::min(p0 + j, npairs - 1)];
+            for (int d = 0; d < 3; ++d) cols.c[j][d] = one.c[0][d];
+            cols.k[j] = one.k[0];
         }
-        // (the per-column restriction of the apply takes its own layout of the partial sums)
-        FEDD_TRY(c->d_co_part.ensure((size_t)ncell * std::max(nsd, 1)));
+        COARSE_DIM(LAUNCH_DX, k_gd_prolong_colours, MULTI_NR, gs, cg, S.act, (const int32_t*)c->d_gd_ent.p, dofs, nns, n_rows, S.ldp,
+                   (const double*)c->d_gd_phi.p, (const double*)c->d_co_mask.p, cols, S.st.V);
+        FEDD_TRY(spmm_owned(c, S.st.V, S.st.W, nullptr, nullptr));
+        hipLaunchKernelGGL(k_gd_restrict_cells_cols, dim3((unsigned)S.lt.ncell, (unsigned)((nsd + 15) / 16), (unsigned)nch), blk, 0, c->stream,
+                           (const int32_t*)c->d_co_cell_ptr.p, (const int32_t*)c->d_co_val[c->co_sorted].p, dofs, nsd, nch, S.ldp,
+                           (const double*)c->d_gd_phi.p, (const double*)S.st.W, c->d_co_part.p);
+        COARSE_DIM(LAUNCH_D, k_gd_restrict_ent_cols, ges, cg, S.act, nns, n_ent, nch, (const double*)c->d_co_part.p, c->d_co_r0.p);
+        if (c->nranks > 1) FEDD_TRY(allreduce_sum(c, c->d_co_r0.p, (int)(n0 * MULTI_NR)));
+        COARSE_DIM(LAUNCH_DX, k_gd_scatter, MULTI_NR, ges, cg, nns, n_ent, cols, (const double*)c->d_co_r0.p, c->d_co_K.p, ld);
     }
-    for (size_t ci = 0; ci < (stacked ? 0 : colours.size()); ++ci)
-                for (int k = 0; k < nns; ++k) {
-                    const GdCol col = colours[ci];
-                    if (dim == 3) hipLaunchKernelGGL(k_gd_prolong_colour<3>, gr, blk, 0, c->stream, cg, act, (const int32_t*)c->d_gd_ent.p, dofs, nns, n_rows, ldp, (const double*)c->d_gd_phi.p, (const double*)c->d_co_mask.p, k, col, v);
-                    else hipLaunchKernelGGL(k_gd_prolong_colour<2>, gr, blk, 0, c->stream, cg, act, (const int32_t*)c->d_gd_ent.p, dofs, nns, n_rows, ldp, (const double*)c->d_gd_phi.p, (const double*)c->d_co_mask.p, k, col, v);
-                    FEDD_TRY(spmv_owned(c, v, w, true));
-                    FEDD_TRY(gdsw_restrict(c, w, c->d_co_r0.p));
-                    if (c->nranks > 1) FEDD_TRY(allreduce_sum(c, c->d_co_r0.p, (int)n0));
-                    if (dim == 3) hipLaunchKernelGGL(k_gd_scatter_col<3>, ge, blk, 0, c->stream, cg, nns, n_ent, k, col, (const double*)c->d_co_r0.p, c->d_co_K.p, ld);
-                    else hipLaunchKernelGGL(k_gd_scatter_col<2>, ge, blk, 0, c->stream, cg, nns, n_ent, k, col, (const double*)c->d_co_r0.p, c->d_co_K.p, ld);
-                }
-    hipLaunchKernelGGL(k_fix_diag, dim3((unsigned)((ld + 3) / 4)), blk, 0, c->stream, c->d_co_K.p, ld, n0);
-    FEDD_TRY(dense_invert_batched(c, c->d_co_K.p, ld, 1, ld * ld, nullptr, (int)(ld / NB), 1, d_bad + 1));
-    int32_t bad[3] = {0, 0, 0};
-    FEDD_HIP(hipMemcpyAsync(bad, d_bad, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    FEDD_HIP(hipStreamSynchronize(c->stream));
-    if (c->nranks > 1) {
-        double hb = (double)bad[1];
-        FEDD_HIP(hipMemcpyAsync(c->d_co_r0.p, &hb, sizeof(hb), hipMemcpyHostToDevice, c->stream));
-        FEDD_TRY(allreduce_sum(c, c->d_co_r0.p, 1));
-        FEDD_HIP(hipMemcpyAsync(&hb, c->d_co_r0.p, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
-        FEDD_HIP(hipStreamSynchronize(c->stream));
-        bad[1] = hb != 0.0;
+    return 0;
+}
+
+// 4b. ... or a column per sweep, restricted as in the apply
+static int gdsw_galerkin_single(fedd_ctx* c, const GdswSetup& S, const std::vector<GdCols<1>>& columns) {
+    const int dim = c->dim, dofs = c->dofs, nns = S.nns;
+    const int64_t n_rows = c->n_rows, n_ent = S.lt.n_ent, n0 = S.lt.n0, ld = S.lt.ld;
+    const CoarseGeom cg = S.lt.cg;
+    const dim3 gr((unsigned)((n_rows + 255) / 256)), ge((unsigned)((n0 + 255) / 256));
+    for (const GdCols<1>& col : columns) {
+        COARSE_DIM(LAUNCH_DX, k_gd_prolong_colours, 1, gr, cg, S.act, (const int32_t*)c->d_gd_ent.p, dofs, nns, n_rows, S.ldp,
+                   (const double*)c->d_gd_phi.p, (const double*)c->d_co_mask.p, col, S.v);
+        FEDD_TRY(spmv_owned(c, S.v, S.w, true));
+        FEDD_TRY(gdsw_restrict(c, S.w, c->d_co_r0.p));
+        if (c->nranks > 1) FEDD_TRY(allreduce_sum(c, c->d_co_r0.p, (int)n0));
+        COARSE_DIM(LAUNCH_DX, k_gd_scatter, 1, ge, cg, nns, n_ent, col, (const double*)c->d_co_r0.p, c->d_co_K.p, ld);
     }
-    FEDD_CHECK(!bad[1], "GDSW setup: K0 is not positive definite (the interior extensions were not solved well enough, or the "
-                        "matrix is not SPD on its free dofs)");
+    return 0;
+}
+
+// 4. K0 = Phi^T A Phi, a colour (entity coordinates modulo the period) and a function at a time
+static int gdsw_galerkin(fedd_ctx* c, const GdswSetup& S) {
+    const int64_t ncell = S.lt.ncell, n0 = S.lt.n0, ld = S.lt.ld;
+    // stacked: chunks per cell, about 2048 rows each, so that few large cells still spread over the device
+    const int nch = !S.stacked ? 1 : (int)std::min<int64_t>(64, std::max<int64_t>(1, (c->n_rows / std::max<int64_t>(ncell, 1) + 2047) / 2048));
+    // partial sums and r0 in their widest layout: the stacked product's [cell][chunk][slot][MULTI_NR] and [n0][MULTI_NR]; the
+    // restriction of the apply reads them as [cell][slot] and [n0]
+    const size_t wide = S.stacked ? MULTI_NR : 1;
+    FEDD_TRY(c->d_co_part.ensure((size_t)ncell * nch * std::max(S.nsd, 1) * wide));
+    FEDD_TRY(c->d_co_r0.ensure(std::max<size_t>(std::max<size_t>((size_t)ld, (size_t)n0 * wide), c->d_co_r0.cap)));
+    FEDD_TRY(c->d_co_z0.ensure((size_t)ld));
+    FEDD_TRY(c->d_co_K.ensure((size_t)ld * ld));
+    FEDD_HIP(hipMemsetAsync(c->d_co_K.p, 0, (size_t)ld * ld * sizeof(double), c->stream));
+    const std::vector<GdCols<1>> columns = gdsw_columns(S.lt.cg, S.nns);
+    if (S.stacked) return gdsw_galerkin_stacked(c, S, columns, nch);
+    return gdsw_galerkin_single(c, S, columns);
+}
+
+static int gdsw_setup(fedd_ctx* c) {
+    ScopedTimer timer(c, FEDD_T_COARSE_SETUP);
+    GdswSetup S;
+    FEDD_TRY(gdsw_geometry(c, S));
+    FEDD_TRY(gdsw_interface(c, S));
+    FEDD_TRY(gdsw_extend(c, S));
+    FEDD_TRY(gdsw_galerkin(c, S));
+    K0Flags flags;
+    FEDD_TRY(invert_k0(c, S.lt, S.d_bad, &flags));
+    FEDD_CHECK(!flags.indefinite, "GDSW setup: K0 is not positive definite (the interior extensions were not solved well enough, or the "
+                                  "matrix is not SPD on its free dofs)");
     FEDD_HIP(hipGetLastError());
     c->have_coarse = true;
     return 0;
@@ -1572,7 +1640,7 @@ static int gdsw_apply_add(fedd_ctx* c, const double* d_r_owned, double* d_z_owne
     }
     hipLaunchKernelGGL(k_dense_mv, dim3((unsigned)((n0 + 3) / 4)), dim3(256), 0, c->stream, (const double*)c->d_co_K.p, ld, n0,
                        (const double*)c->d_co_r0.p, c->d_co_z0.p, alpha);
-    FEDD_TRY(gdsw_prolong<true>(c, c->d_co_z0.p, d_z_owned));
+    FEDD_TRY(gdsw_prolong_add(c, c->d_co_z0.p, d_z_owned));
     FEDD_HIP(hipGetLastError());
     return 0;
 }
@@ -1594,63 +1662,21 @@ int coarse_setup(fedd_ctx* c) {
     // default: one cell per 1000 nodes, at most 12^3 cells (K0 is dense and replicated: 2197^2 doubles
     // = 38 MB to all-reduce and 21 GFLOP to invert per setup; 15^3 cells would be 134 MB and 137 GFLOP)
     if (!(target > 0)) target = std::min(1728.0, std::max(1.0, std::floor(n_global / 1000.0)));
-    CoarseGeom cg;
-    cg.dim = dim;
-    double V = 1.0;
-    for (int d = 0; d < dim; ++d) V *= (hi[d] - lo[d] > 0 ? hi[d] - lo[d] : 1.0);
-    const double H = std::pow(V / target, 1.0 / dim);
-    int64_t ncell = 1, nlat = 1;
-    for (int d = 0; d < 3; ++d) {
-        cg.g[d] = 1;
-        cg.np[d] = 1;
-        cg.lo[d] = 0.0;
-        cg.L[d] = 1.0;
-        if (d >= dim) continue;
-        const double Ld = hi[d] - lo[d];
-        cg.lo[d] = lo[d];
-        cg.L[d] = Ld > 0 ? Ld : 1.0;
-        int g = (int)std::floor(cg.L[d] / H + 0.5);
-        if (g < 1 || !(Ld > 0)) g = 1;
-        cg.g[d] = g;
-        cg.np[d] = g + 1;
-        ncell *= g;
-        nlat *= g + 1;
-    }
-    const int64_t n0 = nlat * dofs;
+    const Lattice lt = make_lattice(c, lo, hi, target, false, dofs, [](int g) { return g + 1; });   // (g + 1 lattice points)
+    const CoarseGeom cg = lt.cg;
+    const int64_t ncell = lt.ncell, nlat = lt.n_ent, n0 = lt.n0, ld = lt.ld;
     FEDD_CHECK(n0 <= COARSE_MAX_DOFS,
                "coarse setup: %lld coarse dofs, the dense coarse solver takes at most %d; lower "
                "fedd_schwarz_set_coarse (now %g cells)", (long long)n0, COARSE_MAX_DOFS, target);
-    const int64_t ld = (n0 + NB - 1) / NB * NB;
-    c->co_geom = cg;
-    c->co_ncell = ncell;
-    c->co_nlat = nlat;
-    c->co_n0 = n0;
-    c->co_ld = ld;
-    const dim3 blk(256), gn((n_own + 255) / 256);
+    lt.record(c);
     // ---- owned nodes grouped by cell, in node order (stable radix split on the cell id) ----
-    for (int q = 0; q < 2; ++q) {
-        FEDD_TRY(c->d_co_key[q].ensure((size_t)n_own));
-        FEDD_TRY(c->d_co_val[q].ensure((size_t)n_own));
-    }
-    FEDD_TRY(c->d_co_cell_ptr.ensure((size_t)ncell + 1));
-    FEDD_TRY(c->d_itmp0.ensure((size_t)n_own));
-#define K_CELL_KEY(D, ...) hipLaunchKernelGGL(k_cell_key<D>, gn, blk, 0, c->stream, __VA_ARGS__)
-    COARSE_DIM(K_CELL_KEY, cg, (const double*)c->d_xyz.p, n_own, c->d_co_key[0].p, c->d_co_val[0].p);
-#undef K_CELL_KEY
-    int cur = 0;
-    FEDD_TRY(sort_nodes_by_cell(c, n_own, ncell, &cur));
-    c->co_sorted = cur;
-    hipLaunchKernelGGL(k_cell_bounds, gn, blk, 0, c->stream, (const int32_t*)c->d_co_key[cur].p, n_own, (int32_t)ncell,
-                       c->d_co_cell_ptr.p);
-    const int32_t* cell_nodes = c->d_co_val[cur].p;
-    // ---- Dirichlet mask over the column space (ghost dofs through the halo) ----
-    FEDD_TRY(c->d_co_mask.ensure((size_t)c->n_cols));
-    FEDD_TRY(c->d_flags.ensure(16));
-    int32_t* d_bad = c->d_flags.p + 3;  // [0] non-neighbour coupling, [1] K0 not definite, [2] free dofs
-    FEDD_HIP(hipMemsetAsync(d_bad, 0, 3 * sizeof(int32_t), c->stream));
-    hipLaunchKernelGGL(k_mask, dim3((unsigned)((c->n_rows + 255) / 256)), blk, 0, c->stream, (const int32_t*)c->d_isdir.p,
-                       c->n_rows, c->d_co_mask.p, d_bad + 2);
-    if (c->n_cols != c->n_rows || !c->halo.peers.empty()) FEDD_TRY(halo_import(c, c->d_co_mask.p, dofs));
+    FEDD_TRY(group_nodes_by_cell(c, ncell, [&](dim3 gn) {
+        COARSE_DIM(LAUNCH_D, k_cell_key, gn, cg, (const double*)c->d_xyz.p, n_own, c->d_co_key[0].p, c->d_co_val[0].p);
+        return 0;
+    }));
+    const int32_t* cell_nodes = c->d_co_val[c->co_sorted].p;
+    int32_t* d_bad = nullptr;
+    FEDD_TRY(coarse_mask(c, &d_bad));
     // ---- K0 = Phi^T A Phi ----
     const int NC = 1 << dim, NS = dim == 3 ? 64 : 16, NW = dim == 3 ? 125 : 25;
     // chunks per cell: about 256 nodes each (4 batches), so that few, well-filled cells still
@@ -1665,41 +1691,24 @@ int coarse_setup(fedd_ctx* c) {
                (const int32_t*)c->d_rowptr.p, (const int32_t*)c->d_colind.p, (const double*)c->d_val.p,
                (const double*)c->d_co_mask.p, dofs, c->d_co_cellK.p, d_bad);
 #undef K_GALERKIN
-#define K_GATHER(D, ...) hipLaunchKernelGGL(k_coarse_gather<D>, dim3((unsigned)((nlat * NW + 255) / 256)), blk, 0, c->stream, __VA_ARGS__)
-    COARSE_DIM(K_GATHER, cg, dofs, nch, nlat, (const double*)c->d_co_cellK.p, c->d_co_K.p, ld);
-#undef K_GATHER
+    COARSE_DIM(LAUNCH_D, k_coarse_gather, dim3((unsigned)((nlat * NW + 255) / 256)), cg, dofs, nch, nlat, (const double*)c->d_co_cellK.p,
+               c->d_co_K.p, ld);
     if (c->nranks > 1) {
         FEDD_CHECK(ld * ld < ((int64_t)1 << 31), "coarse setup: K0 too large for one all-reduce");
         FEDD_TRY(allreduce_sum(c, c->d_co_K.p, (int)(ld * ld)));
     }
-    hipLaunchKernelGGL(k_fix_diag, dim3((unsigned)((ld + 3) / 4)), blk, 0, c->stream, c->d_co_K.p, ld, n0);
     // ---- K0 <- K0^-1 ----
-    FEDD_TRY(dense_invert_batched(c, c->d_co_K.p, ld, 1, ld * ld, nullptr, (int)(ld / NB), 1, d_bad + 1));
-    int32_t bad[3] = {0, 0, 0};
-    FEDD_HIP(hipMemcpyAsync(bad, d_bad, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    FEDD_HIP(hipStreamSynchronize(c->stream));
-    double n_free = (double)bad[2];
-    if (c->nranks > 1) {
-        // every rank must take the same decision: share the flags (and add up the free dofs)
-        double hb[3] = {(double)bad[0], (double)bad[1], n_free};
-        FEDD_TRY(c->d_co_r0.ensure(std::max<size_t>(3, c->d_co_r0.cap)));
-        FEDD_HIP(hipMemcpyAsync(c->d_co_r0.p, hb, sizeof(hb), hipMemcpyHostToDevice, c->stream));
-        FEDD_TRY(allreduce_sum(c, c->d_co_r0.p, 3));
-        FEDD_HIP(hipMemcpyAsync(hb, c->d_co_r0.p, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
-        FEDD_HIP(hipStreamSynchronize(c->stream));
-        bad[0] = hb[0] != 0.0;
-        bad[1] = hb[1] != 0.0;
-        n_free = hb[2];
-    }
+    K0Flags flags;
+    FEDD_TRY(invert_k0(c, lt, d_bad, &flags));
     // more coarse dofs than free fine dofs: K0 = Phi^T A Phi cannot have full rank, its regularised
     // inverse would amplify rounding errors by 1e12 and the operator would stop being linear
-    FEDD_CHECK(n_free == 0.0 || n_free >= (double)n0,
+    FEDD_CHECK(flags.n_free == 0.0 || flags.n_free >= (double)n0,
                "coarse setup: %lld coarse dofs for %.0f free dofs, the lattice is too fine; lower "
-               "fedd_schwarz_set_coarse (now %g cells)", (long long)n0, n_free, target);
-    FEDD_CHECK(!bad[0], "coarse setup: a matrix entry couples lattice cells that are not neighbours "
-                        "(the lattice is finer than the mesh); lower fedd_schwarz_set_coarse (now %g cells)", target);
-    FEDD_CHECK(!bad[1], "coarse setup: K0 is not positive definite (lattice too fine for the mesh?); lower "
-                        "fedd_schwarz_set_coarse (now %g cells)", target);
+               "fedd_schwarz_set_coarse (now %g cells)", (long long)n0, flags.n_free, target);
+    FEDD_CHECK(!flags.coupling, "coarse setup: a matrix entry couples lattice cells that are not neighbours "
+                                "(the lattice is finer than the mesh); lower fedd_schwarz_set_coarse (now %g cells)", target);
+    FEDD_CHECK(!flags.indefinite, "coarse setup: K0 is not positive definite (lattice too fine for the mesh?); lower "
+                                  "fedd_schwarz_set_coarse (now %g cells)", target);
     FEDD_TRY(c->d_co_part.ensure((size_t)ncell * NC * dofs));
     FEDD_TRY(c->d_co_r0.ensure(std::max<size_t>((size_t)ld, c->d_co_r0.cap)));
     FEDD_TRY(c->d_co_z0.ensure((size_t)ld));
@@ -1717,23 +1726,14 @@ static int coarse_apply_alpha(fedd_ctx* c, const double* d_r_owned, double* d_z_
     const int64_t ncell = c->co_ncell, nlat = c->co_nlat, n0 = c->co_n0, ld = c->co_ld;
     const int32_t* cell_nodes = c->d_co_val[c->co_sorted].p;
     const dim3 blk(256);
-#define K_RESTRICT(D, F)                                                                                          \
-    hipLaunchKernelGGL((k_restrict_cells<D, F>), dim3((unsigned)ncell), blk, 0, c->stream, cg,                   \
-                       (const int32_t*)c->d_co_cell_ptr.p, cell_nodes, (const double*)c->d_xyz.p,                 \
-                       (const double*)c->d_co_mask.p, d_r_owned, c->d_co_part.p)
-    if (dim == 3) {
-        if (dofs == 1) K_RESTRICT(3, 1);
-        else if (dofs == 2) K_RESTRICT(3, 2);
-        else K_RESTRICT(3, 3);
-    } else {
-        if (dofs == 1) K_RESTRICT(2, 1);
-        else if (dofs == 2) K_RESTRICT(2, 2);
-        else K_RESTRICT(2, 3);
-    }
+#define K_RESTRICT(D, ...)                                                         \
+    if (dofs == 1) LAUNCH_DX(D, k_restrict_cells, 1, dim3((unsigned)ncell), __VA_ARGS__);      \
+    else if (dofs == 2) LAUNCH_DX(D, k_restrict_cells, 2, dim3((unsigned)ncell), __VA_ARGS__); \
+    else LAUNCH_DX(D, k_restrict_cells, 3, dim3((unsigned)ncell), __VA_ARGS__)
+    COARSE_DIM(K_RESTRICT, cg, (const int32_t*)c->d_co_cell_ptr.p, cell_nodes, (const double*)c->d_xyz.p,
+               (const double*)c->d_co_mask.p, d_r_owned, c->d_co_part.p);
 #undef K_RESTRICT
-#define K_RNODES(D, ...) hipLaunchKernelGGL(k_restrict_nodes<D>, dim3((unsigned)((n0 + 255) / 256)), blk, 0, c->stream, __VA_ARGS__)
-    COARSE_DIM(K_RNODES, cg, dofs, nlat, (const double*)c->d_co_part.p, c->d_co_r0.p);
-#undef K_RNODES
+    COARSE_DIM(LAUNCH_D, k_restrict_nodes, dim3((unsigned)((n0 + 255) / 256)), cg, dofs, nlat, (const double*)c->d_co_part.p, c->d_co_r0.p);
     if (c->nranks > 1) {  // the collective is not part of the kernel time
         timer.stop();
         FEDD_TRY(allreduce_sum(c, c->d_co_r0.p, (int)n0));
@@ -1741,10 +1741,8 @@ static int coarse_apply_alpha(fedd_ctx* c, const double* d_r_owned, double* d_z_
     }
     hipLaunchKernelGGL(k_dense_mv, dim3((unsigned)((n0 + 3) / 4)), blk, 0, c->stream, (const double*)c->d_co_K.p, ld, n0,
                        (const double*)c->d_co_r0.p, c->d_co_z0.p, alpha);
-#define K_PROLONG(D, ...) hipLaunchKernelGGL(k_prolong_add<D>, dim3((unsigned)((c->n_rows + 255) / 256)), blk, 0, c->stream, __VA_ARGS__)
-    COARSE_DIM(K_PROLONG, cg, dofs, c->n_rows, (const double*)c->d_xyz.p, (const double*)c->d_co_mask.p,
-               (const double*)c->d_co_z0.p, d_z_owned);
-#undef K_PROLONG
+    COARSE_DIM(LAUNCH_D, k_prolong_add, dim3((unsigned)((c->n_rows + 255) / 256)), cg, dofs, c->n_rows, (const double*)c->d_xyz.p,
+               (const double*)c->d_co_mask.p, (const double*)c->d_co_z0.p, d_z_owned);
     FEDD_HIP(hipGetLastError());
     return 0;
 }
