@@ -31,6 +31,7 @@ ALE_P, ALE_FIXEDPOINT, ALE_NEWTON = range(3)     # fedd_assemble_advection_ale
 HYPER_NEOHOOKE, HYPER_MOONEY_RIVLIN, HYPER_STVK = range(3)   # fedd_assemble_hyperelastic: model
 HYPER_TANGENT, HYPER_FORCE = 1, 2                            # ... what (or-ed)
 BLOCKPREC_DIAGONAL, BLOCKPREC_TRIANGULAR = 1, 2              # fedd_block_prec_attach: kind
+STAGE_ERR_EUCLIDEAN, STAGE_ERR_L2 = 0, 1                     # fedd_stage_error: kind
 
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
@@ -125,6 +126,13 @@ SIGNATURES = {
     "fedd_multistep_set": [C.c_void_p, C.c_int, _f64p],
     "fedd_multistep_get": [C.c_void_p, C.c_int, _f64p],
     "fedd_multistep_info": [C.c_void_p, _ip, _ip],
+    "fedd_stage_begin": [C.c_void_p, C.c_int],
+    "fedd_stage_push": [C.c_void_p, C.c_int],
+    "fedd_stage_rhs": [C.c_void_p, C.c_int, C.c_int, C.c_int, _f64p, _f64p],
+    "fedd_block_merge_scaled": [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int],
+    "fedd_stage_error": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _f64p],
+    "fedd_stage_get": [C.c_void_p, C.c_int, _f64p, _f64p],
+    "fedd_stage_info": [C.c_void_p, _ip, _ip, _i64p, _i64p],
     "fedd_rhs_axpy": [C.c_void_p, C.c_double, _f64p],
     "fedd_solution_set": [C.c_void_p, _f64p],
     "fedd_dirichlet_rhs": [C.c_void_p, C.c_int, _i32p, _i32p, _f64p],
@@ -202,6 +210,62 @@ SIGNATURES = {
     "fedd_fsi_prec_detach": [C.c_void_p],
     "fedd_fsi_prec_info": [C.c_void_p, _ip, _i64p],
 }
+
+def butcher_table(number):
+    """(c, A) of the reference's Butcher table `number` (TimeSteppingTools::setTableInformationRK, TimeSteppingTools.cpp:309-487):
+    0 = implicit Euler, 1 = Crank-Nicolson, 2 = the pressure-corrected fractional-step theta scheme, 3 = DIRK3L, 4 = DIRK34.
+    c[s] and A[s, j] for the stages s = 0 .. S - 1; all are diagonally implicit with a dummy first stage (a_00 = 0) and
+    stiffly accurate, so b is the last row of A.  The derived constants are evaluated in the reference's order.
+
+    One entry differs from the reference ON PURPOSE: a_22 of table 2 is Theta_t * beta, the middle substep of the fractional-step
+    theta scheme, u_2 = u_1 + Theta_t dt (alpha f_1 + beta f_2).  TimeSteppingTools.cpp:369 writes Theta_t * alpha there; with it
+    row 2 no longer sums to c_2 = Theta + Theta_t and the scheme falls from the order 2 the reference states (convOrder_ = 2, :397)
+    to order 1 (tests/test_singlestep_ref.py measures both).
+
+    Two constants of table 4 differ ON PURPOSE as well: alpha = 0.158983899988677, the smallest root of
+    x^3 - 3 x^2 + (3/2) x - 1/6, and sigma = 0.0966483609791597.  With c = (0, 2 alpha, 1, 1) and this alpha the third-order
+    conditions sum b_i c_i = 1/2, sum b_i c_i^2 = 1/3, sum b_i a_ij c_j = 1/6 give exactly the reference's gamma and beta, and this
+    sigma.  TimeSteppingTools.cpp:426, 429 write 0.1558983899988677 and 0.09666483609791597, each with one digit doubled; with
+    them sum b_i c_i = 0.4922 and the scheme is of order 1 where the reference states 3 (convOrder_ = 3, :453)."""
+    theta = 1.0 - np.sqrt(2.0) / 2.0
+    theta_t = 1.0 - 2.0 * theta
+    alpha = theta_t / (1.0 - theta)
+    beta = 1.0 - alpha
+    if number == 0:
+        c = [0.0, 1.0]
+        a = [[0.0, 0.0],
+             [0.0, 1.0]]
+    elif number == 1:
+        c = [0.0, 1.0]
+        a = [[0.0, 0.0],
+             [0.5, 0.5]]
+    elif number == 2:
+        c = [0.0, theta, theta + theta_t, 1.0]
+        a = [[0.0, 0.0, 0.0, 0.0],
+             [theta * beta, theta * alpha, 0.0, 0.0],
+             [theta * beta, (theta + theta_t) * alpha, theta_t * beta, 0.0],
+             [theta * beta, (theta + theta_t) * alpha, (theta + theta_t) * beta, theta * alpha]]
+    elif number == 3:
+        alpha = 1.0 - np.sqrt(2.0) / 2.0
+        a21 = 1.0 / (4.0 * (1.0 - alpha))
+        c = [0.0, 2.0 * alpha, 1.0]
+        a = [[0.0, 0.0, 0.0],
+             [alpha, alpha, 0.0],
+             [1.0 - a21 - alpha, a21, alpha]]
+    elif number == 4:
+        alpha, beta, gamma, sigma = 0.158983899988677, 1.072486270734370, 0.7685298292769537, 0.0966483609791597
+        c = [0.0, 2.0 * alpha, 1.0, 1.0]
+        a = [[0.0, 0.0, 0.0, 0.0],
+             [alpha, alpha, 0.0, 0.0],
+             [1.0 - beta - alpha, beta, alpha, 0.0],
+             [1.0 - gamma - sigma - alpha, gamma, sigma, alpha]]
+    else:
+        raise ValueError("butcher_table: tables 0 .. 4 are built (got %r)" % (number,))
+    c, a = np.array(c, dtype=np.float64), np.array(a, dtype=np.float64)
+    if a[0, 0] != 0.0:
+        raise ValueError("butcher_table: table %r has a_00 = %g; the first stage must be a dummy stage" % (number, a[0, 0]))
+    return c, a
+
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, _i32p, _i64p, _f64p, _i64p, _f64p, C.c_int)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _f64p, C.c_int)
@@ -975,6 +1039,49 @@ class Context:
         out = np.zeros(self.csr_sizes()[0])
         _chk(self._L.fedd_multistep_get(self._h, int(k), _p(out, _f64p)))
         return out
+
+    def stage_begin(self, max_stages):
+        """opens a single-step (Runge-Kutta) step for up to max_stages (2 .. 8) stages, count = 0; the buffers are kept"""
+        _chk(self._L.fedd_stage_begin(self._h, int(max_stages)))
+
+    def stage_push(self, slot_f):
+        """stage `count` <- the values of M[slot_f] and the device's current solution vector"""
+        _chk(self._L.fedd_stage_push(self._h, int(slot_f)))
+
+    def stage_info(self):
+        """(max_stages, count, nnz, n): max_stages 0 = no open step; nnz and n of the first push"""
+        a, b, c, d = C.c_int(), C.c_int(), C.c_int64(), C.c_int64()
+        _chk(self._L.fedd_stage_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return a.value, b.value, c.value, d.value
+
+    def stage_rhs(self, slot_m, slot_bt, coeff_f, coeff_bt=None):
+        """buildMultiStageRhs: rhs <- [M u_0 + sum_j (coeff_f[j] (F_j u_j) + coeff_bt[j] (B^T p_j)) ; 0], n_prior = len(coeff_f);
+        coeff_bt None = all 0.0 ("Full implicit pressure")"""
+        cf = np.ascontiguousarray(np.atleast_1d(coeff_f), dtype=np.float64)
+        cb = np.zeros_like(cf) if coeff_bt is None else np.ascontiguousarray(np.atleast_1d(coeff_bt), dtype=np.float64)
+        if cb.shape != cf.shape:
+            raise FeddError("stage_rhs: coeff_f has %d entries, coeff_bt %d" % (cf.shape[0], cb.shape[0]))
+        _chk(self._L.fedd_stage_rhs(self._h, int(slot_m), int(slot_bt), cf.shape[0], _p(cf, _f64p), _p(cb, _f64p)))
+
+    def stage_error(self, kind, slot_m, ja, jb):
+        """||U_ja - U_jb||, Euclidean over all rows or sqrt(d^T M d) over the velocity rows; -1 = the current solution"""
+        e = C.c_double()
+        _chk(self._L.fedd_stage_error(self._h, int(kind), int(slot_m), int(ja), int(jb), C.byref(e)))
+        return e.value
+
+    def stage_get(self, j):
+        """(values of F_j, U_j) of stored stage j"""
+        mx, count, nnz, n = self.stage_info()
+        if not 0 <= j < count:      # the lengths of the host buffers come from the store: no such stage, no copy
+            raise FeddError("stage_get: stage %d of %d (fedd_stage_push first; a fedd_mesh_set releases the stage store)" % (j, count))
+        val, u = np.zeros(nnz), np.zeros(n)
+        _chk(self._L.fedd_stage_get(self._h, int(j), _p(val, _f64p), _p(u, _f64p)))
+        return val, u
+
+    def block_merge_scaled(self, slot_a, slot_bt, s_bt, slot_b, slot_c=-1):
+        """block_merge with every B^T value multiplied by s_bt on its way into the merged matrix"""
+        _chk(self._L.fedd_block_merge_scaled(self._h, slot_a, slot_bt, float(s_bt), slot_b, slot_c))
+        self.dofs = 1
 
     def rhs_axpy(self, alpha, f):
         f = np.ascontiguousarray(f, dtype=np.float64)

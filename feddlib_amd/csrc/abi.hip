@@ -206,7 +206,16 @@ static int mesh_set_impl(fedd_ctx* c, int dim, int nen, int64_t n_elem, const in
     c->d_ms_u[0].release();
     c->d_ms_u[1].release();
     c->d_ms_t.release();
-    ++c->mesh_gen;          // the Schwarz structure (schwarz.hip) belongs to the old nodes
+    c->st_max = c->st_count = 0;     // ... and the stage store of a single-step loop (singlestep.hip)
+    c->st_slot = -1;
+    c->st_pattern_id = 0;
+    c->st_nnz = c->st_n = c->st_rows = 0;
+    for (int j = 0; j < fedd::MAX_STAGES; ++j) {
+        c->d_st_val[j].release();
+        c->d_st_u[j].release();
+    }
+    c->d_st_part.release();
+    ++c->mesh_gen;         // the Schwarz structure (schwarz.hip) belongs to the old nodes
     c->have_xref = false;   // the coordinates uploaded below are the new reference of fedd_mesh_move
     c->n_moves = 0;
     c->min_det_ratio = 1.0;
@@ -550,6 +559,15 @@ extern "C" int fedd_block_merge(fedd_ctx* c, int slot_a, int slot_bt, int slot_b
     FEDD_CHECK(slot_bt < fedd::MAX_AUX && slot_b < fedd::MAX_AUX && slot_c < fedd::MAX_AUX, "fedd_block_merge: slot out of range");
     FEDD_HIP(hipSetDevice(c->device));
     return block_merge(c, slot_a, slot_bt, slot_b, slot_c);
+}
+
+extern "C" int fedd_block_merge_scaled(fedd_ctx* c, int slot_a, int slot_bt, double s_bt, int slot_b, int slot_c) {
+    NEED_DEVICE(c);
+    ONE_RANK(c, "fedd_block_merge_scaled");
+    CHECK_SLOT(slot_a);
+    FEDD_CHECK(slot_bt < fedd::MAX_AUX && slot_b < fedd::MAX_AUX && slot_c < fedd::MAX_AUX, "fedd_block_merge_scaled: slot out of range");
+    FEDD_HIP(hipSetDevice(c->device));
+    return block_merge_scaled(c, slot_a, slot_bt, s_bt, slot_b, slot_c);
 }
 
 extern "C" int fedd_velocity_set(fedd_ctx* c, const double* u_rep) {

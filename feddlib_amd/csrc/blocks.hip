@@ -40,9 +40,12 @@ __global__ void k_merge_count(CsrView A, CsrView BT, CsrView B, CsrView C, int32
     cnt[r] = n;
 }
 
+// SCALED (fedd_block_merge_scaled): the values of B^T, the second block column of the rows below nA, are multiplied by s_bt, one
+// product per entry; the unscaled instance is the code fedd_block_merge has always run
+template <bool SCALED>
 __global__ void k_merge_fill(CsrView A, CsrView BT, CsrView B, CsrView C, int32_t nA, int32_t nB, int32_t col_off,
                              const int32_t* __restrict__ rowptr, int32_t* __restrict__ colind,
-                             double* __restrict__ val) {
+                             double* __restrict__ val, double s_bt) {
     const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= nA + nB) return;
     int32_t p = rowptr[r];
@@ -57,13 +60,14 @@ __global__ void k_merge_fill(CsrView A, CsrView BT, CsrView B, CsrView C, int32_
     if (R.rowptr)
         for (int32_t q = R.rowptr[i]; q < R.rowptr[i + 1]; ++q, ++p) {
             colind[p] = R.colind[q] + col_off;
-            val[p] = R.val[q];
+            val[p] = SCALED && r < nA ? s_bt * R.val[q] : R.val[q];
         }
 }
 
 // the same rows with the pattern already in place: values only
+template <bool SCALED>
 __global__ void k_merge_values(CsrView A, CsrView BT, CsrView B, CsrView C, int32_t nA, int32_t nB,
-                               const int32_t* __restrict__ rowptr, double* __restrict__ val) {
+                               const int32_t* __restrict__ rowptr, double* __restrict__ val, double s_bt) {
     const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= nA + nB) return;
     int32_t p = rowptr[r];
@@ -73,7 +77,7 @@ __global__ void k_merge_values(CsrView A, CsrView BT, CsrView B, CsrView C, int3
     if (L.rowptr)
         for (int32_t q = L.rowptr[i]; q < L.rowptr[i + 1]; ++q, ++p) val[p] = L.val[q];
     if (R.rowptr)
-        for (int32_t q = R.rowptr[i]; q < R.rowptr[i + 1]; ++q, ++p) val[p] = R.val[q];
+        for (int32_t q = R.rowptr[i]; q < R.rowptr[i + 1]; ++q, ++p) val[p] = SCALED && r < nA ? s_bt * R.val[q] : R.val[q];
 }
 
 __global__ void k_dof_node(int32_t nA, int32_t nB, int dofsA, int32_t* __restrict__ dof_node) {
@@ -91,6 +95,8 @@ CsrView view(const DevCsr* m) {
     }
     return v;
 }
+
+int merge_blocks(fedd_ctx* c, int slot_a, int slot_bt, int slot_b, int slot_c, bool scaled, double s_bt);
 
 }  // namespace
 
@@ -128,6 +134,16 @@ int matrix_scale(fedd_ctx* c, int slot, double alpha) {
 }
 
 int block_merge(fedd_ctx* c, int slot_a, int slot_bt, int slot_b, int slot_c) {
+    return merge_blocks(c, slot_a, slot_bt, slot_b, slot_c, false, 1.0);
+}
+
+int block_merge_scaled(fedd_ctx* c, int slot_a, int slot_bt, double s_bt, int slot_b, int slot_c) {
+    return merge_blocks(c, slot_a, slot_bt, slot_b, slot_c, true, s_bt);
+}
+
+namespace {
+
+int merge_blocks(fedd_ctx* c, int slot_a, int slot_bt, int slot_b, int slot_c, bool scaled, double s_bt) {
     FEDD_CHECK(c->nranks == 1, "block merge: one rank only for now");
     const DevCsr* A = &c->aux[slot_a];
     const DevCsr* BT = slot_bt >= 0 ? &c->aux[slot_bt] : nullptr;
@@ -154,11 +170,16 @@ int block_merge(fedd_ctx* c, int slot_a, int slot_bt, int slot_b, int slot_c) {
         const uint64_t id = blocks[k] && blocks[k]->valid ? blocks[k]->pattern_id : 0;
         same = same && c->merge_slots[k] == slots[k] && c->merge_ids[k] == id && (id != 0 || !(blocks[k] && blocks[k]->valid));
     }
-    // (a merge that only moves values declares the pattern written too: a missed reuse is cheap, a wrong one is not)
-    system_written(c, SYS_VALUES | SYS_PATTERN);
+    // (a merge that only moves values declares the pattern written too: a missed reuse is cheap, a wrong one is not.  The scaled
+    // merge of a stage loop, which changes s_bt from stage to stage, says what it wrote: values, and the pattern generation stands)
+    system_written(c, scaled && same ? SYS_VALUES : SYS_VALUES | SYS_PATTERN);
     if (same) {
-        hipLaunchKernelGGL(k_merge_values, grid, blk, 0, c->stream, vA, vBT, vB, vC, (int32_t)nA, (int32_t)nB,
-                           (const int32_t*)c->d_rowptr.p, c->d_val.p);
+        if (scaled)
+            hipLaunchKernelGGL(k_merge_values<true>, grid, blk, 0, c->stream, vA, vBT, vB, vC, (int32_t)nA, (int32_t)nB,
+                               (const int32_t*)c->d_rowptr.p, c->d_val.p, s_bt);
+        else
+            hipLaunchKernelGGL(k_merge_values<false>, grid, blk, 0, c->stream, vA, vBT, vB, vC, (int32_t)nA, (int32_t)nB,
+                               (const int32_t*)c->d_rowptr.p, c->d_val.p, 1.0);
         FEDD_HIP(hipMemsetAsync(c->d_rhs.p, 0, (size_t)n * sizeof(double), c->stream));
         FEDD_HIP(hipMemsetAsync(c->d_x.p, 0, (size_t)n * sizeof(double), c->stream));
         FEDD_HIP(hipMemsetAsync(c->d_isdir.p, 0, (size_t)n * sizeof(int32_t), c->stream));
@@ -175,8 +196,12 @@ int block_merge(fedd_ctx* c, int slot_a, int slot_bt, int slot_b, int slot_c) {
     FEDD_TRY(exclusive_scan_i32(c, c->d_rowptr.p, c->d_rowptr.p, n, &nnz));
     FEDD_TRY(c->d_colind.ensure((size_t)nnz));
     FEDD_TRY(c->d_val.ensure((size_t)nnz));
-    hipLaunchKernelGGL(k_merge_fill, grid, blk, 0, c->stream, vA, vBT, vB, vC, (int32_t)nA, (int32_t)nB, (int32_t)A->n_cols,
-                       (const int32_t*)c->d_rowptr.p, c->d_colind.p, c->d_val.p);
+    if (scaled)
+        hipLaunchKernelGGL(k_merge_fill<true>, grid, blk, 0, c->stream, vA, vBT, vB, vC, (int32_t)nA, (int32_t)nB, (int32_t)A->n_cols,
+                           (const int32_t*)c->d_rowptr.p, c->d_colind.p, c->d_val.p, s_bt);
+    else
+        hipLaunchKernelGGL(k_merge_fill<false>, grid, blk, 0, c->stream, vA, vBT, vB, vC, (int32_t)nA, (int32_t)nB, (int32_t)A->n_cols,
+                           (const int32_t*)c->d_rowptr.p, c->d_colind.p, c->d_val.p, 1.0);
     FEDD_TRY(c->d_dof_node.ensure((size_t)n));
     hipLaunchKernelGGL(k_dof_node, grid, blk, 0, c->stream, (int32_t)nA, (int32_t)nB, dofsA, c->d_dof_node.p);
     c->n_rows = n;
@@ -206,5 +231,7 @@ int block_merge(fedd_ctx* c, int slot_a, int slot_bt, int slot_b, int slot_c) {
     }
     return 0;
 }
+
+}  // namespace
 
 }  // namespace fedd

@@ -160,6 +160,7 @@ struct DevCsr {
     uint64_t pattern_id = 0;    // drawn from fedd_ctx::pattern_counter whenever rowptr / colind are rewritten: equal ids = same pattern
     uint64_t value_id = 0;      // drawn from fedd_ctx::value_counter by every writer of val: equal ids = same contents (timestep.hip)
 };
+constexpr int MAX_STAGES = 8;   // stages a single-step (Runge-Kutta) step may store (singlestep.hip): buffers of their own, not slots
 constexpr int MAX_AUX = 7;      // A, B, B^T, C, the linearised velocity block F = A + rho (N | N + W) of Navier-Stokes, and of its time loop
                                 // the velocity mass matrix (5) and the time-combined constant velocity block (cm M) + (ca A) (6)
 
@@ -558,7 +559,16 @@ struct fedd_ctx {
     fedd::DevBuf<double> d_ms_t;                // [ms_n] the combination M is applied to for the right-hand side
     int ms_order = 0, ms_count = 0;             // 0 = no history (fedd_multistep_begin); vectors recorded so far (<= ms_order)
     int64_t ms_n = -1;                          // length of the system at fedd_multistep_begin
-    uint64_t sys_pattern_id = 0;                // the system slot holds the pattern with this DevCsr::pattern_id (copied by
+    // ---- single-step (Runge-Kutta) stage store (singlestep.hip; one rank): buffers of their own, not matrix slots; kept from
+    //      step to step, released by fedd_mesh_set ----
+    fedd::DevBuf<double> d_st_val[fedd::MAX_STAGES];   // [st_nnz] the values of the stage operator F_j, on the pattern of the first push
+    fedd::DevBuf<double> d_st_u[fedd::MAX_STAGES];     // [st_n] the stage solution U_j = [u_j ; p_j]
+    fedd::DevBuf<double> d_st_part;             // fedd_stage_error: partial sums per workgroup | [1] their sum
+    int st_max = 0, st_count = 0;               // 0 = no open step (fedd_stage_begin); stages pushed in this step
+    int st_slot = -1;                           // the slot of the first push: its row pointers and columns are the stages' pattern
+    uint64_t st_pattern_id = 0;                 // ... while it still holds the pattern with this DevCsr::pattern_id
+    int64_t st_nnz = 0, st_n = 0, st_rows = 0;  // nonzeros and rows of that pattern, length of the system at the first push
+    uint64_t sys_pattern_id = 0;               // the system slot holds the pattern with this DevCsr::pattern_id (copied by
     uint64_t sys_pattern_gen = 0;               // fedd_matrix_store / fedd_matrix_combine) ... while pattern_gen still has this value
     uint64_t sys_value_gen = 0;                 // bumped by every writer of the system matrix' values (system_written; Dirichlet rows excepted)
     uint64_t sys_write_count = 0;               // bumped by every system_written, whatever it wrote (Dirichlet rows included)
@@ -858,6 +868,8 @@ int tiles_refresh_coords(fedd_ctx* c);   // the coordinate copies at the head of
 int matrix_store(fedd_ctx* c, int slot);
 int matrix_scale(fedd_ctx* c, int slot, double alpha);
 int block_merge(fedd_ctx* c, int slot_a, int slot_bt, int slot_b, int slot_c);
+// ... with every B^T value multiplied by s_bt on its way into the merged matrix (fedd_block_merge_scaled)
+int block_merge_scaled(fedd_ctx* c, int slot_a, int slot_bt, double s_bt, int slot_b, int slot_c);
 // timestep.hip: the system slot adopts the pattern of the stored block m (fedd_matrix_combine, fedd_matrix_import): buffers, row
 // pointers and columns (copied in c's stream), sizes; the values are the caller's.  n_xcol = the length of d_xcol;
 // zero_other_len: a right-hand side and a solution of another length are zeroed; pattern_id = what sys_pattern_id becomes

@@ -18,13 +18,29 @@ namespace fedd {
 //   x(col)          the entry of the vector (a load, or a load and a product rounded before it is used)
 //   add(col, p)     the rounded product val * x(col) of a kept entry; of a dropped or missing one, col = -1 and p = 0.0
 //   fold<G>(o)      one level of the tree: every sum += __shfl_xor(sum, o, G)
+// Sums that declare `static constexpr int EXTRA = E` carry E further sums over the same columns, each with a value array and a
+// vector of its own (singlestep.hip: the stage operators of a Runge-Kutta step share one pattern, so its row pointers and
+// columns are read once for all of them).  Their loads and products follow the first sum's at every step of the order above:
+//   val_extra(e)        the value array of extra sum e (same pattern as val), nullptr: the sum is off and nothing is loaded for it
+//   x_extra(e, col)     its vector entry
+//   add_extra(e, p)     the rounded product of a kept entry, or 0.0
+// A walk without EXTRA compiles to what it was before they existed.
+template <class Sums, class = void>
+struct extra_sums : std::integral_constant<int, 0> {};
+template <class Sums>
+struct extra_sums<Sums, std::void_t<decltype(Sums::EXTRA)>> : std::integral_constant<int, Sums::EXTRA> {};
+
 template <int G, class Sums>
 __device__ __forceinline__ void row_walk(const int32_t* __restrict__ colind, const double* __restrict__ val, int32_t s, int32_t len,
                                          int g, Sums& sums) {
 #pragma clang fp contract(off)
+    constexpr int E = extra_sums<Sums>::value;
     for (int32_t k0 = g; k0 < len; k0 += 4 * G) {
         int32_t cc[4];
         double vv[4], xx[4];
+        double ve[E > 0 ? E : 1][4], xe[E > 0 ? E : 1][4];
+        (void)ve;
+        (void)xe;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int32_t k = k0 + u * G;
@@ -33,10 +49,32 @@ __device__ __forceinline__ void row_walk(const int32_t* __restrict__ colind, con
             cc[u] = in ? col : -1;
             vv[u] = in ? val[s + k] : 0.0;
         }
+        if constexpr (E > 0) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const double* __restrict__ v = sums.val_extra(e);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) ve[e][u] = v && cc[u] >= 0 ? v[s + k0 + u * G] : 0.0;
+            }
+        }
 #pragma unroll
         for (int u = 0; u < 4; ++u) xx[u] = cc[u] >= 0 ? sums.x(cc[u]) : 0.0;
+        if constexpr (E > 0) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const bool on = sums.val_extra(e) != nullptr;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) xe[e][u] = on && cc[u] >= 0 ? sums.x_extra(e, cc[u]) : 0.0;
+            }
+        }
 #pragma unroll
         for (int u = 0; u < 4; ++u) sums.add(cc[u], vv[u] * xx[u]);
+        if constexpr (E > 0) {
+#pragma unroll
+            for (int e = 0; e < E; ++e)
+#pragma unroll
+                for (int u = 0; u < 4; ++u) sums.add_extra(e, ve[e][u] * xe[e][u]);
+        }
     }
 #pragma unroll
     for (int o = G / 2; o >= 1; o >>= 1) sums.template fold<G>(o);

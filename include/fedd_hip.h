@@ -642,6 +642,84 @@ int fedd_multistep_get(fedd_ctx* ctx, int k, double* u_k);
 int fedd_multistep_info(fedd_ctx* ctx, int* order, int* count);
 
 /* ------------------------------------------------------------------------------------------------
+ * Single-step time stepping for nonlinear block problems (unsteady Navier-Stokes), one rank: the multi-stage part of the
+ * reference's "Class" = "Singlestep" loop, DAESolverInTime::advanceInTimeNonLinear (DAESolverInTime_def.hpp:384-516), for the
+ * diagonally implicit, stiffly accurate Butcher tables with a_00 = 0 of TimeSteppingTools::setTableInformationRK
+ * (TimeSteppingTools.cpp:309-487, tables 0-4), the time definition [[1,1],[0,0]] and size = 2 blocks.  Error conventions as for
+ * Newmark and BDF: "needs a GPU context" on a host-only context (fedd_stage_info excepted), an error that says so on more than
+ * one rank.  No multiplication is fused with an addition.
+ *
+ * What the reference does per step, and the calls that restate it (slots as in "BDF time stepping": 0 = A, 1 = B, 2 = B^T,
+ * 4 = F, 5 = M, 6 = the time-combined constant block):
+ *   stage 0 (dummy)       reAssembleAndFill gives F_0 = A + rho N(u_n); U_0 = [u_n ; p_n] is kept:
+ *                             fedd_stage_begin(S); fedd_assemble_advection(N, rho, slot_add = 0, slot_out = 4); fedd_solution_set(U_0);
+ *                             fedd_stage_push(4)
+ *   stage s = 1 .. S - 1  buildMultiStageRhs: fedd_stage_rhs(5, 2, s, coeff_f, coeff_bt) with coeff_f[j] = -(dt * a_sj) and
+ *                             coeff_bt[j] = coeff_f[j], or 0.0 under "Full implicit pressure".
+ *                         The stage system [(1.0 * M) + (dt * a_ss) (A + rho N(u)), s_bt B^T ; B, C], s_bt = dt * a_ss, or dt under
+ *                             full implicit pressure: fedd_matrix_combine(5, 1.0, 0, dt * a_ss) + fedd_matrix_store(6) when dt * a_ss
+ *                             changed, then per nonlinear iteration fedd_assemble_advection(kind, (dt * a_ss) * rho, 6, 4) and
+ *                             fedd_block_merge_scaled(4, 2, s_bt, 1, C), which moves values only.
+ *                         After the solve, unless s is the last stage: F_s = A + rho N(u_s) (fedd_assemble_advection(N, rho, 0, 4)),
+ *                             fedd_solution_set(U_s), fedd_stage_push(4).  The last stage's solution is the step's result.
+ *   adaptive steps        TimeSteppingTools::adaptiveTimestep / calculateNewDt take ||U_a - U_b||: fedd_stage_error.
+ *
+ *   n   = the length of the current system (the merged one: velocity dofs, then pressure dofs)
+ *   n_m = the rows of the stage operators = the rows of M[slot_m], the velocity block
+ *
+ *   fedd_stage_begin   opens a step for max_stages = 2 .. 8 stages and sets count = 0.  The stages are buffers of their own, NOT
+ *                      matrix slots (the slots stay 0 .. 6): per stored stage one value array of the length of the stored velocity
+ *                      block's nonzeros and one vector of length n, allocated on first need and kept from step to step.
+ *                      Memory per stage: 8 * nnz(FULL velocity pattern) + 8 * n bytes.  fedd_mesh_set* releases the store;
+ *                      fedd_mesh_move, fedd_block_merge*, fedd_assemble_advection*, fedd_matrix_combine and fedd_dirichlet* keep it.
+ *   fedd_stage_push    appends stage j = count: the VALUES of M[slot_f] and the device's current solution vector, device to
+ *                      device.  The first push of a step records the pattern of slot_f (its pattern identity and its slot, whose
+ *                      row pointers and columns fedd_stage_rhs reads); later pushes must present the same slot with the same
+ *                      pattern (fedd_assemble_advection into the same slot keeps it).  Errors: no open step, count ==
+ *                      max_stages, an empty slot, a slot of an earlier mesh, a slot with another pattern, a slot with more rows
+ *                      than the system, a system whose length changed since the first push.
+ *   fedd_stage_rhs     n_prior = 1 .. count; coeff_f, coeff_bt host arrays of length n_prior.  ONE kernel over the n_m velocity
+ *                      rows, every product and every sum rounded on its own, in this order (NORMATIVE):
+ *                          t = rowsum(M[slot_m], u_0)
+ *                          for j = 0 .. n_prior - 1 ascending:
+ *                              mv = coeff_f[j] * rowsum(F_j, u_j)
+ *                              if coeff_bt[j] != 0.0:  mv = mv + (coeff_bt[j] * rowsum(B^T[slot_bt], p_j))
+ *                              t = t + mv
+ *                          rhs[row] = t ;   rhs[n_m .. n) = 0.0
+ *                      u_j = the first n_m entries of stage vector j, p_j the rest.  rowsum is the row sum of
+ *                      fedd_matrix_apply on that block, bit for bit: the block's own lane group (8 lanes up to 32 entries in
+ *                      its longest row, else 16), each lane adding in ascending column order, the same fixed tree.  The row
+ *                      pointers and columns of the stages' pattern are read once per row for all n_prior value arrays, those
+ *                      of B^T once for all p_j; no atomics, two calls agree bit for bit.  slot_bt < 0 is allowed only when
+ *                      every coeff_bt[j] is 0.0.  Where coeff_bt[j] is 0.0 the reference adds 0.0 * (B^T p_j); for finite data
+ *                      that equals skipping the term, which is what happens here.
+ *                      Errors: no stages, n_prior out of range, an empty slot, a slot of the wrong size or mesh, B^T columns
+ *                      != n - n_m, the slot of the first push no longer holding the stages' pattern.
+ *   fedd_block_merge_scaled
+ *                      fedd_block_merge with every B^T value multiplied by s_bt (one product per entry) on its way into the
+ *                      merged matrix; the stored slot is not modified.  Same values-only path and the same resets of right-hand
+ *                      side, solution and Dirichlet marks; s_bt == 1.0 gives the bits of fedd_block_merge.  Where only values
+ *                      move -- a change of s_bt alone is such a case -- the pattern generation stands (fedd_block_merge, which
+ *                      keeps its code path and its bits, declares the pattern written there too).
+ *   fedd_stage_error   *err = ||d||, d = U_ja - U_jb formed on the fly; ja, jb stage indices, -1 = the device's current solution.
+ *                      FEDD_STAGE_ERR_EUCLIDEAN: sqrt(sum_i d_i^2) over all n rows; FEDD_STAGE_ERR_L2: sqrt(sum_i d_i *
+ *                      rowsum(M[slot_m], d)_i) over the velocity rows (slot_m is not read for the Euclidean kind).  Partial sums
+ *                      per wave in a fixed tree, summed in a fixed order by a second small kernel, the root on the host: no
+ *                      floating-point atomics, two calls agree bit for bit.
+ *   fedd_stage_get     stage j = 0 .. count - 1: the value array (nnz doubles) and the vector (n doubles), host pointers, either
+ *                      may be NULL (tests, restarts).
+ *   fedd_stage_info    max_stages (0: no open step), count, and nnz and n of the first push (0 while count is 0).  Needs no device.
+ * ---------------------------------------------------------------------------------------------- */
+enum fedd_stage_err { FEDD_STAGE_ERR_EUCLIDEAN = 0, FEDD_STAGE_ERR_L2 = 1 };
+int fedd_stage_begin(fedd_ctx* ctx, int max_stages);
+int fedd_stage_push(fedd_ctx* ctx, int slot_f);
+int fedd_stage_rhs(fedd_ctx* ctx, int slot_m, int slot_bt, int n_prior, const double* coeff_f, const double* coeff_bt);
+int fedd_block_merge_scaled(fedd_ctx* ctx, int slot_a, int slot_bt, double s_bt, int slot_b, int slot_c);
+int fedd_stage_error(fedd_ctx* ctx, int kind, int slot_m, int ja, int jb, double* err);
+int fedd_stage_get(fedd_ctx* ctx, int j, double* f_val, double* u);
+int fedd_stage_info(fedd_ctx* ctx, int* max_stages, int* count, int64_t* nnz, int64_t* n);
+
+/* ------------------------------------------------------------------------------------------------
  * steady Navier-Stokes (one rank, like the block system it feeds): the matrices NavierStokes::reAssemble builds in every
  * nonlinear iteration (feddlib/problems/specific/NavierStokes_def.hpp:282-321) from the current velocity.
  *   fedd_velocity_set        u_rep[n_rep * dim], node-wise interleaved on the repeated map of fedd_mesh_set: what
